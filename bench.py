@@ -8,7 +8,11 @@ in the reference's 100 000-ray batches.  One "step" = one full frame (307 200 ra
 region; the per-call layout conversions of my path (grid relayout, weight packing) are
 invalidated every step so that they are INSIDE the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+``--dump-outputs DIR``: after the timed steps, rank 0 writes the images the last timed step returned (what a caller of
+``Renderer.render_img`` receives) as ``DIR/depth.npy``, ``DIR/uncertainty.npy`` and ``DIR/color.npy`` in float32 (6 MB).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment: this process touches no GPU, starts N worker
 processes (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, backend
@@ -73,7 +77,21 @@ def parse():
     ap.add_argument('--no-stage-timing', action='store_true')
     ap.add_argument('--no-shard-model', action='store_true', help='skip config.shard_model (its shard-sized launches would mix into a kernel-trace profile of the timed loop)')
     ap.add_argument('--no-extra', action='store_true', help='headline + roofline only (skip sustained / config5 / torch-gpu / dist legs)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s depth / uncertainty / colour images to DIR/<name>.npy (float32)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+def dump_outputs(out_dir, names, tensors):
+    """The timed path's outputs as DIR/<name>.npy, float32 (float64 stays float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(names, tensors):
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -348,6 +366,8 @@ def main():
 
     elapsed, out = timed_loop(step, args.steps, args.warmup)
     depth_img, unc_img, color_img = out
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ('depth', 'uncertainty', 'color'), out)
     assert torch.isfinite(depth_img).all() and torch.isfinite(color_img).all()
     rend.check_overflow(dev)
 

@@ -1,22 +1,29 @@
-"""Build container only (skipped where /root/reference is absent, e.g. on the GPU box): the drop-in classes and
-functions must accept exactly the calls the reference's callers make -- same parameter names, order and defaults as
-the imported reference (src/utils/Renderer.py, src/conv_onet/models/decoder.py, src/common.py).  Extensions are
-allowed only as trailing keyword parameters with defaults (e.g. render_batch_ray(..., depth_max=None))."""
+"""The drop-in classes and functions must accept exactly the calls the reference's callers make -- same parameter names,
+order and defaults as the reference (src/utils/Renderer.py, src/conv_onet/models/decoder.py, src/common.py), whose
+signatures and DF state-dict layout are recorded in tests/golden/reference_signatures.json (tests/golden/make_signature_golden.py).
+Extensions are allowed only as trailing keyword parameters with defaults (e.g. render_batch_ray(..., depth_max=None))."""
 import inspect
+import json
+import os
 
-import pytest
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_signatures.json')
 
-from oracle import ref_import
 
-pytestmark = pytest.mark.skipif(not ref_import.available(), reason='reference checkout not present')
+def _reference():
+    with open(GOLDEN) as f:
+        return json.load(f)
 
 
 def _params(fn):
     return [(p.name, p.kind, p.default) for p in inspect.signature(fn).parameters.values()]
 
 
+def _ref_params(entry):
+    return [(n, getattr(inspect.Parameter, k), d if has else inspect.Parameter.empty) for n, k, has, d in entry]
+
+
 def _assert_compatible(mine, ref, what):
-    pm, pr = _params(mine), _params(ref)
+    pm, pr = _params(mine), _ref_params(ref)
     assert len(pm) >= len(pr), f'{what}: fewer parameters than the reference: {pm} vs {pr}'
     for (n1, k1, d1), (n2, k2, d2) in zip(pm, pr):
         assert n1 == n2, f'{what}: parameter {n1!r} where the reference has {n2!r}'
@@ -34,28 +41,27 @@ def _assert_compatible(mine, ref, what):
 def test_renderer_and_decoder_signatures_match_the_reference():
     import attentive_dfprior_amd as A
     from attentive_dfprior_amd import common, decoder
-    rcommon, rdecoder, rrenderer = ref_import.load()
-    R, RR = A.Renderer, rrenderer.Renderer
+    ref = _reference()['signatures']
+    R = A.Renderer
     for name in ('__init__', 'eval_points', 'sample_grid_tsdf', 'eval_points_tsdf', 'render_batch_ray', 'render_img'):
-        _assert_compatible(getattr(R, name), getattr(RR, name), f'Renderer.{name}')
-    _assert_compatible(decoder.DF.__init__, rdecoder.DF.__init__, 'DF.__init__')
+        _assert_compatible(getattr(R, name), ref[f'Renderer.{name}'], f'Renderer.{name}')
+    _assert_compatible(decoder.DF.__init__, ref['DF.__init__'], 'DF.__init__')
     # DF.forward(p, c_grid, tsdf_volume, tsdf_bnds, stage='low', **kwargs): decoder.py:307
-    _assert_compatible(decoder.DF.forward, rdecoder.DF.forward, 'DF.forward')
-    _assert_compatible(decoder.MLP.__init__, rdecoder.MLP.__init__, 'MLP.__init__')
+    _assert_compatible(decoder.DF.forward, ref['DF.forward'], 'DF.forward')
+    _assert_compatible(decoder.MLP.__init__, ref['MLP.__init__'], 'MLP.__init__')
     for name in ('get_rays', 'get_rays_from_uv', 'select_uv', 'get_sample_uv', 'get_samples', 'raw2outputs_nerf_color',
                  'normalize_3d_coordinate', 'random_select'):
-        _assert_compatible(getattr(common, name), getattr(rcommon, name), f'common.{name}')
+        _assert_compatible(getattr(common, name), ref[f'common.{name}'], f'common.{name}')
+    assert len(ref) == 17
 
 
 def test_state_dict_keys_and_shapes_match_the_reference():
     import attentive_dfprior_amd as A
-    _, rdecoder, _ = ref_import.load()
     mine = A.DF().state_dict()
-    ref = rdecoder.DF(dim=3, c_dim=32, low_grid_len=0.32, high_grid_len=0.16, color_grid_len=0.16, hidden_size=32,
-                      pos_embedding_method='fourier').state_dict()
+    ref = dict((k, tuple(shape)) for k, shape in _reference()['state_dict'])
     assert list(mine.keys()) == list(ref.keys())
     for k in ref:
-        assert tuple(mine[k].shape) == tuple(ref[k].shape), k
+        assert tuple(mine[k].shape) == ref[k], k
 
 
 def test_registry_and_factory_like_the_reference():
