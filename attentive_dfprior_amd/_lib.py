@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ADFP_LIB_PATH') or os.path.join(_HERE, 'libadfp.so')   # override: kernel A/B builds
 
-ABI_VERSION = 131                 # ADFP_VERSION of include/adfp.h this binding was written against
+ABI_VERSION = 132                 # ADFP_VERSION of include/adfp.h this binding was written against
 STATUS_F16_RANGE = 31              # ADFP_STATUS_F16_RANGE: any of the bits below
 STATUS_RANGE_BITS = {'low': 1, 'high': 2, 'color': 4, 'att': 8, 'bwd': 16}      # ADFP_STATUS_F16_RANGE_<net>
 BWD_SCATTER_IN_KERNEL = 1        # ADFP_BWD_SCATTER_IN_KERNEL
@@ -254,7 +254,19 @@ SYMBOLS = [
     ('adfp_decode_single', C.c_int, [C.POINTER(AdfpScene), C.POINTER(AdfpPoints), C.c_int, C.c_void_p, C.c_void_p]),
     ('adfp_attention_rows', C.c_int, [C.POINTER(AdfpScene), C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    ('adfp_mc_workspace_bytes', C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ('adfp_mc_count', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ('adfp_mc_emit', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3),
+                               C.c_int, C.c_void_p, C.c_size_t, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
+    ('adfp_mc_table', C.c_int, [C.c_int, C.c_void_p]),
+    ('adfp_lattice_hull_fill', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_float, C.c_void_p]),
+    ('adfp_mesh_unpack_colors', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 ]
+
+MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER
+MC_MAX_TRI = 5                         # ADFP_MC_MAX_TRI
 
 _lib = None
 

@@ -3287,3 +3287,102 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
     }
     return 0;
 }
+
+// ---- mesh extraction (adfp_mesh.h) ----
+#include "adfp_mesh.h"
+
+static long long mc_tiles(int nx, int ny, int nz) {
+    return ((long long)nx * ny * nz + ADFP_MC_TILE - 1) / ADFP_MC_TILE;
+}
+static size_t mc_counts_bytes(long long ntiles) { return (((size_t)ntiles * 8) + 255) & ~(size_t)255; }
+size_t adfp_mc_workspace_bytes(int nx, int ny, int nz) {
+    if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
+    const long long nt = mc_tiles(nx, ny, nz);
+    return mc_counts_bytes(nt) + (size_t)(nt + 1) * 16;
+}
+static McLattice mc_lattice(const float* values, int nx, int ny, int nz, float level) {
+    McLattice L;
+    L.v = values; L.nx = nx; L.ny = ny; L.nz = nz;
+    L.sy = nz; L.sx = (long long)ny * nz; L.n = L.sx * nx; L.level = level;
+    return L;
+}
+static McWork mc_carve(const void* workspace, int nx, int ny, int nz) {
+    McWork W;
+    W.ntiles = mc_tiles(nx, ny, nz);
+    W.tile_counts = (unsigned*)workspace;
+    W.tile_offsets = (long long*)((char*)workspace + mc_counts_bytes(W.ntiles));
+    return W;
+}
+
+int adfp_mc_count(const float* values, int nx, int ny, int nz, float level, void* workspace, size_t workspace_bytes,
+                  long long* totals, void* stream) {
+    if (!values || !workspace || !totals || nx <= 0 || ny <= 0 || nz <= 0) return ADFP_E_ARG;
+    if (workspace_bytes < adfp_mc_workspace_bytes(nx, ny, nz)) return ADFP_E_WORKSPACE;
+    const McLattice L = mc_lattice(values, nx, ny, nz, level);
+    const McWork W = mc_carve(workspace, nx, ny, nz);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_mc_count, dim3((unsigned)W.ntiles), dim3(ADFP_MC_THREADS), 0, st, L, W);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(ADFP_MC_SCAN_THREADS), 0, st, W, totals);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_mc_emit(const float* values, int nx, int ny, int nz, float level, const float origin[3], const float spacing[3], int outward,
+                 const void* workspace, size_t workspace_bytes, long long n_verts, long long n_faces, float* verts, float* normals,
+                 long long* keys, long long vert_capacity, int* faces, long long face_capacity, void* stream) {
+    if (!values || !workspace || !origin || !spacing || nx <= 0 || ny <= 0 || nz <= 0) return ADFP_E_ARG;
+    if (outward != ADFP_MC_OUT_LOWER && outward != ADFP_MC_OUT_HIGHER) return ADFP_E_ARG;
+    if (n_verts < 0 || n_faces < 0 || vert_capacity < 0 || face_capacity < 0) return ADFP_E_ARG;
+    if (n_verts > 0 && (!verts || !keys)) return ADFP_E_ARG;
+    if (n_faces > 0 && !faces) return ADFP_E_ARG;
+    if (workspace_bytes < adfp_mc_workspace_bytes(nx, ny, nz)) return ADFP_E_WORKSPACE;
+    if (n_verts >= 0x80000000ll) return ADFP_E_UNSUPPORTED;                 // faces index vertices as int32
+    if (vert_capacity < n_verts || face_capacity < n_faces) return ADFP_E_WORKSPACE;
+    if (n_verts == 0 && n_faces == 0) return 0;
+    McEmit e;
+    e.L = mc_lattice(values, nx, ny, nz, level);
+    e.W = mc_carve(workspace, nx, ny, nz);
+    for (int k = 0; k < 3; ++k) { e.org[k] = origin[k]; e.sp[k] = spacing[k]; }
+    e.outward = outward;
+    e.verts = verts; e.normals = normals; e.keys = keys; e.vcap = vert_capacity;
+    e.faces = faces; e.fcap = face_capacity;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_verts > 0) {
+        hipLaunchKernelGGL(k_mc_emit_verts, dim3((unsigned)e.W.ntiles), dim3(ADFP_MC_THREADS), 0, st, e);
+        ADFP_CHECK_LAUNCH();
+    }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_mc_emit_faces, dim3((unsigned)e.W.ntiles), dim3(ADFP_MC_THREADS), 0, st, e);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int adfp_mc_table(int mc_case, signed char* out) {
+    if (mc_case < 0 || mc_case > 255 || !out) return ADFP_E_ARG;
+    memcpy(out, mc_tri_host[mc_case], 3 * ADFP_MC_MAX_TRI);
+    return (int)mc_count_host[mc_case];
+}
+
+int adfp_lattice_hull_fill(float* values, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz,
+                           const double* planes, int n_planes, float fill, void* stream) {
+    if (!values || !xs || !ys || !zs || nx <= 0 || ny <= 0 || nz <= 0 || n_planes < 0 || (n_planes > 0 && !planes)) return ADFP_E_ARG;
+    if (n_planes == 0) return 0;
+    HullFill h;
+    h.v = values; h.ax[0] = xs; h.ax[1] = ys; h.ax[2] = zs; h.nx = nx; h.ny = ny; h.nz = nz;
+    h.n = (long long)nx * ny * nz; h.planes = planes; h.n_planes = n_planes; h.fill = fill;
+    hipLaunchKernelGGL(k_hull_fill, dim3((unsigned)((h.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_mesh_unpack_colors(const float* verts, long long n_verts, const float* color_vol, int nx, int ny, int nz,
+                            unsigned char* colors, void* stream) {
+    if (n_verts < 0 || nx <= 0 || ny <= 0 || nz <= 0 || !color_vol || (n_verts > 0 && (!verts || !colors))) return ADFP_E_ARG;
+    if (n_verts == 0) return 0;
+    hipLaunchKernelGGL(k_unpack_colors, dim3((unsigned)((n_verts + 255) / 256)), dim3(256), 0, (hipStream_t)stream, verts, n_verts,
+                       color_vol, nx, ny, nz, colors);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}

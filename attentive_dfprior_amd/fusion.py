@@ -4,14 +4,16 @@ arguments, ``integrate(color_im, depth_im, cam_intr, cam_pose, obs_weight)`` and
 volumes resident on the MI355X and the per-voxel update in libadfp.so (``adfp_tsdf_integrate``) instead of a
 PyCUDA kernel / numba loops.  ``get_render_volume()`` hands the render path exactly what
 ``get_tsdf.py:95-97`` builds (the permuted, non-contiguous ``[1,1,Z,Y,X]`` view) without leaving the device.
-Mesh extraction (marching cubes, ``get_mesh``) stays the reference's scikit-image code.
+``get_mesh()`` / ``get_point_cloud()`` (src/fusion.py:303-342) extract the level-0 surface on the device as well
+(``mesh.marching_cubes``, libadfp.so ``adfp_mc_*``) and unpack the vertex colours there (``adfp_mesh_unpack_colors``); only the
+results cross to the host.
 """
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, mesh
 from ._lib import lib, ptr, check
 
 
@@ -70,3 +72,21 @@ class TSDFVolume(object):
         buffer (get_tsdf.py:95-97) and the float64 bounds tensor -- still on the device."""
         X, Y, Z = self._tsdf.shape
         return self._tsdf.reshape(1, 1, X, Y, Z).permute(0, 1, 4, 3, 2), torch.from_numpy(self._vol_bnds.copy())
+
+    def _surface(self, normals):
+        verts, faces, norms = mesh.marching_cubes(self._tsdf, level=0., normals=normals, outward='higher')
+        colors = mesh.unpack_colors(verts, self._color)
+        origin = torch.from_numpy(self._vol_origin).to(self.device)
+        world = verts * np.float32(self._voxel_size).item() + origin        # voxel grid coordinates to world coordinates, float32
+        return world, faces, norms, colors
+
+    def get_mesh(self):
+        """(verts [V,3] world f32, faces [F,3] int32, norms [V,3], colors [V,3] uint8) as numpy, like src/fusion.py:324-342:
+        level 0, normals toward free space (higher TSDF), colours of the voxel nearest each vertex."""
+        verts, faces, norms, colors = self._surface(True)
+        return verts.cpu().numpy(), faces.cpu().numpy(), norms.cpu().numpy(), colors.cpu().numpy()
+
+    def get_point_cloud(self):
+        """[V,6] = world vertex and its r, g, b (src/fusion.py:303-322)."""
+        verts, _, _, colors = self._surface(False)
+        return np.hstack([verts.cpu().numpy(), colors.cpu().numpy()])

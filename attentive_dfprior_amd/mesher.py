@@ -1,0 +1,291 @@
+"""
+Drop-in for the reference's ``src/utils/Mesher.py`` ``Mesher``: same constructor, same cfg keys (Mesher.py:30-46), same
+``slam`` attributes, ``get_mesh(...)`` with the reference's signature, return value and ``.ply`` output -- without open3d,
+trimesh or scikit-image.
+
+Where the work runs: the lattice is formed on the device chunk by chunk and queried through the package's ``eval_points``
+(libadfp.so); the convex-hull mask is one kernel (``adfp_lattice_hull_fill``); marching cubes is ``mesh.marching_cubes``
+(``adfp_mc_count`` / ``adfp_mc_emit``); the seen / unseen masks (``point_masks``) are the reference's torch code on the device.
+The host keeps the connected-component culling (scipy.sparse.csgraph) and the file.
+
+Deviations, both documented in INTEGRATION.md:
+  * the mesh bound (``get_bound_from_frames``) is the convex hull of the keyframes' camera centres and back-projected valid
+    depth pixels (scipy.spatial.ConvexHull, per frame, then over the union of the frames' hull vertices), scaled by
+    ``clean_mesh_bound_scale`` about the mean of its vertices; the reference hulls the vertices of an open3d TSDF mesh of the
+    same frames;
+  * marching cubes resolves ambiguous faces by separating the inside corners (include/adfp.h), where scikit-image uses the
+    Lewiner decider; the vertex set (every edge crossing) is the same.
+"""
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import mesh as M
+
+
+class Mesher(object):
+
+    def __init__(self, cfg, args, slam, points_batch_size=500000, ray_batch_size=100000):
+        self.points_batch_size = points_batch_size
+        self.ray_batch_size = ray_batch_size
+        self.renderer = slam.renderer
+        self.scale = cfg['scale']
+        self.occupancy = cfg['occupancy']
+
+        self.resolution = cfg['meshing']['resolution']
+        self.level_set = cfg['meshing']['level_set']
+        self.clean_mesh_bound_scale = cfg['meshing']['clean_mesh_bound_scale']
+        self.remove_small_geometry_threshold = cfg['meshing']['remove_small_geometry_threshold']
+        self.color_mesh_extraction_method = cfg['meshing']['color_mesh_extraction_method']
+        self.get_largest_components = cfg['meshing']['get_largest_components']
+        self.depth_test = cfg['meshing']['depth_test']
+
+        self.bound = slam.bound
+        self.verbose = slam.verbose
+        self.marching_cubes_bound = torch.from_numpy(np.array(cfg['mapping']['marching_cubes_bound']) * self.scale)
+        # The reference builds a dataset reader here (frame_reader, n_img); get_mesh never reads it, so none is constructed.
+        self.H, self.W, self.fx, self.fy, self.cx, self.cy = slam.H, slam.W, slam.fx, slam.fy, slam.cx, slam.cy
+        self.sample_mode = 'bilinear'
+        self.tsdf_bnds = slam.tsdf_bnds
+
+    # ---- Mesher.py:58-217, line for line in torch -------------------------------------------------------------------------
+    def _project(self, points, c2w, device):
+        fx, fy, cx, cy = self.fx, self.fy, self.cx, self.cy
+        w2c = np.linalg.inv(c2w)
+        w2c = torch.from_numpy(w2c).to(device).float()
+        ones = torch.ones_like(points[:, 0]).reshape(-1, 1).to(device)
+        homo_points = torch.cat([points, ones], dim=1).reshape(-1, 4, 1).to(device).float()
+        cam_cord_homo = w2c @ homo_points
+        cam_cord = cam_cord_homo[:, :3]
+        K = torch.from_numpy(np.array([[fx, .0, cx], [.0, fy, cy], [.0, .0, 1.0]]).reshape(3, 3)).to(device)
+        cam_cord[:, 0] *= -1
+        uv = K.float() @ cam_cord.float()
+        z = uv[:, -1:] + 1e-8
+        uv = uv[:, :2] / z
+        uv = uv.float()
+        H, W = self.H, self.W
+        edge = 0
+        cur_mask_seen = (uv[:, 0] < W - edge) & (uv[:, 0] > edge) & (uv[:, 1] < H - edge) & (uv[:, 1] > edge)
+        cur_mask_seen = cur_mask_seen & (z[:, :, 0] < 0)
+        edge = -1000
+        cur_mask_forecast = (uv[:, 0] < W - edge) & (uv[:, 0] > edge) & (uv[:, 1] < H - edge) & (uv[:, 1] > edge)
+        cur_mask_forecast = cur_mask_forecast & (z[:, :, 0] < 0)
+        return cam_cord, uv, cur_mask_seen, cur_mask_forecast
+
+    def point_masks(self, input_points, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames=False):
+        """(seen, forecast, unseen) boolean numpy masks of the points, as Mesher.py:58-217 computes them."""
+        H, W = self.H, self.W
+        if not isinstance(input_points, torch.Tensor):
+            input_points = torch.from_numpy(input_points)
+        input_points = input_points.clone().detach()
+        seen_mask_list, forecast_mask_list, unseen_mask_list = [], [], []
+        for pnts in torch.split(input_points, self.points_batch_size, dim=0):
+            points = pnts.to(device).float()
+            seen_mask = torch.zeros((points.shape[0])).bool().to(device)
+            forecast_mask = torch.zeros((points.shape[0])).bool().to(device)
+            if get_mask_use_all_frames:
+                for i in range(0, idx + 1, 1):
+                    c2w = estimate_c2w_list[i].cpu().numpy()
+                    _, _, cur_mask_seen, cur_mask_forecast = self._project(points, c2w, device)
+                    seen_mask |= cur_mask_seen.reshape(-1)
+                    forecast_mask |= cur_mask_forecast.reshape(-1)
+            else:
+                for keyframe in keyframe_dict:
+                    c2w = keyframe['est_c2w'].cpu().numpy()
+                    cam_cord, uv, cur_mask_seen, cur_mask_forecast = self._project(points, c2w, device)
+                    if self.depth_test:
+                        gt_depth = keyframe['depth'].to(device).reshape(1, 1, H, W)
+                        vgrid = uv.reshape(1, 1, -1, 2)
+                        vgrid[..., 0] = (vgrid[..., 0] / (W - 1) * 2.0 - 1.0)
+                        vgrid[..., 1] = (vgrid[..., 1] / (H - 1) * 2.0 - 1.0)
+                        depth_sample = F.grid_sample(gt_depth, vgrid, padding_mode='zeros', align_corners=True)
+                        depth_sample = depth_sample.reshape(-1)
+                        max_depth = torch.max(depth_sample)
+                        cur_mask_forecast = cur_mask_forecast.reshape(-1)
+                        proj_depth_forecast = -cam_cord[cur_mask_forecast, 2].reshape(-1)
+                        cur_mask_forecast[cur_mask_forecast.clone()] &= proj_depth_forecast < max_depth
+                        cur_mask_seen = cur_mask_seen.reshape(-1)
+                        proj_depth_seen = - cam_cord[cur_mask_seen, 2].reshape(-1)
+                        cur_mask_seen[cur_mask_seen.clone()] &= \
+                            (proj_depth_seen < depth_sample[cur_mask_seen] + 2.4) \
+                            & (depth_sample[cur_mask_seen] - 2.4 < proj_depth_seen)
+                    else:
+                        max_depth = torch.max(keyframe['depth']) * 1.1
+                        cur_mask_forecast = cur_mask_forecast.reshape(-1)
+                        proj_depth_forecast = -cam_cord[cur_mask_forecast, 2].reshape(-1)
+                        cur_mask_forecast[cur_mask_forecast.clone()] &= proj_depth_forecast < max_depth.to(device)
+                        cur_mask_seen = cur_mask_seen.reshape(-1)
+                        proj_depth_seen = - cam_cord[cur_mask_seen, 2].reshape(-1)
+                        cur_mask_seen[cur_mask_seen.clone()] &= proj_depth_seen < max_depth.to(device)
+                    seen_mask |= cur_mask_seen
+                    forecast_mask |= cur_mask_forecast
+            forecast_mask &= ~seen_mask
+            unseen_mask = ~(seen_mask | forecast_mask)
+            seen_mask_list.append(seen_mask.cpu().numpy())
+            forecast_mask_list.append(forecast_mask.cpu().numpy())
+            unseen_mask_list.append(unseen_mask.cpu().numpy())
+        return (np.concatenate(seen_mask_list, axis=0), np.concatenate(forecast_mask_list, axis=0),
+                np.concatenate(unseen_mask_list, axis=0))
+
+    # ---- mesh bound ------------------------------------------------------------------------------------------------------
+    def get_bound_planes(self, keyframe_dict, scale=1):
+        """Facet planes [F,4] (n, d; inside: n . p + d <= 0) of the mesh bound: the convex hull of the keyframes' camera centres
+        and back-projected valid depth pixels, scaled by clean_mesh_bound_scale about its vertices' mean (see the module
+        docstring: the reference hulls an open3d TSDF mesh of the same frames instead)."""
+        from scipy.spatial import ConvexHull
+        H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
+        v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing='ij')
+        pts = []
+        for keyframe in keyframe_dict:
+            c2w = keyframe['est_c2w'].cpu().numpy().astype(np.float64)
+            c2w[:3, 1] *= -1.0                                        # open3d / OpenCV camera, Mesher.py:247-249
+            c2w[:3, 2] *= -1.0
+            depth = keyframe['depth'].cpu().numpy().astype(np.float64)
+            ok = (depth > 0) & (depth < 1000)                        # depth_trunc=1000 of Mesher.py:256-261
+            d = depth[ok]
+            cam = np.stack([(u[ok] - cx) / fx * d, (v[ok] - cy) / fy * d, d], 1)
+            frame = np.concatenate([c2w[:3, 3][None], cam @ c2w[:3, :3].T + c2w[:3, 3]], 0)
+            if len(frame) >= 4:
+                try:
+                    frame = frame[ConvexHull(frame).vertices]
+                except Exception:                                    # a degenerate (planar) frame: keep its points
+                    pass
+            pts.append(frame)
+        hull = ConvexHull(np.concatenate(pts, 0))
+        verts = hull.points[hull.vertices]
+        center = verts.mean(0)
+        verts = center + self.clean_mesh_bound_scale * (verts - center)
+        return ConvexHull(verts).equations
+
+    def get_grid_uniform(self, resolution):
+        """The lattice axes of Mesher.py:365-393 (float64 np.linspace over the marching-cubes bound + 0.05).  The [P,3] point
+        list is not formed on the host: get_mesh builds it on the device chunk by chunk."""
+        bound = self.marching_cubes_bound
+        padding = 0.05
+        x = np.linspace(bound[0][0] - padding, bound[0][1] + padding, resolution)
+        y = np.linspace(bound[1][0] - padding, bound[1][1] + padding, resolution)
+        z = np.linspace(bound[2][0] - padding, bound[2][1] + padding, resolution)
+        # np.linspace over torch scalars hands back float64 tensors; the values are the reference's, as numpy arrays
+        return {"xyz": [np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64), np.asarray(z, dtype=np.float64)]}
+
+    @staticmethod
+    def marching_cubes_geometry(xyz):
+        """(spacing, origin) of the lattice as Mesher.py:464-486 hands them to marching cubes and adds to its vertices."""
+        spacing = (xyz[0][2] - xyz[0][1], xyz[1][2] - xyz[1][1], xyz[2][2] - xyz[2][1])
+        origin = (xyz[0][0], xyz[1][0], xyz[2][0])
+        return spacing, origin
+
+    def eval_points(self, p, decoders, tsdf_volume, tsdf_bnds, c=None, stage='color', device='cuda:0'):
+        """Mesher.py:286-326: raw [P,4]; occupancy 100 outside ``bound``."""
+        ret, _ = self.renderer.eval_points(p, decoders, tsdf_volume, tsdf_bnds, c, stage, device)
+        return ret
+
+    def lattice(self, c, decoders, tsdf_volume, axes, device):
+        """Occupancy ('high') of every lattice point as a device tensor [X,Y,Z] (Mesher.py:437-455 before the hull mask).  The
+        reference also samples the TSDF per chunk (eval_tsdf_mask, :441-442, :446) and never uses the result: skipped."""
+        ax = [torch.from_numpy(np.asarray(a, dtype=np.float64).astype(np.float32)).to(device) for a in axes]
+        X, Y, Z = (int(a.numel()) for a in ax)
+        out = torch.empty(X * Y * Z, dtype=torch.float32, device=device)
+        with torch.no_grad():
+            for s in range(0, X * Y * Z, self.points_batch_size):
+                lin = torch.arange(s, min(s + self.points_batch_size, X * Y * Z), device=device, dtype=torch.int64)
+                k = lin % Z
+                j = (lin // Z) % Y
+                i = lin // (Y * Z)
+                pts = torch.stack([ax[0][i], ax[1][j], ax[2][k]], 1)
+                out[s:s + lin.numel()] = self.eval_points(pts, decoders, tsdf_volume, self.tsdf_bnds, c, 'high', device)[:, 3]
+        return out.reshape(X, Y, Z), ax
+
+    # ---- culling (Mesher.py:492-513) -------------------------------------------------------------------------------------
+    def clean(self, vertices, faces, seen_mask):
+        """Drop faces whose three vertices are unseen, split into components (trimesh.split), keep the largest
+        (get_largest_components) or those above remove_small_geometry_threshold * scale^2 in area, keep referenced vertices.
+        Components follow trimesh's face adjacency: two faces are joined only through an edge that EXACTLY two faces use
+        (trimesh.graph.face_adjacency groups edges with require_count=2).  An edge with four faces -- the fan diagonal that
+        both cells of an ambiguous face can draw (include/adfp.h) -- joins nothing, as it would in the reference."""
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        faces = faces[~(~seen_mask)[faces].all(axis=1)]
+        if len(faces) == 0:
+            return vertices[:0], faces
+        nf = len(faces)
+        e = np.concatenate([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]])
+        e = np.sort(e, 1)
+        fid = np.tile(np.arange(nf), 3)
+        key = e[:, 0].astype(np.int64) * (len(vertices) + 1) + e[:, 1]
+        order = np.argsort(key, kind='stable')
+        ks, fs = key[order], fid[order]
+        _, start, count = np.unique(ks, return_index=True, return_counts=True)
+        two = start[count == 2]                        # edges of exactly two faces: those two faces are adjacent
+        adj = coo_matrix((np.ones(len(two)), (fs[two], fs[two + 1])), shape=(nf, nf))
+        ncomp, label = connected_components(adj, directed=False)
+        v = vertices.astype(np.float64)
+        area = 0.5 * np.linalg.norm(np.cross(v[faces[:, 1]] - v[faces[:, 0]], v[faces[:, 2]] - v[faces[:, 0]]), axis=1)
+        comp_area = np.bincount(label, weights=area, minlength=ncomp)
+        if self.get_largest_components:
+            keep = label == comp_area.argmax()
+        else:
+            keep = (comp_area > self.remove_small_geometry_threshold * self.scale * self.scale)[label]
+        faces = faces[keep]
+        used = np.unique(faces)
+        remap = np.full(len(vertices), -1, np.int64)
+        remap[used] = np.arange(len(used))
+        return vertices[used], remap[faces].astype(np.int32)
+
+    def get_mesh(self, mesh_out_file, c, decoders, keyframe_dict, estimate_c2w_list, idx, tsdf_volume, device='cuda:0',
+                 color=True, clean_mesh=True, get_mask_use_all_frames=False):
+        """Extract the mesh of the scene representation and write it to mesh_out_file (.ply); returns z_uni_m (Mesher.py:395-544)."""
+        if not str(mesh_out_file).lower().endswith('.ply'):
+            raise NotImplementedError(f'{mesh_out_file}: only .ply output is supported')
+        if color and self.color_mesh_extraction_method != 'direct_point_query':
+            raise NotImplementedError(f'color_mesh_extraction_method={self.color_mesh_extraction_method!r}: only direct_point_query')
+        with torch.no_grad():
+            xyz = self.get_grid_uniform(self.resolution)['xyz']
+            z, ax = self.lattice(c, decoders, tsdf_volume, xyz, device)
+            planes = self.get_bound_planes(keyframe_dict, self.scale)
+            M.hull_fill(z, ax, planes, 100.)
+            z_uni_m = z.cpu().numpy()
+            spacing, origin = self.marching_cubes_geometry(xyz)
+            verts, faces, _ = M.marching_cubes(z, level=self.level_set, spacing=spacing, origin=origin, outward='lower')
+            if faces.shape[0] == 0:
+                print('marching_cubes error. Possibly no surface extracted from the level set.')
+                return
+            vertices = verts.cpu().numpy()
+            faces = faces.cpu().numpy()
+            if clean_mesh:
+                seen_mask, _, _ = self.point_masks(verts, keyframe_dict, estimate_c2w_list, idx, device=device,
+                                                   get_mask_use_all_frames=get_mask_use_all_frames)
+                vertices, faces = self.clean(vertices, faces, seen_mask)
+            vertex_colors = None
+            if color:
+                vc = []
+                for pnts in torch.split(torch.from_numpy(vertices).to(device).float(), self.points_batch_size, dim=0):
+                    vc.append(self.eval_points(pnts, decoders, tsdf_volume, self.tsdf_bnds, c, 'color', device)[..., :3])
+                vertex_colors = torch.cat(vc, 0).cpu().numpy() if vc else np.zeros((0, 3), np.float32)
+                vertex_colors = (np.clip(vertex_colors, 0, 1) * 255).astype(np.uint8)
+            vertices, faces, vertex_colors = merge_coincident(vertices, faces, vertex_colors)
+            vertices = vertices / np.float32(self.scale)
+            os.makedirs(os.path.dirname(os.path.abspath(mesh_out_file)), exist_ok=True)
+            M.write_ply(mesh_out_file, vertices, faces, colors=vertex_colors)
+            if self.verbose:
+                print('Saved mesh at', mesh_out_file)
+            return z_uni_m
+
+
+def merge_coincident(vertices, faces, colors=None):
+    """Merge bitwise-equal vertex positions (what trimesh.Trimesh(process=True) does to the coincident vertices marching cubes
+    leaves at exactly-level corners); the first occurrence survives, in order."""
+    if len(vertices) == 0:
+        return vertices, faces, colors
+    bits = np.ascontiguousarray(vertices.astype(np.float32)).view(np.int32).reshape(-1, 3)
+    _, first, inv = np.unique(bits, axis=0, return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    if len(first) == len(vertices):
+        return vertices, faces, colors
+    rank = np.empty(len(first), np.int64)
+    rank[np.argsort(first, kind='stable')] = np.arange(len(first))
+    keep = np.sort(first)
+    new_of_old = rank[inv]
+    return vertices[keep], new_of_old[faces].astype(np.int32), (colors[keep] if colors is not None else None)

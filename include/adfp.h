@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ADFP_VERSION 131
+#define ADFP_VERSION 132
 
 /* error codes (host-detected) */
 #define ADFP_E_ARG        (-1)   /* null pointer / negative size */
@@ -706,6 +706,48 @@ int adfp_decode_single(const adfp_scene* scene /*host*/, const adfp_points* pts 
  * -> fused occupancy out4[4 i + 3] and the attention weight w[i].  scratch_u: n floats (inv_tsdf of the rows). */
 int adfp_attention_rows(const adfp_scene* scene /*host*/, const float* occ, const float* tsdf_val, long long n, float* out4 /*[n,4]*/,
                         float* w /*[n]*/, float* scratch_u, void* stream);
+
+/* ---- mesh extraction (src/utils/Mesher.py:450-486 and src/fusion.py:303-342 call skimage.measure.marching_cubes) ---- */
+/* Marching cubes over a dense lattice values[nx][ny][nz] (f32, z fastest, device).  Conventions (the CPU oracle tests/mesh_ref.py
+ * restates them):
+ *  - a corner is inside iff v > level;
+ *  - an edge carries a vertex iff both endpoints are finite and exactly one is inside; the vertex lies at
+ *    t = (level - v0) / (v1 - v0) from the lower-index endpoint (f32, index space), at origin + (i + t) * spacing per axis;
+ *  - point p = (i*ny + j)*nz + k owns its +x, +y and +z edges (edge key 3 p + axis): every vertex is emitted once (welded);
+ *  - a cell with a non-finite corner emits nothing;
+ *  - an ambiguous face (two diagonally opposite inside corners) is cut so that its inside corners are separated: the rule reads
+ *    only that face, so the mesh is crack-free.  scikit-image's Lewiner decider resolves those faces differently (the vertex
+ *    set, every edge crossing, is the same).  Loops are fan-triangulated from their lowest edge, so the two cells beside an
+ *    ambiguous face can both draw the same diagonal between its crossings: the surface is closed and consistently oriented,
+ *    but four triangles can share such an edge (not a manifold there);
+ *  - order: vertices by ascending edge key, triangles by ascending cell index (the cell's lower corner), then table order.
+ *    The same input gives bit-identical output; no atomics decide the order.
+ * Use: adfp_mc_count (writes the totals V, F to the device array totals[2]) -> the caller reads them and allocates ->
+ * adfp_mc_emit with the same values / level / workspace.  V >= 2^31 is ADFP_E_UNSUPPORTED (faces are int32); capacities below
+ * the totals are ADFP_E_WORKSPACE; nothing is written past a capacity.  origin / spacing are HOST arrays; normals may be NULL
+ * (else: central differences of the lattice, one-sided at the border, interpolated with t, normalised, pointing as `outward`
+ * says); keys: vert_capacity edge keys (device scratch, sorted on return). */
+#define ADFP_MC_MAX_TRI 5          /* triangles per case at most (tools/gen_mc_table.py asserts it) */
+#define ADFP_MC_OUT_LOWER  0     /* geometric normal toward lower values (occupancy: out of the occupied region) */
+#define ADFP_MC_OUT_HIGHER 1     /* toward higher values (TSDF: toward free space) */
+size_t adfp_mc_workspace_bytes(int nx, int ny, int nz);
+int adfp_mc_count(const float* values, int nx, int ny, int nz, float level, void* workspace, size_t workspace_bytes,
+                  long long* totals, void* stream);
+int adfp_mc_emit(const float* values, int nx, int ny, int nz, float level, const float origin[3], const float spacing[3], int outward,
+                 const void* workspace, size_t workspace_bytes, long long n_verts, long long n_faces, float* verts, float* normals,
+                 long long* keys, long long vert_capacity, int* faces, long long face_capacity, void* stream);
+/* Host copy of one case's triangles (local edge ids, 3 per triangle, ADFP_MC_OUT_LOWER winding) into out[3 * ADFP_MC_MAX_TRI]
+ * (host); returns the triangle count.  Corner c = (dx, dy, dz) = bits (0, 1, 2) of c; edge e = 4 * axis + the other two corner
+ * bits (lower axis first). */
+int adfp_mc_table(int mc_case, signed char* out);
+/* The Mesher's hull mask (Mesher.py:436-439, :450): every lattice point (xs[i], ys[j], zs[k]) (f32 axes, device) for which
+ * max_f(n_f . p + d_f) > 0 over the F planes [F][4] = (n, d) (f64, device) gets `fill`, in place. */
+int adfp_lattice_hull_fill(float* values, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz,
+                           const double* planes, int n_planes, float fill, void* stream);
+/* TSDFVolume.get_mesh's colours (src/fusion.py:311-319): round each index-space vertex half-to-even, read the packed colour volume
+ * [nx][ny][nz] there and unpack it to r, g, b bytes (colors: [n_verts][3] uint8). */
+int adfp_mesh_unpack_colors(const float* verts, long long n_verts, const float* color_vol, int nx, int ny, int nz,
+                            unsigned char* colors, void* stream);
 
 #ifdef __cplusplus
 }
