@@ -3386,3 +3386,207 @@ int adfp_mesh_unpack_colors(const float* verts, long long n_verts, const float* 
     ADFP_CHECK_LAUNCH();
     return 0;
 }
+
+// ---- reconstruction evaluation (adfp_recon.h) ----
+#include "adfp_recon.h"
+
+static const long long RECON_MAX_N = 0x7fffffffll - ADFP_RS_TILE;       // the sort's tile arithmetic is int
+static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+static NnLayout nn_layout(long long n) {
+    NnLayout L;
+    L.n = n;
+    L.nleaves = (n + ADFP_NN_LEAF - 1) / ADFP_NN_LEAF;
+    L.P = 1; L.D = 0;
+    while (L.P < L.nleaves) { L.P <<= 1; ++L.D; }
+    L.off_orig = al256((size_t)n * 24);
+    L.off_box = L.off_orig + al256((size_t)n * 4);
+    L.bytes = L.off_box + (size_t)(2 * L.P) * 48;
+    return L;
+}
+// the Morton ordering of a cloud: bounding-box partials, codes, the stable radix sort; perm <- the sorted order
+static size_t morton_ws_bytes(long long n) {
+    return al256(ADFP_NN_BB_BLOCKS * 48) + 4 * al256((size_t)n * 4) + al256(adfp_sort_workspace_bytes(n));
+}
+static int morton_order(const double* p, int n, void* ws, const int** perm, hipStream_t st) {
+    char* w = (char*)ws;
+    double* part = (double*)w; w += al256(ADFP_NN_BB_BLOCKS * 48);
+    int* key = (int*)w; w += al256((size_t)n * 4);
+    int* val = (int*)w; w += al256((size_t)n * 4);
+    int* key2 = (int*)w; w += al256((size_t)n * 4);
+    int* val2 = (int*)w; w += al256((size_t)n * 4);
+    hipLaunchKernelGGL(k_nn_bbox_partial, dim3(ADFP_NN_BB_BLOCKS), dim3(ADFP_NN_THREADS), 0, st, p, n, part);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_nn_morton, dim3((unsigned)((n + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, p, n, part,
+                       key, val);
+    ADFP_CHECK_LAUNCH();
+    const int* kf;
+    return radix_sort_pairs(key, val, key2, val2, n, 30, (int*)w, &kf, perm, st);
+}
+
+size_t adfp_nn_index_bytes(long long n_ref) { return n_ref <= 0 || n_ref > RECON_MAX_N ? 0 : nn_layout(n_ref).bytes; }
+size_t adfp_nn_build_workspace_bytes(long long n_ref) { return n_ref <= 0 || n_ref > RECON_MAX_N ? 0 : morton_ws_bytes(n_ref); }
+
+int adfp_nn_build(const double* ref, long long n_ref, void* index, size_t index_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_ref < 0) return ADFP_E_ARG;
+    if (n_ref == 0) return 0;
+    if (!ref || !index || !workspace) return ADFP_E_ARG;
+    if (n_ref > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (index_bytes < adfp_nn_index_bytes(n_ref) || workspace_bytes < adfp_nn_build_workspace_bytes(n_ref)) return ADFP_E_WORKSPACE;
+    const NnLayout L = nn_layout(n_ref);
+    const int n = (int)n_ref;
+    hipStream_t st = (hipStream_t)stream;
+    const int* perm;
+    int rc = morton_order(ref, n, workspace, &perm, st);
+    if (rc) return rc;
+    double* sp = (double*)index;
+    int* orig = (int*)((char*)index + L.off_orig);
+    double* box = (double*)((char*)index + L.off_box);
+    const unsigned nb = (unsigned)((n + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS);
+    hipLaunchKernelGGL(k_nn_gather, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, ref, n, perm, sp, orig);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_nn_leaves, dim3((unsigned)((L.P + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, sp, n, L.P, box);
+    ADFP_CHECK_LAUNCH();
+    for (long long first = L.P >> 1; first >= 1; first >>= 1) {
+        hipLaunchKernelGGL(k_nn_level, dim3((unsigned)((first + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, first, box);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+size_t adfp_nn_query_workspace_bytes(long long n_query, int flags) {
+    if (n_query <= 0 || n_query > RECON_MAX_N || !(flags & ADFP_NN_SORT_QUERIES)) return 0;
+    return morton_ws_bytes(n_query);
+}
+
+int adfp_nn_query(const void* index, size_t index_bytes, long long n_ref, const double* query, long long n_query, const double* transform,
+                  double radius, int flags, void* workspace, size_t workspace_bytes, double* dist, int* idx, void* stream) {
+    if (n_ref < 0 || n_query < 0 || (flags & ~ADFP_NN_SORT_QUERIES)) return ADFP_E_ARG;
+    if (!(radius > 0.0)) return ADFP_E_ARG;                                // NaN, zero or negative
+    if (n_query == 0) return 0;
+    if (n_ref == 0 || !index || !query || !dist || !idx) return ADFP_E_ARG;
+    if ((flags & ADFP_NN_SORT_QUERIES) && !workspace) return ADFP_E_ARG;
+    if (n_ref > RECON_MAX_N || n_query > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (index_bytes < adfp_nn_index_bytes(n_ref) || workspace_bytes < adfp_nn_query_workspace_bytes(n_query, flags)) return ADFP_E_WORKSPACE;
+    const NnLayout L = nn_layout(n_ref);
+    hipStream_t st = (hipStream_t)stream;
+    NnQueryArgs a;
+    a.sp = (const double*)index;
+    a.orig = (const int*)((const char*)index + L.off_orig);
+    a.box = (const double*)((const char*)index + L.off_box);
+    a.n_ref = (int)n_ref; a.P = L.P; a.D = L.D;
+    a.q = query; a.nq = (int)n_query; a.order = nullptr;
+    a.has_t = transform != nullptr;
+    for (int k = 0; k < 12; ++k) a.t[k] = transform ? transform[k] : 0.0;
+    a.best0 = radius * radius;                              // +inf stays +inf
+    a.dist = dist; a.idx = idx;
+    if (flags & ADFP_NN_SORT_QUERIES) {
+        int rc = morton_order(query, (int)n_query, workspace, &a.order, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_nn_query, dim3((unsigned)((n_query + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+static int red_blocks(long long n) {
+    const long long b = (n + ADFP_RED_THREADS - 1) / ADFP_RED_THREADS;
+    return (int)(b < 1 ? 1 : (b > ADFP_RED_MAX_BLOCKS ? ADFP_RED_MAX_BLOCKS : b));
+}
+size_t adfp_recon_reduce_workspace_bytes(long long n) {
+    if (n < 0 || n > RECON_MAX_N) return 0;
+    return (size_t)red_blocks(n) * ADFP_ICP_MOMENTS * 8;
+}
+
+int adfp_nn_metric_sums(const double* dist, long long n, double threshold, void* workspace, size_t workspace_bytes, double* out, void* stream) {
+    if (n < 0 || !out || !workspace || (n > 0 && !dist)) return ADFP_E_ARG;
+    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_recon_reduce_workspace_bytes(n)) return ADFP_E_WORKSPACE;
+    MetricArgs a;
+    a.d = dist; a.n = (int)n; a.th = threshold; a.nblk = red_blocks(n); a.part = (double*)workspace; a.out = out;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_metric_partial, dim3((unsigned)a.nblk), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_red_final<2>, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a.part, a.nblk, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_icp_moments(const double* src, long long n_src, const double* transform, const double* origin, const double* tgt, long long n_tgt,
+                     const int* idx, void* workspace, size_t workspace_bytes, double* out, void* stream) {
+    if (n_src < 0 || n_tgt < 0 || !transform || !origin || !out || !workspace) return ADFP_E_ARG;
+    if (n_src > 0 && (!src || !idx || (n_tgt > 0 && !tgt))) return ADFP_E_ARG;
+    if (n_src > RECON_MAX_N || n_tgt > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_recon_reduce_workspace_bytes(n_src)) return ADFP_E_WORKSPACE;
+    IcpArgs a;
+    a.src = src; a.n_src = (int)n_src; a.tgt = tgt; a.n_tgt = (int)n_tgt; a.idx = idx;
+    for (int k = 0; k < 12; ++k) a.t[k] = transform[k];
+    for (int k = 0; k < 3; ++k) a.org[k] = origin[k];
+    a.nblk = red_blocks(n_src); a.part = (double*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_icp_partial, dim3((unsigned)a.nblk), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_red_final<ADFP_ICP_MOMENTS>, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a.part, a.nblk, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+static long long scan_tiles(long long n_faces) { return (n_faces + ADFP_SCAN_TILE - 1) / ADFP_SCAN_TILE; }
+size_t adfp_sample_surface_workspace_bytes(long long n_faces) {
+    if (n_faces <= 0 || n_faces > RECON_MAX_N) return 0;
+    return al256((size_t)n_faces * 8) + (size_t)(2 * scan_tiles(n_faces) + 1) * 8;
+}
+
+int adfp_sample_surface(const double* verts, long long n_verts, const int* faces, long long n_faces, const double* u_face, const double* u_bary,
+                        long long count, void* workspace, size_t workspace_bytes, double* points, int* face_index, void* stream) {
+    if (n_verts < 0 || n_faces < 0 || count < 0) return ADFP_E_ARG;
+    if (count == 0) return 0;
+    if (n_faces == 0 || n_verts == 0 || !verts || !faces || !u_face || !u_bary || !workspace || !points || !face_index) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N || count > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_sample_surface_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    SurfSampleArgs a;
+    a.v = verts; a.nv = (int)n_verts; a.f = faces; a.nf = (int)n_faces;
+    a.u_face = u_face; a.u_bary = u_bary; a.count = (int)count;
+    a.cum = (double*)workspace;
+    a.tile_sum = (double*)((char*)workspace + al256((size_t)n_faces * 8));
+    a.ntiles = (int)scan_tiles(n_faces);
+    a.tile_max = a.tile_sum + a.ntiles + 1;
+    a.pts = points; a.face_index = face_index;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_area_tiles, dim3((unsigned)a.ntiles), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_area_tile_scan, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_area_apply, dim3((unsigned)a.ntiles), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_area_tile_max, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sample, dim3((unsigned)((count + ADFP_RED_THREADS - 1) / ADFP_RED_THREADS)), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_cull_vertices(const double* verts, long long n_verts, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
+                       int W, int H, unsigned char* seen, void* stream) {
+    if (n_verts < 0 || n_poses < 0) return ADFP_E_ARG;
+    if (n_verts == 0) return 0;
+    if (!verts || !seen || (n_poses > 0 && !w2c)) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
+    CullArgs a;
+    a.v = verts; a.nv = (int)n_verts; a.w2c = w2c; a.np = (int)n_poses;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.seen = seen;
+    hipLaunchKernelGGL(k_cull_seen, dim3((unsigned)((n_verts + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0,
+                       (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_cull_faces(const unsigned char* seen, long long n_verts, const int* faces, long long n_faces, unsigned char* keep, void* stream) {
+    if (n_verts < 0 || n_faces < 0) return ADFP_E_ARG;
+    if (n_faces == 0) return 0;
+    if (!faces || !keep || (n_verts > 0 && !seen)) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_cull_faces, dim3((unsigned)((n_faces + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0,
+                       (hipStream_t)stream, seen, (int)n_verts, faces, (int)n_faces, keep);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}

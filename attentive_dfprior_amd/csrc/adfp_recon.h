@@ -1,0 +1,505 @@
+// adfp_recon.h -- reconstruction evaluation on the device (src/tools/eval_recon.py and src/tools/cull_mesh.py of the reference):
+//
+//   exact nearest neighbour (f64)   a Morton-ordered leaf sequence of ADFP_NN_LEAF points, an implicit complete binary tree of
+//                                   leaf boxes over it (node k has children 2k, 2k+1; padding leaves carry inverted boxes), and a
+//                                   stackless query: one lane per query point, a 32-bit trail of "sibling done" bits
+//   deterministic reductions (f64)  per-workgroup partials over a grid that depends on n only, then one fixed-order pass: the
+//                                   metric sums and the 17 ICP moments; no float atomics
+//   surface sampling (f64)          trimesh.sample.sample_surface on caller-drawn uniforms: areas, a fixed-order inclusive scan,
+//                                   searchsorted(side='left'), the folded barycentric pair
+//   frustum culling (f32)           cull_mesh.py:49-75 over every pose in one launch, the poses staged through LDS in chunks
+//
+// The library is built -ffp-contract=off: every squared distance is ((dx*dx + dy*dy) + dz*dz) with separate roundings, the
+// arithmetic of scipy's cKDTree (sqeuclidean_distance_double for m = 3).
+#pragma once
+#include "adfp_device.h"
+
+#ifndef ADFP_NN_LEAF
+#define ADFP_NN_LEAF 16            // points per leaf: 200 k x 200 k query 2.9 ms, against 4.0 ms with 32 (tools/recon_bench.py)
+#endif
+#define ADFP_NN_THREADS 256
+#define ADFP_NN_BB_BLOCKS 256      // workgroups of the bounding-box pass (fixed: the partials are reduced by every Morton workgroup)
+#define ADFP_RED_THREADS 256
+#define ADFP_RED_MAX_BLOCKS 1024   // partials of a reduction: min(ceil(n / 256), 1024) workgroups, a function of n alone
+#define ADFP_SCAN_TILE 2048        // elements per workgroup of the area scan (256 threads x 8)
+#define ADFP_CULL_CHUNK 256        // poses per LDS stage of the cull
+
+struct NnLayout {                  // where the pieces of an index live; the same arithmetic on both sides of the ABI
+    long long n; long long nleaves; long long P; int D;
+    size_t off_orig, off_box, bytes;
+};
+
+// squared distance of (x, y, z) to an axis-aligned box [lo, hi]; +inf for an inverted (empty) box.  Never above the squared
+// distance, computed the same way, to any point inside the box: rounding is monotone.
+ADFP_DEV double nn_box_d2(const double* b, double x, double y, double z) {
+    const double dx = fmax(fmax(b[0] - x, x - b[3]), 0.0);
+    const double dy = fmax(fmax(b[1] - y, y - b[4]), 0.0);
+    const double dz = fmax(fmax(b[2] - z, z - b[5]), 0.0);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+ADFP_DEV unsigned nn_spread10(unsigned v) {       // 10 bits -> every third bit
+    v &= 0x3ffu;
+    v = (v | (v << 16)) & 0x030000ffu;
+    v = (v | (v << 8)) & 0x0300f00fu;
+    v = (v | (v << 4)) & 0x030c30c3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+
+// per-workgroup bounding boxes: part[6 * b + (0..5)] = (lo xyz, hi xyz) of the points b, b + NB, ... (grid-stride)
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_bbox_partial(const double* __restrict__ p, int n, double* __restrict__ part) {
+    __shared__ double s[6][ADFP_NN_THREADS];
+    double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x; i < n; i += ADFP_NN_BB_BLOCKS * ADFP_NN_THREADS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double v = p[3 * (long long)i + c];
+            m[c] = fmin(m[c], v);
+            m[3 + c] = fmax(m[3 + c], v);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) s[c][threadIdx.x] = m[c];
+    __syncthreads();
+    for (int h = ADFP_NN_THREADS / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                s[c][threadIdx.x] = fmin(s[c][threadIdx.x], s[c][threadIdx.x + h]);
+                s[3 + c][threadIdx.x] = fmax(s[3 + c][threadIdx.x], s[3 + c][threadIdx.x + h]);
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) part[6 * blockIdx.x + threadIdx.x] = s[threadIdx.x][0];
+}
+
+// every workgroup folds the ADFP_NN_BB_BLOCKS partial boxes itself (no host round trip, no extra launch), then writes the 30-bit
+// Morton code of its points on a 1024^3 lattice over the box, and the identity permutation for the sort
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_morton(const double* __restrict__ p, int n, const double* __restrict__ part,
+                                                                int* __restrict__ key, int* __restrict__ val) {
+    static_assert(ADFP_NN_BB_BLOCKS == ADFP_NN_THREADS, "one partial box per thread");
+    __shared__ double s[6][ADFP_NN_THREADS];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) s[c][threadIdx.x] = part[6 * threadIdx.x + c];
+    __syncthreads();
+    for (int h = ADFP_NN_THREADS / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                s[c][threadIdx.x] = fmin(s[c][threadIdx.x], s[c][threadIdx.x + h]);
+                s[3 + c][threadIdx.x] = fmax(s[3 + c][threadIdx.x], s[3 + c][threadIdx.x + h]);
+            }
+        }
+        __syncthreads();
+    }
+    const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (i >= n) return;
+    unsigned code = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double lo = s[c][0], ext = s[3 + c][0] - lo;
+        double t = ext > 0.0 ? (p[3 * (long long)i + c] - lo) * (1024.0 / ext) : 0.0;
+        t = fmin(fmax(t, 0.0), 1023.0);                    // NaN -> 0 (fmax), the top edge -> the last cell
+        code |= nn_spread10((unsigned)t) << c;
+    }
+    key[i] = (int)code;
+    val[i] = i;
+}
+
+// the sorted points (AoS f64) and their original indices
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_gather(const double* __restrict__ p, int n, const int* __restrict__ perm,
+                                                                double* __restrict__ sp, int* __restrict__ orig) {
+    const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int j = perm[i];
+    sp[3 * (long long)i] = p[3 * (long long)j];
+    sp[3 * (long long)i + 1] = p[3 * (long long)j + 1];
+    sp[3 * (long long)i + 2] = p[3 * (long long)j + 2];
+    orig[i] = j;
+}
+
+// leaf j of [0, P): the box of sorted points [j B, min(j B + B, n)), inverted when empty; written at node P + j
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_leaves(const double* __restrict__ sp, int n, long long P, double* __restrict__ box) {
+    const long long j = (long long)blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (j >= P) return;
+    double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    const long long a = j * ADFP_NN_LEAF, e = a + ADFP_NN_LEAF < n ? a + ADFP_NN_LEAF : n;
+    for (long long s = a; s < e; ++s) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double v = sp[3 * s + c];
+            m[c] = fmin(m[c], v);
+            m[3 + c] = fmax(m[3 + c], v);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) box[6 * (P + j) + c] = m[c];
+}
+
+// one level of the tree: nodes [first, 2 first) = the union of their two children
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_level(long long first, double* __restrict__ box) {
+    const long long k = first + (long long)blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (k >= 2 * first) return;
+    const double* a = box + 12 * k;                       // children 2k and 2k + 1 are adjacent
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        box[6 * k + c] = fmin(a[c], a[6 + c]);
+        box[6 * k + 3 + c] = fmax(a[3 + c], a[9 + c]);
+    }
+}
+
+struct NnQueryArgs {
+    const double* sp; const int* orig; const double* box; int n_ref; long long P; int D;
+    const double* q; int nq; const int* order;            // order: lane i takes query order[i] (Morton order), or NULL
+    int has_t; double t[12];                               // optional 3x4 row-major transform of the queries
+    double best0;                                          // r^2 (radius) or +inf
+    double* dist; int* idx;
+};
+
+// One lane, one query.  Walks the implicit tree without a stack: `trail` bit d = the sibling of the current node at depth d is
+// done (visited or pruned); descend into the nearer child first, prune a box whose squared distance is >= the best so far;
+// on the way up, climb past every level whose bit is set, then step to the sibling and re-test its box against the best.
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_query(NnQueryArgs a) {
+    const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (i >= a.nq) return;
+    const int qi = a.order ? a.order[i] : i;
+    double x = a.q[3 * (long long)qi], y = a.q[3 * (long long)qi + 1], z = a.q[3 * (long long)qi + 2];
+    if (a.has_t) {
+        const double tx = ((a.t[0] * x + a.t[1] * y) + a.t[2] * z) + a.t[3];
+        const double ty = ((a.t[4] * x + a.t[5] * y) + a.t[6] * z) + a.t[7];
+        const double tz = ((a.t[8] * x + a.t[9] * y) + a.t[10] * z) + a.t[11];
+        x = tx; y = ty; z = tz;
+    }
+    double best = a.best0;
+    long long bi = -1;
+    unsigned long long k = 1;
+    int depth = 0;
+    unsigned trail = 0;
+    bool alive = nn_box_d2(a.box + 6, x, y, z) < best;
+    while (alive) {
+        bool up = true;
+        if (depth == a.D) {                                          // a leaf: scan its points
+            const long long s0 = (long long)(k - (unsigned long long)a.P) * ADFP_NN_LEAF;
+            const long long s1 = s0 + ADFP_NN_LEAF < a.n_ref ? s0 + ADFP_NN_LEAF : a.n_ref;
+            for (long long s = s0; s < s1; ++s) {
+                const double dx = a.sp[3 * s] - x, dy = a.sp[3 * s + 1] - y, dz = a.sp[3 * s + 2] - z;
+                const double d = (dx * dx + dy * dy) + dz * dz;
+                if (d < best) { best = d; bi = s; }
+            }
+        } else {
+            const double d0 = nn_box_d2(a.box + 12 * k, x, y, z);
+            const double d1 = nn_box_d2(a.box + 12 * k + 6, x, y, z);
+            const bool first = d0 <= d1;
+            const double dn = first ? d0 : d1, df = first ? d1 : d0;
+            if (dn < best) {
+                k = 2 * k + (first ? 0 : 1);
+                ++depth;
+                trail = df < best ? (trail & ~(1u << depth)) : (trail | (1u << depth));
+                up = false;
+            }
+        }
+        if (up) {
+            for (;;) {
+                while (depth > 0 && ((trail >> depth) & 1u)) { k >>= 1; --depth; }
+                if (depth == 0) { alive = false; break; }
+                k ^= 1ull;
+                trail |= 1u << depth;
+                if (nn_box_d2(a.box + 6 * k, x, y, z) < best) break;
+            }
+        }
+    }
+    a.dist[qi] = bi >= 0 ? sqrt(best) : INFINITY;
+    a.idx[qi] = bi >= 0 ? a.orig[bi] : -1;
+}
+
+// ---- deterministic f64 reductions ----
+// a fixed-shape sum over the workgroup: wave shuffles in a fixed pattern, then the four wave sums in order
+ADFP_DEV double red_block_sum(double v, double* s_wave) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();                                       // s_wave may still be read from the previous call
+    if (lane == 0) s_wave[w] = v;
+    __syncthreads();
+    return ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+struct MetricArgs { const double* d; int n; double th; int nblk; double* part; double* out; };
+
+// partial b: sum of d and count of d < th over elements b * 256 + t + k * (nblk * 256)
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_metric_partial(MetricArgs a) {
+    __shared__ double s_wave[ADFP_RED_THREADS / 64];
+    double sum = 0.0, cnt = 0.0;
+    for (int i = blockIdx.x * ADFP_RED_THREADS + threadIdx.x; i < a.n; i += a.nblk * ADFP_RED_THREADS) {
+        const double d = a.d[i];
+        sum += d;
+        cnt += d < a.th ? 1.0 : 0.0;                       // exact: whole numbers far below 2^53
+    }
+    sum = red_block_sum(sum, s_wave);
+    cnt = red_block_sum(cnt, s_wave);
+    if (threadIdx.x == 0) { a.part[2 * blockIdx.x] = sum; a.part[2 * blockIdx.x + 1] = cnt; }
+}
+
+// the fixed-order pass over the partials of a reduction of `width` doubles each: out[c] = sum_b part[width b + c]
+template <int WIDTH>
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_red_final(const double* __restrict__ part, int nblk, double* __restrict__ out) {
+    __shared__ double s_wave[ADFP_RED_THREADS / 64];
+    for (int c = 0; c < WIDTH; ++c) {
+        double v = 0.0;
+        for (int b = threadIdx.x; b < nblk; b += ADFP_RED_THREADS) v += part[WIDTH * b + c];
+        v = red_block_sum(v, s_wave);
+        if (threadIdx.x == 0) out[c] = v;
+    }
+}
+
+#define ADFP_ICP_MOMENTS 17
+struct IcpArgs {
+    const double* src; int n_src; double t[12]; double org[3];
+    const double* tgt; int n_tgt; const int* idx;
+    int nblk; double* part;
+};
+
+// the ICP moments over correspondences i (idx[i] in [0, n_tgt)): count, sum d^2, sum p, sum q, sum p q^T (row-major), where
+// p = T src_i - org, q = tgt_idx[i] - org and d^2 is the query's squared distance of T src_i to tgt_idx[i]
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_icp_partial(IcpArgs a) {
+    __shared__ double s_wave[ADFP_RED_THREADS / 64];
+    double m[ADFP_ICP_MOMENTS];
+#pragma unroll
+    for (int c = 0; c < ADFP_ICP_MOMENTS; ++c) m[c] = 0.0;
+    for (int i = blockIdx.x * ADFP_RED_THREADS + threadIdx.x; i < a.n_src; i += a.nblk * ADFP_RED_THREADS) {
+        const int j = a.idx[i];
+        if (j < 0 || j >= a.n_tgt) continue;
+        const double x = a.src[3 * (long long)i], y = a.src[3 * (long long)i + 1], z = a.src[3 * (long long)i + 2];
+        const double px = ((a.t[0] * x + a.t[1] * y) + a.t[2] * z) + a.t[3];
+        const double py = ((a.t[4] * x + a.t[5] * y) + a.t[6] * z) + a.t[7];
+        const double pz = ((a.t[8] * x + a.t[9] * y) + a.t[10] * z) + a.t[11];
+        const double qx = a.tgt[3 * (long long)j], qy = a.tgt[3 * (long long)j + 1], qz = a.tgt[3 * (long long)j + 2];
+        const double dx = qx - px, dy = qy - py, dz = qz - pz;
+        const double p[3] = {px - a.org[0], py - a.org[1], pz - a.org[2]};
+        const double q[3] = {qx - a.org[0], qy - a.org[1], qz - a.org[2]};
+        m[0] += 1.0;
+        m[1] += (dx * dx + dy * dy) + dz * dz;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { m[2 + c] += p[c]; m[5 + c] += q[c]; }
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[8 + 3 * r + c] += p[r] * q[c];
+    }
+#pragma unroll
+    for (int c = 0; c < ADFP_ICP_MOMENTS; ++c) {
+        const double v = red_block_sum(m[c], s_wave);
+        if (threadIdx.x == 0) a.part[ADFP_ICP_MOMENTS * blockIdx.x + c] = v;
+    }
+}
+
+// ---- area-weighted surface sampling ----
+struct SurfSampleArgs {
+    const double* v; int nv; const int* f; int nf;
+    const double* u_face; const double* u_bary; int count;
+    double* cum; double* tile_sum; double* tile_max; int ntiles;
+    double* pts; int* face_index;
+};
+
+// area of face i: |cross(v1 - v0, v2 - v0)| / 2 (trimesh.triangles.area); a face with an index out of range has area 0
+ADFP_DEV double tri_area(const SurfSampleArgs& a, int i) {
+    const int i0 = a.f[3 * (long long)i], i1 = a.f[3 * (long long)i + 1], i2 = a.f[3 * (long long)i + 2];
+    if ((unsigned)i0 >= (unsigned)a.nv || (unsigned)i1 >= (unsigned)a.nv || (unsigned)i2 >= (unsigned)a.nv) return 0.0;
+    const double* v0 = a.v + 3 * (long long)i0; const double* v1 = a.v + 3 * (long long)i1; const double* v2 = a.v + 3 * (long long)i2;
+    const double ax = v1[0] - v0[0], ay = v1[1] - v0[1], az = v1[2] - v0[2];
+    const double bx = v2[0] - v0[0], by = v2[1] - v0[1], bz = v2[2] - v0[2];
+    const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+    return sqrt((cx * cx + cy * cy) + cz * cz) * 0.5;
+}
+
+// tile t: the sum of its ADFP_SCAN_TILE areas, thread r summing its 8 consecutive ones, then the workgroup in a fixed tree
+ADFP_DEV double scan_block_inclusive(double v, double* s) {      // Hillis-Steele over the 256 thread values, fixed order
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < ADFP_RED_THREADS; o <<= 1) {
+        const double add = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0.0;
+        __syncthreads();
+        v += add;
+        s[threadIdx.x] = v;
+        __syncthreads();
+    }
+    return v;
+}
+
+#define ADFP_SCAN_PER_THREAD (ADFP_SCAN_TILE / ADFP_RED_THREADS)
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_area_tiles(SurfSampleArgs a) {
+    __shared__ double s[ADFP_RED_THREADS];
+    const long long base = (long long)blockIdx.x * ADFP_SCAN_TILE + (long long)threadIdx.x * ADFP_SCAN_PER_THREAD;
+    double v = 0.0;
+    for (int k = 0; k < ADFP_SCAN_PER_THREAD; ++k) {
+        const long long i = base + k;
+        if (i < a.nf) {
+            const double ar = tri_area(a, (int)i);
+            a.cum[i] = ar;
+            v += ar;
+        }
+    }
+    v = scan_block_inclusive(v, s);
+    if (threadIdx.x == ADFP_RED_THREADS - 1) a.tile_sum[blockIdx.x] = v;
+}
+
+// one workgroup: exclusive prefix of the tile sums, in chunks of 256 with a carried total; tile_sum[ntiles] = the total area
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_area_tile_scan(SurfSampleArgs a) {
+    __shared__ double s[ADFP_RED_THREADS];
+    double carry = 0.0;
+    for (int c0 = 0; c0 < a.ntiles; c0 += ADFP_RED_THREADS) {
+        const int t = c0 + threadIdx.x;
+        const double v = t < a.ntiles ? a.tile_sum[t] : 0.0;
+        const double inc = scan_block_inclusive(v, s);
+        if (t < a.ntiles) a.tile_sum[t] = carry + (inc - v);      // exclusive
+        const double last = s[ADFP_RED_THREADS - 1];
+        __syncthreads();
+        carry += last;
+    }
+    if (threadIdx.x == 0) a.tile_sum[a.ntiles] = carry;
+}
+
+// within each tile: cum[i] = tile prefix + thread prefix + the running sum of the thread's own areas
+ADFP_DEV double scan_block_max_inclusive(double v, double* s) {  // the same walk with fmax: exact, so order does not matter
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < ADFP_RED_THREADS; o <<= 1) {
+        const double other = (int)threadIdx.x >= o ? s[threadIdx.x - o] : -INFINITY;
+        __syncthreads();
+        v = fmax(v, other);
+        s[threadIdx.x] = v;
+        __syncthreads();
+    }
+    return v;
+}
+
+// within each tile: cum[i] = tile prefix + thread prefix + the running sum of the thread's own areas.  A thread's running sum never
+// decreases (areas are >= 0), but its starting prefix comes from a differently rounded scan and can lie an ulp or so below where
+// the previous thread ended.  So every value is raised to the largest value before it in the tile (a max-scan, exact), and the
+// tile's last value goes to tile_max for the same fix across tiles (k_area_tile_max, applied on read by k_sample): the cumulative
+// sums the search sees never decrease, and searchsorted(side='left') keeps its meaning at every boundary.
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_area_apply(SurfSampleArgs a) {
+    __shared__ double s[ADFP_RED_THREADS];
+    const long long base = (long long)blockIdx.x * ADFP_SCAN_TILE + (long long)threadIdx.x * ADFP_SCAN_PER_THREAD;
+    double v = 0.0;
+    for (int k = 0; k < ADFP_SCAN_PER_THREAD; ++k) {
+        const long long i = base + k;
+        if (i < a.nf) v += a.cum[i];
+    }
+    const double inc = scan_block_inclusive(v, s);
+    double run = a.tile_sum[blockIdx.x] + (inc - v);
+    for (int k = 0; k < ADFP_SCAN_PER_THREAD; ++k) {
+        const long long i = base + k;
+        if (i < a.nf) { run += a.cum[i]; a.cum[i] = run; }
+    }
+    __syncthreads();                                       // s is reused by the max-scan
+    const double incmax = scan_block_max_inclusive(run, s);
+    const double before = threadIdx.x > 0 ? s[threadIdx.x - 1] : -INFINITY;
+    for (int k = 0; k < ADFP_SCAN_PER_THREAD; ++k) {
+        const long long i = base + k;
+        if (i < a.nf) a.cum[i] = fmax(a.cum[i], before);
+    }
+    if (threadIdx.x == ADFP_RED_THREADS - 1) a.tile_max[blockIdx.x] = incmax;
+}
+
+// one workgroup: tile_max[t] <- the largest cumulative value of the tiles before t (-inf for the first), in chunks of 256 with a
+// carried maximum
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_area_tile_max(SurfSampleArgs a) {
+    __shared__ double s[ADFP_RED_THREADS];
+    double carry = -INFINITY;
+    for (int c0 = 0; c0 < a.ntiles; c0 += ADFP_RED_THREADS) {
+        const int t = c0 + threadIdx.x;
+        const double v = t < a.ntiles ? a.tile_max[t] : -INFINITY;
+        scan_block_max_inclusive(v, s);
+        const double before = fmax(carry, threadIdx.x > 0 ? s[threadIdx.x - 1] : -INFINITY);
+        const double last = s[ADFP_RED_THREADS - 1];
+        __syncthreads();
+        if (t < a.ntiles) a.tile_max[t] = before;
+        carry = fmax(carry, last);
+    }
+}
+
+// the non-decreasing cumulative sum the search reads
+ADFP_DEV double cum_at(const SurfSampleArgs& a, int i) { return fmax(a.cum[i], a.tile_max[i / ADFP_SCAN_TILE]); }
+
+// draw i: face = first f with cum[f] >= u_face[i] * total (searchsorted side='left'); (a, b) = u_bary[i]; if a + b > 1 both
+// minus 1, then absolute values; point = (a (v1 - v0) + b (v2 - v0)) + v0 (trimesh's order of operations)
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_sample(SurfSampleArgs a) {
+    const int i = blockIdx.x * ADFP_RED_THREADS + threadIdx.x;
+    if (i >= a.count) return;
+    const double u = a.u_face[i] * cum_at(a, a.nf - 1);      // weight_cum[-1], as trimesh scales the draw
+    int lo = 0, hi = a.nf;                                 // first index in [lo, hi) with cum >= u; nf when none
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (cum_at(a, mid) < u) lo = mid + 1; else hi = mid;
+    }
+    const int fi = lo < a.nf ? lo : a.nf - 1;
+    double ra = a.u_bary[2 * (long long)i], rb = a.u_bary[2 * (long long)i + 1];
+    if (ra + rb > 1.0) { ra -= 1.0; rb -= 1.0; }
+    ra = fabs(ra); rb = fabs(rb);
+    const int i0 = a.f[3 * (long long)fi], i1 = a.f[3 * (long long)fi + 1], i2 = a.f[3 * (long long)fi + 2];
+    double* o = a.pts + 3 * (long long)i;
+    if ((unsigned)i0 >= (unsigned)a.nv || (unsigned)i1 >= (unsigned)a.nv || (unsigned)i2 >= (unsigned)a.nv) {
+        o[0] = o[1] = o[2] = NAN;                          // only reachable when every face is degenerate or out of range
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double v0 = a.v[3 * (long long)i0 + c];
+            o[c] = (ra * (a.v[3 * (long long)i1 + c] - v0) + rb * (a.v[3 * (long long)i2 + c] - v0)) + v0;
+        }
+    }
+    a.face_index[i] = fi;
+}
+
+// ---- frustum culling ----
+struct CullArgs {
+    const double* v; int nv; const float* w2c; int np;     // w2c: [np][12], the top three rows of inv(c2w) (f32)
+    float fx, fy, cx, cy, W, H;
+    unsigned char* seen;
+};
+
+// seen[i] = 1 iff some pose projects vertex i into the image: cam = w2c [p, 1], cam.x *= -1, uv = K cam, z = uv.z + 1e-5,
+// uv /= z, 0 <= -z && 0 < u < W && 0 < v < H (cull_mesh.py:49-71, f32 as the reference computes it)
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_cull_seen(CullArgs a) {
+    __shared__ float s_pose[ADFP_CULL_CHUNK * 12];
+    const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    const bool on = i < a.nv;
+    const float x = on ? (float)a.v[3 * (long long)i] : 0.f;
+    const float y = on ? (float)a.v[3 * (long long)i + 1] : 0.f;
+    const float z = on ? (float)a.v[3 * (long long)i + 2] : 0.f;
+    bool seen = false;
+    for (int p0 = 0; p0 < a.np; p0 += ADFP_CULL_CHUNK) {
+        const int m = a.np - p0 < ADFP_CULL_CHUNK ? a.np - p0 : ADFP_CULL_CHUNK;
+        __syncthreads();
+        for (int e = threadIdx.x; e < 12 * m; e += ADFP_NN_THREADS) s_pose[e] = a.w2c[12 * (long long)p0 + e];
+        __syncthreads();
+        if (!on || seen) continue;
+        for (int k = 0; k < m; ++k) {
+            const float* w = s_pose + 12 * k;
+            const float X = -(((w[0] * x + w[1] * y) + w[2] * z) + w[3]);
+            const float Y = ((w[4] * x + w[5] * y) + w[6] * z) + w[7];
+            const float Z = ((w[8] * x + w[9] * y) + w[10] * z) + w[11];
+            const float zz = Z + 1e-5f;
+            const float u = (a.fx * X + a.cx * Z) / zz;
+            const float v = (a.fy * Y + a.cy * Z) / zz;
+            if (0.f <= -zz && u < a.W && u > 0.f && v < a.H && v > 0.f) { seen = true; break; }
+        }
+    }
+    if (on) a.seen[i] = seen ? 1 : 0;
+}
+
+// keep[f] = 1 unless all three vertices of face f are unseen (cull_mesh.py:72-74); an out-of-range index counts as unseen
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_cull_faces(const unsigned char* __restrict__ seen, int nv, const int* __restrict__ f,
+                                                                 int nf, unsigned char* __restrict__ keep) {
+    const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (i >= nf) return;
+    unsigned char k = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int j = f[3 * (long long)i + c];
+        k |= ((unsigned)j < (unsigned)nv) ? seen[j] : (unsigned char)0;
+    }
+    keep[i] = k;
+}

@@ -5,6 +5,7 @@ the conventions -- inside iff v > level, one vertex per crossed lattice edge, th
 vertices and triangles -- are those of include/adfp.h.
 """
 import ctypes as C
+import struct
 
 import numpy as np
 import torch
@@ -123,3 +124,190 @@ def write_ply(path, verts, faces, colors=None, normals=None, ascii=False):
             fr['n'] = 3
             fr['i'] = f
             out.write(fr.tobytes())
+
+
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+class PlyMesh(object):
+    """What read_ply returns: verts float64 [V,3]; faces int64 [F,3] (polygons fan-triangulated (0, i, i+1), as trimesh loads
+    them); normals float64 [V,3] or None; colors uint8 [V,3|4] or None; vertex: every vertex property as a structured array."""
+
+    def __init__(self, vertex, faces):
+        self.vertex = vertex
+        names = vertex.dtype.names
+        self.verts = np.stack([vertex[k].astype(np.float64) for k in 'xyz'], 1) if len(vertex) else np.zeros((0, 3))
+        self.normals = np.stack([vertex[k].astype(np.float64) for k in ('nx', 'ny', 'nz')], 1) \
+            if all(k in names for k in ('nx', 'ny', 'nz')) else None
+        cols = [k for k in ('red', 'green', 'blue', 'alpha') if k in names]
+        self.colors = np.stack([vertex[k] for k in cols], 1).astype(np.uint8) if cols[:3] == ['red', 'green', 'blue'] else None
+        self.faces = faces
+
+
+def _ply_header(data):
+    end = data.find(b'end_header')
+    if not data.startswith(b'ply') or end < 0:
+        raise ValueError('not a PLY file')
+    nl = data.index(b'\n', end)
+    lines = data[:nl].decode('ascii').replace('\r', '').split('\n')
+    fmt, elements = None, []
+    for line in lines[1:]:
+        w = line.split()
+        if not w or w[0] in ('comment', 'obj_info', 'end_header'):
+            continue
+        if w[0] == 'format':
+            fmt = w[1]
+        elif w[0] == 'element':
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == 'property':
+            if w[1] == 'list':
+                elements[-1][2].append((w[4], _PLY_TYPES[w[2]], _PLY_TYPES[w[3]]))
+            else:
+                elements[-1][2].append((w[2], _PLY_TYPES[w[1]], None))
+    if fmt not in ('ascii', 'binary_little_endian', 'binary_big_endian'):
+        raise ValueError(f'PLY format {fmt!r} is not supported')
+    return fmt, elements, nl + 1
+
+
+def _ply_binary_element(body, off, count, props, endian):
+    """-> (dict name -> array (scalars) or list of arrays (lists), new offset)."""
+    if all(lt is None for _, _, lt in props):
+        dt = np.dtype([(n, endian + t) for n, t, _ in props])
+        rec = np.frombuffer(body, dtype=dt, count=count, offset=off)
+        return {n: rec[n] for n, _, _ in props}, off + dt.itemsize * count
+    if count == 0:
+        return {n: (np.zeros(0, t) if lt is None else []) for n, t, lt in props}, off
+    # fast path: every list of the element as long as the first row's
+    fields, pos = [], off
+    for n, t, lt in props:
+        if lt is None:
+            fields.append((n, endian + t))
+            pos += np.dtype(t).itemsize
+        else:
+            k = int(np.frombuffer(body, dtype=endian + t, count=1, offset=pos)[0])
+            fields.append((n + '#n', endian + t))
+            if k:
+                fields.append((n, endian + lt, (k,)))
+            pos += np.dtype(t).itemsize + k * np.dtype(lt).itemsize
+    dt = np.dtype(fields)
+    if off + dt.itemsize * count <= len(body):
+        rec = np.frombuffer(body, dtype=dt, count=count, offset=off)
+        ok = all((rec[n + '#n'] == (rec.dtype[n].shape[0] if n in rec.dtype.names else 0)).all() for n, _, lt in props if lt is not None)
+        if ok:
+            out = {}
+            for n, t, lt in props:
+                if lt is None:
+                    out[n] = rec[n]
+                else:
+                    out[n] = rec[n].reshape(count, -1) if n in rec.dtype.names else np.zeros((count, 0), lt)
+            return out, off + dt.itemsize * count
+    # mixed list lengths: one walk over the rows for the offsets (only the count fields are read), then every property is
+    # gathered with numpy; lists come back ragged, as (flat values, counts)
+    nprop = len(props)
+    isz = [np.dtype(t).itemsize for _, t, _ in props]
+    lsz = [np.dtype(lt).itemsize if lt is not None else 0 for _, _, lt in props]
+    cfmt = [endian + np.dtype(t).char if lt is not None else None for _, t, lt in props]
+    one_byte = [lt is not None and np.dtype(t).itemsize == 1 and np.dtype(t).kind == 'u' for _, t, lt in props]
+    pos_l, cnt_l = [], []
+    row = off
+    for _ in range(count):
+        for j in range(nprop):
+            pos_l.append(row)
+            if cfmt[j] is None:
+                cnt_l.append(0)
+                row += isz[j]
+            else:
+                k = body[row] if one_byte[j] else int(struct.unpack_from(cfmt[j], body, row)[0])
+                cnt_l.append(k)
+                row += isz[j] + k * lsz[j]
+    pos = np.array(pos_l, np.int64).reshape(count, nprop)
+    cnt = np.array(cnt_l, np.int64).reshape(count, nprop)
+    buf = np.frombuffer(body, dtype=np.uint8)
+    out = {}
+    for j, (n, t, lt) in enumerate(props):
+        if lt is None:
+            out[n] = buf[pos[:, j, None] + np.arange(isz[j])].copy().view(endian + t).reshape(count)
+        else:
+            c = cnt[:, j]
+            first = np.repeat(pos[:, j] + isz[j], c)
+            k = np.arange(int(c.sum())) - np.repeat(np.cumsum(c) - c, c)
+            flat = buf[(first + k * lsz[j])[:, None] + np.arange(lsz[j])].copy().view(endian + lt).reshape(-1)
+            out[n] = (flat, c)
+    return out, row
+
+
+def _ply_ascii_element(lines, start, count, props):
+    out = {n: [] for n, _, _ in props}
+    for r in range(count):
+        w = lines[start + r].split()
+        j = 0
+        for n, t, lt in props:
+            if lt is None:
+                out[n].append(w[j])
+                j += 1
+            else:
+                k = int(w[j])
+                out[n].append(np.array([float(x) for x in w[j + 1:j + 1 + k]]).astype(lt))
+                j += 1 + k
+    for n, t, lt in props:
+        if lt is None:
+            kind = np.dtype(t).kind
+            out[n] = np.array([float(x) if kind == 'f' else int(x) for x in out[n]], dtype=t)
+    return out, start + count
+
+
+def _fan(rows):
+    """Polygons (a [F,k] array, a list of index arrays or ragged (flat, counts)) -> triangles (0, i, i+1), in polygon order."""
+    if isinstance(rows, np.ndarray):
+        k = rows.shape[1]
+        if k < 3:
+            return np.zeros((0, 3), np.int64)
+        tri = np.stack([np.stack([rows[:, 0], rows[:, i], rows[:, i + 1]], 1) for i in range(1, k - 1)], 1)
+        return tri.reshape(-1, 3).astype(np.int64)
+    if isinstance(rows, tuple):
+        flat, c = rows
+    else:
+        c = np.array([len(r) for r in rows], np.int64)
+        flat = np.concatenate([np.asarray(r, np.int64) for r in rows]) if len(rows) else np.zeros(0, np.int64)
+    flat = np.asarray(flat).astype(np.int64)
+    start = np.cumsum(c) - c
+    ntri = np.maximum(c - 2, 0)
+    poly = np.repeat(np.arange(len(c)), ntri)
+    t = np.arange(int(ntri.sum())) - np.repeat(np.cumsum(ntri) - ntri, ntri) + 1
+    s0 = start[poly]
+    return np.stack([flat[s0], flat[s0 + t], flat[s0 + t + 1]], 1)
+
+
+def read_ply(path):
+    """Read a PLY mesh: ascii, binary_little_endian or binary_big_endian; any vertex properties (x y z required; nx ny nz and
+    red green blue [alpha] carried through); faces as a list property named vertex_indices or vertex_index, of any count and
+    index types.  Returns a PlyMesh.  Reads what write_ply writes and the Replica ground-truth meshes."""
+    with open(path, 'rb') as fh:
+        data = fh.read()
+    fmt, elements, off = _ply_header(data)
+    endian = {'binary_little_endian': '<', 'binary_big_endian': '>'}.get(fmt)
+    lines = data[off:].decode('ascii').replace('\r', '').split('\n') if fmt == 'ascii' else None
+    pos = 0
+    vertex, faces = None, np.zeros((0, 3), np.int64)
+    for name, count, props in elements:
+        if fmt == 'ascii':
+            vals, pos = _ply_ascii_element(lines, pos, count, props)
+        else:
+            vals, off = _ply_binary_element(data, off, count, props, endian)
+        if name == 'vertex':
+            missing = [k for k in 'xyz' if k not in vals]
+            if missing:
+                raise ValueError(f'{path}: vertex element has no {missing}')
+            scal = [(n, t) for n, t, lt in props if lt is None]
+            vertex = np.empty(count, dtype=[(n, t) for n, t in scal])
+            for n, _ in scal:
+                vertex[n] = vals[n]
+        elif name == 'face':
+            key = 'vertex_indices' if 'vertex_indices' in vals else ('vertex_index' if 'vertex_index' in vals else None)
+            if key is None:
+                raise ValueError(f'{path}: face element has no vertex_indices / vertex_index list')
+            faces = _fan(vals[key])
+    if vertex is None:
+        raise ValueError(f'{path}: no vertex element')
+    return PlyMesh(vertex, faces)

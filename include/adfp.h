@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ADFP_VERSION 132
+#define ADFP_VERSION 133
 
 /* error codes (host-detected) */
 #define ADFP_E_ARG        (-1)   /* null pointer / negative size */
@@ -748,6 +748,61 @@ int adfp_lattice_hull_fill(float* values, const float* xs, const float* ys, cons
  * [nx][ny][nz] there and unpack it to r, g, b bytes (colors: [n_verts][3] uint8). */
 int adfp_mesh_unpack_colors(const float* verts, long long n_verts, const float* color_vol, int nx, int ny, int nz,
                             unsigned char* colors, void* stream);
+
+/* ---- reconstruction evaluation (src/tools/eval_recon.py, src/tools/cull_mesh.py) ----
+ * Counts above 2^31 - 1025 are ADFP_E_UNSUPPORTED (indices are int32 and the radix sort's tile arithmetic is int).  Every
+ * reduction is deterministic: per-workgroup partials over a grid fixed by the count, then one fixed-order pass, no float atomics,
+ * so two runs on the same inputs give the same bits. */
+
+/* Exact nearest neighbour over a reference cloud ref [n_ref][3] (f64), replacing scipy.spatial.cKDTree(ref).query
+ * (eval_recon.py:33-50) and open3d's KDTreeFlann inside registration_icp (eval_recon.py:64-66).
+ * adfp_nn_build fills `index` (adfp_nn_index_bytes(n_ref) bytes, the caller keeps it for the queries): the points in 30-bit
+ * Morton order (their bounding box reduced on the device, adfp_sort_pairs's radix sort), grouped in leaves of 16, and an implicit
+ * complete binary tree of leaf boxes (node k has children 2k, 2k+1; the leaf count is padded to a power of two with empty boxes).
+ * Workspace: adfp_nn_build_workspace_bytes(n_ref), free again when the call's work has run.  n_ref = 0 builds nothing. */
+size_t adfp_nn_index_bytes(long long n_ref);
+size_t adfp_nn_build_workspace_bytes(long long n_ref);
+int adfp_nn_build(const double* ref, long long n_ref, void* index, size_t index_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* For each query point q_i [n_query][3] (f64), transformed first by the HOST 3x4 row-major `transform` when it is not NULL
+ * (x' = ((t0 x + t1 y) + t2 z) + t3, ...): dist[i] = the Euclidean distance to the nearest reference point, idx[i] = that
+ * point's ORIGINAL index (any one of several at the same distance).  Squared distances are ((dx*dx + dy*dy) + dz*dz) in f64,
+ * cKDTree's arithmetic.  radius: only points with d^2 < radius^2 count (INFINITY: no limit); none -> idx -1, dist +inf
+ * (cKDTree's distance_upper_bound).  radius <= 0 or NaN is ADFP_E_ARG.  flags ADFP_NN_SORT_QUERIES: walk the queries in their
+ * own Morton order (workspace adfp_nn_query_workspace_bytes(n_query, flags); 0 without the flag).  n_query = 0 returns 0;
+ * n_ref = 0 with queries is ADFP_E_ARG. */
+#define ADFP_NN_SORT_QUERIES 1
+size_t adfp_nn_query_workspace_bytes(long long n_query, int flags);
+int adfp_nn_query(const void* index, size_t index_bytes, long long n_ref, const double* query, long long n_query, const double* transform,
+                  double radius, int flags, void* workspace, size_t workspace_bytes, double* dist, int* idx, void* stream);
+/* Workspace of the two reductions below: 8 * 17 * min(max(ceil(n / 256), 1), 1024) bytes for n elements. */
+size_t adfp_recon_reduce_workspace_bytes(long long n);
+/* accuracy / completion / completion_ratio (eval_recon.py:33-50): out[0] = sum of dist, out[1] = count of dist < threshold
+ * (device f64 [2]); the means are those over n. */
+int adfp_nn_metric_sums(const double* dist, long long n, double threshold, void* workspace, size_t workspace_bytes, double* out, void* stream);
+/* The moments of one point-to-point ICP step (open3d's TransformationEstimationPointToPoint, eval_recon.py:64-66) over the
+ * correspondences i with idx[i] in [0, n_tgt) (an adfp_nn_query of src under the same transform): with p = T src_i - origin,
+ * q = tgt[idx[i]] - origin, out (device f64 [17]) = count, sum d^2 (d^2 as the query computes it), sum p [3], sum q [3],
+ * sum p q^T [3][3] row-major.  transform [12] and origin [3] are HOST arrays. */
+int adfp_icp_moments(const double* src, long long n_src, const double* transform, const double* origin, const double* tgt, long long n_tgt,
+                     const int* idx, void* workspace, size_t workspace_bytes, double* out, void* stream);
+/* trimesh.sample.sample_surface(mesh, count) (eval_recon.py:115-118) on caller-drawn uniforms u_face [count], u_bary [count][2]
+ * (f64): face areas |cross(v1 - v0, v2 - v0)| / 2, their inclusive scan cum (fixed order; where the parallel scan's rounding
+ * would let cum step down by an ulp, it is held at the larger value before it, so cum never decreases), face = first f with
+ * cum[f] >= u_face * cum[F-1] (numpy searchsorted, side='left'), (a, b) = u_bary folded (a + b > 1: both minus 1, then absolute
+ * values), point = (a (v1 - v0) + b (v2 - v0)) + v0.  Out: points [count][3] f64, face_index [count] int32.  A face with an
+ * index outside [0, n_verts) has area 0.  Workspace: adfp_sample_surface_workspace_bytes(n_faces) = 8 n_faces rounded up to
+ * 256, plus 8 (2 ceil(n_faces / 2048) + 1).  count = 0 returns 0; no faces with draws is ADFP_E_ARG. */
+size_t adfp_sample_surface_workspace_bytes(long long n_faces);
+int adfp_sample_surface(const double* verts, long long n_verts, const int* faces, long long n_faces, const double* u_face, const double* u_bary,
+                        long long count, void* workspace, size_t workspace_bytes, double* points, int* face_index, void* stream);
+/* cull_mesh.py:49-71 over every pose in one launch (no workspace): seen[i] = 1 iff some pose sees vertex i.  w2c [n_poses][12]
+ * (f32, device) = the top three rows of inv(c2w) (the caller inverts in f64 and rounds to f32, as np.linalg.inv of the f32 pose
+ * does); with p the f32 rounding of verts[i] (f64): cam = w2c [p, 1], cam.x *= -1, uv = K cam, z = uv.z + 1e-5, uv /= z,
+ * seen iff 0 <= -z && 0 < u < W && 0 < v < H, all in f32. */
+int adfp_cull_vertices(const double* verts, long long n_verts, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
+                       int W, int H, unsigned char* seen, void* stream);
+/* cull_mesh.py:72-74: keep[f] = 0 iff all three vertices of face f are unseen (an index outside [0, n_verts) counts as unseen). */
+int adfp_cull_faces(const unsigned char* seen, long long n_verts, const int* faces, long long n_faces, unsigned char* keep, void* stream);
 
 #ifdef __cplusplus
 }
