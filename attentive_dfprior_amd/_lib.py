@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ADFP_LIB_PATH') or os.path.join(_HERE, 'libadfp.so')   # override: kernel A/B builds
 
-ABI_VERSION = 133                 # ADFP_VERSION of include/adfp.h this binding was written against
+ABI_VERSION = 134                 # ADFP_VERSION of include/adfp.h this binding was written against
 STATUS_F16_RANGE = 31              # ADFP_STATUS_F16_RANGE: any of the bits below
 STATUS_RANGE_BITS = {'low': 1, 'high': 2, 'color': 4, 'att': 8, 'bwd': 16}      # ADFP_STATUS_F16_RANGE_<net>
 BWD_SCATTER_IN_KERNEL = 1        # ADFP_BWD_SCATTER_IN_KERNEL
@@ -279,12 +279,24 @@ SYMBOLS = [
     ('adfp_cull_vertices', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float,
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ('adfp_cull_faces', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    ('adfp_tri_bvh_bytes', C.c_size_t, [C.c_longlong, C.c_int]),
+    ('adfp_tri_bvh_build_workspace_bytes', C.c_size_t, [C.c_longlong]),
+    ('adfp_tri_bvh_build', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
+    ('adfp_render_depth', C.c_int, [C.c_void_p, C.c_size_t, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_longlong,
+                                    C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    ('adfp_views_in_sight', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ('adfp_depth_l1_workspace_bytes', C.c_size_t, [C.c_longlong, C.c_longlong]),
+    ('adfp_depth_l1_sums', C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER
 MC_MAX_TRI = 5                         # ADFP_MC_MAX_TRI
 NN_SORT_QUERIES = 1                    # ADFP_NN_SORT_QUERIES
 ICP_MOMENTS = 17                       # adfp_icp_moments' out[]
+TRI_LEAF_DEFAULT = 4                   # ADFP_TRI_LEAF_DEFAULT
+TRI_LEAVES = (4, 8, 16)                # the leaf sizes adfp_tri_bvh_build takes
 
 _lib = None
 

@@ -3590,3 +3590,137 @@ int adfp_cull_faces(const unsigned char* seen, long long n_verts, const int* fac
     ADFP_CHECK_LAUNCH();
     return 0;
 }
+
+// ---- mesh depth rendering (adfp_raycast.h) ----
+#include "adfp_raycast.h"
+
+static bool tri_leaf_ok(int leaf) { return leaf == 4 || leaf == 8 || leaf == 16; }
+struct TriLayout { long long nleaves, P; int D; size_t off_orig, off_box, bytes; };
+static TriLayout tri_layout(long long nf, int leaf) {
+    TriLayout L;
+    L.nleaves = (nf + leaf - 1) / leaf;
+    L.P = 1; L.D = 0;
+    while (L.P < L.nleaves) { L.P <<= 1; ++L.D; }
+    L.off_orig = al256((size_t)nf * 72);
+    L.off_box = L.off_orig + al256((size_t)nf * 4);
+    L.bytes = L.off_box + (size_t)(2 * L.P) * 48;
+    return L;
+}
+
+size_t adfp_tri_bvh_bytes(long long n_faces, int leaf) {
+    return n_faces <= 0 || n_faces > RECON_MAX_N || !tri_leaf_ok(leaf) ? 0 : tri_layout(n_faces, leaf).bytes;
+}
+size_t adfp_tri_bvh_build_workspace_bytes(long long n_faces) {
+    return n_faces <= 0 || n_faces > RECON_MAX_N ? 0 : al256((size_t)n_faces * 24) + morton_ws_bytes(n_faces);
+}
+
+int adfp_tri_bvh_build(const double* verts, long long n_verts, const int* faces, long long n_faces, int leaf, void* bvh, size_t bvh_bytes,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_verts < 0 || n_faces < 0 || !tri_leaf_ok(leaf)) return ADFP_E_ARG;
+    if (n_faces == 0) return 0;
+    if (!faces || !bvh || !workspace || (n_verts > 0 && !verts)) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf) || workspace_bytes < adfp_tri_bvh_build_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    const TriLayout L = tri_layout(n_faces, leaf);
+    const int nf = (int)n_faces, nv = (int)n_verts;
+    hipStream_t st = (hipStream_t)stream;
+    double* cen = (double*)workspace;
+    const unsigned nb = (unsigned)((nf + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS);
+    hipLaunchKernelGGL(k_tri_centroids, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, verts, nv, faces, nf, cen);
+    ADFP_CHECK_LAUNCH();
+    const int* perm;
+    int rc = morton_order(cen, nf, (char*)workspace + al256((size_t)nf * 24), &perm, st);
+    if (rc) return rc;
+    double* tri = (double*)bvh;
+    int* orig = (int*)((char*)bvh + L.off_orig);
+    double* box = (double*)((char*)bvh + L.off_box);
+    hipLaunchKernelGGL(k_tri_gather, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, verts, nv, faces, nf, perm, tri, orig);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_tri_leaves, dim3((unsigned)((L.P + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, tri, nf,
+                       leaf, L.P, box);
+    ADFP_CHECK_LAUNCH();
+    for (long long first = L.P >> 1; first >= 1; first >>= 1) {
+        hipLaunchKernelGGL(k_nn_level, dim3((unsigned)((first + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, first, box);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+#define RT_MAX_SIDE 32768
+#define RT_VIEWS_PER_LAUNCH 32768                    // grid y
+int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
+                      long long n_views, int H, int W, double fx, double fy, double cx, double cy, float* depth, void* stream) {
+    if (n_faces < 0 || n_views < 0 || !tri_leaf_ok(leaf) || H <= 0 || W <= 0) return ADFP_E_ARG;
+    if (!(far > 0.0) || !(fx != 0.0) || !(fy != 0.0) || !isfinite(far) || !isfinite(fx) || !isfinite(fy) ||
+        !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    if (n_views == 0) return 0;
+    if (!depth || (n_faces > 0 && (!bvh || !c2w || !near))) return ADFP_E_ARG;
+    if (n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_faces == 0) {
+        hipError_t e = hipMemsetAsync(depth, 0, (size_t)n_views * H * W * sizeof(float), st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    const TriLayout L = tri_layout(n_faces, leaf);
+    RenderArgs a;
+    a.tri = (const double*)bvh;
+    a.box = (const double*)((const char*)bvh + L.off_box);
+    a.nf = (int)n_faces; a.leaf = leaf; a.P = L.P; a.D = L.D;
+    a.c2w = c2w; a.near = near; a.far = far;
+    a.H = H; a.W = W; a.nbx = (W + 15) / 16; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.depth = depth;
+    const unsigned nblk = (unsigned)a.nbx * (unsigned)((H + 15) / 16);
+    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
+        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
+        a.view0 = (int)v0;
+        hipLaunchKernelGGL(k_render_depth, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int adfp_views_in_sight(const double* points, long long n_points, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
+                        int W, int H, int* any, void* stream) {
+    if (n_points < 0 || n_poses < 0) return ADFP_E_ARG;
+    if (n_poses == 0) return 0;
+    if (!w2c || !any || (n_points > 0 && !points)) return ADFP_E_ARG;
+    if (n_points > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(any, 0, (size_t)n_poses * sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+    if (n_points == 0) return 0;
+    SightArgs a;
+    a.v = points; a.nv = (int)n_points; a.w2c = w2c; a.np = (int)n_poses;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.any = any;
+    hipLaunchKernelGGL(k_views_in_sight, dim3((unsigned)((n_points + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+size_t adfp_depth_l1_workspace_bytes(long long n_views, long long n_pixels) {
+    if (n_views < 0 || n_pixels < 0 || n_pixels > RECON_MAX_N || n_views > RECON_MAX_N) return 0;
+    return (size_t)n_views * red_blocks(n_pixels) * 8;
+}
+
+int adfp_depth_l1_sums(const float* a, const float* b, long long n_views, long long n_pixels, void* workspace, size_t workspace_bytes,
+                       double* out, void* stream) {
+    if (n_views < 0 || n_pixels < 0) return ADFP_E_ARG;
+    if (n_views == 0) return 0;
+    if (!out || !workspace || (n_pixels > 0 && (!a || !b))) return ADFP_E_ARG;
+    if (n_pixels > RECON_MAX_N || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_depth_l1_workspace_bytes(n_views, n_pixels)) return ADFP_E_WORKSPACE;
+    L1Args r;
+    r.a = a; r.b = b; r.n = n_pixels; r.nblk = red_blocks(n_pixels); r.part = (double*)workspace; r.out = out;
+    hipStream_t st = (hipStream_t)stream;
+    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
+        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
+        L1Args c = r;
+        c.a = a + v0 * n_pixels; c.b = b + v0 * n_pixels; c.part = r.part + v0 * r.nblk;
+        hipLaunchKernelGGL(k_l1_partial, dim3((unsigned)r.nblk, (unsigned)nv), dim3(ADFP_RED_THREADS), 0, st, c);
+        ADFP_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_l1_final, dim3((unsigned)n_views), dim3(ADFP_RED_THREADS), 0, st, r.part, r.nblk, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}

@@ -1,0 +1,239 @@
+// adfp_raycast.h -- depth rendering of triangle meshes on the device (calc_2d_metric of the reference's src/tools/eval_recon.py):
+//
+//   triangle BVH (f64)      the NN index's construction over triangles: Morton codes of the centroids (adfp_recon.h's box and
+//                           code kernels, the radix sort), leaves of `leaf` triangles holding their nine vertex coordinates and
+//                           original face indices, an implicit complete binary tree of leaf boxes (padding leaves inverted)
+//   depth render (f64)      one lane per pixel, a wave per 8x8 tile, four tiles per workgroup, views along grid y; the stackless
+//                           trail-bit walk of k_nn_query ordered by entry t; Woop, Benthin & Wald's watertight test in f64
+//   views in sight (f32)    check_proj of eval_recon.py:70-96 for a batch of poses: k_cull_seen's test, a wave ballot per pose
+//                           and one integer atomic OR
+//   depth L1 sums (f64)     per view, sum |a - b| of two f32 depth images, reduced as k_metric_partial / k_red_final do
+//
+// The exact contract (camera, intersection, clipping, pruning) is stated in include/adfp.h; tests/depth_ref.py restates it in numpy.
+#pragma once
+#include "adfp_recon.h"
+
+// triangles per leaf: 4, 8 or 16 at run time.  ADFP_TRI_LEAF_DEFAULT (include/adfp.h) is 4: 100 views at 500 x 500 of a 1.18 M-face
+// room render in 50.6 ms with leaves of 4, 58.5 ms with 8 and 73.0 ms with 16 (tools/recon_bench.py --2d, medians)
+#define ADFP_RT_THREADS 256        // four waves: a 16 x 16 pixel block of four 8 x 8 tiles
+#define ADFP_RT_BOX_PAD 0x1p-24    // boxes grow by this times (max |mesh coordinate| + max |camera origin|) at query time
+
+// triangle i's centroid ((v0 + v1) + v2) / 3, NaN for a face with an index outside [0, nv): the box pass (fmin / fmax) skips it
+// and the Morton pass sends it to code 0
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_tri_centroids(const double* __restrict__ v, int nv, const int* __restrict__ f, int nf,
+                                                                     double* __restrict__ c) {
+    const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (i >= nf) return;
+    const int i0 = f[3 * (long long)i], i1 = f[3 * (long long)i + 1], i2 = f[3 * (long long)i + 2];
+    const bool ok = (unsigned)i0 < (unsigned)nv && (unsigned)i1 < (unsigned)nv && (unsigned)i2 < (unsigned)nv;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        c[3 * (long long)i + k] = ok ? ((v[3 * (long long)i0 + k] + v[3 * (long long)i1 + k]) + v[3 * (long long)i2 + k]) / 3.0 : NAN;
+}
+
+// the sorted triangles: tri[9 s .. 9 s + 9) = v0, v1, v2 of face perm[s] (NaN for an out-of-range face: never hit), orig[s] = perm[s]
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_tri_gather(const double* __restrict__ v, int nv, const int* __restrict__ f, int nf,
+                                                                  const int* __restrict__ perm, double* __restrict__ tri, int* __restrict__ orig) {
+    const int s = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (s >= nf) return;
+    const int j = perm[s];
+    int id[3];
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        id[c] = f[3 * (long long)j + c];
+        ok = ok && (unsigned)id[c] < (unsigned)nv;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tri[9 * (long long)s + 3 * c + k] = ok ? v[3 * (long long)id[c] + k] : NAN;
+    orig[s] = j;
+}
+
+// leaf j of [0, P): the box of the vertices of sorted triangles [j leaf, min(j leaf + leaf, nf)), inverted when it holds none
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_tri_leaves(const double* __restrict__ tri, int nf, int leaf, long long P,
+                                                                  double* __restrict__ box) {
+    const long long j = (long long)blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    if (j >= P) return;
+    double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    const long long a = j * leaf, e = a + leaf < nf ? a + leaf : nf;
+    for (long long s = a; s < e; ++s) {
+        for (int c = 0; c < 9; ++c) {                      // fmin / fmax drop the NaN of an out-of-range face
+            const double x = tri[9 * s + c];
+            m[c % 3] = fmin(m[c % 3], x);
+            m[3 + c % 3] = fmax(m[3 + c % 3], x);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) box[6 * (P + j) + c] = m[c];
+}
+
+struct RenderArgs {
+    const double* tri; const double* box; int nf; int leaf; long long P; int D;
+    const double* c2w; const double* near; double far;       // c2w [views][12] (3x4 row-major), near [views]
+    int H, W, nbx; double fx, fy, cx, cy;
+    int view0;                                                // first view of this launch
+    float* depth;                                             // [views][H][W]
+};
+
+// Does the ray o + t D meet box b, grown by pad, at some t in [near, best]?  Inverted boxes never do.  An axis with D = 0 is a
+// containment test (no 0 x inf); elsewhere the slab of each axis is [(lo - o) inv, (hi - o) inv] sorted, with finite factors.
+// *tin = the entry t.  The pad is far above the rounding of both this test and the triangle test (include/adfp.h).
+ADFP_DEV bool rt_box(const double* b, double pad, const double* o, const double* D, const double* inv, double near, double best,
+                     double* tin) {
+    if (!(b[0] <= b[3])) return false;
+    double tn = -INFINITY, tf = INFINITY;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double lo = b[c] - pad, hi = b[3 + c] + pad;
+        if (D[c] == 0.0) {
+            if (o[c] < lo || o[c] > hi) return false;
+        } else {
+            const double t0 = (lo - o[c]) * inv[c], t1 = (hi - o[c]) * inv[c];
+            tn = fmax(tn, fmin(t0, t1));
+            tf = fmin(tf, fmax(t0, t1));
+        }
+    }
+    *tin = tn;
+    return tn <= tf && tn <= best && tf >= near;
+}
+
+// One lane, one pixel (row i, col j) of view p.  d = ((j - cx) / fx, (i - cy) / fy, 1); a vertex goes to camera space as
+// cam_c = ((R0c e0 + R1c e1) + R2c e2), e = v - o; the shear A' = (Ax - dx Az, Ay - dy Az); U = Cx By - Cy Bx, V = Ax Cy - Ay Cx,
+// W = Bx Ay - By Ax; a miss when their signs are mixed or det = (U + V) + W is 0; z = ((U Az + V Bz) + W Cz) / det; the depth is
+// the least z with near <= z <= far, rounded to f32, or 0.
+__global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int bx = (int)(blockIdx.x % (unsigned)a.nbx), by = (int)(blockIdx.x / (unsigned)a.nbx);
+    const int col = bx * 16 + (w & 1) * 8 + (lane & 7);
+    const int row = by * 16 + (w >> 1) * 8 + (lane >> 3);
+    if (row >= a.H || col >= a.W) return;                   // no barrier below
+    const long long p = (long long)a.view0 + blockIdx.y;
+    const double* m = a.c2w + 12 * p;
+    double R[9], o[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = m[4 * r + c];
+        o[r] = m[4 * r + 3];
+    }
+    const double near = a.near[p], far = a.far;
+    const double dx = ((double)col - a.cx) / a.fx, dy = ((double)row - a.cy) / a.fy;
+    double Dw[3], inv[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        double t = (R[3 * r] * dx + R[3 * r + 1] * dy) + R[3 * r + 2];
+        if (fabs(t) < 1e-200) t = 0.0;                       // parallel to the axis: a containment test, never 0 x inf
+        Dw[r] = t;
+        inv[r] = t != 0.0 ? 1.0 / t : 0.0;
+    }
+    const double* rb = a.box + 6;                           // the root: the mesh's box
+    const double M = fmax(fmax(fmax(fabs(rb[0]), fabs(rb[3])), fmax(fabs(rb[1]), fabs(rb[4]))), fmax(fabs(rb[2]), fabs(rb[5])));
+    const double pad = ADFP_RT_BOX_PAD * (M + fmax(fmax(fabs(o[0]), fabs(o[1])), fabs(o[2])));
+    double best = far;
+    bool found = false;
+    unsigned long long k = 1;
+    int depth = 0;
+    unsigned trail = 0;
+    double tin;
+    bool alive = a.nf > 0 && rt_box(rb, pad, o, Dw, inv, near, best, &tin);
+    while (alive) {
+        bool up = true;
+        if (depth == a.D) {                                  // a leaf: test its triangles
+            const long long s0 = (long long)(k - (unsigned long long)a.P) * a.leaf;
+            const long long s1 = s0 + a.leaf < a.nf ? s0 + a.leaf : a.nf;
+            for (long long s = s0; s < s1; ++s) {
+                const double* t = a.tri + 9 * s;
+                double cam[9];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const double e0 = t[3 * q] - o[0], e1 = t[3 * q + 1] - o[1], e2 = t[3 * q + 2] - o[2];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) cam[3 * q + c] = (R[c] * e0 + R[3 + c] * e1) + R[6 + c] * e2;
+                }
+                const double Ax = cam[0] - dx * cam[2], Ay = cam[1] - dy * cam[2];
+                const double Bx = cam[3] - dx * cam[5], By = cam[4] - dy * cam[5];
+                const double Cx = cam[6] - dx * cam[8], Cy = cam[7] - dy * cam[8];
+                const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+                if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) continue;
+                const double det = (U + V) + W;
+                if (det == 0.0) continue;
+                const double z = ((U * cam[2] + V * cam[5]) + W * cam[8]) / det;
+                if (z >= near && z <= best) { best = z; found = true; }     // NaN (an out-of-range face) fails here
+            }
+        } else {
+            double t0, t1;
+            const bool h0 = rt_box(a.box + 12 * k, pad, o, Dw, inv, near, best, &t0);
+            const bool h1 = rt_box(a.box + 12 * k + 6, pad, o, Dw, inv, near, best, &t1);
+            if (h0 || h1) {
+                const bool first = h0 && (!h1 || t0 <= t1);
+                k = 2 * k + (first ? 0 : 1);
+                ++depth;
+                const bool other = first ? h1 : h0;
+                trail = other ? (trail & ~(1u << depth)) : (trail | (1u << depth));
+                up = false;
+            }
+        }
+        if (up) {
+            for (;;) {
+                while (depth > 0 && ((trail >> depth) & 1u)) { k >>= 1; --depth; }
+                if (depth == 0) { alive = false; break; }
+                k ^= 1ull;
+                trail |= 1u << depth;
+                if (rt_box(a.box + 6 * k, pad, o, Dw, inv, near, best, &tin)) break;
+            }
+        }
+    }
+    a.depth[(p * a.H + row) * (long long)a.W + col] = found ? (float)best : 0.f;
+}
+
+// any[p] |= 1 iff pose p projects some point into the image (k_cull_seen's f32 test, cull_mesh.py:49-71 = eval_recon.py:70-96);
+// any[] is zeroed by the entry before the launch
+struct SightArgs {
+    const double* v; int nv; const float* w2c; int np;
+    float fx, fy, cx, cy, W, H;
+    int* any;
+};
+
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_views_in_sight(SightArgs a) {
+    __shared__ float s_pose[ADFP_CULL_CHUNK * 12];
+    const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
+    const bool on = i < a.nv;
+    const float x = on ? (float)a.v[3 * (long long)i] : 0.f;
+    const float y = on ? (float)a.v[3 * (long long)i + 1] : 0.f;
+    const float z = on ? (float)a.v[3 * (long long)i + 2] : 0.f;
+    for (int p0 = 0; p0 < a.np; p0 += ADFP_CULL_CHUNK) {
+        const int m = a.np - p0 < ADFP_CULL_CHUNK ? a.np - p0 : ADFP_CULL_CHUNK;
+        __syncthreads();
+        for (int e = threadIdx.x; e < 12 * m; e += ADFP_NN_THREADS) s_pose[e] = a.w2c[12 * (long long)p0 + e];
+        __syncthreads();
+        for (int k = 0; k < m; ++k) {
+            const bool s = on && cull_sees(s_pose + 12 * k, x, y, z, a.fx, a.fy, a.cx, a.cy, a.W, a.H);
+            if (__ballot(s) && (threadIdx.x & 63) == 0) atomicOr(a.any + p0 + k, 1);
+        }
+    }
+}
+
+// per view p (grid y): partial b = sum of (double)|a - b| (the f32 difference) over pixels b * 256 + t + k * (nblk * 256)
+struct L1Args { const float* a; const float* b; long long n; int nblk; double* part; double* out; };
+
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_l1_partial(L1Args a) {
+    __shared__ double s_wave[ADFP_RED_THREADS / 64];
+    const long long base = (long long)blockIdx.y * a.n;
+    double sum = 0.0;
+    for (long long i = (long long)blockIdx.x * ADFP_RED_THREADS + threadIdx.x; i < a.n; i += (long long)a.nblk * ADFP_RED_THREADS)
+        sum += (double)fabsf(a.a[base + i] - a.b[base + i]);
+    sum = red_block_sum(sum, s_wave);
+    if (threadIdx.x == 0) a.part[(long long)blockIdx.y * a.nblk + blockIdx.x] = sum;
+}
+
+// out[p] = the partials of view p (grid x) summed in k_red_final's fixed order
+__global__ __launch_bounds__(ADFP_RED_THREADS) void k_l1_final(const double* __restrict__ part, int nblk, double* __restrict__ out) {
+    __shared__ double s_wave[ADFP_RED_THREADS / 64];
+    const double* q = part + (long long)blockIdx.x * nblk;
+    double v = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += ADFP_RED_THREADS) v += q[b];
+    v = red_block_sum(v, s_wave);
+    if (threadIdx.x == 0) out[blockIdx.x] = v;
+}

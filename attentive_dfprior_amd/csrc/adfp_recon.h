@@ -460,8 +460,19 @@ struct CullArgs {
     unsigned char* seen;
 };
 
-// seen[i] = 1 iff some pose projects vertex i into the image: cam = w2c [p, 1], cam.x *= -1, uv = K cam, z = uv.z + 1e-5,
-// uv /= z, 0 <= -z && 0 < u < W && 0 < v < H (cull_mesh.py:49-71, f32 as the reference computes it)
+// does pose w (12 f32: the top three rows of inv(c2w)) project (x, y, z) into the image: cam = w [p, 1], cam.x *= -1, uv = K cam,
+// z = uv.z + 1e-5, uv /= z, 0 <= -z && 0 < u < W && 0 < v < H (cull_mesh.py:49-71, f32 as the reference computes it)
+ADFP_DEV bool cull_sees(const float* w, float x, float y, float z, float fx, float fy, float cx, float cy, float W, float H) {
+    const float X = -(((w[0] * x + w[1] * y) + w[2] * z) + w[3]);
+    const float Y = ((w[4] * x + w[5] * y) + w[6] * z) + w[7];
+    const float Z = ((w[8] * x + w[9] * y) + w[10] * z) + w[11];
+    const float zz = Z + 1e-5f;
+    const float u = (fx * X + cx * Z) / zz;
+    const float v = (fy * Y + cy * Z) / zz;
+    return 0.f <= -zz && u < W && u > 0.f && v < H && v > 0.f;
+}
+
+// seen[i] = 1 iff some pose projects vertex i into the image (cull_sees)
 __global__ __launch_bounds__(ADFP_NN_THREADS) void k_cull_seen(CullArgs a) {
     __shared__ float s_pose[ADFP_CULL_CHUNK * 12];
     const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
@@ -477,14 +488,7 @@ __global__ __launch_bounds__(ADFP_NN_THREADS) void k_cull_seen(CullArgs a) {
         __syncthreads();
         if (!on || seen) continue;
         for (int k = 0; k < m; ++k) {
-            const float* w = s_pose + 12 * k;
-            const float X = -(((w[0] * x + w[1] * y) + w[2] * z) + w[3]);
-            const float Y = ((w[4] * x + w[5] * y) + w[6] * z) + w[7];
-            const float Z = ((w[8] * x + w[9] * y) + w[10] * z) + w[11];
-            const float zz = Z + 1e-5f;
-            const float u = (a.fx * X + a.cx * Z) / zz;
-            const float v = (a.fy * Y + a.cy * Z) / zz;
-            if (0.f <= -zz && u < a.W && u > 0.f && v < a.H && v > 0.f) { seen = true; break; }
+            if (cull_sees(s_pose + 12 * k, x, y, z, a.fx, a.fy, a.cx, a.cy, a.W, a.H)) { seen = true; break; }
         }
     }
     if (on) a.seen[i] = seen ? 1 : 0;

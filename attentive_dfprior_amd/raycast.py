@@ -1,0 +1,124 @@
+"""Depth rendering of triangle meshes on the device (libadfp.so, csrc/adfp_raycast.h): a triangle BVH, batched f64 depth renders
+with the watertight ray/triangle test, check_proj over a batch of poses and per-view depth L1 sums.  recon_eval.calc_2d_metric is
+built on these; the conventions (camera, intersection, clipping) are include/adfp.h's "mesh depth rendering".
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import lib, ptr, check
+from .recon import device_of, as_points, _ws
+
+
+def _faces(faces, dev):
+    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.asarray(faces, dtype=np.int64))
+    return f.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+
+
+def _c2w_rows(c2w, dev):
+    """[P,4,4] / [4,4] / [P,3,4] (numpy or tensor) -> f64 device [P,12]: the top three rows of each pose."""
+    t = c2w if torch.is_tensor(c2w) else torch.from_numpy(np.asarray(c2w, dtype=np.float64))
+    t = t.detach().to(device=dev, dtype=torch.float64)
+    if t.dim() == 2:
+        t = t[None]
+    if t.dim() != 3 or t.shape[1] not in (3, 4) or t.shape[2] != 4:
+        raise ValueError(f'c2w must be [P,4,4] or [4,4], got {tuple(t.shape)}')
+    return t[:, :3, :].reshape(-1, 12).contiguous()
+
+
+class MeshBVH(object):
+    """A triangle BVH over (verts [V,3], faces [F,3]) on the device (adfp_tri_bvh_build): faces in Morton order of their centroids,
+    leaves of `leaf` triangles (4, 8 or 16) with their f64 vertices, an implicit binary tree of leaf boxes.  A face with an index
+    outside [0, V) is never hit."""
+
+    def __init__(self, verts, faces, device=None, leaf=_lib.TRI_LEAF_DEFAULT):
+        dev = torch.device(device) if device is not None else device_of(verts, faces)
+        self.device = dev
+        if leaf not in _lib.TRI_LEAVES:
+            raise ValueError(f'MeshBVH: leaf must be one of {_lib.TRI_LEAVES}, got {leaf}')
+        self.leaf = int(leaf)
+        v = as_points(verts, dev, 'vertices')
+        f = _faces(faces, dev)
+        self.n_verts, self.n_faces = int(v.shape[0]), int(f.shape[0])
+        if self.n_faces >= 2 ** 31 - 1024 or self.n_verts >= 2 ** 31 - 1024:
+            raise ValueError(f'MeshBVH: {self.n_faces} faces / {self.n_verts} vertices are more than the BVH takes')
+        L = lib()
+        self.bvh = _ws(L.adfp_tri_bvh_bytes(self.n_faces, self.leaf), dev)
+        if self.n_faces:
+            wsb = L.adfp_tri_bvh_build_workspace_bytes(self.n_faces)
+            ws = _ws(wsb, dev)
+            with _lib.device_guard(dev):
+                check(L.adfp_tri_bvh_build(ptr(v) if self.n_verts else None, self.n_verts, ptr(f), self.n_faces, self.leaf,
+                                           ptr(self.bvh), self.bvh.numel(), ptr(ws), wsb, _lib.current_stream(dev)),
+                      'adfp_tri_bvh_build')
+
+    def render_depth(self, c2w, H, W, fx, fy, cx, cy, near, far):
+        """f32 device tensor [P,H,W]: camera z of the nearest surface with near <= z <= far, 0 where there is none.  c2w: [P,4,4]
+        or [4,4] (OpenCV axes, f64, numpy or tensor); near: a scalar or [P]; far: a scalar."""
+        dev = self.device
+        m = _c2w_rows(c2w, dev)
+        P = int(m.shape[0])
+        nr = torch.as_tensor(near, dtype=torch.float64).reshape(-1).to(dev)
+        if nr.numel() == 1:
+            nr = nr.expand(P)
+        if nr.numel() != P:
+            raise ValueError(f'render_depth: {nr.numel()} near values for {P} views')
+        nr = nr.contiguous()
+        depth = torch.empty((P, int(H), int(W)), dtype=torch.float32, device=dev)
+        if P == 0:
+            return depth
+        with _lib.device_guard(dev):
+            check(lib().adfp_render_depth(ptr(self.bvh) if self.n_faces else None, self.bvh.numel(), self.n_faces, self.leaf, ptr(m),
+                                          ptr(nr), float(far), P, int(H), int(W), float(fx), float(fy), float(cx), float(cy),
+                                          ptr(depth), _lib.current_stream(dev)), 'adfp_render_depth')
+        return depth
+
+
+def proj_rows(c2w_list):
+    """[P,12] float32: the top three rows of inv(c2w') for each pose, c2w' = c2w with columns 1 and 2 negated, inverted in f64
+    and rounded to f32 (eval_recon.py:75-80)."""
+    out = np.empty((len(c2w_list), 12), dtype=np.float32)
+    for k, c2w in enumerate(c2w_list):
+        m = np.array(c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else c2w, dtype=np.float64, copy=True)
+        m[:3, 1] *= -1.0
+        m[:3, 2] *= -1.0
+        out[k] = np.linalg.inv(m)[:3, :4].astype(np.float32).reshape(-1)
+    return out
+
+
+def views_in_sight(points, c2w_list, H, W, fx, fy, cx, cy, device=None):
+    """bool device tensor [P]: check_proj(points, W, H, fx, fy, cx, cy, c2w) for each pose of c2w_list (adfp_views_in_sight)."""
+    dev = torch.device(device) if device is not None else device_of(points)
+    v = as_points(points, dev, 'points')
+    w = torch.from_numpy(proj_rows(c2w_list)).to(dev).contiguous()
+    P = int(w.shape[0])
+    out = torch.empty(P, dtype=torch.int32, device=dev)
+    if P == 0:
+        return out.bool()
+    n = int(v.shape[0])
+    with _lib.device_guard(dev):
+        check(lib().adfp_views_in_sight(ptr(v) if n else None, n, ptr(w), P, float(fx), float(fy), float(cx), float(cy), int(W),
+                                        int(H), ptr(out), _lib.current_stream(dev)), 'adfp_views_in_sight')
+    return out.bool()
+
+
+def depth_l1_sums(a, b):
+    """f64 device tensor [P]: per view, the sum over pixels of |a - b| (the f32 difference, widened) for two f32 [P,...] tensors
+    (adfp_depth_l1_sums; deterministic)."""
+    if a.shape != b.shape:
+        raise ValueError(f'depth_l1_sums: shapes {tuple(a.shape)} and {tuple(b.shape)} differ')
+    dev = a.device
+    a = a.detach().to(torch.float32).contiguous()
+    b = b.detach().to(device=dev, dtype=torch.float32).contiguous()
+    P = int(a.shape[0]) if a.dim() else 1
+    n = int(a.numel() // P) if P else 0
+    out = torch.empty(P, dtype=torch.float64, device=dev)
+    if P == 0:
+        return out
+    L = lib()
+    wsb = L.adfp_depth_l1_workspace_bytes(P, n)
+    ws = _ws(wsb, dev)
+    with _lib.device_guard(dev):
+        check(L.adfp_depth_l1_sums(ptr(a) if n else None, ptr(b) if n else None, P, n, ptr(ws), wsb, ptr(out),
+                                   _lib.current_stream(dev)), 'adfp_depth_l1_sums')
+    return out

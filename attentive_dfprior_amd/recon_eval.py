@@ -13,12 +13,18 @@ The reference imports open3d and trimesh at module level and scores with scipy's
   * calc_3d_metric (:99-125): meshes read by mesh.read_ply, the alignment applied to the reconstruction's vertices in f64, 200 000
     area-weighted samples per mesh (adfp_sample_surface on uniforms drawn by torch), the three numbers x100, printed as the
     reference prints them and returned as a dict.
-calc_2d_metric is not built (see its docstring).
+  * calc_2d_metric (:139-219): the views are drawn from the reference's streams (np.random for the origins, Python's random for
+    the targets) and screened against the ground truth's unseen points in batches (raycast.views_in_sight, check_proj's f32 test);
+    both meshes are rendered in chunks of views by an exact f64 ray caster (raycast.MeshBVH.render_depth) in place of open3d's
+    OpenGL depth buffer; the per-view L1 comes from a deterministic reduction (raycast.depth_l1_sums).  The deviations from the
+    reference are listed in INTEGRATION.md 2b.
 
-    python -m attentive_dfprior_amd.recon_eval --rec_mesh REC.ply --gt_mesh GT.ply -3d
+    python -m attentive_dfprior_amd.recon_eval --rec_mesh REC.ply --gt_mesh GT.ply -2d -3d
 """
 import argparse
 import math
+import os
+import random
 import sys
 
 import numpy as np
@@ -26,6 +32,7 @@ import torch
 
 from . import mesh
 from .recon import NNIndex, device_of, as_points, metric_sums, icp_moments, sample_surface, draw_uniforms
+from .raycast import MeshBVH, views_in_sight, depth_l1_sums
 
 SAMPLES = 200000                      # eval_recon.py:115, :118
 ICP_THRESHOLD = 0.1                   # eval_recon.py:63
@@ -176,13 +183,200 @@ def calc_3d_metric(rec_meshfile, gt_meshfile, align=True):
     return r
 
 
-NO_2D = ('calc_2d_metric (depth L1 over rendered views) is not built: it needs open3d\'s OpenGL depth capture and '
-         'trimesh.bounds.oriented_bounds, neither of which is available here')
+# calc_2d_metric's camera (eval_recon.py:144-150) and far plane (:195, set_constant_z_far)
+H_2D = W_2D = 500
+FOCAL_2D = 300.0
+FAR_2D = 20.0
+UP_2D = [0, 0, -1]                    # eval_recon.py:171
+NEAR_FRACTION = 0.01                  # near = 0.01 x the largest AABB extent of the rendered mesh
+
+
+def setup_seed(seed):
+    """Seed every stream the evaluation draws from: torch (CPU and GPU), numpy's global stream and Python's random."""
+    torch.manual_seed(seed)
+    torch.cuda.manual_seed_all(seed)
+    np.random.seed(seed)
+    random.seed(seed)
+    torch.backends.cudnn.deterministic = True
+
+
+def normalize(x):
+    """x scaled to unit length."""
+    return x / np.linalg.norm(x)
+
+
+def viewmatrix(z, up, pos):
+    """The 3x4 camera-to-world [x y z pos] looking along z: x = unit(up x z), y = unit(z x x)."""
+    axis_z = normalize(z)
+    axis_x = normalize(np.cross(up, axis_z))
+    axis_y = normalize(np.cross(axis_z, axis_x))
+    return np.stack([axis_x, axis_y, axis_z, pos], 1)
+
+
+def check_proj(points, W, H, fx, fy, cx, cy, c2w):
+    """Whether the pose c2w projects any of points [N,3] into the W x H image (eval_recon.py:70-96), as a numpy bool: one pose
+    through raycast.views_in_sight."""
+    return np.bool_(bool(views_in_sight(points, [np.asarray(c2w, dtype=np.float64)], H, W, fx, fy, cx, cy)[0]))
+
+
+def _min_area_rect(p2):
+    """The minimum-area rectangle around 2D points over the directions of their hull's edges: (u, v, ext_u, ext_v, mid_u, mid_v),
+    u and v the unit axes."""
+    from scipy.spatial import ConvexHull
+    ring = p2[ConvexHull(p2).vertices]
+    e = np.roll(ring, -1, 0) - ring
+    e = e[np.linalg.norm(e, axis=1) > 0]
+    u = e / np.linalg.norm(e, axis=1)[:, None]
+    v = np.stack([-u[:, 1], u[:, 0]], 1)
+    pu, pv = ring @ u.T, ring @ v.T
+    lo_u, hi_u, lo_v, hi_v = pu.min(0), pu.max(0), pv.min(0), pv.max(0)
+    j = int(np.argmin((hi_u - lo_u) * (hi_v - lo_v)))
+    return u[j], v[j], hi_u[j] - lo_u[j], hi_v[j] - lo_v[j], (lo_u[j] + hi_u[j]) * 0.5, (lo_v[j] + hi_v[j]) * 0.5
+
+
+def oriented_bounds(verts):
+    """trimesh.bounds.oriented_bounds(mesh) (ordered=True), restated with scipy's ConvexHull: for each distinct normal of the hull's
+    faces, the hull is projected onto that normal's plane, and the box is the 2D minimum-area rectangle over the projected hull's
+    edge directions times the height along the normal; the smallest volume wins.  Returns (to_origin 4x4, extents [3]): extents
+    ascending, to_origin the rigid transform taking the box to the origin, its axes permuted to that order and sign-fixed to a
+    right-handed frame."""
+    from scipy.spatial import ConvexHull
+    v = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    hull = ConvexHull(v)
+    hv = v[hull.vertices]
+    normals = hull.equations[:, :3] / np.linalg.norm(hull.equations[:, :3], axis=1)[:, None]
+    lead = np.argmax(np.abs(normals) > 1e-12, axis=1)
+    normals = normals * np.sign(normals[np.arange(len(normals)), lead])[:, None]          # n and -n are one plane direction
+    _, first = np.unique(np.round(normals, 9), axis=0, return_index=True)
+    best = None
+    for n in normals[np.sort(first)]:
+        a = np.array([1.0, 0.0, 0.0]) if abs(n[0]) < 0.9 else np.array([0.0, 1.0, 0.0])
+        e0 = normalize(np.cross(n, a))
+        e1 = np.cross(n, e0)
+        h = hv @ n
+        height = h.max() - h.min()
+        u, w, eu, ew, mu, mw = _min_area_rect(np.stack([hv @ e0, hv @ e1], 1))
+        vol = eu * ew * height
+        if best is None or vol < best[0]:
+            axes = np.stack([u[0] * e0 + u[1] * e1, w[0] * e0 + w[1] * e1, n])
+            best = (vol, axes, np.array([eu, ew, height]), np.array([mu, mw, (h.max() + h.min()) * 0.5]))
+    _, axes, ext, mid = best
+    centre = mid @ axes                                                  # mid is in the (u, w, n) frame
+    order = np.argsort(ext, kind='stable')
+    axes, ext = axes[order], ext[order]
+    if np.linalg.det(axes) < 0:
+        axes[2] = -axes[2]
+    to_origin = np.eye(4)
+    to_origin[:3, :3] = axes
+    to_origin[:3, 3] = -(axes @ centre)
+    return to_origin, ext
+
+
+def get_cam_position(gt_meshfile):
+    """The box the cameras are drawn from (eval_recon.py:128-136): the ground truth's oriented bounds with the extents scaled by
+    (0.3, 0.7, 0.7) (smallest, middle, largest) and the box moved up by 0.4 along world z.  Returns (extents, transform)."""
+    to_origin, extents = oriented_bounds(mesh.read_ply(gt_meshfile).verts)
+    extents = extents * np.array([0.3, 0.7, 0.7])
+    transform = np.linalg.inv(to_origin)
+    transform[2, 3] += 0.4
+    return extents, transform
+
+
+def volume_rectangular(extents, count, transform=None):
+    """trimesh.sample.volume_rectangular restated: count points uniform in a box of `extents` centred at the origin, from numpy's
+    global stream (np.random.random((count, 3)) - 0.5, times extents), then moved by transform as
+    x' = ((T00 x + T01 y) + T02 z) + T03.  count draws at once consume the stream as count draws of one."""
+    s = (np.random.random((count, 3)) - 0.5) * np.asarray(extents, dtype=np.float64)
+    return s if transform is None else apply_transform(s, transform)
+
+
+def sample_views(pc_unseen, extents, transform, n_imgs, H=H_2D, W=W_2D, fx=FOCAL_2D, fy=FOCAL_2D, cx=H_2D / 2.0 - 0.5,
+                 cy=W_2D / 2.0 - 0.5, device=None):
+    """The views of calc_2d_metric (eval_recon.py:167-186): candidates drawn as the reference draws them (per candidate three
+    numpy uniforms for the origin, then three Python random.uniform(-1e4, 1e4) rounded to 0.01 for the target), screened in batches
+    by views_in_sight, and accepted exactly as the reference's sequential loop accepts them: the first n_imgs candidates that see
+    none of pc_unseen.  A candidate whose viewmatrix is degenerate (target parallel to up) is rejected.  The last batch is drawn
+    whole, so both global streams end up further on than the reference leaves them.  Returns (c2w list [4x4], candidates the
+    sequential loop would have drawn)."""
+    out, used = [], 0
+    while len(out) < n_imgs:
+        k = min(1024, max(32, 2 * (n_imgs - len(out))))
+        origins = volume_rectangular(extents, k, transform)
+        cands, ok = [], []
+        for c in range(k):
+            target = np.array([round(random.uniform(-10000, +10000), 2) for _ in range(3)]) - np.array(origins[c])
+            with np.errstate(all='ignore'):
+                m = viewmatrix(target, UP_2D, origins[c])
+            c2w = np.eye(4)
+            c2w[:3, :] = m
+            ok.append(bool(np.isfinite(c2w).all()))
+            cands.append(c2w)
+        seen = views_in_sight(pc_unseen, [c if o else np.eye(4) for c, o in zip(cands, ok)], H, W, fx, fy, cx, cy,
+                              device).cpu().numpy()
+        for c in range(k):
+            used += 1
+            if ok[c] and not seen[c]:
+                out.append(cands[c])
+                if len(out) == n_imgs:
+                    break
+    return out, used
+
+
+def pc_unseen_file(gt_meshfile):
+    return gt_meshfile.replace('.ply', '_pc_unseen.npy')
+
+
+def load_pc_unseen(gt_meshfile):
+    path = pc_unseen_file(gt_meshfile)
+    if not os.path.exists(path):
+        raise FileNotFoundError(
+            f'{path} is missing: calc_2d_metric needs the ground truth\'s unseen-region points beside it.  The file ships with '
+            'NICE-SLAM\'s culled Replica meshes; it is not built by cull_mesh.')
+    return np.load(path)
+
+
+def metric_2d(rec_meshfile, gt_meshfile, align=True, n_imgs=1000, pc_unseen=None, near=None, far=FAR_2D, chunk=100, device=None):
+    """calc_2d_metric's number without the printing: (Depth L1 in cm, the accepted c2w list).  The views come from sample_views
+    over get_cam_position's box; both meshes are rendered at 500 x 500 (fx = fy = 300, cx = cy = 249.5) in chunks of `chunk`
+    views, near defaulting per mesh to 0.01 x the largest AABB extent of its vertices (the reconstruction's after alignment), far
+    = 20.  The per-view L1 is depth_l1_sums / (H W), and the result is 100 x the mean over views (f64).  pc_unseen: the ground
+    truth's unseen-region points; None reads them from the _pc_unseen.npy file beside gt_meshfile."""
+    dev = torch.device(device) if device is not None else device_of()
+    if pc_unseen is None:
+        pc_unseen = load_pc_unseen(gt_meshfile)
+    H, W, f = H_2D, W_2D, FOCAL_2D
+    cx, cy = H / 2.0 - 0.5, W / 2.0 - 0.5
+    gt = mesh.read_ply(gt_meshfile)
+    rec = mesh.read_ply(rec_meshfile)
+    rv = rec.verts
+    if align:
+        rv = apply_transform(rv, get_align_transformation(rec_meshfile, gt_meshfile))
+    extents, transform = get_cam_position(gt_meshfile)
+    views, _ = sample_views(pc_unseen, extents, transform, n_imgs, H, W, f, f, cx, cy, dev)
+
+    def near_of(v):
+        if near is not None:
+            return float(near)
+        v = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+        return NEAR_FRACTION * float((v.max(0) - v.min(0)).max()) if len(v) else 0.0
+
+    bvh_gt, bvh_rec = MeshBVH(gt.verts, gt.faces, dev), MeshBVH(rv, rec.faces, dev)
+    n_gt, n_rec = near_of(gt.verts), near_of(rv)
+    sums = []
+    for c0 in range(0, len(views), chunk):
+        c2w = np.stack(views[c0:c0 + chunk])
+        sums.append(depth_l1_sums(bvh_gt.render_depth(c2w, H, W, f, f, cx, cy, n_gt, far),
+                                  bvh_rec.render_depth(c2w, H, W, f, f, cx, cy, n_rec, far)))
+    errors = torch.cat(sums).cpu().numpy() / (H * W) if sums else np.zeros(0)
+    return float(np.mean(errors) * 100) if len(errors) else float('nan'), views
 
 
 def calc_2d_metric(rec_meshfile, gt_meshfile, align=True, n_imgs=1000):
-    """Not built: the reference renders depth through open3d's OpenGL visualiser (eval_recon.py:139-219)."""
-    raise NotImplementedError(NO_2D)
+    """2D reconstruction metric (eval_recon.py:139-219): the mean depth L1 over n_imgs rendered views, printed in cm as the
+    reference prints it, and returned.  Needs the ground truth's _pc_unseen.npy beside gt_meshfile."""
+    d, _ = metric_2d(rec_meshfile, gt_meshfile, align, n_imgs)
+    print('Depth L1: ', d)
+    return d
 
 
 def main(argv=None):
@@ -197,7 +391,7 @@ def main(argv=None):
     if args.metric_2d:
         try:
             calc_2d_metric(args.rec_mesh, args.gt_mesh, n_imgs=1000)
-        except NotImplementedError as e:
+        except FileNotFoundError as e:
             sys.exit(str(e))
 
 

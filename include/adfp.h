@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ADFP_VERSION 133
+#define ADFP_VERSION 134
 
 /* error codes (host-detected) */
 #define ADFP_E_ARG        (-1)   /* null pointer / negative size */
@@ -803,6 +803,55 @@ int adfp_cull_vertices(const double* verts, long long n_verts, const float* w2c,
                        int W, int H, unsigned char* seen, void* stream);
 /* cull_mesh.py:72-74: keep[f] = 0 iff all three vertices of face f are unseen (an index outside [0, n_verts) counts as unseen). */
 int adfp_cull_faces(const unsigned char* seen, long long n_verts, const int* faces, long long n_faces, unsigned char* keep, void* stream);
+
+/* ---- mesh depth rendering (eval_recon.py:139-219, calc_2d_metric) ----
+ * Triangle BVH.  adfp_tri_bvh_build fills `bvh` (adfp_tri_bvh_bytes(n_faces, leaf) bytes, kept by the caller for the renders):
+ * the faces in 30-bit Morton order of their centroids ((v0 + v1) + v2) / 3 (the NN index's box, code and sort passes), in leaves
+ * of `leaf` triangles (4, 8 or 16; ADFP_TRI_LEAF_DEFAULT) that hold each triangle's nine f64 vertex coordinates and its original
+ * face index, and an implicit complete binary tree of leaf boxes (node k has children 2k, 2k+1; the leaf count is padded to a power
+ * of two with inverted boxes).  A face with an index outside [0, n_verts) is never hit.  Workspace:
+ * adfp_tri_bvh_build_workspace_bytes(n_faces) = 24 n_faces rounded up to 256 plus adfp_nn_build_workspace_bytes(n_faces).
+ * n_faces = 0 builds nothing.  bvh bytes: 72 n_faces and 4 n_faces, each rounded up to 256, plus 96 P (P = leaves rounded up to a
+ * power of two). */
+#define ADFP_TRI_LEAF_DEFAULT 4
+size_t adfp_tri_bvh_bytes(long long n_faces, int leaf);
+size_t adfp_tri_bvh_build_workspace_bytes(long long n_faces);
+int adfp_tri_bvh_build(const double* verts, long long n_verts, const int* faces, long long n_faces, int leaf, void* bvh, size_t bvh_bytes,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* Depth images of n_views views in one launch: depth [n_views][H][W] (f32, device).  c2w [n_views][12] (f64, device) = the top three
+ * rows of each camera-to-world matrix [R | o], R a rotation; near [n_views] (f64, device) per view, `far` shared (host).
+ *   Camera: OpenCV axes (x right, y down, z forward), the extrinsic inv(c2w) of open3d's PinholeCameraParameters.  Pixel (row i,
+ *     col j) has d = ((j - cx) / fx, (i - cy) / fy, 1) in camera space, in f64 in that order; the world ray is o + t R d, so t is
+ *     camera z.
+ *   Intersection: Woop, Benthin & Wald (2013), watertight, in f64, the axis permutation fixed to z and the shear Sx = -dx,
+ *     Sy = -dy, Sz = 1.  Each vertex v goes to camera space first: e = v - o (per component), cam_c = ((R0c e0 + R1c e1) + R2c e2).
+ *     Then Ax' = Ax - dx Az, Ay' = Ay - dy Az (the same for B, C); U = Cx' By' - Cy' Bx', V = Ax' Cy' - Ay' Cx',
+ *     W = Bx' Ay' - By' Ax'.  A miss when U, V, W have mixed signs or det = (U + V) + W is 0, else z = ((U Az + V Bz) + W Cz) / det.
+ *     Edges count as inside (a ray through a shared edge or vertex hits at least one of its triangles); back faces count.
+ *   Depth: the least z over all hits with near <= z <= far, rounded to f32; 0 where there is none.  Clipping is per pixel (GL
+ *     clipping followed by a z-buffer).  The result is a minimum over a set: independent of the traversal order, equal to a brute
+ *     force over all faces bit for bit (tests/depth_ref.py), two runs give the same bits.
+ *   Pruning is conservative: every box tested is first grown by 2^-24 (max |coordinate| of the mesh's box + max |o|), a margin
+ *     far above the rounding of both the slab test and the triangle test, so boxes of zero thickness keep a width; an axis along
+ *     which R d is 0 (|R d| < 1e-200) is a containment test instead of a slab, so no 0 x inf arises.  The walk is k_nn_query's
+ *     stackless trail-bit walk: the child with the smaller entry t first, a box pruned when its entry t exceeds the best z or its
+ *     exit t lies below near.
+ * n_faces = 0 writes zeros (bvh, c2w and near may be NULL); n_views = 0 does nothing.  far must be positive and finite, fx, fy
+ * nonzero; H, W in [1, 32768]. */
+int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
+                      long long n_views, int H, int W, double fx, double fy, double cx, double cy, float* depth, void* stream);
+/* check_proj (eval_recon.py:70-96) for a batch of poses: any[p] (int32, device) = 1 iff pose p projects some point into the
+ * image, else 0.  w2c [n_poses][12] (f32, device) = the top three rows of inv(c2w'), c2w' = c2w with columns 1 and 2 negated,
+ * inverted in f64 and rounded to f32 by the caller; the per-point test is adfp_cull_vertices's.  n_poses = 0 does nothing;
+ * no points gives all zeros. */
+int adfp_views_in_sight(const double* points, long long n_points, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
+                        int W, int H, int* any, void* stream);
+/* Per view p: out[p] (f64, device) = sum over n_pixels of (double)|a - b|, the f32 difference widened, for a, b [n_views][n_pixels]
+ * (f32, device); per-workgroup partials over min(max(ceil(n_pixels / 256), 1), 1024) workgroups, then one fixed-order pass.
+ * Workspace: adfp_depth_l1_workspace_bytes = 8 n_views times that workgroup count.  n_views = 0 does nothing. */
+size_t adfp_depth_l1_workspace_bytes(long long n_views, long long n_pixels);
+int adfp_depth_l1_sums(const float* a, const float* b, long long n_views, long long n_pixels, void* workspace, size_t workspace_bytes,
+                       double* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,12 +4,15 @@
     metric reduction, next to scipy's cKDTree (build + query) at workers=1 (what eval_recon.py runs) and workers=16;
   * the same query with the reconstruction moved by 3 x the room's extent (the disjoint case; issue bar: <= 10 x overlapping);
   * ICP between two room meshes extracted at 512^3 (one moved by ~3 degrees / 5 cm): vertex counts, iterations, time per iteration;
-  * culling of 1 M vertices against 2 000 poses, next to cull_mesh.py's per-pose loop restated in torch on the GPU.
+  * culling of 1 M vertices against 2 000 poses, next to cull_mesh.py's per-pose loop restated in torch on the GPU;
+  * --2d: the 2D metric alone -- the triangle BVH build over the 512^3 room (~1 M faces) and the depth render of one chunk of
+    100 views at 500 x 500 (M rays/s), for each leaf size, and the whole metric_2d for 1 000 views on two synthetic 512^3 rooms
+    (no ICP); median and range.
 ADFP_LIB_PATH selects another build of the library (an A/B of leaf sizes: --nn_only runs the 3D-metric legs alone).
 Device legs: warm-up, then `--reps` repetitions between torch.cuda events (host clock around a synchronised call where the leg
 reads results back), min and median.
 
-    python tools/recon_bench.py [--reps 5]
+    python tools/recon_bench.py [--reps 5] [--2d]
 """
 import argparse
 import json
@@ -119,6 +122,51 @@ def torch_cull_loop(pc, poses, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339
     return whole
 
 
+def spread(fn, reps):
+    """Host clock around a synchronised call, after one warm-up: median and range in ms."""
+    fn()
+    t = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return {'median_ms': round(float(np.median(t)), 3), 'min_ms': round(min(t), 3), 'max_ms': round(max(t), 3)}
+
+
+def leg_2d(reps, res, n_imgs, chunk):
+    import tempfile
+    from attentive_dfprior_amd import _lib, raycast
+    out = {}
+    v, f = room(res)
+    rv, rf = room(res, moved=True)
+    vn, fn_ = v.cpu().numpy(), f.cpu().numpy()
+    out['faces'] = int(f.shape[0])
+    rng = np.random.default_rng(0)
+    pc = np.stack([rng.uniform(-1.6, -1.0, 2000), rng.uniform(0.6, 1.1, 2000), np.full(2000, 0.9)], 1)    # a ceiling corner
+    with tempfile.TemporaryDirectory() as d:
+        gt_p, rec_p = os.path.join(d, 'gt.ply'), os.path.join(d, 'rec.ply')
+        mesh.write_ply(gt_p, vn, fn_)
+        mesh.write_ply(rec_p, rv.cpu().numpy(), rf.cpu().numpy())
+        extents, transform = recon_eval.get_cam_position(gt_p)
+        views, _ = recon_eval.sample_views(pc, extents, transform, chunk, device=DEV)
+        c2w = np.stack(views)
+        H = W = recon_eval.H_2D
+        near = recon_eval.NEAR_FRACTION * float((vn.max(0) - vn.min(0)).max())
+        for leaf in _lib.TRI_LEAVES:
+            h = {}
+            b = timed(lambda: h.__setitem__('b', raycast.MeshBVH(v, f, DEV, leaf=leaf)), reps)
+            bvh = h['b']
+            r = timed(lambda: bvh.render_depth(c2w, H, W, 300.0, 300.0, 249.5, 249.5, near, 20.0), reps)
+            out[f'leaf{leaf}'] = {'bvh_build': b, 'render_100_views': r,
+                                  'mrays_per_s_median': round(len(views) * H * W / (r['median_ms'] * 1e-3) / 1e6, 1)}
+        out['metric_2d_1000_views'] = spread(lambda: recon_eval.metric_2d(rec_p, gt_p, align=False, n_imgs=n_imgs, pc_unseen=pc,
+                                                                           chunk=chunk, device=DEV), reps)
+        out['metric_2d_note'] = f'{n_imgs} views, chunks of {chunk}, read_ply + oriented bounds + view sampling + 2 BVH builds + renders'
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
@@ -127,9 +175,16 @@ def main():
     ap.add_argument('--cull_verts', type=int, default=1000000)
     ap.add_argument('--cull_poses', type=int, default=2000)
     ap.add_argument('--nn_only', action='store_true', help='only the two 3D-metric legs (for an A/B of library builds)')
+    ap.add_argument('--2d', dest='two_d', action='store_true', help='only the 2D-metric legs (BVH build, render, metric_2d)')
+    ap.add_argument('--res_2d', type=int, default=512)
+    ap.add_argument('--n_imgs', type=int, default=1000)
     a = ap.parse_args()
     from attentive_dfprior_amd import _lib
     out = {'device': torch.cuda.get_device_name(0), 'reps': a.reps, 'lib': os.path.basename(_lib.LIB_PATH)}
+    if a.two_d:
+        out['metric_2d'] = leg_2d(a.reps, a.res_2d, a.n_imgs, 100)
+        print(json.dumps(out))
+        return
     v, f = room(256)
     g = torch.Generator().manual_seed(0)
     gt, _ = recon.sample_surface(v, f, a.n, generator=g)
