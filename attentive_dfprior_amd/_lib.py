@@ -289,6 +289,18 @@ SYMBOLS = [
                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ('adfp_depth_l1_workspace_bytes', C.c_size_t, [C.c_longlong, C.c_longlong]),
     ('adfp_depth_l1_sums', C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ('adfp_render_depth_cull', C.c_int, [C.c_void_p, C.c_size_t, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
+                                         C.c_longlong, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                         C.c_void_p, C.c_void_p]),
+    ('adfp_refuse_touch', C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                    C.c_double, C.c_int, C.c_float, C.c_double, C.c_double, C.POINTER(C.c_int * 3),
+                                    C.POINTER(C.c_int * 3), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('adfp_refuse_integrate', C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int * 3), C.POINTER(C.c_int * 3), C.c_double,
+                                        C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
+                                        C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    ('adfp_voxel_down_sample_workspace_bytes', C.c_size_t, [C.c_longlong]),
+    ('adfp_voxel_down_sample', C.c_int, [C.c_void_p, C.c_longlong, C.c_double, C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3),
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER
@@ -297,6 +309,8 @@ NN_SORT_QUERIES = 1                    # ADFP_NN_SORT_QUERIES
 ICP_MOMENTS = 17                       # adfp_icp_moments' out[]
 TRI_LEAF_DEFAULT = 4                   # ADFP_TRI_LEAF_DEFAULT
 TRI_LEAVES = (4, 8, 16)                # the leaf sizes adfp_tri_bvh_build takes
+CULL = {'none': 0, 'back': 1, 'front': 2}     # ADFP_CULL_NONE / ADFP_CULL_BACK / ADFP_CULL_FRONT
+UNIT_VOXELS = 16                        # ADFP_UNIT_VOXELS
 
 _lib = None
 

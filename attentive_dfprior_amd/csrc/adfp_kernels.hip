@@ -3648,9 +3648,11 @@ int adfp_tri_bvh_build(const double* verts, long long n_verts, const int* faces,
 
 #define RT_MAX_SIDE 32768
 #define RT_VIEWS_PER_LAUNCH 32768                    // grid y
-int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
-                      long long n_views, int H, int W, double fx, double fy, double cx, double cy, float* depth, void* stream) {
+static int render_depth_launch(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near,
+                               double far, long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull,
+                               float* depth, void* stream) {
     if (n_faces < 0 || n_views < 0 || !tri_leaf_ok(leaf) || H <= 0 || W <= 0) return ADFP_E_ARG;
+    if (cull != ADFP_CULL_NONE && cull != ADFP_CULL_BACK && cull != ADFP_CULL_FRONT) return ADFP_E_ARG;
     if (!(far > 0.0) || !(fx != 0.0) || !(fy != 0.0) || !isfinite(far) || !isfinite(fx) || !isfinite(fy) ||
         !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
     if (n_views == 0) return 0;
@@ -3674,10 +3676,27 @@ int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int 
     for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
         const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
         a.view0 = (int)v0;
-        hipLaunchKernelGGL(k_render_depth, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
+        if (cull == ADFP_CULL_BACK)
+            hipLaunchKernelGGL(k_render_depth_cull<ADFP_CULL_BACK>, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
+        else if (cull == ADFP_CULL_FRONT)
+            hipLaunchKernelGGL(k_render_depth_cull<ADFP_CULL_FRONT>, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
+        else
+            hipLaunchKernelGGL(k_render_depth, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
         ADFP_CHECK_LAUNCH();
     }
     return 0;
+}
+
+int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
+                      long long n_views, int H, int W, double fx, double fy, double cx, double cy, float* depth, void* stream) {
+    return render_depth_launch(bvh, bvh_bytes, n_faces, leaf, c2w, near, far, n_views, H, W, fx, fy, cx, cy, ADFP_CULL_NONE, depth,
+                               stream);
+}
+
+int adfp_render_depth_cull(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near,
+                           double far, long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull,
+                           float* depth, void* stream) {
+    return render_depth_launch(bvh, bvh_bytes, n_faces, leaf, c2w, near, far, n_views, H, W, fx, fy, cx, cy, cull, depth, stream);
 }
 
 int adfp_views_in_sight(const double* points, long long n_points, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
@@ -3721,6 +3740,141 @@ int adfp_depth_l1_sums(const float* a, const float* b, long long n_views, long l
         ADFP_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(k_l1_final, dim3((unsigned)n_views), dim3(ADFP_RED_THREADS), 0, st, r.part, r.nblk, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- ScanNet mesh evaluation (adfp_refuse.h) ----
+#include "adfp_refuse.h"
+
+static bool box_ok(const int lo[3], const int dim[3], long long* nunits) {
+    long long n = 1;
+    for (int c = 0; c < 3; ++c) {
+        if (dim[c] <= 0) return false;
+        n *= dim[c];
+        if (n > 0x7fffffffll) { *nunits = -1; return true; }
+    }
+    *nunits = n;
+    return true;
+}
+
+int adfp_refuse_touch(const float* depth, long long n_views, int H, int W, const double* c2w, double fx, double fy, double cx, double cy,
+                      int stride, float depth_trunc, double sdf_trunc, double unit_length, const int unit_lo[3], const int unit_dim[3],
+                      unsigned char* touched, int* outside, void* stream) {
+    if (n_views < 0 || H <= 0 || W <= 0 || stride < 1 || !unit_lo || !unit_dim) return ADFP_E_ARG;
+    if (!(fx != 0.0) || !(fy != 0.0) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    if (!(sdf_trunc >= 0.0) || !isfinite(sdf_trunc) || !(unit_length > 0.0) || !isfinite(unit_length) || !(depth_trunc > 0.f))
+        return ADFP_E_ARG;
+    long long nunits = 0;
+    if (!box_ok(unit_lo, unit_dim, &nunits)) return ADFP_E_ARG;
+    if (n_views == 0) return 0;
+    if (!depth || !c2w || !touched || !outside) return ADFP_E_ARG;
+    if (nunits < 0 || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(touched, 0, (size_t)n_views * (size_t)nunits, st);
+    if (e != hipSuccess) return (int)e;
+    TouchArgs a;
+    a.depth = depth; a.H = H; a.W = W; a.stride = stride; a.nsx = (W + stride - 1) / stride; a.nsy = (H + stride - 1) / stride;
+    a.c2w = c2w; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.depth_trunc = depth_trunc; a.trunc = sdf_trunc; a.unit = unit_length;
+    for (int c = 0; c < 3; ++c) { a.lo[c] = unit_lo[c]; a.dim[c] = unit_dim[c]; }
+    a.nunits = nunits; a.touched = touched; a.outside = outside;
+    const unsigned nblk = (unsigned)(((long long)a.nsx * a.nsy + ADFP_TOUCH_THREADS - 1) / ADFP_TOUCH_THREADS);
+    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
+        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
+        a.view0 = (int)v0;
+        hipLaunchKernelGGL(k_refuse_touch, dim3(nblk, (unsigned)nv), dim3(ADFP_TOUCH_THREADS), 0, st, a);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+#define FUSE_MAX_VIEWS 65536
+int adfp_refuse_integrate(float* tsdf, float* weight, const int unit_lo[3], const int unit_dim[3], double voxel, const int* units,
+                          long long n_units, const float* depth, const float* w2c, const unsigned char* touched, long long n_views, int H,
+                          int W, float fx, float fy, float cx, float cy, float sdf_trunc, float depth_trunc, void* stream) {
+    if (n_units < 0 || n_views < 0 || H <= 0 || W <= 0 || !unit_lo || !unit_dim) return ADFP_E_ARG;
+    if (!(voxel > 0.0) || !isfinite(voxel) || !(sdf_trunc > 0.f) || !isfinite(sdf_trunc) || !(depth_trunc > 0.f)) return ADFP_E_ARG;
+    if (!(fx != 0.f) || !(fy != 0.f) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    long long nunits = 0;
+    if (!box_ok(unit_lo, unit_dim, &nunits)) return ADFP_E_ARG;
+    if (n_units == 0 || n_views == 0) return 0;
+    if (!tsdf || !weight || !units || !depth || !w2c || !touched) return ADFP_E_ARG;
+    if (nunits < 0 || n_units > nunits || n_views > FUSE_MAX_VIEWS || H > RT_MAX_SIDE || W > RT_MAX_SIDE) return ADFP_E_UNSUPPORTED;
+    FuseArgs a;
+    a.tsdf = tsdf; a.weight = weight;
+    for (int c = 0; c < 3; ++c) { a.dim[c] = unit_dim[c]; a.org[c] = (long long)unit_lo[c] * ADFP_UNIT; }
+    a.ny = (long long)unit_dim[1] * ADFP_UNIT; a.nz = (long long)unit_dim[2] * ADFP_UNIT; a.nunits = nunits;
+    a.units = units; a.depth = depth; a.w2c = w2c; a.touched = touched; a.n_views = (int)n_views; a.H = H; a.W = W;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.trunc = sdf_trunc; a.inv_trunc = 1.0f / sdf_trunc; a.depth_trunc = depth_trunc;
+    a.safe_w = (float)W - 0.0001f; a.safe_h = (float)H - 0.0001f; a.voxel = voxel;
+    hipLaunchKernelGGL(k_refuse_integrate, dim3((unsigned)n_units), dim3(ADFP_FUSE_THREADS), 0, (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+#define VDS_MAX_CELLS_PER_AXIS (1ll << 21)
+static long long vds_tiles(long long n) { return (n + ADFP_VDS_TILE - 1) / ADFP_VDS_TILE; }
+size_t adfp_voxel_down_sample_workspace_bytes(long long n) {
+    if (n <= 0 || n > RECON_MAX_N) return 0;
+    const long long T = vds_tiles(n);
+    return al256((size_t)n * 8) + 5 * al256((size_t)n * 4) + al256((size_t)T * 4) + al256((size_t)T * 8) + al256(adfp_sort_workspace_bytes(n));
+}
+
+int adfp_voxel_down_sample(const double* points, long long n, double voxel_size, const double min_bound[3], const double max_bound[3],
+                           void* workspace, size_t workspace_bytes, double* out, int* counts, long long* total, void* stream) {
+    if (n < 0 || !(voxel_size > 0.0) || !isfinite(voxel_size) || !total) return ADFP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        hipError_t e = hipMemsetAsync(total, 0, sizeof(long long), st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    if (!points || !min_bound || !max_bound || !workspace || !out || !counts) return ADFP_E_ARG;
+    VdsArgs a;
+    unsigned long long ncell = 1;
+    for (int c = 0; c < 3; ++c) {
+        if (!isfinite(min_bound[c]) || !isfinite(max_bound[c]) || !(min_bound[c] <= max_bound[c])) return ADFP_E_ARG;
+        a.vmin[c] = min_bound[c] - voxel_size * 0.5;
+        const double f = floor((max_bound[c] - a.vmin[c]) / voxel_size);
+        if (!(f < (double)VDS_MAX_CELLS_PER_AXIS)) return ADFP_E_UNSUPPORTED;
+        a.dim[c] = (long long)f + 1;
+        ncell *= (unsigned long long)a.dim[c];
+    }
+    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_voxel_down_sample_workspace_bytes(n)) return ADFP_E_WORKSPACE;
+    const long long T = vds_tiles(n);
+    char* w = (char*)workspace;
+    a.key64 = (unsigned long long*)w; w += al256((size_t)n * 8);
+    a.key = (int*)w; w += al256((size_t)n * 4);
+    int* key_tmp = (int*)w; w += al256((size_t)n * 4);
+    a.perm = (int*)w; w += al256((size_t)n * 4);
+    int* perm_tmp = (int*)w; w += al256((size_t)n * 4);
+    a.start = (int*)w; w += al256((size_t)n * 4);
+    a.tile_counts = (unsigned*)w; w += al256((size_t)T * 4);
+    a.tile_offsets = (long long*)w; w += al256((size_t)T * 8);
+    void* sort_ws = w;
+    const size_t sort_wsb = adfp_sort_workspace_bytes(n);
+    a.p = points; a.n = (int)n; a.vs = voxel_size; a.ntiles = (int)T; a.total = total; a.out = out; a.counts = counts;
+    int bits = 0;
+    while (bits < 64 && ((ncell - 1) >> bits) != 0ull) ++bits;
+    if (bits == 0) bits = 1;
+    const unsigned nb = (unsigned)((n + ADFP_VDS_THREADS - 1) / ADFP_VDS_THREADS);
+    hipLaunchKernelGGL(k_vds_keys, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    for (int shift = 0; shift < bits; shift += 31) {                     // LSD: low segment first, every pass stable
+        hipLaunchKernelGGL(k_vds_segment, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a, shift);
+        ADFP_CHECK_LAUNCH();
+        const int kb = bits - shift < 31 ? bits - shift : 31;
+        int rc = adfp_sort_pairs(a.key, a.perm, key_tmp, perm_tmp, n, kb, sort_ws, sort_wsb, stream);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_vds_tile_heads, dim3((unsigned)T), dim3(ADFP_VDS_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_vds_tile_scan, dim3(1), dim3(ADFP_VDS_SCAN_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_vds_starts, dim3((unsigned)T), dim3(ADFP_VDS_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_vds_mean, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a);
     ADFP_CHECK_LAUNCH();
     return 0;
 }

@@ -102,8 +102,11 @@ ADFP_DEV bool rt_box(const double* b, double pad, const double* o, const double*
 // One lane, one pixel (row i, col j) of view p.  d = ((j - cx) / fx, (i - cy) / fy, 1); a vertex goes to camera space as
 // cam_c = ((R0c e0 + R1c e1) + R2c e2), e = v - o; the shear A' = (Ax - dx Az, Ay - dy Az); U = Cx By - Cy Bx, V = Ax Cy - Ay Cx,
 // W = Bx Ay - By Ax; a miss when their signs are mixed or det = (U + V) + W is 0; z = ((U Az + V Bz) + W Cz) / det; the depth is
-// the least z with near <= z <= far, rounded to f32, or 0.
-__global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) {
+// the least z with near <= z <= far, rounded to f32, or 0.  CULL (ADFP_CULL_*): BACK keeps only hits with det > 0, FRONT only hits
+// with det < 0 (det = -(n . R d), n = (v1 - v0) x (v2 - v0): det > 0 is a face whose normal points toward the camera); the culled
+// modes write 0 for a view whose pose holds a non-finite entry.  CULL = NONE is k_render_depth, instruction for instruction.
+template <int CULL>
+ADFP_DEV void render_depth_body(const RenderArgs& a) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int bx = (int)(blockIdx.x % (unsigned)a.nbx), by = (int)(blockIdx.x / (unsigned)a.nbx);
     const int col = bx * 16 + (w & 1) * 8 + (lane & 7);
@@ -111,6 +114,12 @@ __global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) 
     if (row >= a.H || col >= a.W) return;                   // no barrier below
     const long long p = (long long)a.view0 + blockIdx.y;
     const double* m = a.c2w + 12 * p;
+    if (CULL != ADFP_CULL_NONE) {                           // uniform over the workgroup: one view per grid row
+        bool fin = true;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) fin = fin && isfinite(m[e]);
+        if (!fin) { a.depth[(p * a.H + row) * (long long)a.W + col] = 0.f; return; }
+    }
     double R[9], o[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -159,6 +168,8 @@ __global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) 
                 if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) continue;
                 const double det = (U + V) + W;
                 if (det == 0.0) continue;
+                if (CULL == ADFP_CULL_BACK && !(det > 0.0)) continue;
+                if (CULL == ADFP_CULL_FRONT && !(det < 0.0)) continue;
                 const double z = ((U * cam[2] + V * cam[5]) + W * cam[8]) / det;
                 if (z >= near && z <= best) { best = z; found = true; }     // NaN (an out-of-range face) fails here
             }
@@ -187,6 +198,10 @@ __global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) 
     }
     a.depth[(p * a.H + row) * (long long)a.W + col] = found ? (float)best : 0.f;
 }
+
+__global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) { render_depth_body<ADFP_CULL_NONE>(a); }
+template <int CULL>
+__global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth_cull(RenderArgs a) { render_depth_body<CULL>(a); }
 
 // any[p] |= 1 iff pose p projects some point into the image (k_cull_seen's f32 test, cull_mesh.py:49-71 = eval_recon.py:70-96);
 // any[] is zeroed by the entry before the launch

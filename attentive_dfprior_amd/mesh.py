@@ -311,3 +311,30 @@ def read_ply(path):
     if vertex is None:
         raise ValueError(f'{path}: no vertex element')
     return PlyMesh(vertex, faces)
+
+
+def read_obj(path):
+    """Read a Wavefront OBJ mesh: 'v x y z [r g b ...]' (extra columns ignored) and 'f' with a, a/b, a//c or a/b/c corners, 1-based
+    or negative (relative to the vertices read so far) indices, polygons fan-triangulated (0, i, i+1) as read_ply does.  Every
+    other statement is skipped.  Returns a PlyMesh (vertex x y z as float64)."""
+    verts, polys = [], []
+    with open(path, 'r') as fh:
+        for line in fh:
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == 'v':
+                if len(w) < 4:
+                    raise ValueError(f'{path}: vertex line {line.strip()!r} has fewer than three coordinates')
+                verts.append((float(w[1]), float(w[2]), float(w[3])))
+            elif w[0] == 'f':
+                idx = []
+                for c in w[1:]:
+                    k = int(c.split('/')[0])
+                    idx.append(k - 1 if k > 0 else len(verts) + k)
+                polys.append(np.array(idx, np.int64))
+    vertex = np.empty(len(verts), dtype=[('x', '<f8'), ('y', '<f8'), ('z', '<f8')])
+    if verts:
+        v = np.array(verts, np.float64)
+        vertex['x'], vertex['y'], vertex['z'] = v[:, 0], v[:, 1], v[:, 2]
+    return PlyMesh(vertex, _fan(polys) if polys else np.zeros((0, 3), np.int64))

@@ -52,9 +52,12 @@ class MeshBVH(object):
                                            ptr(self.bvh), self.bvh.numel(), ptr(ws), wsb, _lib.current_stream(dev)),
                       'adfp_tri_bvh_build')
 
-    def render_depth(self, c2w, H, W, fx, fy, cx, cy, near, far):
+    def render_depth(self, c2w, H, W, fx, fy, cx, cy, near, far, cull='none'):
         """f32 device tensor [P,H,W]: camera z of the nearest surface with near <= z <= far, 0 where there is none.  c2w: [P,4,4]
-        or [4,4] (OpenCV axes, f64, numpy or tensor); near: a scalar or [P]; far: a scalar."""
+        or [4,4] (OpenCV axes, f64, numpy or tensor); near: a scalar or [P]; far: a scalar.  cull: 'none' (adfp_render_depth),
+        'back' or 'front' (adfp_render_depth_cull: front faces have their normal (v1 - v0) x (v2 - v0) toward the camera)."""
+        if cull not in _lib.CULL:
+            raise ValueError(f"render_depth: cull must be one of {tuple(_lib.CULL)}, got {cull!r}")
         dev = self.device
         m = _c2w_rows(c2w, dev)
         P = int(m.shape[0])
@@ -68,9 +71,15 @@ class MeshBVH(object):
         if P == 0:
             return depth
         with _lib.device_guard(dev):
-            check(lib().adfp_render_depth(ptr(self.bvh) if self.n_faces else None, self.bvh.numel(), self.n_faces, self.leaf, ptr(m),
-                                          ptr(nr), float(far), P, int(H), int(W), float(fx), float(fy), float(cx), float(cy),
-                                          ptr(depth), _lib.current_stream(dev)), 'adfp_render_depth')
+            if cull == 'none':
+                check(lib().adfp_render_depth(ptr(self.bvh) if self.n_faces else None, self.bvh.numel(), self.n_faces, self.leaf,
+                                              ptr(m), ptr(nr), float(far), P, int(H), int(W), float(fx), float(fy), float(cx),
+                                              float(cy), ptr(depth), _lib.current_stream(dev)), 'adfp_render_depth')
+            else:
+                check(lib().adfp_render_depth_cull(ptr(self.bvh) if self.n_faces else None, self.bvh.numel(), self.n_faces,
+                                                   self.leaf, ptr(m), ptr(nr), float(far), P, int(H), int(W), float(fx), float(fy),
+                                                   float(cx), float(cy), _lib.CULL[cull], ptr(depth), _lib.current_stream(dev)),
+                      'adfp_render_depth_cull')
         return depth
 
 

@@ -840,6 +840,18 @@ int adfp_tri_bvh_build(const double* verts, long long n_verts, const int* faces,
  * nonzero; H, W in [1, 32768]. */
 int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
                       long long n_views, int H, int W, double fx, double fy, double cx, double cy, float* depth, void* stream);
+/* The same render with back- or front-face culling (pyrender's GL_CULL_FACE, evaluate_scannet.py:120-136).  cull = ADFP_CULL_NONE
+ * is adfp_render_depth bit for bit (the same kernel).  Facing is the sign of the watertight test's det = (U + V) + W: in real
+ * arithmetic det = -(n . R d) with n = (v1 - v0) x (v2 - v0) (the shear has determinant 1), so det > 0 is a FRONT face, one whose
+ * normal points toward the camera (GL's counter-clockwise front face, seen from the camera), and det < 0 a BACK face.
+ * ADFP_CULL_BACK keeps only hits with det > 0, ADFP_CULL_FRONT only hits with det < 0.  In the culled modes a view whose c2w holds
+ * a non-finite entry is all zeros.  Another cull value is ADFP_E_ARG; the other arguments and errors are adfp_render_depth's. */
+#define ADFP_CULL_NONE  0
+#define ADFP_CULL_BACK  1
+#define ADFP_CULL_FRONT 2
+int adfp_render_depth_cull(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near,
+                           double far, long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull,
+                           float* depth, void* stream);
 /* check_proj (eval_recon.py:70-96) for a batch of poses: any[p] (int32, device) = 1 iff pose p projects some point into the
  * image, else 0.  w2c [n_poses][12] (f32, device) = the top three rows of inv(c2w'), c2w' = c2w with columns 1 and 2 negated,
  * inverted in f64 and rounded to f32 by the caller; the per-point test is adfp_cull_vertices's.  n_poses = 0 does nothing;
@@ -852,6 +864,62 @@ int adfp_views_in_sight(const double* points, long long n_points, const float* w
 size_t adfp_depth_l1_workspace_bytes(long long n_views, long long n_pixels);
 int adfp_depth_l1_sums(const float* a, const float* b, long long n_views, long long n_pixels, void* workspace, size_t workspace_bytes,
                        double* out, void* stream);
+
+/* ---- ScanNet mesh evaluation (src/tools/evaluate_scannet.py: refuse, evaluate) ----
+ * refuse() renders the predicted mesh from every 10th pose and fuses the depths into open3d's ScalableTSDFVolume.  open3d is not
+ * a dependency; the three entries below are our reading of its legacy integration (unpinned: no open3d to compare against), over a
+ * DENSE box of whole units instead of a hash map of them.  A unit is ADFP_UNIT_VOXELS^3 voxels; unit (a, b, c) covers world voxel
+ * indices 16 a .. 16 a + 15 (per axis), and world voxel k has its centre at (k + 0.5) voxel.  A box is unit_lo[3] (HOST, world
+ * unit indices of its first unit) and unit_dim[3] (HOST, units per axis, each >= 1); its units are numbered (a dim1 + b) dim2 + c
+ * (relative indices), its voxels form the lattice [16 dim0][16 dim1][16 dim2], z fastest.  A box of more than 2^31 - 1 units is
+ * ADFP_E_UNSUPPORTED. */
+#define ADFP_UNIT_VOXELS 16
+/* Unit touch marks (ScalableTSDFVolume::Integrate's allocation): for view p of n_views and each pixel (row v, col u) with
+ * u % stride == 0 and v % stride == 0 of depth [n_views][H][W] (f32, device) whose d satisfies 0 < d <= depth_trunc (f32):
+ * x = ((u - cx) d) / fx, y = ((v - cy) d) / fy, and the point P = ((m0 x + m1 y) + m2 d) + m3 per row of c2w [n_views][12] (f64,
+ * device; the camera pose that back-projects, open3d's extrinsic.inverse()), all in f64.  Every unit from floor((P - sdf_trunc) /
+ * unit_length) to floor((P + sdf_trunc) / unit_length), per axis, gets touched[p][unit] = 1 (u8, device, [n_views][units of the
+ * box]; zeroed by the call first; plain stores of 1, no atomics).  A point with a non-finite bound touches nothing (nothing
+ * non-finite is converted to an integer).  A point whose range reaches outside the box marks the part inside and adds 1 to
+ * *outside (one device int; never zeroed by the call: the caller zeroes it and checks it is 0).  n_views = 0 does nothing.
+ * Errors: ADFP_E_ARG for a null pointer, n_views < 0, H or W < 1, stride < 1, fx or fy 0 or non-finite, cx or cy non-finite,
+ * sdf_trunc < 0 or non-finite, unit_length <= 0 or non-finite, depth_trunc <= 0, unit_dim < 1; ADFP_E_UNSUPPORTED for H or
+ * W > 32768 and the box above. */
+int adfp_refuse_touch(const float* depth, long long n_views, int H, int W, const double* c2w, double fx, double fy, double cx, double cy,
+                      int stride, float depth_trunc, double sdf_trunc, double unit_length, const int unit_lo[3], const int unit_dim[3],
+                      unsigned char* touched, int* outside, void* stream);
+/* Unit-gated integration of a chunk of views (IntegrateWithDepthToCameraDistanceMultiplier as we read it), in place on tsdf and
+ * weight (f32, device, the box's lattice).  units [n_units] (int32, device): the unit ids to visit (ids outside the box are
+ * skipped); normally those that some view of the chunk touched.  For every voxel of a listed unit and for each view k of
+ * [0, n_views) IN ORDER with touched[k][unit] != 0 (so that chunking never changes a bit), with (x, y, z) the voxel centre
+ * ((k_c + 0.5) voxel in f64, rounded to f32) and w2c [n_views][12] (f32, device; inv(pose) in f64 rounded to f32), all in f32:
+ *   cam = ((r0 x + r1 y) + r2 z) + t per row; cam.z <= 0 (or NaN) skips the view;
+ *   u_f = ((cam.x fx) / cam.z + cx) + 0.5f, v_f likewise; the voxel is used only if 0.0001 <= u_f < W - 0.0001 and
+ *   0.0001 <= v_f < H - 0.0001 (W - 0.0001f in f32); u = (int)u_f, v = (int)v_f;
+ *   d = depth[k][v][u]; a d outside (0, depth_trunc] is no observation;
+ *   sdf = (d - cam.z) * sqrtf((du du + dv dv) + 1), du = (u - cx) / fx, dv = (v - cy) / fy (correctly rounded sqrt and divisions);
+ *   if sdf > -sdf_trunc: t = fminf(1, sdf * (1 / sdf_trunc)), tsdf = (tsdf w + t) / (w + 1), w = w + 1.
+ * Voxels of units not listed keep their values.  n_units = 0 or n_views = 0 does nothing.  Errors: ADFP_E_ARG for a null pointer,
+ * n_units or n_views < 0, H or W < 1, voxel or sdf_trunc <= 0 or non-finite, depth_trunc <= 0, fx or fy 0 or non-finite, cx or cy
+ * non-finite, unit_dim < 1; ADFP_E_UNSUPPORTED for n_units above the box's unit count, n_views > 65536, H or W > 32768 and the box
+ * above. */
+int adfp_refuse_integrate(float* tsdf, float* weight, const int unit_lo[3], const int unit_dim[3], double voxel, const int* units,
+                          long long n_units, const float* depth, const float* w2c, const unsigned char* touched, long long n_views, int H,
+                          int W, float fx, float fy, float cx, float cy, float sdf_trunc, float depth_trunc, void* stream);
+/* open3d's PointCloud::voxel_down_sample as we read it, over points [n][3] (f64, device) whose bounds the caller passes
+ * (min_bound, max_bound: HOST f64 [3], the exact per-axis minimum and maximum of the points): vmin = min_bound - voxel_size * 0.5,
+ * cells per axis N_c = floor((max_bound_c - vmin_c) / voxel_size) + 1 (more than 2^21 is ADFP_E_UNSUPPORTED), a point's cell
+ * i_c = floor((p_c - vmin_c) / voxel_size), its key (i_0 N_1 + i_1) N_2 + i_2.  The points are sorted stably by key with
+ * adfp_sort_pairs, in passes of 31 key bits from the lowest when the key is wider.  out [n][3] (f64, device, capacity n) gets one
+ * point per occupied cell in ascending key order: the f64 sum of its points, in input order, over their count (each component
+ * divided); counts [n] (int32) the counts; total (one device long long) the number of cells.  Deterministic: no atomics decide
+ * anything.  Workspace: adfp_voxel_down_sample_workspace_bytes(n) = 8 n + 5 x 4 n + 4 T + 8 T + adfp_sort_workspace_bytes(n),
+ * each rounded up to 256, T = ceil(n / 1024); 0 for n <= 0.  n = 0 writes total = 0.  Errors: ADFP_E_ARG for a null pointer, n < 0,
+ * voxel_size <= 0 or non-finite, non-finite bounds or min_bound > max_bound; ADFP_E_UNSUPPORTED for n > 2^31 - 1025;
+ * ADFP_E_WORKSPACE. */
+size_t adfp_voxel_down_sample_workspace_bytes(long long n);
+int adfp_voxel_down_sample(const double* points, long long n, double voxel_size, const double min_bound[3], const double max_bound[3],
+                           void* workspace, size_t workspace_bytes, double* out, int* counts, long long* total, void* stream);
 
 #ifdef __cplusplus
 }
