@@ -8,7 +8,13 @@ in the reference's 100 000-ray batches.  One "step" = one full frame (307 200 ra
 region; the per-call layout conversions of my path (grid relayout, weight packing) are
 invalidated every step so that they are INSIDE the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes the outputs if ``--dump-outputs``
+is given and prints the result line.  ``--full`` adds, after that and before the line is printed, every other leg this file knows
+(`weak`, `config.shard_model`, `strong`, `train_allreduce`, `roofline`, the exact-f32 and x20-grid frames, `sustained`, the other
+configurations, `torch_gpu_baseline`, `cpu_baseline` and the parity against the oracle); ``--no-extra``, ``--no-stage-timing``,
+``--no-shard-model`` and ``--cpu-rays`` trim a ``--full`` run and change nothing in a plain one.
 
 ``--dump-outputs DIR``: after the timed steps, rank 0 writes the images the last timed step returned (what a caller of
 ``Renderer.render_img`` receives) as ``DIR/depth.npy``, ``DIR/uncertainty.npy`` and ``DIR/color.npy`` in float32 (6 MB).  The
@@ -23,11 +29,11 @@ Headline at every N ("strong" scaling: the work of a step is ONE 640x480 frame w
 ``Renderer.render_img``; at N > 1 it is the same frame RAY-SHARDED (attentive_dfprior_amd.dist.render_img_sharded: rank r renders the
 contiguous pixel range [r HW/N, (r+1) HW/N) with the far clamps of the reference's 100 000-ray batches taken over the whole frame, ONE
 packed all-gather of 28 B per ray hands every rank the images -- bit for bit render_img's) with the all-gather INSIDE the timed region;
-value = rays of the frame x steps / max-over-ranks time.  `weak` (N > 1) keeps the round-1..4 headline beside it: one whole frame per
-rank, no data-path collective.  `config.shard_model` (N = 1) times a 1/2, 1/4 and 1/8 shard of the frame on the one GPU, per-step fixed
-costs included, and states the efficiency bound t(full) / (k t(1/k)) they imply for N = k.
+value = rays of the frame x steps / max-over-ranks time.  With ``--full``, `weak` (N > 1) keeps the round-1..4 headline beside it: one
+whole frame per rank, no data-path collective.  `config.shard_model` (N = 1, ``--full``) times a 1/2, 1/4 and 1/8 shard of the frame on
+the one GPU, per-step fixed costs included, and states the efficiency bound t(full) / (k t(1/k)) they imply for N = k.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line with the contract fields; with ``--full`` also
   roofline        dominant kernel (colour decoder): executed-MFMA FLOP and algorithmic FLOP per launch / HIP-event
                   time of that kernel alone on the launch stream
   roofline_tsdf   the HBM-side trilerp stage (k_tsdf): 32 algorithmic bytes per sample (room0: cache-resident)
@@ -73,10 +79,12 @@ def parse():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--scene', default='room0')
-    ap.add_argument('--cpu-rays', type=int, default=20000, help='ray sample of the CPU baseline leg (0 = skip)')
-    ap.add_argument('--no-stage-timing', action='store_true')
-    ap.add_argument('--no-shard-model', action='store_true', help='skip config.shard_model (its shard-sized launches would mix into a kernel-trace profile of the timed loop)')
-    ap.add_argument('--no-extra', action='store_true', help='headline + roofline only (skip sustained / config5 / torch-gpu / dist legs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every other leg (scaling, roofline, other precisions and configurations, baselines, parity)')
+    ap.add_argument('--cpu-rays', type=int, default=20000, help='--full: ray sample of the CPU baseline leg (0 = skip)')
+    ap.add_argument('--no-stage-timing', action='store_true', help='--full: skip the per-kernel timing (roofline)')
+    ap.add_argument('--no-shard-model', action='store_true', help='--full: skip config.shard_model (its shard-sized launches would mix into a kernel-trace profile of the timed loop)')
+    ap.add_argument('--no-extra', action='store_true', help='--full: headline + roofline only (skip sustained / config5 / torch-gpu / dist legs)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write the last timed step\'s depth / uncertainty / colour images to DIR/<name>.npy (float32)')
     args = ap.parse_args()
@@ -395,13 +403,14 @@ def main():
         'source_hash': source_hash(),
     }
 
-    if n_gpus > 1:
+    # ---- --full only, from here to the result line: every leg beyond the headline ---------------------------
+    if args.full and n_gpus > 1:
         # the round-1..4 headline, kept beside the sharded one: one whole frame PER RANK (its own pose), no data-path collective
         el_w, _ = timed_loop(frame_step, max(2, min(args.steps, 5)), 1)
         result['weak'] = {'value': n_gpus * n_rays * max(2, min(args.steps, 5)) / el_w, 'unit': 'rays/s', 'n_gpus': n_gpus, 'scaling': 'weak',
                           'ms_per_step': el_w / max(2, min(args.steps, 5)) * 1e3,
                           'workload': 'one whole 640x480 frame per rank per step (one pose per rank), no data-path collective'}
-    elif rank == 0 and not args.no_shard_model:
+    elif args.full and rank == 0 and not args.no_shard_model:
         try:
             result['config']['shard_model'] = shard_model(rend, dec, scene, tsdf_bnds, c2w, gt_depth, dev, n_rays, ms_per_step)
             result['config']['k8_speedup_bound_incl_gather'] = result['config']['shard_model']['k8']['speedup_bound_incl_gather']
@@ -409,7 +418,7 @@ def main():
             result['config']['shard_model'] = {'error': repr(e)[:300]}
 
     # ---- legs every rank takes part in ---------------------------------------------------------------------
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         own_group = False
         # RCCL prints its version banner on C-level stdout when the first communicator comes up: keep stdout = the ONE
         # JSON line by pointing fd 1 at stderr for the duration of these legs (and flushing libc's buffer before it returns)
@@ -445,9 +454,9 @@ def main():
             result.update(legs)
 
     # ---- rank-0 legs -----------------------------------------------------------------------------------------
-    if rank == 0 and not args.no_stage_timing:
+    if args.full and rank == 0 and not args.no_stage_timing:
         result.update(stage_timing(L, _lib, rend, dec, scene, tsdf_bnds, c2w, gt_depth, dev, NS, NF))
-    if rank == 0 and n_gpus == 1 and not args.no_extra:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_extra:
         if os.environ.get('ADFP_MATH', 'f16x3') == 'f16x3':
             # the same frame with every product on the exact f32-input MFMA (ADFP_MATH=f32), for reference:
             # the f16x3 split reproduces f32 products to 2^-22, this is the bit-exact mode
@@ -497,7 +506,7 @@ def main():
                 result[name] = leg()
             except Exception as e:
                 result[name] = {'error': repr(e)[:300]}
-    if rank == 0 and n_gpus == 1 and args.cpu_rays > 0:
+    if args.full and rank == 0 and n_gpus == 1 and args.cpu_rays > 0:
         result.update(cpu_leg(rend, dec, sd, scene, tsdf_bnds, c2w, gt_depth, depth_img, color_img, dev, NS, NF, args.cpu_rays))
     if rank == 0:
         # the evidence a reader of the line needs, inside the objects the driver's record keeps whole (`config`, `roofline`)

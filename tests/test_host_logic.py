@@ -202,3 +202,16 @@ def test_limiter_model_input_is_this_build():
     assert mix['mfma'] == 360 and 1500 < mix['valu'] < 2600 and mix['lds'] > 100      # one 32-point tile, both networks: 2 x 180 MFMAs
     text = open(os.path.join(root, 'profiles', 'r06_isa_mix_lc16.txt')).read()
     assert text.index('[tile loop only]') < text.index('12DecodeLCArgs:')               # the loop first, the whole kernel after it
+
+
+def test_bench_full_is_opt_in(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs the headline alone; every other leg waits for `--full`."""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
+    assert bench.parse().full is True
