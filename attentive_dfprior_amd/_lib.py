@@ -301,6 +301,8 @@ SYMBOLS = [
     ('adfp_voxel_down_sample_workspace_bytes', C.c_size_t, [C.c_longlong]),
     ('adfp_voxel_down_sample', C.c_int, [C.c_void_p, C.c_longlong, C.c_double, C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3),
                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('adfp_keyframe_overlap', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER

@@ -108,6 +108,12 @@ def get_sample_uv(H0, H1, W0, W1, n, depth, color, device='cuda:0'):
     return select_uv(ii, jj, n, depth, color, device=device)
 
 
+def draw_pixels(H0, H1, W0, W1, n, device):
+    """The pixel draw of get_sample_uv (src/common.py:101-102): ONE ``torch.randint`` of shape [n] over the window's pixels in
+    row-major order, on ``device``.  get_samples and the Mapper's keyframe selection (keyframes.py) draw through here."""
+    return torch.randint((H1 - H0) * (W1 - W0), (n,), device=device).clamp(0, (H1 - H0) * (W1 - W0))
+
+
 def get_samples(H0, H1, W0, W1, n, H, W, fx, fy, cx, cy, c2w, depth, color, device):
     """n random rays of one frame with their depth / colour (reference src/common.py:127-136).
 
@@ -119,7 +125,7 @@ def get_samples(H0, H1, W0, W1, n, H, W, fx, fy, cx, cy, c2w, depth, color, devi
             and depth.dtype == torch.float32 and color.dtype == torch.float32 and depth.dim() == 2 and tuple(color.shape) == (depth.shape[0], depth.shape[1], 3)):
         Hd, Wd = depth.shape
         with _lib.device_guard(depth.device):
-            pick = torch.randint((H1 - H0) * (W1 - W0), (n,), device=depth.device).clamp(0, (H1 - H0) * (W1 - W0))     # src/common.py:101-102
+            pick = draw_pixels(H0, H1, W0, W1, n, depth.device)
             d, c = depth.contiguous(), color.contiguous()
             i = torch.empty((n,), dtype=torch.float32, device=depth.device)
             j = torch.empty_like(i)

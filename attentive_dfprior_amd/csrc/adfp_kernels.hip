@@ -282,17 +282,22 @@ __global__ void k_get_rays(int H, int W, float fx, float fy, float cx, float cy,
 // a2: get_rays_from_uv (common.py:76-91): the rays through n given pixels, and the gradient w.r.t. the camera pose that
 // the Tracker and the Mapper's bundle adjustment take through them (src/Tracker.py:97, src/Mapper.py:425)
 // =====================================================================================
+// The ray through pixel (pi, pj) (column, row) of the camera c2w (rows 0-2 of a row-major [4,4] or [3,4]); also the sample points of
+// the Mapper's keyframe selection (adfp_keyframes.h)
+ADFP_DEV void ray_from_uv(float pi, float pj, float fx, float fy, float cx, float cy, const float* __restrict__ c2w, float* ro, float* rd) {
+    const float dx = (pi - cx) / fx, dy = -(pj - cy) / fy, dz = -1.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        // torch.sum(dirs * c2w[:3,:3], -1): products then left-to-right adds
+        rd[k] = __fadd_rn(__fadd_rn(__fmul_rn(dx, c2w[4 * k + 0]), __fmul_rn(dy, c2w[4 * k + 1])), __fmul_rn(dz, c2w[4 * k + 2]));
+        ro[k] = c2w[4 * k + 3];
+    }
+}
 __global__ void k_rays_from_uv(const float* __restrict__ pi, const float* __restrict__ pj, int n, float fx, float fy, float cx, float cy,
                                const float* __restrict__ c2w, float* __restrict__ ro, float* __restrict__ rd) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    const float dx = (pi[idx] - cx) / fx, dy = -(pj[idx] - cy) / fy, dz = -1.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        // torch.sum(dirs * c2w[:3,:3], -1): products then left-to-right adds
-        rd[3 * idx + k] = __fadd_rn(__fadd_rn(__fmul_rn(dx, c2w[4 * k + 0]), __fmul_rn(dy, c2w[4 * k + 1])), __fmul_rn(dz, c2w[4 * k + 2]));
-        ro[3 * idx + k] = c2w[4 * k + 3];
-    }
+    ray_from_uv(pi[idx], pj[idx], fx, fy, cx, cy, c2w, ro + 3 * idx, rd + 3 * idx);
 }
 // g_c2w[k][m] = sum_n g_d[n][k] * dirs[n][m] (m < 3), g_c2w[k][3] = sum_n g_o[n][k]; rows 3 of the 4x4 get zero.
 // One workgroup: pixel batches are a few hundred to a few thousand rays.
@@ -3878,3 +3883,6 @@ int adfp_voxel_down_sample(const double* points, long long n, double voxel_size,
     ADFP_CHECK_LAUNCH();
     return 0;
 }
+
+// ---- the Mapper's keyframe selection (adfp_keyframes.h) ----
+#include "adfp_keyframes.h"

@@ -920,6 +920,24 @@ int adfp_refuse_integrate(float* tsdf, float* weight, const int unit_lo[3], cons
 size_t adfp_voxel_down_sample_workspace_bytes(long long n);
 int adfp_voxel_down_sample(const double* points, long long n, double voxel_size, const double min_bound[3], const double max_bound[3],
                            void* workspace, size_t workspace_bytes, double* out, int* counts, long long* total, void* stream);
+/* ---- The Mapper's overlap keyframe selection (src/Mapper.py:160-222, Mapper.keyframe_selection_overlap) ----------------------
+ * counts[k] (int32, device, [K]) = how many of the current frame's n * N_samples sample points keyframe k sees, in ONE launch.
+ * Sample points: idx [n] (int64, device) are the caller's one torch.randint draw over H W (pixel idx[t] = row idx / W, column
+ * idx % W of the [H,W] f32 depth_img); ray t is adfp_rays_from_uv's through that pixel under c2w (device, row-major [4,4] f32, with
+ * fx .. cy rounded to f32); sample s of N_samples has t_s = torch.linspace(0, 1, N_samples)[s] (torch's CPU rule: step =
+ * 1 / (N_samples - 1) in f32, t_s = fma(step, s, 0) for s < N_samples / 2, else fma(-step, N_samples - 1 - s, 1)); with d the
+ * pixel's depth, near = d 0.8, far = d + 0.5, z = near (1 - t_s) + far t_s and point = o + d_ray z, every other product and sum
+ * rounded on its own in f32.  Point q = t N_samples + s goes to pts_out [q][3] (f32, device) when pts_out is not NULL.
+ * Inside test per keyframe: w2c = inverse of poses[k] (row-major [4,4] f32, device; inverted in f64 and rounded to f32);
+ * cam = ((w0 x + w1 y) + w2 z) + w3 per row of w2c in f32; X = -cam.x; in f64: Z = cam.z + 1e-5, u = (fx X + cx cam.z) / Z,
+ * v = (fy cam.y + cy cam.z) / Z, both rounded to f32; inside = edge < u < W - edge and edge < v < H - edge (in f32) and Z < 0.
+ * A drawn index outside [0, H W) gives a NaN point (inside nowhere); a singular pose sees nothing.  Deterministic (no atomics).
+ * K = 0 launches nothing (pts_out is not written).  Errors: ADFP_E_ARG for K < 0, n <= 0, N_samples < 1, H or W < 1, a null idx,
+ * depth_img, c2w or counts, null poses with K > 0, fx or fy 0 or non-finite, cx or cy non-finite; ADFP_E_UNSUPPORTED for
+ * n N_samples above 2^31 - 4097. */
+int adfp_keyframe_overlap(const long long* idx, int n, const float* depth_img, int H, int W, const float* c2w, int N_samples,
+                          const float* poses, int K, double fx, double fy, double cx, double cy, int edge, int* counts, float* pts_out,
+                          void* stream);
 
 #ifdef __cplusplus
 }
