@@ -303,6 +303,25 @@ SYMBOLS = [
                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('adfp_keyframe_overlap', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                         C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # mesh clean-up
+    ('adfp_mesh_seen_mask', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                      C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ('adfp_mesh_face_labels_workspace_bytes', C.c_size_t, [C.c_longlong]),
+    ('adfp_mesh_face_labels_begin', C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p]),
+    ('adfp_mesh_face_labels_rounds', C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
+    ('adfp_mesh_component_keep_workspace_bytes', C.c_size_t, [C.c_longlong]),
+    ('adfp_mesh_component_keep', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    ('adfp_mesh_compact_workspace_bytes', C.c_size_t, [C.c_longlong, C.c_longlong]),
+    ('adfp_mesh_compact_plan', C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ('adfp_mesh_compact_emit', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
+    ('adfp_mesh_merge_workspace_bytes', C.c_size_t, [C.c_longlong]),
+    ('adfp_mesh_merge_plan', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ('adfp_mesh_merge_emit', C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    ('adfp_mesh_color_bytes', C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER
@@ -313,6 +332,8 @@ TRI_LEAF_DEFAULT = 4                   # ADFP_TRI_LEAF_DEFAULT
 TRI_LEAVES = (4, 8, 16)                # the leaf sizes adfp_tri_bvh_build takes
 CULL = {'none': 0, 'back': 1, 'front': 2}     # ADFP_CULL_NONE / ADFP_CULL_BACK / ADFP_CULL_FRONT
 UNIT_VOXELS = 16                        # ADFP_UNIT_VOXELS
+SEEN_RULE = {'frustum': 0, 'max_depth': 1, 'depth_test': 2}     # ADFP_SEEN_FRUSTUM / _MAX_DEPTH / _DEPTH_TEST
+LABEL_ROUNDS_MAX = 128                  # above the worst case of adfp_mesh_face_labels_rounds (2 log2(F) + 2 < 66)
 
 _lib = None
 

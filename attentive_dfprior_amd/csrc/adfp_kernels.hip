@@ -3579,7 +3579,8 @@ int adfp_cull_vertices(const double* verts, long long n_verts, const float* w2c,
     CullArgs a;
     a.v = verts; a.nv = (int)n_verts; a.w2c = w2c; a.np = (int)n_poses;
     a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.seen = seen;
-    hipLaunchKernelGGL(k_cull_seen, dim3((unsigned)((n_verts + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0,
+    a.vf = nullptr; a.depth = nullptr; a.dmax = nullptr; a.Wi = W; a.Hi = H; a.rW = 0.f; a.rH = 0.f;
+    hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_CULL_MESH>, dim3((unsigned)((n_verts + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0,
                        (hipStream_t)stream, a);
     ADFP_CHECK_LAUNCH();
     return 0;
@@ -3886,3 +3887,322 @@ int adfp_voxel_down_sample(const double* points, long long n, double voxel_size,
 
 // ---- the Mapper's keyframe selection (adfp_keyframes.h) ----
 #include "adfp_keyframes.h"
+
+// ---- mesh clean-up (adfp_meshclean.h; the seen mask is adfp_recon.h's k_cull_seen) ----
+#include "adfp_meshclean.h"
+
+static unsigned mcl_blocks(long long n) { return (unsigned)((n + ADFP_MCL_THREADS - 1) / ADFP_MCL_THREADS); }
+static long long mcl_tiles(long long n) { return (n + ADFP_MCL_TILE - 1) / ADFP_MCL_TILE; }
+static int mcl_bits(long long top) { int b = 1; while (b < 31 && (top >> b) != 0) ++b; return b; }     // top < 2^bits
+static char* mcl_take(char*& w, size_t bytes) { char* p = w; w += al256(bytes); return p; }
+// pos[i] = set flags before i, total[0] = their number; tc / to: mcl_tiles(n) entries each
+static int mcl_scan(const unsigned char* flag, long long n, unsigned* tc, long long* to, int* pos, long long* total, hipStream_t st) {
+    if (n == 0) { hipError_t e = hipMemsetAsync(total, 0, sizeof(long long), st); return e == hipSuccess ? 0 : (int)e; }
+    MclScan s; s.flag = flag; s.n = (int)n; s.ntiles = (int)mcl_tiles(n); s.tile_counts = tc; s.tile_offsets = to; s.pos = pos; s.total = total;
+    hipLaunchKernelGGL(k_mcl_tile_count, dim3((unsigned)s.ntiles), dim3(ADFP_MCL_THREADS), 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mcl_tile_scan, dim3(1), dim3(ADFP_MCL_THREADS), 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mcl_positions, dim3((unsigned)s.ntiles), dim3(ADFP_MCL_THREADS), 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" {
+
+int adfp_mesh_seen_mask(const float* verts, long long n_verts, const float* w2c, long long n_poses, int rule, const float* depth,
+                        const float* depth_max, float fx, float fy, float cx, float cy, int W, int H, unsigned char* seen, void* stream) {
+    if (n_verts < 0 || n_poses < 0 || W < 1 || H < 1) return ADFP_E_ARG;
+    if (rule != ADFP_SEEN_FRUSTUM && rule != ADFP_SEEN_MAX_DEPTH && rule != ADFP_SEEN_DEPTH_TEST) return ADFP_E_ARG;
+    if (n_verts == 0) return 0;
+    if (!verts || !seen || (n_poses > 0 && !w2c)) return ADFP_E_ARG;
+    if (n_poses > 0 && ((rule == ADFP_SEEN_MAX_DEPTH && !depth_max) || (rule == ADFP_SEEN_DEPTH_TEST && !depth))) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_poses > RECON_MAX_N / 12 || W > 32768 || H > 32768) return ADFP_E_UNSUPPORTED;
+    if (rule == ADFP_SEEN_DEPTH_TEST && (W < 2 || H < 2)) return ADFP_E_UNSUPPORTED;       // the sample grid divides by W - 1, H - 1
+    CullArgs a;
+    a.v = nullptr; a.vf = verts; a.nv = (int)n_verts; a.w2c = w2c; a.np = (int)n_poses;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.seen = seen;
+    a.depth = depth; a.dmax = depth_max; a.Wi = W; a.Hi = H;
+    a.rW = W > 1 ? 1.0f / (float)(W - 1) : 0.f; a.rH = H > 1 ? 1.0f / (float)(H - 1) : 0.f;
+    const dim3 grid(mcl_blocks(n_verts)), block(ADFP_NN_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (rule == ADFP_SEEN_FRUSTUM) hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_FRUSTUM>, grid, block, 0, st, a);
+    else if (rule == ADFP_SEEN_MAX_DEPTH) hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_MAX_DEPTH>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_DEPTH_TEST>, grid, block, 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+static bool mcl_mesh_too_large(long long n_verts, long long n_faces) { return n_verts > RECON_MAX_N || n_faces > RECON_MAX_N / 3; }
+
+size_t adfp_mesh_face_labels_workspace_bytes(long long n_faces) {
+    if (n_faces <= 0 || n_faces > RECON_MAX_N / 3) return 0;
+    const size_t e = (size_t)n_faces * 3;
+    return 6 * al256(e * 4) + al256(adfp_sort_workspace_bytes((long long)e));
+}
+
+int adfp_mesh_face_labels_begin(const int* faces, long long n_faces, long long n_verts, const unsigned char* keep, int* mate, int* labels,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_faces < 0 || n_verts < 0) return ADFP_E_ARG;
+    if (n_faces == 0) return 0;
+    if (!faces || !mate || !labels || !workspace) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_face_labels_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    const long long ne = 3 * n_faces;
+    char* w = (char*)workspace;
+    int* lo = (int*)mcl_take(w, (size_t)ne * 4);
+    int* hi = (int*)mcl_take(w, (size_t)ne * 4);
+    int* key = (int*)mcl_take(w, (size_t)ne * 4);
+    int* key_tmp = (int*)mcl_take(w, (size_t)ne * 4);
+    int* perm = (int*)mcl_take(w, (size_t)ne * 4);
+    int* perm_tmp = (int*)mcl_take(w, (size_t)ne * 4);
+    const size_t swb = adfp_sort_workspace_bytes(ne);
+    hipStream_t st = (hipStream_t)stream;
+    const int bits = mcl_bits(n_verts);                                     // keys lie in [0, n_verts]
+    hipLaunchKernelGGL(k_mcl_edges, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, (int)n_verts, keep, lo, hi,
+                       perm, labels);
+    ADFP_CHECK_LAUNCH();
+    const int* src[2] = {hi, lo};                                          // by the larger vertex, then (stable) by the smaller
+    for (int ps = 0; ps < 2; ++ps) {
+        hipLaunchKernelGGL(k_mcl_gather, dim3(mcl_blocks(ne)), dim3(ADFP_MCL_THREADS), 0, st, src[ps], perm, (int)ne, key);
+        ADFP_CHECK_LAUNCH();
+        int rc = adfp_sort_pairs(key, perm, key_tmp, perm_tmp, ne, bits, w, swb, stream);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_mcl_mates, dim3(mcl_blocks(ne)), dim3(ADFP_MCL_THREADS), 0, st, lo, hi, perm, (int)ne, (int)n_verts, mate);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_mesh_face_labels_rounds(const int* mate, int* labels, long long n_faces, int rounds, int* changed, void* stream) {
+    if (n_faces < 0 || rounds < 1 || !changed) return ADFP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_faces == 0) { hipError_t e = hipMemsetAsync(changed, 0, sizeof(int), st); return e == hipSuccess ? 0 : (int)e; }
+    if (!mate || !labels) return ADFP_E_ARG;
+    if (n_faces > RECON_MAX_N / 3) return ADFP_E_UNSUPPORTED;
+    for (int r = 0; r < rounds; ++r) {
+        hipError_t e = hipMemsetAsync(changed, 0, sizeof(int), st);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(k_mcl_hook, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, mate, labels, (int)n_faces, changed);
+        ADFP_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_mcl_compress, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, labels, (int)n_faces);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+#define MCL_BEST_BLOCKS 1024
+size_t adfp_mesh_component_keep_workspace_bytes(long long n_faces) {
+    if (n_faces <= 0 || n_faces > RECON_MAX_N / 3) return 0;
+    const size_t f = (size_t)n_faces, T = (size_t)mcl_tiles(n_faces);
+    return 2 * al256(f * 8) + 4 * al256(f * 4) + al256(T) + 2 * al256(T * 8) + al256(MCL_BEST_BLOCKS * 8) + al256(MCL_BEST_BLOCKS * 4) + 2 * 256 +
+           al256(adfp_sort_workspace_bytes(n_faces));
+}
+
+int adfp_mesh_component_keep(const float* verts, long long n_verts, const int* faces, long long n_faces, const int* labels, int largest,
+                             double threshold, unsigned char* keep, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_faces < 0 || n_verts < 0 || (largest != 0 && largest != 1) || (!largest && threshold != threshold)) return ADFP_E_ARG;
+    if (n_faces == 0) return 0;
+    if (!faces || !labels || !keep || !workspace || (n_verts > 0 && !verts)) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_component_keep_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    const size_t f = (size_t)n_faces, T = (size_t)mcl_tiles(n_faces);
+    char* w = (char*)workspace;
+    double* area = (double*)mcl_take(w, f * 8);
+    double* comp_area = (double*)mcl_take(w, f * 8);
+    int* key = (int*)mcl_take(w, f * 4);
+    int* key_tmp = (int*)mcl_take(w, f * 4);
+    int* perm = (int*)mcl_take(w, f * 4);
+    int* perm_tmp = (int*)mcl_take(w, f * 4);
+    MclSeg s;
+    s.tile_flag = (unsigned char*)mcl_take(w, T);
+    s.tile_sum = (double*)mcl_take(w, T * 8);
+    s.carry = (double*)mcl_take(w, T * 8);
+    double* part_val = (double*)mcl_take(w, MCL_BEST_BLOCKS * 8);
+    int* part_lab = (int*)mcl_take(w, MCL_BEST_BLOCKS * 4);
+    double* best_val = (double*)mcl_take(w, 8);
+    int* best_lab = (int*)mcl_take(w, 4);
+    hipStream_t st = (hipStream_t)stream;
+    const int nf = (int)n_faces;
+    const dim3 grid(mcl_blocks(n_faces)), block(ADFP_MCL_THREADS);
+    hipLaunchKernelGGL(k_mcl_areas, grid, block, 0, st, verts, faces, nf, labels, area, key, perm);
+    ADFP_CHECK_LAUNCH();
+    int rc = adfp_sort_pairs(key, perm, key_tmp, perm_tmp, n_faces, mcl_bits(n_faces), w, adfp_sort_workspace_bytes(n_faces), stream);
+    if (rc) return rc;
+    s.key = key; s.perm = perm; s.area = area; s.n = nf; s.nf = nf; s.ntiles = (int)T; s.comp_area = comp_area;
+    hipLaunchKernelGGL(k_mcl_seg<0>, dim3((unsigned)T), block, 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mcl_seg_carry, dim3(1), dim3(64), 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mcl_seg<1>, dim3((unsigned)T), block, 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    if (largest) {
+        MclBest b;
+        const unsigned nb = grid.x < MCL_BEST_BLOCKS ? grid.x : MCL_BEST_BLOCKS;
+        b.labels = labels; b.val = comp_area; b.lab = nullptr; b.n = nf; b.out_val = part_val; b.out_lab = part_lab;
+        hipLaunchKernelGGL(k_mcl_best, dim3(nb), block, 0, st, b);
+        ADFP_CHECK_LAUNCH();
+        b.labels = nullptr; b.val = part_val; b.lab = part_lab; b.n = (int)nb; b.out_val = best_val; b.out_lab = best_lab;
+        hipLaunchKernelGGL(k_mcl_best, dim3(1), block, 0, st, b);
+        ADFP_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_mcl_keep, grid, block, 0, st, labels, nf, comp_area, largest ? best_lab : (const int*)nullptr, threshold, keep);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+// compaction workspace: fkeep [F], used [V] (bytes), fpos [F], vpos [V] (ints), tile counts / offsets for the longer of the two
+struct MclCompact { unsigned char* fkeep; unsigned char* used; int* fpos; int* vpos; unsigned* tc; long long* to; };
+static MclCompact mcl_compact_carve(void* workspace, long long nv, long long nf) {
+    MclCompact c;
+    char* w = (char*)workspace;
+    const size_t T = (size_t)mcl_tiles(nv > nf ? nv : nf);
+    c.fkeep = (unsigned char*)mcl_take(w, (size_t)nf);
+    c.used = (unsigned char*)mcl_take(w, (size_t)nv);
+    c.fpos = (int*)mcl_take(w, (size_t)nf * 4);
+    c.vpos = (int*)mcl_take(w, (size_t)nv * 4);
+    c.tc = (unsigned*)mcl_take(w, T * 4);
+    c.to = (long long*)mcl_take(w, T * 8);
+    return c;
+}
+size_t adfp_mesh_compact_workspace_bytes(long long n_verts, long long n_faces) {
+    if (n_verts < 0 || n_faces < 0 || mcl_mesh_too_large(n_verts, n_faces)) return 0;
+    const size_t T = (size_t)mcl_tiles(n_verts > n_faces ? n_verts : n_faces);
+    return al256((size_t)n_faces) + al256((size_t)n_verts) + al256((size_t)n_faces * 4) + al256((size_t)n_verts * 4) + al256(T * 4) + al256(T * 8);
+}
+
+int adfp_mesh_compact_plan(const int* faces, long long n_faces, long long n_verts, const unsigned char* keep, void* workspace,
+                           size_t workspace_bytes, long long* totals, void* stream) {
+    if (n_faces < 0 || n_verts < 0 || !totals) return ADFP_E_ARG;
+    if (n_faces > 0 && (!faces || !keep)) return ADFP_E_ARG;
+    if ((n_faces > 0 || n_verts > 0) && !workspace) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_compact_workspace_bytes(n_verts, n_faces)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const MclCompact c = mcl_compact_carve(workspace, n_verts, n_faces);
+    if (n_verts > 0) { hipError_t e = hipMemsetAsync(c.used, 0, (size_t)n_verts, st); if (e != hipSuccess) return (int)e; }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_mcl_mark, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, (int)n_verts, keep, c.fkeep,
+                           c.used);
+        ADFP_CHECK_LAUNCH();
+    }
+    int rc = mcl_scan(c.used, n_verts, c.tc, c.to, c.vpos, totals, st);
+    if (rc) return rc;
+    return mcl_scan(c.fkeep, n_faces, c.tc, c.to, c.fpos, totals + 1, st);
+}
+
+int adfp_mesh_compact_emit(const float* verts, long long n_verts, const int* faces, long long n_faces, const void* workspace,
+                           size_t workspace_bytes, float* verts_out, long long n_verts_out, int* faces_out, long long n_faces_out, void* stream) {
+    if (n_faces < 0 || n_verts < 0 || n_verts_out < 0 || n_faces_out < 0 || n_verts_out > n_verts || n_faces_out > n_faces) return ADFP_E_ARG;
+    if (n_verts_out == 0 && n_faces_out == 0) return 0;
+    if (!workspace || !verts || (n_faces_out > 0 && (!faces || !faces_out)) || (n_verts_out > 0 && !verts_out)) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_compact_workspace_bytes(n_verts, n_faces)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const MclCompact c = mcl_compact_carve((void*)workspace, n_verts, n_faces);
+    if (n_verts_out > 0) {
+        hipLaunchKernelGGL(k_mcl_take_rows, dim3(mcl_blocks(n_verts)), dim3(ADFP_MCL_THREADS), 0, st, verts, (const unsigned char*)nullptr,
+                           (int)n_verts, c.used, c.vpos, verts_out, (unsigned char*)nullptr);
+        ADFP_CHECK_LAUNCH();
+    }
+    if (n_faces_out > 0) {
+        hipLaunchKernelGGL(k_mcl_take_faces, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, c.fkeep, c.fpos, c.vpos,
+                           (int)n_verts, faces_out);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// merge workspace: key, key_tmp, perm, perm_tmp, gid, first, rep, pos, vmap [V] ints, head, survive [V] bytes, tiles, the sort's
+struct MclMerge { int* key; int* key_tmp; int* perm; int* perm_tmp; int* gid; int* first; int* rep; int* pos; int* vmap;
+                  unsigned char* head; unsigned char* survive; unsigned* tc; long long* to; void* sort_ws; };
+static MclMerge mcl_merge_carve(void* workspace, long long nv) {
+    MclMerge m;
+    char* w = (char*)workspace;
+    int** ints[9] = {&m.key, &m.key_tmp, &m.perm, &m.perm_tmp, &m.gid, &m.first, &m.rep, &m.pos, &m.vmap};
+    for (int k = 0; k < 9; ++k) *ints[k] = (int*)mcl_take(w, (size_t)nv * 4);
+    m.head = (unsigned char*)mcl_take(w, (size_t)nv);
+    m.survive = (unsigned char*)mcl_take(w, (size_t)nv);
+    m.tc = (unsigned*)mcl_take(w, (size_t)mcl_tiles(nv) * 4);
+    m.to = (long long*)mcl_take(w, (size_t)mcl_tiles(nv) * 8);
+    m.sort_ws = w;
+    return m;
+}
+size_t adfp_mesh_merge_workspace_bytes(long long n_verts) {
+    if (n_verts <= 0 || n_verts > RECON_MAX_N) return 0;
+    const size_t v = (size_t)n_verts, T = (size_t)mcl_tiles(n_verts);
+    return 9 * al256(v * 4) + 2 * al256(v) + al256(T * 4) + al256(T * 8) + al256(adfp_sort_workspace_bytes(n_verts));
+}
+
+int adfp_mesh_merge_plan(const float* verts, long long n_verts, void* workspace, size_t workspace_bytes, long long* total, void* stream) {
+    if (n_verts < 0 || !total) return ADFP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_verts == 0) { hipError_t e = hipMemsetAsync(total, 0, sizeof(long long), st); return e == hipSuccess ? 0 : (int)e; }
+    if (!verts || !workspace) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_merge_workspace_bytes(n_verts)) return ADFP_E_WORKSPACE;
+    const MclMerge m = mcl_merge_carve(workspace, n_verts);
+    const int n = (int)n_verts;
+    const dim3 grid(mcl_blocks(n_verts)), block(ADFP_MCL_THREADS);
+    const unsigned* bits = (const unsigned*)verts;
+    const size_t swb = adfp_sort_workspace_bytes(n_verts);
+    hipLaunchKernelGGL(k_mcl_iota, grid, block, 0, st, m.perm, n);
+    ADFP_CHECK_LAUNCH();
+    for (int ps = 0; ps < 6; ++ps) {                       // 96 key bits in stable passes of 16, the lowest first
+        hipLaunchKernelGGL(k_mcl_bits_key, grid, block, 0, st, bits, m.perm, n, 2 - ps / 2, 16 * (ps & 1), m.key);
+        ADFP_CHECK_LAUNCH();
+        int rc = adfp_sort_pairs(m.key, m.perm, m.key_tmp, m.perm_tmp, n_verts, 16, m.sort_ws, swb, stream);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_mcl_heads, grid, block, 0, st, bits, m.perm, n, m.head);
+    ADFP_CHECK_LAUNCH();
+    int rc = mcl_scan(m.head, n_verts, m.tc, m.to, m.gid, total, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mcl_group_first, grid, block, 0, st, m.perm, n, m.head, m.gid, m.first);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mcl_rep, grid, block, 0, st, m.perm, n, m.head, m.gid, m.first, m.rep, m.survive);
+    ADFP_CHECK_LAUNCH();
+    rc = mcl_scan(m.survive, n_verts, m.tc, m.to, m.pos, total, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mcl_vmap, grid, block, 0, st, m.rep, m.pos, n, m.vmap);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_mesh_merge_emit(const float* verts, const unsigned char* colors, long long n_verts, const int* faces, long long n_faces,
+                         const void* workspace, size_t workspace_bytes, float* verts_out, unsigned char* colors_out, long long n_verts_out,
+                         int* faces_out, void* stream) {
+    if (n_verts < 0 || n_faces < 0 || n_verts_out < 0 || n_verts_out > n_verts) return ADFP_E_ARG;
+    if (n_verts == 0 && n_faces == 0) return 0;
+    if ((n_verts > 0 && (!workspace || !verts || !verts_out)) || (n_faces > 0 && (!faces || !faces_out))) return ADFP_E_ARG;
+    if ((colors != nullptr) != (colors_out != nullptr)) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_merge_workspace_bytes(n_verts)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    MclMerge m;
+    memset(&m, 0, sizeof(m));
+    if (n_verts > 0) {
+        m = mcl_merge_carve((void*)workspace, n_verts);
+        hipLaunchKernelGGL(k_mcl_take_rows, dim3(mcl_blocks(n_verts)), dim3(ADFP_MCL_THREADS), 0, st, verts, colors, (int)n_verts, m.survive, m.pos,
+                           verts_out, colors_out);
+        ADFP_CHECK_LAUNCH();
+    }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_mcl_take_faces, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces,
+                           (const unsigned char*)nullptr, (const int*)nullptr, m.vmap, (int)n_verts, faces_out);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int adfp_mesh_color_bytes(const float* rgb, long long n, int stride, unsigned char* out, void* stream) {
+    if (n < 0 || stride < 3) return ADFP_E_ARG;
+    if (n == 0) return 0;
+    if (!rgb || !out) return ADFP_E_ARG;
+    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_mcl_color_bytes, dim3(mcl_blocks(n)), dim3(ADFP_MCL_THREADS), 0, (hipStream_t)stream, rgb, n, stride, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+}   // extern "C"

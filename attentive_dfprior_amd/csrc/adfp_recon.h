@@ -454,41 +454,95 @@ __global__ __launch_bounds__(ADFP_RED_THREADS) void k_sample(SurfSampleArgs a) {
 }
 
 // ---- frustum culling ----
+// Which test k_cull_seen restates: cull_mesh.py's over f64 vertices, or one of the three branches of the Mesher's point_masks
+// (src/utils/Mesher.py:58-217, the *seen* mask only) over f32 vertices.  The values 0..2 are ADFP_SEEN_* of include/adfp.h.
+#define ADFP_CULL_RULE_CULL_MESH (-1)
+#define ADFP_CULL_RULE_FRUSTUM   0      // get_mask_use_all_frames: the frustum only
+#define ADFP_CULL_RULE_MAX_DEPTH 1      // depth_test = False: and -cam.z < dmax[k] (the caller's 1.1 max(depth_k))
+#define ADFP_CULL_RULE_DEPTH_TEST 2     // depth_test = True: and |(-cam.z) - depth_k(uv)| < 2.4 (bilinear sample)
 struct CullArgs {
     const double* v; int nv; const float* w2c; int np;     // w2c: [np][12], the top three rows of inv(c2w) (f32)
     float fx, fy, cx, cy, W, H;
     unsigned char* seen;
+    // the Mesher's rules only
+    const float* vf;                                       // [nv][3] f32 vertices
+    const float* depth; const float* dmax;                 // [np][Hi][Wi] depth images / [np] depth bounds
+    int Wi, Hi; float rW, rH;                              // rW = 1 / (W - 1), rH = 1 / (H - 1), rounded to f32 on the host
 };
 
-// does pose w (12 f32: the top three rows of inv(c2w)) project (x, y, z) into the image: cam = w [p, 1], cam.x *= -1, uv = K cam,
-// z = uv.z + 1e-5, uv /= z, 0 <= -z && 0 < u < W && 0 < v < H (cull_mesh.py:49-71, f32 as the reference computes it)
-ADFP_DEV bool cull_sees(const float* w, float x, float y, float z, float fx, float fy, float cx, float cy, float W, float H) {
+// pose w (12 f32: the top three rows of inv(c2w)) applied to (x, y, z): cam = w [p, 1], cam.x *= -1, uv = K cam, zz = uv.z + eps,
+// uv /= zz, all in f32.  Returns the frustum test.  MESHER = false: cull_mesh.py:49-71 (eps 1e-5, 0 <= -zz); true: Mesher._project
+// (eps 1e-8, zz < 0).  Z = cam.z, before eps.
+template <bool MESHER>
+ADFP_DEV bool cull_project(const float* w, float x, float y, float z, float fx, float fy, float cx, float cy, float W, float H,
+                           float& u, float& v, float& Z) {
     const float X = -(((w[0] * x + w[1] * y) + w[2] * z) + w[3]);
     const float Y = ((w[4] * x + w[5] * y) + w[6] * z) + w[7];
-    const float Z = ((w[8] * x + w[9] * y) + w[10] * z) + w[11];
-    const float zz = Z + 1e-5f;
-    const float u = (fx * X + cx * Z) / zz;
-    const float v = (fy * Y + cy * Z) / zz;
-    return 0.f <= -zz && u < W && u > 0.f && v < H && v > 0.f;
+    Z = ((w[8] * x + w[9] * y) + w[10] * z) + w[11];
+    const float zz = Z + (MESHER ? 1e-8f : 1e-5f);
+    u = (fx * X + cx * Z) / zz;
+    v = (fy * Y + cy * Z) / zz;
+    const bool front = MESHER ? zz < 0.f : 0.f <= -zz;
+    return front && u < W && u > 0.f && v < H && v > 0.f;
+}
+// does pose w project (x, y, z) into the image, by cull_mesh.py's rule
+ADFP_DEV bool cull_sees(const float* w, float x, float y, float z, float fx, float fy, float cx, float cy, float W, float H) {
+    float u, v, Z;
+    return cull_project<false>(w, x, y, z, fx, fy, cx, cy, W, H, u, v, Z);
 }
 
-// seen[i] = 1 iff some pose projects vertex i into the image (cull_sees)
+// F.grid_sample(depth[1,1,H,W], grid, 'bilinear', padding_mode='zeros', align_corners=True) at pixel (u, v), with the grid the
+// Mesher forms (Mesher.py:118-121): g = u * (1 / (W - 1)) * 2 - 1 (torch divides by a host scalar through its reciprocal),
+// ix = ((g + 1) / 2) * (W - 1), the four corner weights from the integer corners, corners outside the image contribute nothing,
+// summed nw, ne, sw, se.  Called only with 0 < u < W, 0 < v < H, so the integer conversions are in range.
+ADFP_DEV float cull_depth_sample(const float* img, float u, float v, int W, int H, float rW, float rH) {
+    const float gx = (u * rW) * 2.f - 1.f, gy = (v * rH) * 2.f - 1.f;
+    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1), iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
+    const int x0 = (int)floorf(ix), y0 = (int)floorf(iy), x1 = x0 + 1, y1 = y0 + 1;
+    const float nw = ((float)x1 - ix) * ((float)y1 - iy), ne = (ix - (float)x0) * ((float)y1 - iy);
+    const float sw = ((float)x1 - ix) * (iy - (float)y0), se = (ix - (float)x0) * (iy - (float)y0);
+    const bool xa = x0 >= 0 && x0 < W, xb = x1 >= 0 && x1 < W, ya = y0 >= 0 && y0 < H, yb = y1 >= 0 && y1 < H;
+    float out = 0.f;
+    if (xa && ya) out += img[(long long)y0 * W + x0] * nw;
+    if (xb && ya) out += img[(long long)y0 * W + x1] * ne;
+    if (xa && yb) out += img[(long long)y1 * W + x0] * sw;
+    if (xb && yb) out += img[(long long)y1 * W + x1] * se;
+    return out;
+}
+
+// seen[i] = 1 iff some pose sees vertex i by RULE: one lane per vertex, the poses staged through LDS ADFP_CULL_CHUNK at a time
+template <int RULE>
 __global__ __launch_bounds__(ADFP_NN_THREADS) void k_cull_seen(CullArgs a) {
+    constexpr bool MESHER = RULE != ADFP_CULL_RULE_CULL_MESH;
     __shared__ float s_pose[ADFP_CULL_CHUNK * 12];
+    __shared__ float s_far[RULE == ADFP_CULL_RULE_MAX_DEPTH ? ADFP_CULL_CHUNK : 1];
     const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
     const bool on = i < a.nv;
-    const float x = on ? (float)a.v[3 * (long long)i] : 0.f;
-    const float y = on ? (float)a.v[3 * (long long)i + 1] : 0.f;
-    const float z = on ? (float)a.v[3 * (long long)i + 2] : 0.f;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (on) {
+        if (MESHER) { x = a.vf[3 * (long long)i]; y = a.vf[3 * (long long)i + 1]; z = a.vf[3 * (long long)i + 2]; }
+        else { x = (float)a.v[3 * (long long)i]; y = (float)a.v[3 * (long long)i + 1]; z = (float)a.v[3 * (long long)i + 2]; }
+    }
     bool seen = false;
     for (int p0 = 0; p0 < a.np; p0 += ADFP_CULL_CHUNK) {
         const int m = a.np - p0 < ADFP_CULL_CHUNK ? a.np - p0 : ADFP_CULL_CHUNK;
         __syncthreads();
         for (int e = threadIdx.x; e < 12 * m; e += ADFP_NN_THREADS) s_pose[e] = a.w2c[12 * (long long)p0 + e];
+        if (RULE == ADFP_CULL_RULE_MAX_DEPTH)
+            for (int e = threadIdx.x; e < m; e += ADFP_NN_THREADS) s_far[e] = a.dmax[p0 + e];
         __syncthreads();
         if (!on || seen) continue;
         for (int k = 0; k < m; ++k) {
-            if (cull_sees(s_pose + 12 * k, x, y, z, a.fx, a.fy, a.cx, a.cy, a.W, a.H)) { seen = true; break; }
+            float u, v, Z;
+            bool s = cull_project<MESHER>(s_pose + 12 * k, x, y, z, a.fx, a.fy, a.cx, a.cy, a.W, a.H, u, v, Z);
+            if (RULE == ADFP_CULL_RULE_MAX_DEPTH) s = s && -Z < s_far[k];
+            if (RULE == ADFP_CULL_RULE_DEPTH_TEST) {
+                if (s) {
+                    const float d = cull_depth_sample(a.depth + (long long)(p0 + k) * a.Hi * a.Wi, u, v, a.Wi, a.Hi, a.rW, a.rH);
+                    s = -Z < d + 2.4f && d - 2.4f < -Z;
+                }
+            }
+            if (s) { seen = true; break; }
         }
     }
     if (on) a.seen[i] = seen ? 1 : 0;

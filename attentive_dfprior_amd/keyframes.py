@@ -179,7 +179,7 @@ class KeyframeStore(object):
     buffers grow geometrically from ``capacity``; growing copies the existing keyframes.
 
     ``frame(i)`` gives ``(c2w, depth, color)`` device views in the shapes ``common.get_samples_multi`` takes in its single-launch
-    path; ``poses(n)`` the contiguous [n,4,4] block ``keyframe_selection_overlap`` reads; ``ids`` the frame indices (the reference's
+    path; ``poses(n)`` the contiguous [n,4,4] block ``keyframe_selection_overlap`` reads, ``depths(n)`` the [n,H,W] depth block; ``ids`` the frame indices (the reference's
     ``keyframe_list``)."""
 
     def __init__(self, H, W, device, capacity=16):
@@ -233,6 +233,10 @@ class KeyframeStore(object):
     def poses(self, n=None):
         """The first n (default: all) keyframe poses, a contiguous [n,4,4] f32 view."""
         return self._c2w[:self._n if n is None else int(n)]
+
+    def depths(self, n=None):
+        """The first n (default: all) keyframe depth images, a contiguous [n,H,W] f32 view (what Mesher.seen_mask reads)."""
+        return self._depth[:self._n if n is None else int(n)]
 
     def frame(self, i):
         """(c2w [4,4], depth [H,W], color [H,W,3]) of keyframe i: device views."""

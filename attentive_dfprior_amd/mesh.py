@@ -80,6 +80,162 @@ def unpack_colors(verts_index, color_vol):
     return out
 
 
+# ---- mesh clean-up on the device (csrc/adfp_meshclean.h; contracts: include/adfp.h, "mesh clean-up") ---------------------------
+def _mesh_tensors(verts, faces, what):
+    if faces is None:
+        raise ValueError(f'{what}: faces is None')
+    require_cuda(faces, f'{what} faces')
+    f = faces.detach().reshape(-1, 3).to(torch.int32).contiguous()
+    if verts is None:
+        return None, f
+    require_cuda(verts, f'{what} verts')
+    return verts.detach().reshape(-1, 3).to(f.device, torch.float32).contiguous(), f
+
+
+def _check_indices(faces, n_verts, what):
+    """Reject indices outside [0, n_verts) on the host (one read-back); the kernels never dereference them either way."""
+    if faces.numel():
+        lo, hi = (int(x) for x in torch.stack(torch.aminmax(faces)).tolist())
+        if lo < 0 or hi >= n_verts:
+            raise ValueError(f'{what}: face indices span [{lo}, {hi}], outside [0, {n_verts})')
+
+
+def _ws(nbytes, dev):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def _face_labels(faces, n_verts, keep=None):
+    """labels int32 [F] (-1 where keep is 0) of contiguous int32 device faces; see face_components."""
+    dev = faces.device
+    F = int(faces.shape[0])
+    labels = torch.empty(F, dtype=torch.int32, device=dev)
+    if F == 0:
+        return labels
+    L = lib()
+    mate = torch.empty(3 * F, dtype=torch.int32, device=dev)
+    changed = torch.empty(1, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        st = _lib.current_stream(dev)
+        nbytes = L.adfp_mesh_face_labels_workspace_bytes(F)
+        if nbytes == 0:
+            raise RuntimeError(f'face_components: {F} faces are more than the int32 sort carries')
+        ws = _ws(nbytes, dev)
+        check(L.adfp_mesh_face_labels_begin(ptr(faces), F, int(n_verts), ptr(keep), ptr(mate), ptr(labels), ptr(ws), nbytes, st),
+              'adfp_mesh_face_labels_begin')
+        del ws
+        done, step = 0, 4
+        while True:
+            check(L.adfp_mesh_face_labels_rounds(ptr(mate), ptr(labels), F, step, ptr(changed), st), 'adfp_mesh_face_labels_rounds')
+            done += step
+            if int(changed.item()) == 0:                  # the convergence flag: one scalar per `step` rounds
+                return labels
+            if done >= _lib.LABEL_ROUNDS_MAX:
+                raise RuntimeError(f'face_components: no fixed point after {done} rounds (the worst case is 2 log2(F) + 2)')
+
+
+def face_components(faces, n_verts):
+    """Component label of every face (int32 [F], device): two faces are joined only through an edge that exactly two faces use
+    (trimesh.graph.face_adjacency, what Mesher.clean derives with scipy); a face's label is the smallest face index of its
+    component, so the labels order the components as scipy does (by first face) and do not depend on any launch order."""
+    _, f = _mesh_tensors(None, faces, 'face_components')
+    _check_indices(f, int(n_verts), 'face_components')
+    return _face_labels(f, int(n_verts))
+
+
+def _clean_components(v, f, seen, min_area, largest):
+    dev = f.device
+    V, F = int(v.shape[0]), int(f.shape[0])
+    L = lib()
+    with _lib.device_guard(dev):
+        st = _lib.current_stream(dev)
+        keep = torch.empty(max(F, 1), dtype=torch.uint8, device=dev)
+        check(L.adfp_cull_faces(ptr(seen) if V else None, V, ptr(f) if F else None, F, ptr(keep), st), 'adfp_cull_faces')
+        labels = _face_labels(f, V, keep)
+        if F:
+            nbytes = L.adfp_mesh_component_keep_workspace_bytes(F)
+            ws = _ws(nbytes, dev)
+            check(L.adfp_mesh_component_keep(ptr(v) if V else None, V, ptr(f), F, ptr(labels), 1 if largest else 0,
+                                             0.0 if largest else float(min_area), ptr(keep), ptr(ws), nbytes, st),
+                  'adfp_mesh_component_keep')
+        nbytes = L.adfp_mesh_compact_workspace_bytes(V, F)
+        ws = _ws(nbytes, dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        check(L.adfp_mesh_compact_plan(ptr(f) if F else None, F, V, ptr(keep), ptr(ws), nbytes, ptr(totals), st), 'adfp_mesh_compact_plan')
+        nv, nf = (int(t) for t in totals.tolist())                       # the counts: one read-back
+        vo = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        fo = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        check(L.adfp_mesh_compact_emit(ptr(v) if V else None, V, ptr(f) if F else None, F, ptr(ws), nbytes, ptr(vo) if nv else None, nv,
+                                       ptr(fo) if nf else None, nf, st), 'adfp_mesh_compact_emit')
+    return vo, fo
+
+
+def clean_components(verts, faces, seen, min_area=None, largest=False):
+    """Mesher.clean on device tensors: drop the faces whose three vertices are unseen (seen: bool / uint8 [V]), split the rest into
+    components (face_components), keep the component of largest area (largest=True; the first among equals) or those whose area
+    exceeds min_area, keep the referenced vertices.  Returns (verts f32 [V',3], faces int32 [F',3]): kept faces in their order,
+    vertices in ascending index, the arrays Mesher.clean returns.  Areas are summed in f64 in a fixed order that is not
+    np.bincount's: a component within rounding of min_area (or of the runner-up) can fall on the other side."""
+    v, f = _mesh_tensors(verts, faces, 'clean_components')
+    if not largest and min_area is None:
+        raise ValueError('clean_components: min_area is required unless largest=True')
+    require_cuda(seen, 'clean_components seen')
+    s = seen.detach().reshape(-1).to(f.device).ne(0).to(torch.uint8).contiguous()
+    if s.shape[0] != v.shape[0]:
+        raise ValueError(f'clean_components: seen has {s.shape[0]} entries for {v.shape[0]} vertices')
+    _check_indices(f, int(v.shape[0]), 'clean_components')
+    return _clean_components(v, f, s, min_area, largest)
+
+
+def _merge_coincident(v, f, c):
+    dev = v.device
+    V, F = int(v.shape[0]), int(f.shape[0])
+    if V == 0:
+        return v, f, c
+    L = lib()
+    with _lib.device_guard(dev):
+        st = _lib.current_stream(dev)
+        nbytes = L.adfp_mesh_merge_workspace_bytes(V)
+        ws = _ws(nbytes, dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        check(L.adfp_mesh_merge_plan(ptr(v), V, ptr(ws), nbytes, ptr(total), st), 'adfp_mesh_merge_plan')
+        n = int(total.item())
+        if n == V:                                          # nothing coincides: the inputs, as the host function returns them
+            return v, f, c
+        vo = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        co = torch.empty((n, 3), dtype=torch.uint8, device=dev) if c is not None else None
+        fo = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        check(L.adfp_mesh_merge_emit(ptr(v), ptr(c), V, ptr(f) if F else None, F, ptr(ws), nbytes, ptr(vo), ptr(co), n,
+                                     ptr(fo) if F else None, st), 'adfp_mesh_merge_emit')
+    return vo, fo, co
+
+
+def merge_coincident(verts, faces, colors=None):
+    """mesher.merge_coincident on device tensors: vertices whose three f32 bit patterns are equal collapse into their first
+    occurrence, survivors keep their order, faces and colours (uint8 [V,3]) follow.  Returns (verts, faces, colors)."""
+    v, f = _mesh_tensors(verts, faces, 'merge_coincident')
+    c = None
+    if colors is not None:
+        require_cuda(colors, 'merge_coincident colors')
+        c = colors.detach().reshape(-1, 3).to(v.device, torch.uint8).contiguous()
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f'merge_coincident: {c.shape[0]} colours for {v.shape[0]} vertices')
+    return _merge_coincident(v, f, c)
+
+
+def color_bytes(rgb):
+    """(clip(rgb[:, :3], 0, 1) * 255) truncated to uint8 [n,3] on the device; rgb: float32 rows of at least three channels."""
+    require_cuda(rgb, 'color_bytes rgb')
+    x = rgb.detach().to(torch.float32)
+    x = x.reshape(-1, x.shape[-1]).contiguous()
+    if x.shape[1] < 3:
+        raise ValueError(f'color_bytes: rows of {x.shape[1]} channels')
+    out = torch.empty((x.shape[0], 3), dtype=torch.uint8, device=x.device)
+    with _lib.device_guard(x.device):
+        check(lib().adfp_mesh_color_bytes(ptr(x) if x.shape[0] else None, int(x.shape[0]), int(x.shape[1]), ptr(out) if x.shape[0] else None,
+                                          _lib.current_stream(x.device)), 'adfp_mesh_color_bytes')
+    return out
+
+
 def _np(x):
     if x is None:
         return None

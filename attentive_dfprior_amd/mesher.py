@@ -5,8 +5,11 @@ trimesh or scikit-image.
 
 Where the work runs: the lattice is formed on the device chunk by chunk and queried through the package's ``eval_points``
 (libadfp.so); the convex-hull mask is one kernel (``adfp_lattice_hull_fill``); marching cubes is ``mesh.marching_cubes``
-(``adfp_mc_count`` / ``adfp_mc_emit``); the seen / unseen masks (``point_masks``) are the reference's torch code on the device.
-The host keeps the connected-component culling (scipy.sparse.csgraph) and the file.
+(``adfp_mc_count`` / ``adfp_mc_emit``); the seen mask is one launch over all poses (``seen_mask``, ``adfp_mesh_seen_mask``); the
+component culling, the colour bytes and the merge of coincident vertices are ``mesh.clean_components`` / ``color_bytes`` /
+``merge_coincident`` (csrc/adfp_meshclean.h).  The host keeps the mesh bound (scipy ConvexHull) and the file.  ``point_masks``
+(the reference's torch code, the only source of the forecast / unseen masks), ``clean`` (scipy.sparse.csgraph) and the module's
+``merge_coincident`` remain as the host statements of the same steps: the tests compare the device path against them.
 
 Deviations, both documented in INTEGRATION.md:
   * the mesh bound (``get_bound_from_frames``) is the convex hull of the keyframes' camera centres and back-projected valid
@@ -129,6 +132,48 @@ class Mesher(object):
         return (np.concatenate(seen_mask_list, axis=0), np.concatenate(forecast_mask_list, axis=0),
                 np.concatenate(unseen_mask_list, axis=0))
 
+    def seen_mask(self, verts, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames=False, keyframe_store=None):
+        """The *seen* mask of point_masks as a bool device tensor [V], every pose in ONE launch (adfp_mesh_seen_mask): what
+        get_mesh culls with.  The poses are inverted on the host exactly as _project does (np.linalg.inv in the pose's own dtype,
+        then f32): one read-back of [K,4,4].  Depth images come from ``keyframe_store`` (a keyframes.KeyframeStore holding the
+        same keyframes in the same order: its resident [K,H,W] block is read in place) or are stacked from ``keyframe_dict``
+        once.  Agrees with point_masks(...)[0] except where the two f32 evaluations of the projection can round to different
+        sides of a bound (rocBLAS's order for w2c @ p is not ours): points within rounding of an image edge, of z = 0 or of a
+        depth bound."""
+        H, W = self.H, self.W
+        dev = torch.device(device)
+        pts = verts if isinstance(verts, torch.Tensor) else torch.from_numpy(np.asarray(verts))
+        pts = pts.detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
+        if get_mask_use_all_frames:
+            mats = [estimate_c2w_list[i] for i in range(0, idx + 1, 1)]
+        else:
+            mats = [keyframe['est_c2w'] for keyframe in keyframe_dict]
+        seen = torch.zeros(pts.shape[0], dtype=torch.uint8, device=dev)
+        K = len(mats)
+        if K == 0 or pts.shape[0] == 0:
+            return seen.bool()
+        c2w = torch.stack([m.detach() for m in mats]).cpu().numpy()
+        w2c = torch.from_numpy(np.ascontiguousarray(np.linalg.inv(c2w)[:, :3, :])).to(dev).float().reshape(K, 12).contiguous()
+        depth = far = None
+        rule = 'frustum'
+        if not get_mask_use_all_frames:
+            rule = 'depth_test' if self.depth_test else 'max_depth'
+            if keyframe_store is not None:
+                if len(keyframe_store) < K:
+                    raise ValueError(f'seen_mask: the store holds {len(keyframe_store)} keyframes, keyframe_dict {K}')
+                depth = keyframe_store.depths(K)
+            else:
+                depth = torch.stack([keyframe['depth'] for keyframe in keyframe_dict]).to(dev, torch.float32)
+            depth = depth.reshape(K, H, W).contiguous()
+            if not self.depth_test:
+                far = (depth.reshape(K, -1).amax(1) * 1.1).contiguous()          # torch.max(depth) * 1.1, per keyframe
+        with M._lib.device_guard(dev):
+            M.check(M.lib().adfp_mesh_seen_mask(M.ptr(pts), int(pts.shape[0]), M.ptr(w2c), K, M._lib.SEEN_RULE[rule],
+                                                M.ptr(depth) if self.depth_test else None, M.ptr(far), float(self.fx), float(self.fy),
+                                                float(self.cx), float(self.cy), int(W), int(H), M.ptr(seen),
+                                                M._lib.current_stream(dev)), 'adfp_mesh_seen_mask')
+        return seen.bool()
+
     # ---- mesh bound ------------------------------------------------------------------------------------------------------
     def get_bound_planes(self, keyframe_dict, scale=1):
         """Facet planes [F,4] (n, d; inside: n . p + d <= 0) of the mesh bound: the convex hull of the keyframes' camera centres
@@ -234,9 +279,33 @@ class Mesher(object):
         remap[used] = np.arange(len(used))
         return vertices[used], remap[faces].astype(np.int32)
 
+    def mesh_arrays(self, verts, faces, c, decoders, keyframe_dict, estimate_c2w_list, idx, tsdf_volume, device='cuda:0',
+                    color=True, clean_mesh=True, get_mask_use_all_frames=False, keyframe_store=None):
+        """get_mesh from the marching-cubes output (device verts f32 [V,3], faces int32 [F,3]) to the arrays write_ply takes
+        (numpy vertices / scale, faces, uint8 colours or None): culling, colour query and bytes, vertex merge on the device, then
+        one copy of each array."""
+        with torch.no_grad():
+            if clean_mesh:
+                seen = self.seen_mask(verts, keyframe_dict, estimate_c2w_list, idx, device,
+                                      get_mask_use_all_frames=get_mask_use_all_frames, keyframe_store=keyframe_store)
+                verts, faces = M._clean_components(verts, faces, seen.to(torch.uint8),
+                                                   self.remove_small_geometry_threshold * self.scale * self.scale,
+                                                   bool(self.get_largest_components))
+            vertex_colors = None
+            if color:
+                vc = [M.color_bytes(self.eval_points(pnts, decoders, tsdf_volume, self.tsdf_bnds, c, 'color', device))
+                      for pnts in torch.split(verts, self.points_batch_size, dim=0)]
+                vertex_colors = torch.cat(vc, 0) if vc else torch.zeros((0, 3), dtype=torch.uint8, device=verts.device)
+            verts, faces, vertex_colors = M._merge_coincident(verts, faces, vertex_colors)
+            vertices = verts.cpu().numpy() / np.float32(self.scale)
+            return vertices, faces.cpu().numpy(), (vertex_colors.cpu().numpy() if vertex_colors is not None else None)
+
     def get_mesh(self, mesh_out_file, c, decoders, keyframe_dict, estimate_c2w_list, idx, tsdf_volume, device='cuda:0',
-                 color=True, clean_mesh=True, get_mask_use_all_frames=False):
-        """Extract the mesh of the scene representation and write it to mesh_out_file (.ply); returns z_uni_m (Mesher.py:395-544)."""
+                 color=True, clean_mesh=True, get_mask_use_all_frames=False, keyframe_store=None):
+        """Extract the mesh of the scene representation and write it to mesh_out_file (.ply); returns z_uni_m (Mesher.py:395-544).
+        From marching cubes to the file everything stays on the device (seen_mask, mesh.clean_components' kernels, the colour
+        query and bytes, mesh.merge_coincident's kernels); the host receives the final vertices, faces and colours, one copy each.
+        keyframe_store: a keyframes.KeyframeStore of the same keyframes, whose resident depth block seen_mask then reads."""
         if not str(mesh_out_file).lower().endswith('.ply'):
             raise NotImplementedError(f'{mesh_out_file}: only .ply output is supported')
         if color and self.color_mesh_extraction_method != 'direct_point_query':
@@ -252,21 +321,9 @@ class Mesher(object):
             if faces.shape[0] == 0:
                 print('marching_cubes error. Possibly no surface extracted from the level set.')
                 return
-            vertices = verts.cpu().numpy()
-            faces = faces.cpu().numpy()
-            if clean_mesh:
-                seen_mask, _, _ = self.point_masks(verts, keyframe_dict, estimate_c2w_list, idx, device=device,
-                                                   get_mask_use_all_frames=get_mask_use_all_frames)
-                vertices, faces = self.clean(vertices, faces, seen_mask)
-            vertex_colors = None
-            if color:
-                vc = []
-                for pnts in torch.split(torch.from_numpy(vertices).to(device).float(), self.points_batch_size, dim=0):
-                    vc.append(self.eval_points(pnts, decoders, tsdf_volume, self.tsdf_bnds, c, 'color', device)[..., :3])
-                vertex_colors = torch.cat(vc, 0).cpu().numpy() if vc else np.zeros((0, 3), np.float32)
-                vertex_colors = (np.clip(vertex_colors, 0, 1) * 255).astype(np.uint8)
-            vertices, faces, vertex_colors = merge_coincident(vertices, faces, vertex_colors)
-            vertices = vertices / np.float32(self.scale)
+            vertices, faces, vertex_colors = self.mesh_arrays(verts, faces, c, decoders, keyframe_dict, estimate_c2w_list, idx,
+                                                              tsdf_volume, device, color, clean_mesh, get_mask_use_all_frames,
+                                                              keyframe_store)
             os.makedirs(os.path.dirname(os.path.abspath(mesh_out_file)), exist_ok=True)
             M.write_ply(mesh_out_file, vertices, faces, colors=vertex_colors)
             if self.verbose:

@@ -939,6 +939,78 @@ int adfp_keyframe_overlap(const long long* idx, int n, const float* depth_img, i
                           const float* poses, int K, double fx, double fy, double cx, double cy, int edge, int* counts, float* pts_out,
                           void* stream);
 
+/* ---- mesh clean-up (src/utils/Mesher.py:58-217 point masks, :492-513 the trimesh culling, Trimesh(process=True)'s vertex merge) ----
+ * Everything between marching cubes and the file, on the device.  Meshes: verts [V][3] f32, faces [F][3] int32.  V above
+ * 2^31 - 1025 or 3 F above 2^31 - 1025 is ADFP_E_UNSUPPORTED (the half-edges are sorted with adfp_sort_pairs); a null pointer or a
+ * negative count ADFP_E_ARG; a short workspace ADFP_E_WORKSPACE.  A face with an index outside [0, V) is never dereferenced: it
+ * gets no label, is never kept, and maps to -1 in a merge.  No atomics decide a result; the same input gives the same bits. */
+
+/* The Mesher's *seen* mask over every pose in one launch (no workspace): seen[i] = 1 iff some pose p sees vertex i.  w2c
+ * [n_poses][12] (f32, device) = the top three rows of inv(c2w) as np.linalg.inv of the f32 pose gives them.  Mesher._project in
+ * f32, each product and sum rounded on its own: cam = ((w0 x + w1 y) + w2 z) + w3 per row, X = -cam.x, Z = cam.z, zz = Z + 1e-8,
+ * u = (fx X + cx Z) / zz, v = (fy cam.y + cy Z) / zz; frustum: zz < 0 && 0 < u < W && 0 < v < H.  rule:
+ *   ADFP_SEEN_FRUSTUM     the frustum only (get_mask_use_all_frames);
+ *   ADFP_SEEN_MAX_DEPTH   and -Z < depth_max[p] (depth_test = False; depth_max [n_poses] f32: the caller's 1.1 * max(depth[p]));
+ *   ADFP_SEEN_DEPTH_TEST  and d - 2.4 < -Z < d + 2.4 with d = F.grid_sample(depth[p], bilinear, zeros, align_corners=True) at the
+ *                         grid the Mesher forms: g = (u * (1 / (W - 1))) * 2 - 1, ix = ((g + 1) / 2) * (W - 1) (likewise v, H), corner
+ *                         weights (x1 - ix)(y1 - iy), (ix - x0)(y1 - iy), (x1 - ix)(iy - y0), (ix - x0)(iy - y0), products summed in
+ *                         that order, corners outside the image skipped; depth [n_poses][H][W] f32.  H or W < 2: ADFP_E_UNSUPPORTED.
+ * The forecast / unseen masks are not computed.  Another rule, a rule without its depth array, H or W < 1: ADFP_E_ARG; H or
+ * W > 32768, n_poses > (2^31 - 1025) / 12: ADFP_E_UNSUPPORTED.  n_poses = 0 writes zeros. */
+#define ADFP_SEEN_FRUSTUM    0
+#define ADFP_SEEN_MAX_DEPTH  1
+#define ADFP_SEEN_DEPTH_TEST 2
+int adfp_mesh_seen_mask(const float* verts, long long n_verts, const float* w2c, long long n_poses, int rule, const float* depth,
+                        const float* depth_max, float fx, float fy, float cx, float cy, int W, int H, unsigned char* seen, void* stream);
+
+/* Face components as trimesh.split forms them: two faces are joined only through an edge {a, b} that EXACTLY two half-edges use
+ * (a face (a, a, c) uses {a, c} twice and joins nothing).  A face takes part iff keep is NULL or keep[f] != 0, and its indices
+ * lie in [0, n_verts).  _begin orders the 3 F half-edges by (min, max) with two stable sorts and writes mate [3 F] (int32: the
+ * face across half-edge 3 f + c, or -1) and the start labels[f] = f (-1 for a face that takes no part).  _rounds runs `rounds`
+ * rounds of: every mate pair with different roots hooks the larger root under the smaller (atomicMin), then every face points at
+ * its root; *changed (one device int) = 1 iff the LAST of them hooked anything.  The caller repeats _rounds until it reads 0;
+ * then labels[f] = the smallest face index of f's component.  Labels only descend, so every walk ends, and 2 log2(F) + 2 rounds
+ * are the worst case (csrc/adfp_meshclean.h).  Workspace of _begin: 6 x 12 F bytes, each rounded up to 256, plus
+ * adfp_sort_workspace_bytes(3 F); free after the call.  n_faces = 0 does nothing (changed = 0). */
+size_t adfp_mesh_face_labels_workspace_bytes(long long n_faces);
+int adfp_mesh_face_labels_begin(const int* faces, long long n_faces, long long n_verts, const unsigned char* keep /*or NULL*/, int* mate,
+                                int* labels, void* workspace, size_t workspace_bytes, void* stream);
+int adfp_mesh_face_labels_rounds(const int* mate, int* labels, long long n_faces, int rounds, int* changed, void* stream);
+
+/* The keep rule of Mesher.py:497-510 on final labels: area[f] = 0.5 |cross(v1 - v0, v2 - v0)| in f64 from the f32 vertices, as
+ * numpy forms it (cross = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0), no FMA, sqrt((x x + y y) + z z)); a component's area =
+ * the sum over its faces in ascending face order by a segmented scan of fixed shape (8 consecutive faces per lane, 256 lanes by
+ * doubling steps, tiles of 2048 in order) -- not np.bincount's order, so the last bits can differ.  largest = 1: keep[f] = 1 iff f
+ * lies in the component of largest area, the smallest label among equals (np.argmax's first); largest = 0: iff its component's
+ * area > threshold.  Faces without a label get 0.  Workspace: adfp_mesh_component_keep_workspace_bytes(n_faces).  A NaN threshold
+ * or largest outside {0, 1} is ADFP_E_ARG. */
+size_t adfp_mesh_component_keep_workspace_bytes(long long n_faces);
+int adfp_mesh_component_keep(const float* verts, long long n_verts, const int* faces, long long n_faces, const int* labels, int largest,
+                             double threshold, unsigned char* keep, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Compaction: the faces with keep[f] != 0 in their order, the vertices they use in ascending index, the faces re-indexed.
+ * _plan writes totals[2] (device long long) = (vertices, faces) that remain and keeps the positions in the workspace; the caller
+ * reads the totals, allocates, and calls _emit with the same workspace and those totals (nothing is written past them). */
+size_t adfp_mesh_compact_workspace_bytes(long long n_verts, long long n_faces);
+int adfp_mesh_compact_plan(const int* faces, long long n_faces, long long n_verts, const unsigned char* keep, void* workspace,
+                           size_t workspace_bytes, long long* totals, void* stream);
+int adfp_mesh_compact_emit(const float* verts, long long n_verts, const int* faces, long long n_faces, const void* workspace,
+                           size_t workspace_bytes, float* verts_out, long long n_verts_out, int* faces_out, long long n_faces_out, void* stream);
+
+/* Coincident vertices: vertices whose three f32 bit patterns are equal (-0.0 and +0.0 differ, equal NaN patterns merge) collapse
+ * into the one of lowest index; survivors keep their order.  _plan groups the vertices with six stable 16-bit passes of
+ * adfp_sort_pairs over the raw words and writes *total (device long long) = the survivors; _emit writes them (and their colours
+ * [V][3] uint8 when colors / colors_out are given: both or neither) and all n_faces faces re-indexed. */
+size_t adfp_mesh_merge_workspace_bytes(long long n_verts);
+int adfp_mesh_merge_plan(const float* verts, long long n_verts, void* workspace, size_t workspace_bytes, long long* total, void* stream);
+int adfp_mesh_merge_emit(const float* verts, const unsigned char* colors, long long n_verts, const int* faces, long long n_faces,
+                         const void* workspace, size_t workspace_bytes, float* verts_out, unsigned char* colors_out, long long n_verts_out,
+                         int* faces_out, void* stream);
+
+/* (np.clip(c, 0, 1) * 255).astype(np.uint8) of Mesher.py:523-524 in f32: out [n][3] bytes from rows of `stride` >= 3 floats (the
+ * first three are used); NaN gives 0. */
+int adfp_mesh_color_bytes(const float* rgb, long long n, int stride, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

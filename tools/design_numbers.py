@@ -19,6 +19,37 @@ def stats(path):
 def main(template, d):
     v = {}
     P = lambda n: os.path.join(d, n)
+    # the Mesher's tail: host methods against the device path (tools/mesh_bench.py)
+    mt = json.load(open(P('mesh_tail_bench.json')))['by_resolution']
+
+    def thousands(n):
+        return f'{n:,}'.replace(',', ' ')
+    legs = [('seen mask, 4 keyframes (`point_masks` / `seen_mask`)', 'seen_mask_4_keyframes'),
+            ('seen mask, 300 poses, `get_mask_use_all_frames`', 'seen_mask_300_poses_all_frames'),
+            ('culling (`Mesher.clean` / `mesh.clean_components`)', 'clean'),
+            ('vertex merge, 1 % planted duplicates', 'merge_coincident'),
+            ('whole tail: marching-cubes output → arrays for `write_ply`', 'whole_tail')]
+    rows = []
+    for name, key in legs:
+        cells = []
+        for res in ('256', '512'):
+            h, dv = mt[res]['tail'][key]['host'], mt[res]['tail'][key]['device']
+            cells.append('%.1f (%.1f, %.1f) | %.2f (%.2f, %.2f)' % (h['median_ms'], h['min_ms'], h['spread_ms'], dv['median_ms'], dv['min_ms'],
+                                                                    dv['spread_ms']))
+        rows.append('| %s | %s |' % (name, ' | '.join(cells)))
+    v['mt_table'] = '\n'.join(rows)
+    for res in ('256', '512'):
+        r = mt[res]
+        v['mt_v' + res], v['mt_f' + res] = thousands(r['verts']), thousands(r['faces'])
+        v['mt_kv' + res], v['mt_kf' + res] = thousands(r['tail']['kept_verts']), thousands(r['tail']['kept_faces'])
+        v['mt_h' + res] = '%.1f' % r['tail']['whole_tail']['host']['median_ms']
+        v['mt_d' + res] = '%.2f' % r['tail']['whole_tail']['device']['median_ms']
+        v['mt_bound' + res] = '%.0f' % r['get_bound_planes_host_ms']
+    rep = json.load(open(P('mesh_tail_bench_256_repeat.json')))['by_resolution']['256']['tail']
+    v['mt_rep_lo'] = '%.2f' % min(rep['clean']['device']['all_ms'])
+    v['mt_rep_hi'] = '%.2f' % max(rep['clean']['device']['all_ms'])
+    v['mt_rep_tail'] = '%.2f' % rep['whole_tail']['device']['median_ms']
+    v['mt_getmesh512'] = '%.0f' % (mt['512']['get_mesh_total']['median_s'] * 1e3)
     # ---- parity / gradient stats
     t = open(P('r06_parity_stats.txt')).read()
     m = re.search(r'tol 0\.0001: (\d+) tensors, worst (\S+) of the limit', t)
