@@ -6,9 +6,9 @@
 //   k_decode_bwd<...>  decoder backward: recompute forward (ReLU masks), transposed MFMA chains
 //                      out of the SAME padded LDS image, feature-gradient scatter into the
 //                      channels-last grid gradient with 128-B shaped float atomics
-//   k_outer            weight gradients: dW = sum_points g (x) input as 32x32 MFMA outer
-//                      products over point-major staging rows, atomically added to the flat
-//                      (state_dict order) gradient
+//   k_outer_lds        weight gradients: dW = sum_points g (x) input as 32x32 MFMA outer
+//                      products over point-major staging rows, summed into one copy of the flat
+//                      (state_dict order) gradient per workgroup (k_reduce_partials adds them up)
 #pragma once
 #include "adfp_device.h"
 
@@ -701,7 +701,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(AttBwdArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-// weight gradients: one 32x32 outer-product block per (job, point-chunk) wave
+// weight gradients: 32x32 outer-product blocks, one per job of the table
 // ------------------------------------------------------------------------------------------
 struct OuterJob { int colA, colB, dst, rs, cs, nr, j0, nc; };
 #define OUTER_MAX_JOBS 56
@@ -713,44 +713,10 @@ struct OuterArgs {
     int njobs; int rows_per_wave;
     OuterJob jobs[OUTER_MAX_JOBS];
 };
-__global__ __launch_bounds__(64) void k_outer(OuterArgs a) {
-    const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
-    int hi = a.chunk_hi;
-    if (a.count_ptr) { const int cnt = *a.count_ptr; hi = hi < cnt ? hi : cnt; }
-    const int rows = hi - a.chunk_lo;
-    const int m0 = blockIdx.x * a.rows_per_wave;
-    if (m0 >= rows) return;
-    const int m1 = (m0 + a.rows_per_wave < rows) ? m0 + a.rows_per_wave : rows;
-    const OuterJob jb = a.jobs[blockIdx.y];
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    for (int m = m0; m < m1; m += 32) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int pt = m + 2 * s + h;
-            float va = 0.f, vb = 0.f;
-            if (pt < m1) {
-                const float* row = a.stage + (long long)pt * a.ncols;
-                va = row[jb.colA + i];
-                vb = row[jb.colB + i];
-            }
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(va, vb, acc, 0, 0, 0);
-        }
-    }
-    const int j = i - jb.j0;
-    if (j >= 0 && j < jb.nc) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = kmapH(r, h);
-            if (row < jb.nr && acc[r] != 0.f) atomicAdd(a.flat + jb.dst + row * jb.rs + j * jb.cs, acc[r]);
-        }
-    }
-}
 
-// The same job table, staged through LDS.  k_outer reads every staging column block once per job that
-// uses it (2 x 128 B per point per job, ~7.7 KB per point for a decoder whose row is 3 KB) and runs at the
-// rate L2 delivers those 128-B pieces.  Here a 512-thread workgroup streams its rows ONCE, 16 at a time,
+// The job table, staged through LDS.  One wave per (job, point-chunk) with its operands straight from L2 read every
+// staging column block once per job that uses it (2 x 128 B per point per job, ~7.7 KB per point for a decoder whose
+// row is 3 KB) and ran at the rate L2 delivers those 128-B pieces.  Here a 512-thread workgroup streams its rows ONCE, 16 at a time,
 // coalesced into a double-buffered LDS tile of whole staging rows, and its 8 waves split the jobs (up to 7
 // accumulator blocks per wave); every MFMA operand is a conflict-free ds_read_b32.  One barrier per 16 rows.
 // Two jobs may write the same gradient element only through DIFFERENT (row, column) sub-blocks, so within a

@@ -36,9 +36,6 @@
 // fit) and every case with the in-kernel scatter keep the two-kernel path.
 #pragma once
 #include "adfp_backward_h.h"
-#ifdef ADFP_STAMPS
-__device__ unsigned long long g_phase_fused[8];       // debug build only: wave-cycles per phase of k_decode_bwd_fused, summed over waves
-#endif
 
 struct DecodeBwdFArgs {
     PtsDev P; NormDev nb;
@@ -169,9 +166,6 @@ __global__ __launch_bounds__(256) void k_decode_bwd_fused(DecodeBwdFArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
 
-#ifdef ADFP_STAMPS
-    unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = clock64();
-#endif
     // the small per-point inputs of a tile (position, mask words, d out) are fetched one tile ahead, too: into the SAME registers,
     // once the five layers of the current tile have consumed them (a second register set spilled)
     struct Small { double pt[3]; unsigned mw[3]; float go[4]; };
@@ -189,7 +183,6 @@ __global__ __launch_bounds__(256) void k_decode_bwd_fused(DecodeBwdFArgs a) {
     Small cur;
     if (wave < ntiles) fetch_small(wave, cur);
     for (int tile = wave; tile < ntiles; tile += nwaves) {
-        ADFP_PHASE(0);                                           // loop overhead
         const int loc = tile * 32 + p;
         const bool valid = loc < a.total;
         const int q = valid ? loc : 0;
@@ -247,9 +240,7 @@ __global__ __launch_bounds__(256) void k_decode_bwd_fused(DecodeBwdFArgs a) {
         const float ssc = isc * gS;                              // chain scale -> the global scale S of the summed products
         if (h == 0) *(f32x4*)(ptab + 4 * p) = f32x4{pf[0], pf[1], pf[2], ssc};
 
-        ADFP_PHASE(1);                                           // point, masks, d out, d/d h_4, scale
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // c, h_4, h_3, h_2 of this tile have landed (issued during the previous one)
-        ADFP_PHASE(2);                                           // waiting for the DMA
         // ---------------- the grid features: the right-hand side of the five fc_c products ----------------
         f16x8 cTh[2], cTl[2];
         operand_x(xs + rot * SLOT, cTh, cTl);
@@ -276,7 +267,6 @@ __global__ __launch_bounds__(256) void k_decode_bwd_fused(DecodeBwdFArgs a) {
             rowsum_job(acc[15], gTh, gTl, p, FSLOT_BO);          // [row FSLOT_WO(o)][column FSLOT_BO]
         }
 
-        ADFP_PHASE(3);                                           // c, output layer
         f32x16 gc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) gc[r] = 0.f;
@@ -329,7 +319,6 @@ __global__ __launch_bounds__(256) void k_decode_bwd_fused(DecodeBwdFArgs a) {
             }
             if (i > 0) gh = gn;
         }
-        ADFP_PHASE(4);                                           // the five layers
         if (a.gc_out && valid) stage_block_scaled(a.gc_out + 32ll * q, 0, h, gc, isc);
         if (more) fetch_small(tnext, cur);                       // the next tile's inputs, in flight during the Fourier blocks
 
@@ -407,11 +396,7 @@ __global__ __launch_bounds__(256) void k_decode_bwd_fused(DecodeBwdFArgs a) {
             // [row = feature 32 b + j][column FSLOT_EB(b, k)] += sum_p d/d(p @ B)_j x_k
             outer_job(acc[15], aTh, aTl, bTh, bTl);
         }
-        ADFP_PHASE(5);                                           // Fourier blocks
     }
-#ifdef ADFP_STAMPS
-    if (lane == 0) for (int k = 0; k < 6; ++k) atomicAdd(&g_phase_fused[k], ph_[k]);
-#endif
     if (!(a.skip && *a.skip)) report_range(a.status, amax, ADFP_STATUS_F16_RANGE_BWD);
 
     // ---------------- the waves' accumulators -> the workgroup's copy of the flat gradient ----------------

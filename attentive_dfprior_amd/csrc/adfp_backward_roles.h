@@ -32,7 +32,7 @@
 #include "adfp_backward_fused.h"
 
 // share of the workgroups per role, in 1/256: proportional to (time of the role alone) x (its workgroups) measured with the
-// timing-only builds -DADFP_EXP_ONLY_ROLE=0/1/2 (tools/ab_roles.sh, profiles/r05_ab_backward_roles.txt)
+// timing-only builds that ran one role's workgroups at a time (profiles/r05_ab_backward_roles.txt)
 #ifndef ROLE_SHARE_P
 #define ROLE_SHARE_P 106
 #endif
@@ -40,16 +40,8 @@
 #define ROLE_SHARE_H 78
 #endif
 
-#ifdef ADFP_STAMPS_ROLES           // debug build (tools/roles_span.py): per workgroup (role, wall-clock start, end of the tile loop, end), 100 MHz
-__device__ unsigned long long g_roles_span[4 * 256];
-#endif
-
 template <int NOUT, int ROLE>
 __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int nP, int nH) {
-#ifdef ADFP_STAMPS_ROLES
-    const unsigned long long t_start_ = wall_clock64();
-    unsigned long long t_loop_ = 0;
-#endif
     constexpr int CDIM = 32;
     using LT = DecLayoutHT<CDIM, NOUT>;
     using ST = DecStage<CDIM>;
@@ -69,14 +61,7 @@ __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int 
     static_assert(NWV * 3 * 16 * 64 <= LDS_WORDS, "the reduction's three blocks per wave");
     __shared__ __attribute__((aligned(16))) unsigned ldsu[LDS_WORDS];
     const int bid = (int)blockIdx.x, nwg = (int)gridDim.x;
-#ifdef ADFP_EXP_COMPILE_ROLE       // ISA experiments: the kernel with one role's code only (tools/isa_mix.py per role)
-    const int role = ADFP_EXP_COMPILE_ROLE;
-#else
     const int role = bid < nP ? 0 : (bid < nP + nH ? 1 : 2);                 // block-uniform (scalar)
-#endif
-#ifdef ADFP_EXP_ONLY_ROLE          // timing experiment (tools/ab_roles.sh): only one role's workgroups do anything -- that role's own time at its share
-    if (role != ADFP_EXP_ONLY_ROLE) return;
-#endif
     auto copy_words = [&](int dst, int src, int n) {                         // n words of the packed image -> LDS (multiples of 4)
         image_to_lds<512>(ldsu + dst, a.packed_t + src, n / 4);
     };
@@ -103,7 +88,7 @@ __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int 
     const int xw = role == 0 ? XW_P : (role == 1 ? XW_H : XW_C);
     // Tiles of a workgroup are handed to its waves through an LDS ticket (the last word of wave 0's region, spare in every role): the
     // SIMD arbiter favours the older of its two waves, and with a fixed split the four old waves of a workgroup were done a fifth
-    // of the launch before the four young ones, which then ran alone on their SIMDs (per-workgroup stamps, tools/roles_span.py).
+    // of the launch before the four young ones, which then ran alone on their SIMDs (per-workgroup stamps).
     int* s_ticket = (int*)(ldsu + img_words + xw - 1);
     if (threadIdx.x == 0) *s_ticket = NWV;                                   // local tile numbers 0 .. 7 are the waves' first tiles
     __syncthreads();
@@ -280,9 +265,6 @@ __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int 
         }
     };
 
-#ifdef ADFP_EXP_ROLES_PRIO          // timing experiment: the YOUNG wave of every SIMD (waves 4-7 start later) at a raised issue priority
-    if (wvu >= 4) __builtin_amdgcn_s_setprio(2);
-#endif
     Small cur;
     if (role == 2) {
         // =====================================================================================================================
@@ -353,9 +335,6 @@ __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int 
             jc = jn;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ADFP_STAMPS_ROLES
-        t_loop_ = wall_clock64();
-#endif
         __syncthreads();
         put(0, acc[0]); put(1, acc[1]); put(2, acc[2]);
         __syncthreads();
@@ -404,12 +383,10 @@ __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int 
             auto take = [&](int k, f16x8* hTh, f16x8* hTl) {
                 const bool two = more || k < 3, one = more || k < 4;            // are the requests of the next two / one uses out?
                 // uses 0-2: the next tile's small inputs (5 operations, requested after this tile's head) are younger as well
-#ifndef ADFP_EXP_H_NOWAIT          // timing experiment: the blocks are not waited for (what the memory waits of this role cost)
                 if (k < 3 && more) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
                 else if (two) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
                 else if (one) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
                 const int sl = slot_of(k);
                 operand_x(xs + sl * SLOT, hTh, hTl);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // the reads have returned before the DMA may overwrite the slot
@@ -471,9 +448,6 @@ __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int 
             jc = jn;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ADFP_STAMPS_ROLES
-        t_loop_ = wall_clock64();
-#endif
         __syncthreads();
         put(0, acc[0]); put(1, acc[1]); put(2, acc[2]);
         __syncthreads();
@@ -716,9 +690,6 @@ __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int 
             jc = jn;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ADFP_STAMPS_ROLES
-        t_loop_ = wall_clock64();
-#endif
         __syncthreads();
         put(0, acc[0]); put(1, acc[1]); put(2, acc[2]);
         __syncthreads();
@@ -743,12 +714,6 @@ __global__ __launch_bounds__(512) void k_decode_bwd_roles(DecodeBwdFArgs a, int 
         });
     }
     if (!(a.skip && *a.skip)) report_range(a.status, amax, ADFP_STATUS_F16_RANGE_BWD);
-#ifdef ADFP_STAMPS_ROLES
-    if (NOUT == 4 && threadIdx.x == 0 && blockIdx.x < 256) {
-        g_roles_span[4 * blockIdx.x] = (unsigned long long)role; g_roles_span[4 * blockIdx.x + 1] = t_start_;
-        g_roles_span[4 * blockIdx.x + 2] = t_loop_; g_roles_span[4 * blockIdx.x + 3] = wall_clock64();
-    }
-#endif
 }
 
 // Which role's workgroups hold element e of the flat gradient (0 = P, 1 = H, 2 = C): the write-out at the end of k_decode_bwd_roles.

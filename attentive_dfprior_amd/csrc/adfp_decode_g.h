@@ -1,6 +1,6 @@
 // adfp_decode_g.h -- LOW + COLOR decoder in one launch (stage color, inference) on v_mfma_f32_16x16x32_f16.
 //
-// Same arithmetic as k_decode_lc (adfp_decode_h.h): every f32 operand split a = a_hi + a_lo into two f16, three MFMA products
+// Same arithmetic as k_decode_h (adfp_decode_h.h): every f32 operand split a = a_hi + a_lo into two f16, three MFMA products
 // per f32 product, f32 accumulation; same per-point work (f64 point, f64 normalisation, 8-corner gather, Fourier features with
 // exact turn reduction, 5 layers, VALU output layer).  What changes is the MFMA SHAPE: the 32 units x 32 points of a layer are
 // four 16 x 16 output blocks (2 out-blocks x 2 point-blocks), each fed K = 32 inputs per instruction, instead of one 32 x 32 block
@@ -118,22 +118,6 @@ __global__ void k_pack_decoder_g(const float* __restrict__ flat, unsigned* __res
 
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 
-// debug build (-DADFP_STAMPS_G, tools/phase_g.sh): wave-cycles per phase of a tile, summed over waves.  Slots: [0..7] k_decode_high_g,
-// [8..15] / [16..23] the low / colour network of k_decode_lc16; phase 0 = tile claim + point, 1 = gather + exchange + split,
-// 2 = Fourier features, 3 = the five layers, 4 = output layer, 5 = stores
-#ifdef ADFP_STAMPS_G
-__device__ unsigned long long g_phase_g[24];
-__device__ unsigned long long g_wave_span_g[2 * 4096];      // k_decode_lc16: per wave (wall-clock start, end), 100 MHz
-#define ADFP_PHG_PARAMS , unsigned long long* ph_, unsigned long long& last_
-#define ADFP_PHG_ARGS(base) , ph_ + (base), last_
-#define ADFP_PHG(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = clock64(); \
-                         __builtin_amdgcn_sched_barrier(0); ph_[k] += now_ - last_; last_ = now_; } while (0)
-#else
-#define ADFP_PHG_PARAMS
-#define ADFP_PHG_ARGS(base)
-#define ADFP_PHG(k) do {} while (0)
-#endif
-
 // x (first operand): lanes 32-63 receive y of lane l - 32;  y: lanes 0-31 receive x of lane l + 32  (tools/micro/layout_probe_16x16x32.hip)
 ADFP_DEV void swap_halves(float& x, float& y) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
@@ -174,17 +158,13 @@ ADFP_DEV void mfma_chain_g(f32x4g acc[2][2], const unsigned* __restrict__ w, con
 //        order).  The lane's units 16 ob + 4 g .. + 3 are one 16-byte piece: 2 pieces of c and of every h_i per point, 24 stores
 //        per lane and tile.  The head [x, y, z, 1, 0 ...] (128 B of the 896) is NOT stored: k_decode_bwd_roles / _fused recompute
 //        the Fourier features from the points, and k_outer_h builds the head from the points (OuterHArgs.x_skip4).
-// the training rows' stores: plain, or (timing experiment -DADFP_EXP_NT_ROWS) non-temporal -- written once, read once ~300 us later
+// the training rows' stores
 ADFP_DEV void row_store(float* p, const f32x4 v) {
-#if defined(ADFP_EXP_NT_ROWS)
-    __builtin_nontemporal_store(v, (f32x4*)p);
-#else
     *(f32x4*)p = v;
-#endif
 }
 template <int CDIM, int NOUT, int TRAIN = 0>
 ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& grid, const GridDev& grid1, const float pn[3], const float (*pf)[3],
-                           int lane, float& amax, float (*out)[NOUT], unsigned* __restrict__ mw, float* srow0, unsigned rowbits ADFP_PHG_PARAMS) {
+                           int lane, float& amax, float (*out)[NOUT], unsigned* __restrict__ mw, float* srow0, unsigned rowbits) {
     using L = DecLayoutG<CDIM, NOUT>;
     using ST = DecStage<CDIM>;
     const int g = lane >> 4;
@@ -193,9 +173,6 @@ ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& gri
     if constexpr (TRAIN) {
         srow[0] = (rowbits & 1u) ? srow0 : nullptr;
         srow[1] = (rowbits & 2u) ? srow0 + 16 * ST::NXM : nullptr;
-#if defined(ADFP_EXP_TRAIN_NOX)            // timing experiment: no layer-input rows at all (masks only)
-        srow[0] = nullptr; srow[1] = nullptr;
-#endif
     }
     // every LDS access below is one of three lane-dependent bases plus an immediate: the weight rows (4 l), the unit-order rows
     // (biases, output layer: 4 g) and the Fourier rows (32 g)
@@ -206,67 +183,22 @@ ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& gri
 #pragma unroll
     for (int kc = 0; kc < L::KG_C; ++kc) {          // high decoder: K-group 0 = its own grid, K-group 1 = the low grid (decoder.py:182-187)
         float c[16];
-#if defined(ADFP_EXP_NOGATHER)     // timing experiments (tools/ab_high.sh): no gather at all / no second gather
-        for (int r = 0; r < 16; ++r) c[r] = pn[r % 3] * (float)(r + 1 + 16 * kc);
-#elif defined(ADFP_EXP_NOGATHER1)
-        if (kc == 0) gather16(grid, pn, g & 1, c); else for (int r = 0; r < 16; ++r) c[r] = pn[r % 3] * (float)(r + 1);
-#else
         gather16(kc == 0 ? grid : grid1, pn, g & 1, c);   // c[r] <-> channel kmapH(r, g & 1) of the front point: pieces g&1, +2, +4, +6 of the voxel line
-#endif
         // lower lanes (block 0) keep K-group g = c[0..3], c[8..11] and give K-group g + 2 = c[4..7], c[12..15]; upper lanes (block 1,
         // g = 2, 3) keep c[4..7], c[12..15] and give c[0..3], c[8..11]: swap_halves(x, y) moves x.upper <-> y.lower
         float x[8] = {c[0], c[1], c[2], c[3], c[8], c[9], c[10], c[11]};
         float y[8] = {c[4], c[5], c[6], c[7], c[12], c[13], c[14], c[15]};
 #pragma unroll
         for (int s = 0; s < 8; ++s) swap_halves(x[s], y[s]);
-#if !defined(ADFP_EXP_TRAIN_NOC)          // timing experiment (tools/build_ab_libs.sh): the training forward without the c piece of the rows
         if constexpr (TRAIN) {
             static_assert(!TRAIN || CDIM == 32, "training rows: 32-channel decoders");
             if (srow[0]) { row_store(srow[0] + ST::xm(ST::SC) + 4 * g, f32x4{x[0], x[1], x[2], x[3]}); row_store(srow[0] + ST::xm(ST::SC) + 16 + 4 * g, f32x4{x[4], x[5], x[6], x[7]}); }
             if (srow[1]) { row_store(srow[1] + ST::xm(ST::SC) + 4 * g, f32x4{y[0], y[1], y[2], y[3]}); row_store(srow[1] + ST::xm(ST::SC) + 16 + 4 * g, f32x4{y[4], y[5], y[6], y[7]}); }
         }
-#endif
         split8(x, ch[kc][0], cl[kc][0], amax);      // block 0: channels unit16(8 g + j)
         split8(y, ch[kc][1], cl[kc][1], amax);      // block 1
     }
-    ADFP_PHG(1);
     f16x8 eh[L::KG_E][2], el[L::KG_E][2];
-#if defined(ADFP_PB_MFMA)
-    // p @ B on the f32 matrix pipe (round 6; role P of k_decode_bwd_roles does the same, bit-identical to the fma chain below:
-    // tools/micro/mfma_f32_fma_order.hip).  One v_mfma_f32_32x32x2_f32 pair per K-group: D[slot][point], K = 3 as (x, y) then (z, 0)
-    // -- each k step an f32 fma, so an element is fmaf(z, bz, fmaf(y, by, x * bx)).  Operands: A = the Fourier rows, lane
-    // (i = l & 31, k = l >> 5) reads ONE row -- the row of slot sigma(i) -- instead of eight; B = the positions, lane (c = l & 31)
-    // = point 16 (g & 1) + n.  D: lane (n, g) holds, for ITS point pb = g & 1, the 16 rows (r & 3) + 8 (r >> 2) + 4 (g >> 1); sigma
-    // places K-group 2 (g >> 1)'s eight slots in registers 0-7 and K-group 2 (g >> 1) + 1's in registers 8-15, so the lane pair
-    // (l, l ^ 16) -- same rows, the two point blocks -- trade what the other needs with eight v_permlane16_swap: afterwards
-    // a[s] = slot 8 g + s of point n, b[s] = the same slot of point 16 + n, on every lane.
-    {
-        const int i31 = lane & 31;
-        const int slot = 16 * ((i31 >> 2) & 1) + 8 * (i31 >> 4) + (i31 & 3) + 4 * ((i31 >> 3) & 1);
-        const float* bsl = (const float*)ldsu + L::P_BM + 4 * slot;
-        const bool k1 = lane >= 32, odd = (g & 1) != 0;
-        const float px = odd ? pf[1][0] : pf[0][0], py = odd ? pf[1][1] : pf[0][1], pz = odd ? pf[1][2] : pf[0][2];
-        const float pxy = k1 ? py : px, pz0 = k1 ? 0.f : pz;
-#pragma unroll
-        for (int kg = 0; kg < L::KG_E; ++kg) {
-            const f32x4 bm = *(const f32x4*)(bsl + 128 * kg);
-            f32x16 av;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) av[r] = 0.f;
-            av = __builtin_amdgcn_mfma_f32_32x32x2f32(k1 ? bm.y : bm.x, pxy, av, 0, 0, 0);
-            av = __builtin_amdgcn_mfma_f32_32x32x2f32(k1 ? 0.f : bm.z, pz0, av, 0, 0, 0);
-            float e0[8], e1[8];
-#pragma unroll
-            for (int s_ = 0; s_ < 8; ++s_) {
-                const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(av[s_]), __float_as_uint(av[8 + s_]), false, false);
-                e0[s_] = adfp_sinf(__uint_as_float(sw[0]));
-                e1[s_] = adfp_sinf(__uint_as_float(sw[1]));
-            }
-            split8<false>(e0, eh[kg][0], el[kg][0], amax);
-            split8<false>(e1, eh[kg][1], el[kg][1], amax);
-        }
-    }
-#else
 #pragma unroll
     for (int kg = 0; kg < L::KG_E; ++kg) {
         float e0[8], e1[8];
@@ -279,8 +211,6 @@ ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& gri
         split8<false>(e0, eh[kg][0], el[kg][0], amax);
         split8<false>(e1, eh[kg][1], el[kg][1], amax);
     }
-#endif
-    ADFP_PHG(2);
     __builtin_amdgcn_sched_barrier(0);
     f32x4g acc[2][2];
     f16x8 hh[1][2], hl[1][2];
@@ -323,7 +253,6 @@ ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& gri
             }
         }
     }
-    ADFP_PHG(3);
     // output_linear on the VALU in f32: the lane holds units 16 ob + 4 g + r of its two points; the four K-groups add up by two
     // exchanges (lanes l ^ 16, l ^ 32)
 #pragma unroll
@@ -341,7 +270,6 @@ ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& gri
             out[pb][o] = s + ((const float*)ldsu)[L::P_BO + o];
         }
     }
-    ADFP_PHG(4);
     if constexpr (TRAIN) {
         // layer i's 16 bits: the low half of its register for i = 1, 3, 4, the high half for i = 0, 2; nibbles [ob0 pb0][ob0 pb1][ob1 pb0][ob1 pb1]
         const int sh = 4 * (g >> 1);
@@ -365,7 +293,19 @@ ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& gri
     }
 }
 
-// DecodeLCArgs is k_decode_lc's; packed_low / packed_color point at the G images
+// =============================================================================================
+// LOW + COLOR in ONE launch (stage color, inference).  Both decoders run on every sample point of a ray batch with the same
+// position; as two launches each of them reconstructed the point (f64 o + d z), normalised it (f64), took its ticket, loaded its
+// z_vals and stored its part of the 16-byte raw row on its own (partial-line stores from two kernels: 20.6 + 16.7 B written per
+// sample for 16 B of payload, profiles/r02_pmc_hbm_traffic.csv).  Here a wave does the point work once per tile, evaluates the
+// low network and then the colour network out of two weight images that share the CU's LDS (still one 768-thread workgroup per
+// CU, 3 waves per SIMD) and writes raw as ONE 16-byte store per point -- and a frame has one launch tail per batch instead of two.
+//
+// The second image lies beyond the 64 KB reach of a ds_read's immediate offset.  With its address a compile-time constant the
+// compiler materialised one address register per distinct offset and hoisted them all out of the tile loop (109 spilled
+// VGPRs); with the image's word offset an opaque per-tile register value (off_low / off_col below) every access is
+// (offset + lane term) + small immediate again, and nothing that derives from it is loop invariant.
+// =============================================================================================
 template <int NT>
 __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16(DecodeLCArgs a) {
     using LL = DecLayoutG<32, 1>;
@@ -386,10 +326,6 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16(DecodeLCArgs a) {
     const TilePlan plan = tile_plan(ntiles, (int)gridDim.x, NT / 64, a.pool != nullptr);
     float amax_low = image_out_of_range<LL::P_FLAG, LL::NFLAG>(lds_low) ? INFINITY : 0.f;
     float amax_col = image_out_of_range<LC::P_FLAG, LC::NFLAG>(lds_col) ? INFINITY : 0.f;
-#ifdef ADFP_STAMPS_G
-    unsigned long long ph_[24] = {}, last_ = clock64();
-    const unsigned long long wstart_ = wall_clock64();
-#endif
     for (int j = threadIdx.x >> 6, tile; (tile = claim_tile_pool<NT / 64>(j, &s_next, s_ring, plan, ntiles, a.pool, a.status)) >= 0;) {
         // front point: point n of block 0 on lanes 0-31 (both K-groups g = 0, 1 of the pair), of block 1 on lanes 32-63
         const int idx = tile * 32 + 16 * (g >> 1) + n;
@@ -412,16 +348,14 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16(DecodeLCArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) swap_halves(pf[0][k], pf[1][k]);
         float occ[2][1], rgb[2][4];
-        int off_low = 0, off_col = LL::P_TOTAL;        // word offsets of the two images, opaque and per tile (see k_decode_lc)
+        int off_low = 0, off_col = LL::P_TOTAL;        // word offsets of the two images, opaque and per tile
         asm volatile("" : "+v"(off_low), "+v"(off_col));
-#ifdef ADFP_STAMPS_G
-        ph_[14] += 1;
-#endif
-        ADFP_PHG(8);
-        decode_net_g<32, 1>(lds_all + off_low, a.g_low, a.g_low, pn, pf, lane, amax_low, occ, nullptr, nullptr, 0u ADFP_PHG_ARGS(8));
+        decode_net_g<32, 1>(lds_all + off_low, a.g_low, a.g_low, pn, pf, lane, amax_low, occ, nullptr, nullptr, 0u);
+        // the colour network starts here, not earlier: without the opaque pass the optimiser hoists its trilinear set-up and
+        // gather above the low network's layers and the two networks' operand sets no longer fit 168 registers
         asm volatile("" : "+v"(pn[0]), "+v"(pn[1]), "+v"(pn[2]), "+v"(occ[0][0]), "+v"(occ[1][0]));
         __builtin_amdgcn_sched_barrier(0);
-        decode_net_g<32, 4>(lds_all + off_col, a.g_color, a.g_color, pn, pf, lane, amax_col, rgb, nullptr, nullptr, 0u ADFP_PHG_ARGS(16));
+        decode_net_g<32, 4>(lds_all + off_col, a.g_color, a.g_color, pn, pf, lane, amax_col, rgb, nullptr, nullptr, 0u);
         // the front point's lane with g & 1 == 0 stores its row: lanes 0-15 block 0, lanes 32-47 block 1
         if (valid && (g & 1) == 0) {
             const int pb = g >> 1;
@@ -431,15 +365,7 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16(DecodeLCArgs a) {
             *(f32x4*)(a.raw + 4ll * q) = pnan ? f32x4{nanv, nanv, nanv, o} : c4;
             if (a.write_w) a.w[q] = 1.f;
         }
-        ADFP_PHG(21);
     }
-#ifdef ADFP_STAMPS_G
-    { const unsigned long long wend_ = wall_clock64();       // before the phase atomics below (3 072 waves x 16 atomics on 16 addresses)
-      const int wv_ = blockIdx.x * (NT / 64) + (threadIdx.x >> 6); if (lane == 0 && wv_ < 4096) { g_wave_span_g[2 * wv_] = wstart_ | (ph_[14] << 48); g_wave_span_g[2 * wv_ + 1] = wend_; } }
-#if ADFP_STAMPS_G != 2      // (= 2: spans only -- the 49 000 atomics below queue up in L2 in front of the still running waves' gathers and fake a tail)
-    if (lane == 0) for (int k = 8; k < 24; ++k) atomicAdd(&g_phase_g[k], ph_[k]);
-#endif
-#endif
     report_range(a.status, amax_low, ADFP_STATUS_F16_RANGE_LOW, a.call_flag);
     report_range(a.status, amax_col, ADFP_STATUS_F16_RANGE_COLOR, a.call_flag);
 }
@@ -503,9 +429,6 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16_train(DecodeLCTrai
         // the rows of the lane's two points (point 16 pb + n of the tile): row of point-block 0 + which of the two exist
         const int i0 = tile * 32 + n;
         const unsigned rowbits = (i0 < count ? 1u : 0u) | (i0 + 16 < count ? 2u : 0u);
-#ifdef ADFP_STAMPS_G
-        unsigned long long ph_[24] = {}, last_ = 0;      // not collected for the training kernel
-#endif
         float occ[2][1], rgb[2][4];
         unsigned mw[3];
         int off_low = 0, off_col = LL::P_TOTAL;
@@ -516,13 +439,13 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16_train(DecodeLCTrai
             for (int k = 0; k < 4; ++k) { rgb[0][k] = 0.f; rgb[1][k] = 0.f; }
         }
         if (do_low) {
-            decode_net_g<32, 1, 1>(lds_all + off_low, a.g_low, a.g_low, pn, pf, lane, amax_low, occ, mw, t.act_low + (long long)i0 * ST::NXM, t.act_low ? rowbits : 0u ADFP_PHG_ARGS(8));
+            decode_net_g<32, 1, 1>(lds_all + off_low, a.g_low, a.g_low, pn, pf, lane, amax_low, occ, mw, t.act_low + (long long)i0 * ST::NXM, t.act_low ? rowbits : 0u);
             if (valid) { unsigned* mrow = t.masks_low + ((long long)q * 2 + (g & 1)) * 3; mrow[0] = mw[0]; mrow[1] = mw[1]; mrow[2] = mw[2]; }
         }
         asm volatile("" : "+v"(pn[0]), "+v"(pn[1]), "+v"(pn[2]), "+v"(occ[0][0]), "+v"(occ[1][0]));
         __builtin_amdgcn_sched_barrier(0);
         if (do_col) {
-            decode_net_g<32, 4, 1>(lds_all + off_col, a.g_color, a.g_color, pn, pf, lane, amax_col, rgb, mw, t.act_color + (long long)i0 * ST::NXM, t.act_color ? rowbits : 0u ADFP_PHG_ARGS(16));
+            decode_net_g<32, 4, 1>(lds_all + off_col, a.g_color, a.g_color, pn, pf, lane, amax_col, rgb, mw, t.act_color + (long long)i0 * ST::NXM, t.act_color ? rowbits : 0u);
             if (valid) { unsigned* mrow = t.masks_color + ((long long)q * 2 + (g & 1)) * 3; mrow[0] = mw[0]; mrow[1] = mw[1]; mrow[2] = mw[2]; }
         }
         if (valid && (g & 1) == 0) {
@@ -552,11 +475,7 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16_train(DecodeLCTrai
 // =============================================================================================
 template <int NT>
 __global__ __launch_bounds__(NT, NT / 256) void k_decode_high_g(DecodeArgs a) {
-#ifdef ADFP_EXP_HIGH_AS_LOW        // timing experiment (tools/inband_bisect.sh): the LOW network's body (32 grid channels, one gather) in THIS
-    using L = DecLayoutG<32, 1>;   // kernel's launch shape -- list-indexed tiles, one image in LDS, 512 threads; a.packed = the low G image
-#else
     using L = DecLayoutG<64, 1>;
-#endif
     __shared__ __attribute__((aligned(16))) unsigned ldsu[L::P_TOTAL];
     __shared__ int s_next;
     __shared__ unsigned long long s_ring[ADFP_POOL_RING];
@@ -569,21 +488,14 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_high_g(DecodeArgs a) {
     const int ntiles = (count + 31) >> 5;
     const TilePlan plan = tile_plan(ntiles, (int)gridDim.x, NT / 64, a.pool != nullptr);
     float amax = image_out_of_range<L::P_FLAG, L::NFLAG>(ldsu) ? INFINITY : 0.f;
-#ifdef ADFP_STAMPS_G
-    unsigned long long ph_[8] = {}, last_ = clock64();
-#endif
     for (int j = threadIdx.x >> 6, tile; (tile = claim_tile_pool<NT / 64>(j, &s_next, s_ring, plan, ntiles, a.pool, a.status)) >= 0;) {
         const int idx = tile * 32 + 16 * (g >> 1) + n;
         const bool valid = idx < count;
-#ifdef ADFP_HIGH_IDENTITY      // timing experiment: the same number of tiles over CONTIGUOUS points (no list indirection; results are not the network's)
-        const int q = valid ? idx : 0;
-#else
         const int q = a.list[valid ? idx : 0];
-#endif
         float pn[3], pf[2][3];
         bool pnan;
         // the point's low-decoder value (added to the output at the end of the tile): requested NOW -- waited for after the network
-        // it was a full memory latency per tile with nothing in flight (13 % of the wave's tile time, tools/phase_g.py)
+        // it was a full memory latency per tile with nothing in flight (13 % of the wave's tile time)
         const float low_occ = (a.single || !valid) ? 0.f : a.raw[4ll * q + 3];
         {
             double pt[3];
@@ -596,27 +508,13 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_high_g(DecodeArgs a) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) swap_halves(pf[0][k], pf[1][k]);
         float out[2][1];
-#ifdef ADFP_STAMPS_G
-        ph_[6] += 1;
-#endif
-        ADFP_PHG(0);
-#ifdef ADFP_EXP_HIGH_AS_LOW
-        decode_net_g<32, 1>(ldsu, a.g1, a.g1, pn, pf, lane, amax, out, nullptr, nullptr, 0u ADFP_PHG_ARGS(0));
-#else
-        decode_net_g<64, 1>(ldsu, a.g0, a.g1, pn, pf, lane, amax, out, nullptr, nullptr, 0u ADFP_PHG_ARGS(0));
-#endif
+        decode_net_g<64, 1>(ldsu, a.g0, a.g1, pn, pf, lane, amax, out, nullptr, nullptr, 0u);
         if (valid && (g & 1) == 0) {
             const float o = g >> 1 ? out[1][0] : out[0][0];
             const float v = pnan ? __builtin_nanf("") : o;
             a.att_occ[idx] = a.single ? v : v + low_occ;    // high + low, decoder.py:342
         }
-        ADFP_PHG(5);
     }
-#ifdef ADFP_STAMPS_G
-#if ADFP_STAMPS_G != 2
-    if (lane == 0) for (int k = 0; k < 8; ++k) atomicAdd(&g_phase_g[k], ph_[k]);
-#endif
-#endif
     report_range(a.status, amax, ADFP_STATUS_F16_RANGE_HIGH, a.call_flag);
 }
 

@@ -7,9 +7,8 @@
 // an f16 MFMA stream ~2 instructions per 32-cycle slot, and a wave's own fillers cost 2.5-4 cycles each.
 // The exact-f32 decoder therefore costs  64 cyc x 240 f32 MFMAs + the VALU work  per 32-point tile, the MFMA
 // term is 70 % of it and f32-input MFMA runs at 1/16 of the f16 rate.  Three f16 MFMAs per 16 k-values
-// replace eight f32 MFMAs: 90 x 32 cycles instead of 240 x 64.  Per-phase stamps of this kernel (debug build
-// -DADFP_STAMPS, tools/ab_stage.py): gather 32 %, Fourier features 25 %, the five layers 33 %, output layer +
-// store 8 % of the wave-cycles.
+// replace eight f32 MFMAs: 90 x 32 cycles instead of 240 x 64.  Per-phase stamps of this kernel: gather 32 %,
+// Fourier features 25 %, the five layers 33 %, output layer + store 8 % of the wave-cycles.
 //
 // Accuracy (tools/micro/f16x3_accuracy.hip, K = 128): max error relative to the largest output
 // 3.6e-7 for O(1) operands and 9.5e-7 for O(0.03) operands, against 3.6e-7 / 2.5e-7 for the exact f32
@@ -146,24 +145,6 @@ __global__ void k_pack_decoder_h(const float* __restrict__ flat, unsigned* __res
 // pair): an operand at or beyond the f16 range (65504) cannot be split -- cvt_pkrtz saturates it -- so the kernels
 // raise the sticky ADFP_STATUS_F16_RANGE bit of adfp_scene.status when amax reaches it (CHECK = false for values
 // that are bounded by construction: sines).
-#ifdef ADFP_SPLIT_MASK
-// 3 VALU per value: and, sub, 2 x cvt_pkrtz per pair.  hi = x truncated to 11 significant bits (a mask;
-// exactly representable in f16), lo = x - hi.
-template <bool CHECK = true>
-ADFP_DEV void split8(const float* __restrict__ x, f16x8& hi, f16x8& lo, float& amax) {
-    u32x4 uh, ul;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float a = x[2 * j], b = x[2 * j + 1];
-        if (CHECK) amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b)), amax);
-        const float ah = f16_hi_part(a), bh = f16_hi_part(b);
-        uh[j] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ah, bh));
-        ul[j] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a - ah, b - bh));
-    }
-    hi = __builtin_bit_cast(f16x8, uh);
-    lo = __builtin_bit_cast(f16x8, ul);
-}
-#else
 // 1.5 VALU per value: hi = cvt_pkrtz (round toward zero = the 11-bit truncation) for a pair, then lo = x - hi as ONE
 // v_fma_mixlo_f16 / v_fma_mixhi_f16 per value: the f16 half is widened inside the instruction, the difference is formed exactly
 // in f32 and lands, rounded to f16, in the low / high half of the packed register -- no separate conversion of the remainders
@@ -193,7 +174,6 @@ ADFP_DEV void split8(const float* __restrict__ x, f16x8& hi, f16x8& lo, float& a
     // the f32 values it still has to look at
     if (CHECK) asm volatile("" : "+v"(amax));
 }
-#endif
 #define ADFP_F16_MAX 65504.0f
 // once per wave, after its tile loop: the sticky word for the host (which network, so that it can switch that one to the exact
 // image) and the CALL's flag (device memory, zeroed by the call) that arms the f32 fallback kernel and the backward's gate
@@ -217,15 +197,6 @@ ADFP_DEV void mfma_chain_h(f32x16& acc, const unsigned* __restrict__ w, int lane
     }
     __builtin_amdgcn_sched_barrier(0);   // keep the scheduler from hoisting the next chain's LDS reads
 }
-
-#ifdef ADFP_STAMPS
-__device__ unsigned long long g_stamps[2 * 8192];     // debug build only: per-wave start/end wall clock (100 MHz)
-__device__ unsigned long long g_phase[8];             // debug build only: wave-cycles per tile phase, summed over waves
-#define ADFP_PHASE(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = clock64(); \
-                           __builtin_amdgcn_sched_barrier(0); ph_[k] += now_ - last_; last_ = now_; } while (0)
-#else
-#define ADFP_PHASE(k) do {} while (0)
-#endif
 
 // relu + the fc_c bias, recording which units are active: bit (15 - r) of the low half of `m` = (relu(acc[r]) > 0), the
 // predicate of torch's relu backward.  Two instructions per unit (0 - bits has its sign bit set exactly for bits > 0;
@@ -254,9 +225,6 @@ template <int CDIM, int NOUT, int ROLE, int NT, int TRAIN = 0>
 __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : (ROLE == ROLE_HIGH ? 1 : 2))) void k_decode_h(DecodeArgs a) {
     using L = DecLayoutH<CDIM, NOUT>;
     using ST = DecStage<CDIM>;
-#ifdef ADFP_STAMPS
-    const unsigned long long stamp0 = wall_clock64();
-#endif
     __shared__ __attribute__((aligned(16))) unsigned ldsu[L::P_TOTAL];
     __shared__ int s_next;
     image_to_lds<NT, L::P_TOTAL / 4>(ldsu, a.packed);
@@ -269,12 +237,8 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : (ROLE == ROLE_HIGH ? 1 
     const int count = (ROLE == ROLE_HIGH && a.count_ptr) ? *a.count_ptr : a.P.n;
     const int ntiles = (count + 31) >> 5;
 
-#ifdef ADFP_STAMPS
-    unsigned long long ph_[6] = {0, 0, 0, 0, 0, 0}, last_ = clock64();
-#endif
     float amax = image_out_of_range<L::P_FLAG, L::NFLAG>(ldsu) ? INFINITY : 0.f;      // max |operand| this wave has split (f16 range guard); a weight out of range
     for (int j = threadIdx.x >> 6, tile; (tile = claim_tile<NT / 64>(j, &s_next, ntiles)) >= 0;) {
-        ADFP_PHASE(0);                                  // ticket + loop overhead
         const int idx = tile * 32 + p;
         const bool valid = idx < count;
         int q = valid ? idx : 0;
@@ -305,7 +269,6 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : (ROLE == ROLE_HIGH ? 1 
 #pragma unroll
             for (int ks = 0; ks < L::KS_C; ++ks) split8(c + 8 * ks, ch[ks], cl[ks], amax);
         }
-        ADFP_PHASE(1);                                  // point, normalise, gather, split c
         // Fourier features sin(p @ B) (decoder.py:26-30) -> split halves (6 k-steps)
         f16x8 eh[L::KS_E], el[L::KS_E];
 #pragma unroll
@@ -319,7 +282,6 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : (ROLE == ROLE_HIGH ? 1 
             }
             split8<false>(e, eh[ks], el[ks], amax);     // |sin| <= 1
         }
-        ADFP_PHASE(2);                                  // Fourier features
 
         __builtin_amdgcn_sched_barrier(0);
         // h = relu(W_i h + b_i) + (Wc_i c + bc_i); skip-concat [emb, h] feeds layer 3 (decoder.py:192-199)
@@ -347,7 +309,6 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : (ROLE == ROLE_HIGH ? 1 
             }
         }
 
-        ADFP_PHASE(3);                                  // 5 layers
         // output_linear on the VALU in f32: each half holds 16 of the 32 hidden units
         float out[NOUT];
 #pragma unroll
@@ -378,157 +339,22 @@ __global__ __launch_bounds__(NT, (NT >= 512 ? NT / 256 : (ROLE == ROLE_HIGH ? 1 
                 a.att_occ[idx] = a.single ? out[0] : out[0] + a.raw[4ll * q + 3];    // high + low, decoder.py:342
             }
         }
-        ADFP_PHASE(4);                                  // output layer + store
     }
     report_range(a.status, amax, ROLE == ROLE_LOW ? ADFP_STATUS_F16_RANGE_LOW : (ROLE == ROLE_HIGH ? ADFP_STATUS_F16_RANGE_HIGH : ADFP_STATUS_F16_RANGE_COLOR),
                  a.call_flag);
-#ifdef ADFP_STAMPS
-    if (lane == 0) for (int k = 0; k < 5; ++k) atomicAdd(&g_phase[k], ph_[k]);
-    const int wave = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    if (lane == 0 && wave < 8192) { g_stamps[2 * wave] = stamp0; g_stamps[2 * wave + 1] = wall_clock64(); }
-#endif
 }
 
-// =============================================================================================
-// LOW + COLOR in ONE launch (stage color, inference).  Both decoders run on every sample point of a ray batch with the same
-// position; as two launches each of them reconstructed the point (f64 o + d z), normalised it (f64), took its ticket, loaded its
-// z_vals and stored its part of the 16-byte raw row on its own (partial-line stores from two kernels: 20.6 + 16.7 B written per
-// sample for 16 B of payload, profiles/r02_pmc_hbm_traffic.csv).  Here a wave does the point work once per tile, evaluates the
-// low network and then the colour network out of two weight images that share the CU's LDS (65 + 65 KB of 160 KB; still one
-// 768-thread workgroup per CU, 3 waves per SIMD) and writes raw as ONE 16-byte store per point -- and a frame has one launch
-// tail per batch instead of two.  decode_net_h is k_decode_h's per-tile network evaluation (32-channel grids, no training
-// state), kept textually parallel to it.
-// =============================================================================================
-template <int NOUT>
-ADFP_DEV void decode_net_h(const unsigned* __restrict__ ldsu, const GridDev& g, const float pn[3], const float pf[3], int h, int lane_off,
-                           float& amax, float* __restrict__ out) {
-    // `ldsu` = the workgroup's LDS array + this network's image offset, an opaque per-tile register value at the call site (see
-    // k_decode_lc).  Every LDS access below is one of four lane-dependent bases plus an immediate below 64 KB: the weight rows
-    // (lane_off), the bias rows (4 h), the Fourier rows (16 h) and the output rows (16 NOUT h).
-    using L = DecLayoutH<32, NOUT>;
-    const unsigned* wl = ldsu + lane_off;
-    const float* bh = (const float*)ldsu + 4 * h;
-    const float* b16 = (const float*)ldsu + 16 * h;
-    const float* bw = (const float*)ldsu + 16 * NOUT * h;
-    f16x8 ch[L::KS_C], cl[L::KS_C];
-    {
-        float c[16];
-        gather16(g, pn, h, c);
-#pragma unroll
-        for (int ks = 0; ks < L::KS_C; ++ks) split8(c + 8 * ks, ch[ks], cl[ks], amax);
-    }
-    f16x8 eh[L::KS_E], el[L::KS_E];
-#pragma unroll
-    for (int ks = 0; ks < L::KS_E; ++ks) {
-        float e[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const f32x4 bm = *(const f32x4*)(b16 + L::P_BM + unit_of_h(ks, 0, j) * 4);       // unit_of_h(ks, h, j) = unit_of_h(ks, 0, j) + 4 h
-            const float arg = fmaf(pf[2], bm.z, fmaf(pf[1], bm.y, pf[0] * bm.x));
-            e[j] = adfp_sinf(arg);
-        }
-        split8<false>(e, eh[ks], el[ks], amax);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    f32x16 acc;
-    f16x8 hh[2], hl[2];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        bias_init(acc, bh + L::P_BP(i), 0);
-        if (i == 0) mfma_chain_h<L::KS_E>(acc, wl + L::P_WP(0), 0, eh, el);
-        else if (i == 3) {
-            mfma_chain_h<L::KS_E>(acc, wl + L::P_WP(3), 0, eh, el);
-            mfma_chain_h<2>(acc, wl + L::P_WP(3) + L::KS_E * 512, 0, hh, hl);
-        } else mfma_chain_h<2>(acc, wl + L::P_WP(i), 0, hh, hl);
-        relu_bias(acc, bh + L::P_BC(i), 0);
-        mfma_chain_h<L::KS_C>(acc, wl + L::P_WC(i), 0, ch, cl);
-        if (i < 4) {
-            float t[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) t[r] = acc[r];
-            split8(t, hh[0], hl[0], amax);
-            split8(t + 8, hh[1], hl[1], amax);
-        }
-    }
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-        const float* wo = bw + L::P_WO + o * 16;
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s = fmaf(acc[r], wo[r], s);
-        s += __shfl_xor(s, 32);
-        out[o] = s + ((const float*)ldsu)[L::P_BO + o];
-    }
-}
-
+// arguments of the fused LOW + COLOR launches (k_decode_lc16, adfp_decode_g.h)
 struct DecodeLCArgs {
     PtsDev P; NormDev nb; double b[6];
     GridDev g_low, g_color;
-    const unsigned* packed_low; const unsigned* packed_color;     // H images
+    const unsigned* packed_low; const unsigned* packed_color;     // G images
     const unsigned char* flags;                                   // ADFP_F_BAND per point (or NULL)
     float* raw; float* w;
     int write_w, apply_bound;
     int* status; int* call_flag;
     int* pool;                 // k_decode_lc16: device counter of the chip-wide tile tail (claim_tile_pool), zero at launch, or NULL
 };
-template <int NT>
-__global__ __launch_bounds__(NT, NT / 256) void k_decode_lc(DecodeLCArgs a) {
-    using LL = DecLayoutH<32, 1>;
-    using LC = DecLayoutH<32, 4>;
-    __shared__ __attribute__((aligned(16))) unsigned lds_all[LL::P_TOTAL + LC::P_TOTAL];      // the low image, then the colour image
-    __shared__ int s_next;
-    unsigned* lds_low = lds_all;
-    unsigned* lds_col = lds_all + LL::P_TOTAL;
-    image_to_lds<NT, LL::P_TOTAL / 4>(lds_low, a.packed_low);
-    image_to_lds<NT, LC::P_TOTAL / 4>(lds_col, a.packed_color);
-    if (threadIdx.x == 0) s_next = NT / 64;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, p = lane & 31, h = lane >> 5;
-    const int lane_off = h * 128 + p * 4;
-    const int count = a.P.n;
-    const int ntiles = (count + 31) >> 5;
-    float amax_low = image_out_of_range<LL::P_FLAG, LL::NFLAG>(lds_low) ? INFINITY : 0.f;
-    float amax_col = image_out_of_range<LC::P_FLAG, LC::NFLAG>(lds_col) ? INFINITY : 0.f;
-    // The second image lies beyond the 64 KB reach of a ds_read's immediate offset.  With its address a compile-time constant the
-    // compiler materialised one address register per distinct offset and hoisted them all out of the tile loop (109 spilled
-    // VGPRs); with the image's word offset an opaque register value every access is (offset + lane term) + small immediate again.
-    for (int j = threadIdx.x >> 6, tile; (tile = claim_tile<NT / 64>(j, &s_next, ntiles)) >= 0;) {
-        const int idx = tile * 32 + p;
-        const bool valid = idx < count;
-        const int q = valid ? idx : 0;
-        float pn[3], pf[3];
-        bool pnan, keep_occ;                            // everything the f64 point is needed for, so that it dies before the networks
-        {
-            double pt[3];
-            load_point(a.P, q, pt);
-            normalize3(a.nb, pt, pn);
-            pf[0] = (float)pt[0]; pf[1] = (float)pt[1]; pf[2] = (float)pt[2];   // p.float() decoder.py:189
-            pnan = (pt[0] != pt[0]) | (pt[1] != pt[1]) | (pt[2] != pt[2]);
-            const unsigned f = a.flags ? a.flags[q] : 0u;
-            // in-band points keep the true low value for the HIGH pass; the attention pass overwrites them afterwards
-            keep_occ = (f & ADFP_F_BAND) || in_bound(pt, a.b) || !a.apply_bound;           // Renderer.py:64
-        }
-        float occ[1], rgb[4];
-        int off_low = 0, off_col = LL::P_TOTAL;        // word offsets of the two images in lds_all, opaque and per tile: nothing that
-        asm volatile("" : "+v"(off_low), "+v"(off_col));   // derives from them is loop invariant (hoisted address registers were spilled)
-        const unsigned* img_low = lds_all + off_low;
-        const unsigned* img_col = lds_all + off_col;
-        decode_net_h<1>(img_low, a.g_low, pn, pf, h, lane_off, amax_low, occ);
-        // the colour network starts here, not earlier: without the opaque pass the optimiser hoists its trilinear set-up and
-        // gather above the low network's layers and the two networks' operand sets no longer fit 168 registers
-        asm volatile("" : "+v"(pn[0]), "+v"(pn[1]), "+v"(pn[2]), "+v"(pf[0]), "+v"(pf[1]), "+v"(pf[2]), "+v"(occ[0]));
-        __builtin_amdgcn_sched_barrier(0);
-        decode_net_h<4>(img_col, a.g_color, pn, pf, h, lane_off, amax_col, rgb);
-        if (valid && h == 0) {
-            const float nanv = __builtin_nanf("");     // a NaN position renders NaN like the reference's (nan_point_outputs)
-            const float o = pnan ? nanv : (keep_occ ? occ[0] : 100.f);
-            *(f32x4*)(a.raw + 4ll * q) = pnan ? f32x4{nanv, nanv, nanv, o} : f32x4{rgb[0], rgb[1], rgb[2], o};
-            if (a.write_w) a.w[q] = 1.f;
-        }
-    }
-    report_range(a.status, amax_low, ADFP_STATUS_F16_RANGE_LOW, a.call_flag);
-    report_range(a.status, amax_col, ADFP_STATUS_F16_RANGE_COLOR, a.call_flag);
-}
 
 // =============================================================================================
 // attention fusion mlp_tsdf (a11) on f16 MFMA with the same 3-product split

@@ -247,28 +247,7 @@ ADFP_DEV float adfp_turns(float x) {
     float t = fmaf(x, 0.15915494f, -k);
     return fmaf(x, 6.4206382432985265e-09f, t);
 }
-#ifdef ADFP_SIN_POLY
-ADFP_DEV float adfp_sinf(float x) {
-    const float k = rintf(x * 0.636619772f);
-    float r = fmaf(k, -1.57079601e+00f, x);
-    r = fmaf(k, -3.13916473e-07f, r);
-    r = fmaf(k, -5.39030253e-15f, r);
-    const int n = (int)k;
-    const float r2 = r * r;
-    float s = fmaf(r2, 2.86567956e-6f, -1.98559923e-4f);
-    s = fmaf(s, r2, 8.33338592e-3f);
-    s = fmaf(s, r2, -1.66666672e-1f);
-    s = fmaf(s * r2, r, r);
-    float c = fmaf(r2, 2.44677067e-5f, -1.38877297e-3f);
-    c = fmaf(c, r2, 4.16666567e-2f);
-    c = fmaf(c, r2, -0.5f);
-    c = fmaf(c, r2, 1.0f);
-    float v = (n & 1) ? c : s;
-    return (n & 2) ? -v : v;
-}
-#else
 ADFP_DEV float adfp_sinf(float x) { return __builtin_amdgcn_sinf(adfp_turns(x)); }
-#endif
 ADFP_DEV void adfp_sincosf(float x, float& sn, float& cs) {
     const float t = adfp_turns(x);
     sn = __builtin_amdgcn_sinf(t);
@@ -542,8 +521,8 @@ ADFP_DEV float wave_scan_mul(float v, int lane, float& total) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Tile hand-out with a CHIP-WIDE tail (round 4).  Per-wave end stamps of the fused decoder launch (tools/phase_g.py, spans-only
-// build) showed the waves of a workgroup ending within 23 us of each other but the WORKGROUPS 1 352 ... 1 444 us after the start
+// Tile hand-out with a CHIP-WIDE tail (round 4).  Per-wave end stamps of the fused decoder launch
+// showed the waves of a workgroup ending within 23 us of each other but the WORKGROUPS 1 352 ... 1 444 us after the start
 // (one XCD 3.4 % behind the others): with every workgroup owning the same number of tiles the launch waits for its slowest CU
 // while the others idle -- 4.9 % of the launch.  So a workgroup owns only its first `j_static` slots (whole rows of the fixed
 // split); the tiles behind them (from `pool_base` on) are handed out in CHUNKS of NWW consecutive tiles from ONE device counter,
@@ -607,35 +586,17 @@ ADFP_DEV int claim_tile_pool(int& j, int* s_next, unsigned long long* s_ring, co
 //   wg_tile(j) = blockIdx.x * NWW + (j % NWW) + (j / NWW) * (gridDim.x * NWW),   j = 0, 1, 2, ...
 // (the same set a fixed wave-strided split would give it) and its waves take slots j from an LDS
 // ticket.  The SIMD arbiter favours the oldest wave, so with a fixed split the young waves of every
-// SIMD finished ~20 % after the old ones (measured per-wave end stamps, tools/ab_stage.py).
+// SIMD finished ~20 % after the old ones (measured per-wave end stamps).
 // *s_next must be initialised to NWW before the barrier that precedes the loop; wave w starts at j = w.
 // Returns the tile of slot j (or -1 when the workgroup's tiles are exhausted) and advances j.
 // ---------------------------------------------------------------------------------------------
 template <int NWW>
 ADFP_DEV int claim_tile(int& j, int* s_next, int ntiles) {
-#ifdef ADFP_XCD_TILES
-    // XCD-aware variant: workgroup b runs on XCD b % 8 (round-robin dispatch); give every XCD one CONTIGUOUS
-    // eighth of the tiles (a band of image rows) so that its private L2 sees one eighth of the frustum's grid
-    // lines instead of a 1-in-8 sample of all of them.
-    int tile;
-    if ((gridDim.x & 7) == 0) {
-        const int xcd = blockIdx.x & 7, bl = blockIdx.x >> 3, gl = gridDim.x >> 3;
-        const int per = ((ntiles + 7) / 8 + NWW - 1) / NWW * NWW;            // tiles per XCD, whole slots
-        const int loc = bl * NWW + (j % NWW) + (j / NWW) * (gl * NWW);
-        if (loc >= per) return -1;
-        tile = xcd * per + loc;
-    } else tile = blockIdx.x * NWW + (j % NWW) + (j / NWW) * (gridDim.x * NWW);
-#else
     const int tile = blockIdx.x * NWW + (j % NWW) + (j / NWW) * (gridDim.x * NWW);
-#endif
     if (tile >= ntiles) return -1;
-#ifdef ADFP_STATIC_TILES        // A/B switch: the fixed split
-    j += NWW;
-#else
     int jn = 0;
     if ((threadIdx.x & 63) == 0) jn = atomicAdd(s_next, 1);
     j = __builtin_amdgcn_readfirstlane(jn);
-#endif
     return tile;
 }
 

@@ -210,15 +210,6 @@ __global__ void k_pack_decoder(const float* __restrict__ flat, float* __restrict
     const int s = dec_src_index<CDIM, NOUT>(t);
     packed[t] = s < 0 ? 0.f : flat[s];
 }
-// gradient of the packed image -> gradient of the flat parameters (every flat element has
-// exactly one packed position)
-template <int CDIM, int NOUT>
-__global__ void k_unpack_decoder_grad(const float* __restrict__ packed, float* __restrict__ flat) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= DecLayout<CDIM, NOUT>::P_TOTAL) return;
-    const int s = dec_src_index<CDIM, NOUT>(t);
-    if (s >= 0) flat[s] = packed[t];
-}
 
 __device__ int att_src_index(int t) {
     using A = AttLayout;
@@ -1043,33 +1034,11 @@ __global__ __launch_bounds__(256) void k_composite(const float* __restrict__ raw
 #include "adfp_backward_h.h"
 #include "adfp_backward_fused.h"
 #include "adfp_backward_roles.h"
-#ifdef ADFP_STAMPS_ROLES
-extern "C" int adfp_debug_roles_span(unsigned long long* host_out) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_roles_span), sizeof(unsigned long long) * 4 * 256);
-}
-#endif
-#ifdef ADFP_STAMPS
-extern "C" int adfp_debug_phases_fused(unsigned long long* host_out, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_phase_fused), 64);
-    if (!rc && reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; rc = (int)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_fused), z, 64); }
-    return rc;
-}
-#endif
 #include "adfp_fusion.h"
 #include "adfp_mapping.h"
 #include "adfp_mapper_iter.h"
 #include "adfp_tracker_iter.h"
 #include "adfp_decode_g.h"
-#ifdef ADFP_STAMPS_G
-extern "C" int adfp_debug_phases_g(unsigned long long* host_out, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_phase_g), 192);
-    if (!rc && reset) { unsigned long long z[24] = {}; rc = (int)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_g), z, 192); }
-    return rc;
-}
-extern "C" int adfp_debug_wave_span_g(unsigned long long* host_out, int n_waves) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_wave_span_g), (size_t)n_waves * 16);
-}
-#endif
 
 // adfp_ray_sort_keys (adfp.h): Morton keys of (origin cell, surface-point cell) per ray
 __device__ __forceinline__ unsigned morton3(unsigned x, unsigned y, unsigned z, int bits) {
@@ -1681,17 +1650,6 @@ int adfp_sample_tsdf(const adfp_tsdf* tsdf, const double tsdf_bnds[3][2], const 
     return launch_tsdf(&sc, P, nullptr, nullptr, nullptr, nullptr, nullptr, out, (hipStream_t)stream);
 }
 
-#ifdef ADFP_STAMPS
-extern "C" int adfp_debug_stamps(unsigned long long* host_out, int n_waves) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), (size_t)n_waves * 16);
-}
-extern "C" int adfp_debug_phases(unsigned long long* host_out, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_phase), 64);
-    if (!rc && reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; rc = (int)hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, 64); }
-    return rc;
-}
-#endif
-
 static int decode_grid(int ntiles, int waves_per_wg, int wg_per_cu) {
     int g = (ntiles + waves_per_wg - 1) / waves_per_wg;
     const int cap = num_cu() * wg_per_cu;
@@ -1731,7 +1689,7 @@ static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, in
     a.raw = raw; a.w = w; a.att_occ = nullptr; a.write_w = 1; a.apply_bound = apply_bound;   // attention overwrites w on the band
     a.status = sc->status; a.masks = nullptr; a.act = nullptr; a.single = 0; a.call_flag = call_flag;
     const int ntiles = (P.n + 31) / 32;
-    // stage color, inference, both networks f16-split: LOW and COLOR on every point in ONE launch (k_decode_lc)
+    // stage color, inference, both networks f16-split: LOW and COLOR on every point in ONE launch (k_decode_lc16)
     const bool fused_lc = stage == ADFP_STAGE_COLOR && !state && sc->h_low && sc->h_color;
     if (fused_lc) {
         DecodeLCArgs f;
@@ -1740,18 +1698,11 @@ static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, in
         f.packed_low = (const unsigned*)sc->h_low; f.packed_color = (const unsigned*)sc->h_color;
         f.flags = a.flags; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = apply_bound; f.status = sc->status; f.call_flag = call_flag;
         f.pool = ws.counter ? ws.counter + 10 : nullptr;            // zero: this call's 64-byte counter block was cleared above (or by the caller)
-#ifdef ADFP_LC_32X32          // A/B build: the 32x32x16 form of the fused launch (adfp_decode_h.h)
-        hipLaunchKernelGGL((k_decode_lc<ADFP_LC_NT>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
-#else
         f.packed_low += DecLayoutH<32, 1>::P_TOTAL; f.packed_color += DecLayoutH<32, 4>::P_TOTAL;       // the G images
         hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
-#endif
         ADFP_CHECK_LAUNCH();
     }
     // stage color, TRAINING, both networks f16-split with mask room: the same ONE launch, leaving masks (+ layer inputs)
-#ifdef ADFP_LC_32X32
-    const bool fused_lc_train = false;
-#else
     const bool fused_lc_train = stage == ADFP_STAGE_COLOR && state && sc->h_low && sc->h_color && state->masks_low && state->masks_color;
     if (fused_lc_train) {
         DecodeLCTrainArgs t;
@@ -1767,7 +1718,6 @@ static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, in
         else hipLaunchKernelGGL((k_decode_lc16_train<ADFP_LCT_NT, false>), dim3(decode_grid(ntiles, ADFP_LCT_NT / 64, 1)), dim3(ADFP_LCT_NT), 0, st, t);
         ADFP_CHECK_LAUNCH();
     }
-#endif
     // LOW on every point
     a.g0 = make_grid(sc->low); a.g1 = a.g0;
     if (fused_lc || fused_lc_train) {
@@ -1809,17 +1759,9 @@ static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, in
             else hipLaunchKernelGGL((k_decode_h<64, 1, ROLE_HIGH, 512, 1>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
             a.masks = nullptr; a.act = nullptr;
         } else if (sc->h_high) {
-#ifdef ADFP_LC_32X32
-            a.packed = (const float*)sc->h_high;
-            hipLaunchKernelGGL((k_decode_h<64, 1, ROLE_HIGH, ADFP_HIGH_NT>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
-#else
             a.packed = (const float*)((const unsigned*)sc->h_high + DecLayoutH<64, 1>::P_TOTAL);          // the G image
-#ifdef ADFP_EXP_HIGH_AS_LOW
-            a.packed = (const float*)((const unsigned*)sc->h_low + DecLayoutH<32, 1>::P_TOTAL);           // timing experiment: see k_decode_high_g
-#endif
             a.pool = ws.counter ? ws.counter + 11 : nullptr;
             hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
-#endif
         } else {
             a.packed = sc->w_high;
             hipLaunchKernelGGL((k_decode<64, 1, ROLE_HIGH, 512>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
@@ -1833,14 +1775,9 @@ static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, in
             t.packed = (const float*)sc->h_att; t.masks = state->masks_att; t.act = state->act_att;
             hipLaunchKernelGGL((k_attention_h<1, 256>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, t);
         } else if (sc->h_att) {
-#ifdef ADFP_LC_32X32
-            t.packed = (const float*)sc->h_att;
-            hipLaunchKernelGGL(k_attention_h<0>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
-#else
             t.packed = (const float*)((const unsigned*)sc->h_att + AttLayoutH::P_TOTAL);                 // the G image
             t.pool = ws.counter ? ws.counter + 12 : nullptr;
             hipLaunchKernelGGL(k_attention_g<512>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
-#endif
         } else {
             t.packed = sc->w_att;
             hipLaunchKernelGGL(k_attention, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
@@ -1879,12 +1816,8 @@ extern "C" int adfp_decode_stage(const adfp_scene* sc, const adfp_points* pts, i
         f.packed_low = (const unsigned*)sc->h_low; f.packed_color = (const unsigned*)sc->h_color;
         f.flags = nullptr; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = 1; f.status = sc->status; f.call_flag = nullptr; f.pool = tile_counter;
         if (tile_counter) { hipError_t e = zero_async(tile_counter, 4, (hipStream_t)stream); if (e != hipSuccess) return (int)e; }
-#ifdef ADFP_LC_32X32
-        hipLaunchKernelGGL((k_decode_lc<ADFP_LC_NT>), dim3(decode_grid((P.n + 31) / 32, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, (hipStream_t)stream, f);
-#else
         f.packed_low += DecLayoutH<32, 1>::P_TOTAL; f.packed_color += DecLayoutH<32, 4>::P_TOTAL;       // the G images
         hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT>), dim3(decode_grid((P.n + 31) / 32, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, (hipStream_t)stream, f);
-#endif
         ADFP_CHECK_LAUNCH();
         return 0;
     }
@@ -2642,18 +2575,12 @@ static void attention_jobs(OuterArgs& a) {
 // weight gradients of one network: outer_begin (zero the per-workgroup copies), launch_outer per staging chunk,
 // outer_end (sum the copies into the flat gradient)
 static int outer_begin(const BwdWorkspace& bw, int n_floats, hipStream_t st) {
-#ifdef ADFP_OUTER_SIMPLE
-    return 0;
-#else
     (void)n_floats;
     return (int)zero_async(bw.partial, (size_t)OUTER_NSLOT * bw.part_stride * 4, st);
-#endif
 }
 static int outer_end(const BwdWorkspace& bw, int n_floats, float* flat, hipStream_t st) {
-#ifndef ADFP_OUTER_SIMPLE
     hipLaunchKernelGGL(k_reduce_partials, dim3((n_floats + 255) / 256), dim3(256), 0, st, bw.partial, OUTER_NSLOT, bw.part_stride, n_floats, flat);
     ADFP_CHECK_LAUNCH();
-#endif
     return 0;
 }
 static int outer_end_scaled(const BwdWorkspace& bw, int n_floats, float* flat, hipStream_t st) {
@@ -2666,17 +2593,12 @@ static int launch_outer(OuterArgs& oa, const BwdWorkspace& bw, const int* count_
     oa.stage = stage; oa.count_ptr = count_ptr; oa.chunk_lo = lo; oa.chunk_hi = hi; oa.flat = flat;
     oa.partial = bw.partial; oa.part_stride = bw.part_stride;
     const int rows = hi - lo;
-#ifdef ADFP_OUTER_SIMPLE       // A/B switch: one wave per (job, 512 rows), operands straight from L2
-    oa.rows_per_wave = 512;
-    hipLaunchKernelGGL(k_outer, dim3((rows + oa.rows_per_wave - 1) / oa.rows_per_wave, oa.njobs), dim3(64), 0, st, oa);
-#else
     if (oa.ncols > OUTER_MAXCOLS || (oa.ncols & 3) || oa.njobs > OUTER_NW * OUTER_JW) return ADFP_E_UNSUPPORTED;
     // rows per workgroup: at most OUTER_NSLOT workgroups (each owns one private gradient copy), at least 64 rows each
     int per = (rows + OUTER_NSLOT - 1) / OUTER_NSLOT;
     per = ((per < 64 ? 64 : per) + OUTER_RT - 1) / OUTER_RT * OUTER_RT;
     oa.rows_per_wave = per;
     hipLaunchKernelGGL(k_outer_lds, dim3((rows + per - 1) / per), dim3(512), 0, st, oa);
-#endif
     ADFP_CHECK_LAUNCH();
     return 0;
 }
@@ -2713,16 +2635,6 @@ static int run_decode_bwd_p(DecodeBwdArgs a, int total, const int* count_ptr, fl
 // left.  Weight gradients: the G part of the staging rows is chunked like the exact path's rows (so that a chunk is still in
 // the Infinity Cache when k_outer_h reads it back); the X part lies in `act` for all rows.
 #define ADFP_BWDH_NT 384
-#ifdef ADFP_TUNE_ROLE_SHARES       // tuning builds only (the product library reads no environment): ADFP_ROLE_SHARES="<P>,<H>" of 256
-static int role_share_env(int which, int dflt) {
-    const char* e = getenv("ADFP_ROLE_SHARES");
-    int v[2];
-    if (!e || sscanf(e, "%d,%d", &v[0], &v[1]) != 2 || v[0] < 1 || v[1] < 1 || v[0] + v[1] > 254) return dflt;
-    return v[which];
-}
-#else
-static constexpr int role_share_env(int, int dflt) { return dflt; }
-#endif
 // sort of the call's points for k_scatter_sorted (set up once per backward call by backward_points)
 // Sorts n (key, value) pairs by the low key_bits bits of the key, stable.  The two buffer pairs are used in turn; *key_fin / *val_fin
 // = the pair the last pass wrote (a / b).  table: ADFP_RS_DIGITS * (ceil(n / ADFP_RS_TILE) + 1) ints.
@@ -2888,9 +2800,7 @@ static int run_decode_bwd_h(const DecodeBwdArgs& o, const void* t, const unsigne
                 int cus = num_cu(); if (cus > OUTER_NSLOT) cus = OUTER_NSLOT;
                 int g = 3 * ((ntiles + 7) / 8);
                 nslot = g < 3 ? 3 : (g > cus ? cus : g);
-                // (a -DADFP_TUNE_ROLE_SHARES build takes the split from the environment: how the shares were tuned, tools/build_ab_libs.sh)
-                static const int share_p = role_share_env(0, ROLE_SHARE_P), share_h = role_share_env(1, ROLE_SHARE_H);
-                int nP = (nslot * share_p + 128) / 256, nH = (nslot * share_h + 128) / 256;
+                int nP = (nslot * ROLE_SHARE_P + 128) / 256, nH = (nslot * ROLE_SHARE_H + 128) / 256;
                 if (nP < 1) nP = 1;
                 if (nH < 1) nH = 1;
                 while (nP + nH > nslot - 1) { if (nP > nH) --nP; else --nH; }

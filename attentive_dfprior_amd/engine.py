@@ -82,16 +82,8 @@ def _align256(n):
 class Engine(object):
     def __init__(self):
         import os
-        # ADFP_BWD_* bits handed to the backward entries (adfp_backward_args.options).  ADFP_SCATTER=cache in the environment of
-        # the HOST process selects the in-kernel scatter (kernel A/B runs); the library itself reads no environment.
-        self.bwd_options = _lib.BWD_SCATTER_IN_KERNEL if os.environ.get('ADFP_SCATTER', '')[:1] == 'c' else 0
-        if os.environ.get('ADFP_WGRAD', '')[:1] == 's':          # weight gradients through the staged two-kernel path (A/B runs)
-            self.bwd_options |= _lib.BWD_STAGED_WGRAD
-        if os.environ.get('ADFP_WGRAD', '')[:1] == 'o':          # ... inside the chain kernel, the ONE-wave-per-SIMD kernel of round 3-4 (A/B runs)
-            self.bwd_options |= _lib.BWD_FUSED_ONE_WAVE
-        # which part of the split weight images an INFERENCE call keeps current: 'g' (the 16x16x32 kernels of this library);
-        # ADFP_IMAGES=hg in the host's environment keeps both (A/B runs against a library built with -DADFP_LC_32X32)
-        self.inference_images = os.environ.get('ADFP_IMAGES', 'g')
+        # ADFP_BWD_* bits handed to the backward entries (adfp_backward_args.options): 0 = the library's own choice of path
+        self.bwd_options = 0
         # Test / diagnostic switch: the training state also carries dbg_masks_* buffers, into which the EXACT backward kernels
         # export the ReLU decisions they recomputed (adfp_train_state.dbg_masks_*; relu_masks() decodes them)
         self.export_relu_masks = False
@@ -411,14 +403,13 @@ class Engine(object):
                   32x32x16 kernels), otherwise -> G (k_decode_high_g / k_attention_g)
           low / colour decoder: inside the fused low + colour launch -- stage colour, both split, and either no training state
                   (k_decode_lc16) or mask room for BOTH (k_decode_lc16_train) -> G; on their own (stages low / high, the other
-                  one latched to exact, a training call with mask room for one of them only) -> H (k_decode_h)
-        self.inference_images replaces 'g' (ADFP_IMAGES=hg: a library built with -DADFP_LC_32X32 reads H everywhere)."""
+                  one latched to exact, a training call with mask room for one of them only) -> H (k_decode_h)"""
         has = (lambda n: ('masks_' + n) in state) if state is not None else (lambda n: False)
         if net in ('high', 'att'):
-            return 'h' if has(net) else self.inference_images
+            return 'h' if has(net) else 'g'
         fused = stage == 'color' and 'low' not in latch and 'color' not in latch and \
             (state is None or (has('low') and has('color')))
-        return self.inference_images if fused else 'h'
+        return 'g' if fused else 'h'
 
     @staticmethod
     def train_state(P, stage, dev, decoders, need_flat=None, extra=()):

@@ -63,7 +63,6 @@ def test_every_consumer_sees_the_current_weights(monkeypatch):
 def test_image_parts_rule():
     from attentive_dfprior_amd.engine import Engine
     eng = Engine()
-    eng.inference_images = 'g'
     masks = {'masks_low': True, 'masks_high': True, 'masks_att': True, 'masks_color': True}
     for n in ('low', 'color'):                                   # the fused low + colour launch, inference and training
         assert eng.image_parts('color', n, set(), masks) == 'g' and eng.image_parts('color', n, set(), None) == 'g'

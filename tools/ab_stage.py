@@ -76,38 +76,6 @@ def main(reps=int(os.environ.get("AB_REPS", "8"))):
     res['tsdf_gbps'] = 32.0 * P / (res['tsdf_ms'][0] * 1e-3) / 1e9
     res['in_band_points'] = int(cnt[0].item())
     print(json.dumps(res))
-    if hasattr(L, 'adfp_debug_stamps') or os.environ.get('ADFP_STAMPS'):
-        # debug build (-DADFP_STAMPS): per-wave start/end wall clock of the last k_decode_h launch
-        import numpy as np
-        L.adfp_decode_stage(C.byref(sc), C.byref(ap), 2, _lib.ptr(raw), _lib.ptr(wb), _lib.ptr(cnt[1:]), st)
-        torch.cuda.synchronize()
-        nw = 256 * 12
-        buf = (C.c_ulonglong * (2 * nw))()
-        L.adfp_debug_stamps.argtypes = [C.c_void_p, C.c_int]
-        assert L.adfp_debug_stamps(buf, nw) == 0
-        a = np.frombuffer(buf, dtype=np.uint64).reshape(nw, 2).astype(np.int64)
-        t0 = a[:, 0].min()
-        s0, e0 = (a[:, 0] - t0) / 100.0, (a[:, 1] - t0) / 100.0          # us
-        print('wave start us: min %.1f p50 %.1f max %.1f' % (s0.min(), np.median(s0), s0.max()))
-        print('wave end   us: min %.1f p10 %.1f p50 %.1f p90 %.1f max %.1f mean %.1f' % (
-            e0.min(), np.percentile(e0, 10), np.median(e0), np.percentile(e0, 90), e0.max(), e0.mean()))
-        wg_end = e0.reshape(256, 12).max(1)
-        print('per-workgroup end us (sorted, every 16th):', np.sort(wg_end)[::16].round(1).tolist())
-        print('within-WG spread us (max-min of wave ends): mean %.1f max %.1f' % (
-            (e0.reshape(256, 12).max(1) - e0.reshape(256, 12).min(1)).mean(), (e0.reshape(256, 12).max(1) - e0.reshape(256, 12).min(1)).max()))
-        x = wg_end.reshape(32, 8)      # blockIdx % 8 = XCD
-        print('per-XCD mean WG end us:', x.mean(0).round(1).tolist())
-        ph = (C.c_ulonglong * 8)()
-        L.adfp_debug_phases.argtypes = [C.c_void_p, C.c_int]
-        L.adfp_debug_phases(ph, 1)
-        L.adfp_decode_stage(C.byref(sc), C.byref(ap), 2, _lib.ptr(raw), _lib.ptr(wb), _lib.ptr(cnt[1:]), st)
-        torch.cuda.synchronize()
-        L.adfp_debug_phases(ph, 1)
-        tot = float(sum(ph[:5]))
-        names = ['ticket/loop', 'point+gather+split c', 'Fourier', '5 layers', 'output+store']
-        ntile = P / 32
-        print('phase shares of wave-cycles (colour decoder):', {n: round(ph[k] / tot, 3) for k, n in enumerate(names)},
-              'wave-cycles per tile:', {n: round(ph[k] / ntile) for k, n in enumerate(names)})
 
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 """Timing of the TRAINING forward alone (render_forward(train=True), colour stage, colour decoder + attention MLP trainable) at the
 Mapper's batch sizes: ms per call by HIP events, for kernel A/B builds (ADFP_LIB_PATH) whose backward state may be incomplete
-(timing-only switches ADFP_EXP_TRAIN_*): nothing here runs a backward."""
+(timing-only builds that leave stores out): nothing here runs a backward."""
 import os
 import sys
 

@@ -1,7 +1,7 @@
 # Round-6 measurement collection (one gpurun call; everything lands in gpurun_out/, the summaries are copied to profiles/ by hand
 # apart from the three PMC files bench.py reads, which are copied here so that the bench lines carry this build's traffic).
 #
-#   bash tools/collect_profiles.sh [section ...]        sections: tests pmc bench shard train diag config5 loops ab    (default: all)
+#   bash tools/collect_profiles.sh [section ...]        sections: tests pmc bench shard train diag config5 loops    (default: all)
 #
 # Every command's stderr is kept (gpurun_out/r05_logs/<step>.err) and a step that exits non-zero is reported, its target file is
 # moved to the logs (<step>.failed_output: no empty or half-written summary is left to be copied), and the script itself exits 1 at the end.
@@ -13,7 +13,7 @@ R=r06
 L=$O/${R}_logs
 mkdir -p $L
 FAILED=""
-SECTIONS="${*:-tests pmc bench shard train diag config5 loops ab}"
+SECTIONS="${*:-tests pmc bench shard train diag config5 loops}"
 want() { case " $SECTIONS " in *" $1 "*) return 0;; esac; return 1; }
 
 # run <step> <command ...>: stdout -> logs/<step>.out
@@ -120,19 +120,6 @@ if want loops; then
   python tools/mapping_loop.py --frames 200 --every-frame 5 --fused 2> $L/loop_fused.err | tail -1 >> $O/${R}_mapping_loop.json || FAILED="$FAILED loop_fused"
   ADFP_HOST_TIMING=1 into $O/${R}_host_breakdown.txt host_breakdown python tools/host_breakdown.py --rays 1000 5000
   [ -d tools/ab_r05 ] && into $O/${R}_host_ab.txt host_ab bash tools/host_ab.sh
-fi
-
-if want ab; then
-  into $O/${R}_ab_fourier_mfma.txt ab_fourier_mfma bash tools/ab_fourier_mfma.sh
-  into $O/${R}_ab_backward_roles.txt ab_roles bash tools/ab_roles.sh
-  ADFP_LIB_PATH=$PWD/tools/ab_libs/libadfp_roles_span.so python tools/roles_span.py 2> $L/roles_span.err | tail -4 >> $O/${R}_ab_backward_roles.txt || FAILED="$FAILED roles_span"
-  {
-    for lib in "" train_NOX train_NOC; do
-      for rep in 1 2; do
-        if [ -n "$lib" ]; then ADFP_LIB_PATH=$PWD/tools/ab_libs/libadfp_$lib.so python tools/ab_train_fwd.py 5000 48 300; else python tools/ab_train_fwd.py 5000 48 300; fi
-      done
-    done
-  } > $O/${R}_ab_train_forward.txt 2> $L/ab_train_forward.err || FAILED="$FAILED ab_train_forward"
 fi
 
 { hostname; rocm-smi --showproductname 2> $L/box.err | head -8; } > $O/${R}_box.txt
