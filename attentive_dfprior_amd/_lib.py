@@ -163,6 +163,7 @@ class AdfpTrackLossArgs(C.Structure):
 
 
 Bound = (C.c_double * 2) * 3
+_BOUND_SCENE = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]
 
 # every symbol include/adfp.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -322,6 +323,14 @@ SYMBOLS = [
     ('adfp_mesh_merge_emit', C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     ('adfp_mesh_color_bytes', C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
+    # mesh bound: the scene is (depth, poses, K, H, W, fx, fy, cx, cy)
+    ('adfp_bound_support_workspace_bytes', C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    ('adfp_bound_support', C.c_int, _BOUND_SCENE + [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    ('adfp_bound_classify_workspace_bytes', C.c_size_t, [C.c_longlong]),
+    ('adfp_bound_classify', C.c_int, _BOUND_SCENE + [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('adfp_bound_points', C.c_int, _BOUND_SCENE + [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER
@@ -333,7 +342,8 @@ TRI_LEAVES = (4, 8, 16)                # the leaf sizes adfp_tri_bvh_build takes
 CULL = {'none': 0, 'back': 1, 'front': 2}     # ADFP_CULL_NONE / ADFP_CULL_BACK / ADFP_CULL_FRONT
 UNIT_VOXELS = 16                        # ADFP_UNIT_VOXELS
 SEEN_RULE = {'frustum': 0, 'max_depth': 1, 'depth_test': 2}     # ADFP_SEEN_FRUSTUM / _MAX_DEPTH / _DEPTH_TEST
-LABEL_ROUNDS_MAX = 128                  # above the worst case of adfp_mesh_face_labels_rounds (2 log2(F) + 2 < 66)
+BOUND_MAX_DIRECTIONS = 1024             # ADFP_BOUND_MAX_DIRECTIONS
+LABEL_ROUNDS_MAX = 128                # above the worst case of adfp_mesh_face_labels_rounds (2 log2(F) + 2 < 66)
 
 _lib = None
 

@@ -4116,3 +4116,124 @@ int adfp_mesh_color_bytes(const float* rgb, long long n, int stride, unsigned ch
 }
 
 }   // extern "C"
+
+// ---- mesh bound (adfp_bound.h) ----
+#include "adfp_bound.h"
+
+static const long long BND_MAX_IDS = 1ll << 40;                    // tile numbers stay int
+static long long bnd_tiles(long long n) { return (n + ADFP_BND_TILE - 1) / ADFP_BND_TILE; }
+static bool bnd_finite_host(double x) { return x == x && x - x == 0.0; }
+// 0, or the error of a scene description; fills s
+static int bnd_scene(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy, BndScene& s) {
+    if (K < 0 || H < 1 || W < 1) return ADFP_E_ARG;
+    if (!bnd_finite_host(fx) || !bnd_finite_host(fy) || fx == 0.0 || fy == 0.0 || !bnd_finite_host(cx) || !bnd_finite_host(cy)) return ADFP_E_ARG;
+    if (K > 0 && (!depth || !poses)) return ADFP_E_ARG;
+    if (H > 32768 || W > 32768) return ADFP_E_UNSUPPORTED;
+    s.depth = depth; s.poses = poses; s.K = K; s.H = H; s.W = W; s.HW1 = (long long)H * W + 1;
+    if (K > BND_MAX_IDS / s.HW1) return ADFP_E_UNSUPPORTED;
+    s.n_ids = K * s.HW1; s.fx = fx; s.fy = fy; s.cx = cx; s.cy = cy;
+    return 0;
+}
+static int bnd_sup_blocks(long long n_ids) { const long long t = bnd_tiles(n_ids); return (int)(t < ADFP_BND_SUP_BLOCKS ? t : ADFP_BND_SUP_BLOCKS); }
+
+extern "C" {
+
+size_t adfp_bound_support_workspace_bytes(long long K, int H, int W, int D) {
+    if (K <= 0 || H < 1 || W < 1 || H > 32768 || W > 32768 || D < 1 || D > ADFP_BOUND_MAX_DIRECTIONS) return 0;
+    if (K > BND_MAX_IDS / ((long long)H * W + 1)) return 0;
+    const size_t nb = (size_t)bnd_sup_blocks(K * ((long long)H * W + 1));
+    return 2 * al256(nb * (size_t)D * 8) + al256(nb * 48) + al256(nb * 16);
+}
+
+int adfp_bound_support(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                       const double* directions, int D, void* workspace, size_t workspace_bytes, long long* best_id, double* aabb,
+                       long long* counts, void* stream) {
+    BndSupport a;
+    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, a.s);
+    if (rc) return rc;
+    if (D < 1 || D > ADFP_BOUND_MAX_DIRECTIONS || !directions || !best_id || !aabb || !counts) return ADFP_E_ARG;
+    if (K == 0) return 0;
+    if (!workspace) return ADFP_E_ARG;
+    if (workspace_bytes < adfp_bound_support_workspace_bytes(K, H, W, D)) return ADFP_E_WORKSPACE;
+    a.dirs = directions; a.D = D; a.n_tiles = bnd_tiles(a.s.n_ids); a.nbx = bnd_sup_blocks(a.s.n_ids);
+    char* w = (char*)workspace;
+    a.part_dot = (double*)mcl_take(w, (size_t)a.nbx * D * 8);
+    a.part_id = (long long*)mcl_take(w, (size_t)a.nbx * D * 8);
+    a.part_box = (double*)mcl_take(w, (size_t)a.nbx * 48);
+    a.part_cnt = (long long*)mcl_take(w, (size_t)a.nbx * 16);
+    a.best_id = best_id; a.aabb = aabb; a.counts = counts;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_bnd_support, dim3((unsigned)a.nbx, (unsigned)((D + ADFP_BND_THREADS - 1) / ADFP_BND_THREADS)), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_bnd_support_fold, dim3((unsigned)D + 1), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+size_t adfp_bound_classify_workspace_bytes(long long n_in) {
+    if (n_in <= 0 || n_in > BND_MAX_IDS) return 0;
+    const size_t T = (size_t)bnd_tiles(n_in);
+    return al256(T * (ADFP_BND_TILE / 64) * 8) + al256(T * 4) + al256(T * 8);
+}
+
+int adfp_bound_classify(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                        const long long* ids_in, long long n_in, const double* planes, int F, double eps, void* workspace,
+                        size_t workspace_bytes, long long* ids_out, long long ids_cap, long long* count, long long* far_id, double* far_dist,
+                        void* stream) {
+    BndClassify a;
+    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, a.s);
+    if (rc) return rc;
+    if (n_in < 0 || ids_cap < 0 || F < 1 || !planes || !count || !far_id || !far_dist || !(eps >= 0.0) || !bnd_finite_host(eps)) return ADFP_E_ARG;
+    if (!ids_in && n_in != a.s.n_ids) return ADFP_E_ARG;                // NULL: all ids of the scene
+    if (n_in > BND_MAX_IDS) return ADFP_E_UNSUPPORTED;
+    if (n_in > 0 && (!workspace || (ids_cap > 0 && !ids_out))) return ADFP_E_ARG;
+    if (n_in > 0 && workspace_bytes < adfp_bound_classify_workspace_bytes(n_in)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(far_id, 0xff, (size_t)F * 8, st);     // -1: no point
+    if (e != hipSuccess) return (int)e;
+    e = hipMemsetAsync(far_dist, 0, (size_t)F * 8, st);
+    if (e != hipSuccess) return (int)e;
+    if (n_in == 0) { e = hipMemsetAsync(count, 0, sizeof(long long), st); return e == hipSuccess ? 0 : (int)e; }
+    const long long T = bnd_tiles(n_in);
+    char* w = (char*)workspace;
+    a.mask = (unsigned long long*)mcl_take(w, (size_t)T * (ADFP_BND_TILE / 64) * 8);
+    a.tile_counts = (unsigned*)mcl_take(w, (size_t)T * 4);
+    long long* tile_offsets = (long long*)mcl_take(w, (size_t)T * 8);
+    a.tile_offsets = tile_offsets;
+    a.ids_in = ids_in; a.n_in = n_in; a.planes = planes; a.F = F; a.eps = eps;
+    a.ids_out = ids_out; a.ids_cap = ids_cap; a.count = count;
+    a.far_bits = (unsigned long long*)far_dist; a.far_id = (unsigned long long*)far_id;
+    hipLaunchKernelGGL(k_bnd_flag, dim3((unsigned)T), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    MclScan s; s.flag = nullptr; s.n = 0; s.ntiles = (int)T; s.tile_counts = a.tile_counts; s.tile_offsets = tile_offsets; s.pos = nullptr; s.total = count;
+    hipLaunchKernelGGL(k_mcl_tile_scan, dim3(1), dim3(ADFP_MCL_THREADS), 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_bnd_emit, dim3((unsigned)T), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    if (ids_cap == 0) return 0;
+    const long long cap_tiles = bnd_tiles(n_in < ids_cap ? n_in : ids_cap);
+    const unsigned fb = (unsigned)(cap_tiles < ADFP_BND_FAR_BLOCKS ? cap_tiles : ADFP_BND_FAR_BLOCKS);
+    a.ids_in = nullptr;                                                  // the farthest passes read ids_out
+    hipLaunchKernelGGL(k_bnd_far<0>, dim3(fb), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_bnd_far<1>, dim3(fb), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_bound_points(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                      const long long* ids, long long n, double* out, void* stream) {
+    BndScene s;
+    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, s);
+    if (rc) return rc;
+    if (n < 0) return ADFP_E_ARG;
+    if (n == 0) return 0;
+    if (!ids || !out) return ADFP_E_ARG;
+    if (n > BND_MAX_IDS) return ADFP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_bnd_points, dim3((unsigned)((n + ADFP_BND_THREADS - 1) / ADFP_BND_THREADS)), dim3(ADFP_BND_THREADS), 0, (hipStream_t)stream,
+                       s, ids, n, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+}   // extern "C"

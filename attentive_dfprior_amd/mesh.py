@@ -6,6 +6,7 @@ vertices and triangles -- are those of include/adfp.h.
 """
 import ctypes as C
 import struct
+import time
 
 import numpy as np
 import torch
@@ -240,6 +241,228 @@ def _np(x):
     if x is None:
         return None
     return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+# ---- mesh bound: the convex hull of the keyframes' camera centres and back-projected valid depth pixels, as a quickhull in
+# rounds (csrc/adfp_bound.h; contracts and the fixed formulae: include/adfp.h, "mesh bound").  A point is named by its id
+# k (H W + 1) + j: j = 0 the camera centre of keyframe k, j = 1 + row W + col a pixel.  The device does the point work (support
+# pass, classification, compaction, per-facet farthest); Qhull keeps the facets of the few hundred vertices on the host.  The
+# *_host functions are the numpy statement of the same formulae and rounds, bit for bit, and run without a GPU.
+BOUND_DIRECTIONS = 64          # D of the support pass (tools/bound_bench.py measures the choice)
+BOUND_MAX_ROUNDS = 64
+BOUND_EPS_REL = 1e-12          # eps = this x the largest AABB extent: two decades above the f64 rounding of a plane evaluation
+_BOUND_CAP_ALL = 1 << 25       # candidate lists up to this length get a survivor buffer of their own length; longer ones a quarter
+
+
+def bound_directions(D=BOUND_DIRECTIONS):
+    """The support pass's fixed directions [D,3] f64: +x, -x, +y, -y, +z, -z (so the AABB falls out), then D - 6 points of the
+    Fibonacci lattice on the unit sphere (z_i = 1 - (2 i + 1) / n, azimuth i pi (3 - sqrt 5))."""
+    if not 6 <= D <= _lib.BOUND_MAX_DIRECTIONS:
+        raise ValueError(f'bound_directions: D must lie in [6, {_lib.BOUND_MAX_DIRECTIONS}], got {D}')
+    axes = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float64)
+    n = D - 6
+    i = np.arange(n, dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / max(n, 1)
+    r = np.sqrt(1.0 - z * z)
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.ascontiguousarray(np.concatenate([axes, np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)]))
+
+
+def _bound_scene_arrays(depth, c2w):
+    d = _np(depth)
+    m = _np(c2w)
+    if d.ndim != 3 or m.shape != (d.shape[0], 4, 4):
+        raise ValueError(f'mesh bound: depth must be [K,H,W] and c2w [K,4,4], got {d.shape} and {m.shape}')
+    return np.ascontiguousarray(d, np.float32), np.ascontiguousarray(m, np.float32)
+
+
+def depth_points_host(depth, c2w, fx, fy, cx, cy):
+    """(ids int64 [n] ascending, points f64 [n,3]) of every point of the scene -- depth [K,H,W] f32, c2w [K,4,4] f32 -- by the fixed
+    formulae of include/adfp.h, elementwise (no matrix product), so that adfp_bound_points gives the same bits."""
+    depth, c2w = _bound_scene_arrays(depth, c2w)
+    K, H, W = depth.shape
+    fx, fy, cx, cy = float(fx), float(fy), float(cx), float(cy)
+    M = c2w.astype(np.float64)
+    row, col = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing='ij')
+    ids, pts = [], []
+    for k in range(K):
+        R0, R1, R2, t = M[k, :3, 0], -M[k, :3, 1], -M[k, :3, 2], M[k, :3, 3]
+        d = depth[k].astype(np.float64)
+        with np.errstate(invalid='ignore', over='ignore'):
+            ok = (d > 0) & (d < 1000)
+            d = d[ok]
+            x = ((col[ok] - cx) / fx) * d
+            y = ((row[ok] - cy) / fy) * d
+            p = np.stack([((R0[c] * x + R1[c] * y) + R2[c] * d) + t[c] for c in range(3)], 1)
+        base = k * (H * W + 1)
+        ids += [np.array([base], np.int64), base + 1 + np.flatnonzero(ok.reshape(-1)).astype(np.int64)]
+        pts += [t[None].copy(), p]
+    if K == 0:
+        return np.zeros(0, np.int64), np.zeros((0, 3))
+    return np.concatenate(ids), np.concatenate(pts)
+
+
+class _HostBound(object):
+    """The numpy statement of adfp_bound_support / _classify / _points over the stored points of depth_points_host."""
+
+    def __init__(self, depth, c2w, fx, fy, cx, cy):
+        self.ids, self.pts = depth_points_host(depth, c2w, fx, fy, cx, cy)
+
+    def support(self, dirs):
+        fin = np.isfinite(self.pts).all(1)
+        p = self.pts[fin]
+        ids = self.ids[fin]
+        best = np.full(len(dirs), -1, np.int64)
+        if len(p):
+            for i, u in enumerate(dirs):
+                dot = (u[0] * p[:, 0] + u[1] * p[:, 1]) + u[2] * p[:, 2]
+                j = int(np.argmax(dot))                          # the first among equals: the lowest id
+                if dot[j] > -np.inf:
+                    best[i] = ids[j]
+        aabb = np.concatenate([p.min(0), p.max(0)]) if len(p) else np.array([np.inf] * 3 + [-np.inf] * 3)
+        return best, aabb, int(fin.sum()), int((~fin).sum())
+
+    def points(self, ids):
+        ids = np.asarray(ids, np.int64)
+        out = np.full((len(ids), 3), np.nan)
+        if len(self.ids) and len(ids):
+            j = np.minimum(np.searchsorted(self.ids, ids), len(self.ids) - 1)
+            hit = self.ids[j] == ids
+            out[hit] = self.pts[j[hit]]
+        return out
+
+    def classify(self, cand, planes, eps):
+        ids = self.ids if cand is None else cand
+        p = self.points(ids) if cand is not None else self.pts
+        m = np.full(len(ids), -np.inf)
+        fac = np.full(len(ids), -1, np.int64)
+        with np.errstate(invalid='ignore'):
+            for f, (nx, ny, nz, d) in enumerate(planes):
+                s = ((nx * p[:, 0] + ny * p[:, 1]) + nz * p[:, 2]) + d
+                w = s > m
+                m[w] = s[w]
+                fac[w] = f
+            keep = m > eps
+        ids, m, fac = ids[keep], m[keep], fac[keep]
+        far_id = np.full(len(planes), -1, np.int64)
+        far_dist = np.zeros(len(planes))
+        if len(ids):
+            order = np.lexsort((ids, -m, fac))                    # per facet: the largest m first, the lowest id among equals
+            first = order[np.concatenate([[True], fac[order][1:] != fac[order][:-1]])]
+            far_id[fac[first]] = ids[first]
+            far_dist[fac[first]] = m[first]
+        return ids, len(ids), far_id, far_dist
+
+
+class _DeviceBound(object):
+    """The same three operations through libadfp.so over device tensors: depth [K,H,W] f32, c2w [K,4,4] f32."""
+
+    def __init__(self, depth, c2w, fx, fy, cx, cy):
+        require_cuda(depth, 'depth_hull depth')
+        self.dev = depth.device
+        self.depth = depth.detach().to(torch.float32).contiguous()
+        if self.depth.dim() != 3 or tuple(c2w.shape) != (self.depth.shape[0], 4, 4):
+            raise ValueError(f'depth_hull: depth must be [K,H,W] and c2w [K,4,4], got {tuple(depth.shape)} and {tuple(c2w.shape)}')
+        self.poses = c2w.detach().to(self.dev, torch.float32).contiguous()
+        K, H, W = (int(s) for s in self.depth.shape)
+        self.K, self.H, self.W = K, H, W
+        self.n_ids = K * (H * W + 1)
+        self.scene = (ptr(self.depth), ptr(self.poses), K, H, W, float(fx), float(fy), float(cx), float(cy))
+
+    def support(self, dirs):
+        L = lib()
+        D = int(dirs.shape[0])
+        d = torch.from_numpy(np.ascontiguousarray(dirs, np.float64)).to(self.dev)
+        out = torch.empty(D + 8, dtype=torch.int64, device=self.dev)          # best ids, aabb (f64 bits), counts
+        with _lib.device_guard(self.dev):
+            nbytes = L.adfp_bound_support_workspace_bytes(self.K, self.H, self.W, D)
+            ws = _ws(nbytes, self.dev)
+            base = out.data_ptr()
+            check(L.adfp_bound_support(*self.scene, ptr(d), D, ptr(ws), nbytes, C.c_void_p(base), C.c_void_p(base + 8 * D),
+                                       C.c_void_p(base + 8 * (D + 6)), _lib.current_stream(self.dev)), 'adfp_bound_support')
+            h = out.cpu().numpy()
+        return h[:D].copy(), h[D:D + 6].view(np.float64).copy(), int(h[D + 6]), int(h[D + 7])
+
+    def points(self, ids):
+        ids = np.ascontiguousarray(ids, np.int64)
+        out = torch.empty((len(ids), 3), dtype=torch.float64, device=self.dev)
+        if len(ids):
+            t = torch.from_numpy(ids).to(self.dev)
+            with _lib.device_guard(self.dev):
+                check(lib().adfp_bound_points(*self.scene, ptr(t), len(ids), ptr(out), _lib.current_stream(self.dev)), 'adfp_bound_points')
+        return out.cpu().numpy()
+
+    def classify(self, cand, planes, eps):
+        L = lib()
+        F = int(planes.shape[0])
+        ids_in, n_in = (None, self.n_ids) if cand is None else cand
+        pl = torch.from_numpy(np.ascontiguousarray(planes, np.float64)).to(self.dev)
+        res = torch.empty(2 * F + 1, dtype=torch.int64, device=self.dev)      # far ids, far distances (f64 bits), the count
+        cap = n_in if n_in <= _BOUND_CAP_ALL else max(_BOUND_CAP_ALL, n_in // 4)
+        with _lib.device_guard(self.dev):
+            st = _lib.current_stream(self.dev)
+            nbytes = L.adfp_bound_classify_workspace_bytes(n_in)
+            ws = _ws(nbytes, self.dev)
+            base = res.data_ptr()
+            while True:
+                out = torch.empty(max(cap, 1), dtype=torch.int64, device=self.dev)
+                check(L.adfp_bound_classify(*self.scene, ptr(ids_in), n_in, ptr(pl), F, float(eps), ptr(ws), nbytes, ptr(out), cap,
+                                            C.c_void_p(base + 16 * F), C.c_void_p(base), C.c_void_p(base + 8 * F), st), 'adfp_bound_classify')
+                h = res.cpu().numpy()                                         # the round's one synchronisation
+                count = int(h[2 * F])
+                if count <= cap:
+                    break
+                cap = count                                                   # more survivors than the buffer held: once more, in full
+        return (out, count), count, h[:F].copy(), h[F:2 * F].view(np.float64).copy()
+
+
+def _hull_rounds(b, directions, max_rounds):
+    from scipy.spatial import ConvexHull
+    dirs = bound_directions() if directions is None else np.ascontiguousarray(directions, np.float64).reshape(-1, 3)
+    best, aabb, _, n_bad = b.support(dirs)
+    if n_bad:
+        raise ValueError(f'depth_hull: {n_bad} points are not finite (a pose or an intrinsic holds a NaN or an inf)')
+    V = np.unique(best[best >= 0])
+    eps = BOUND_EPS_REL * float((aabb[3:] - aabb[:3]).max())
+    cand, stats = None, []
+    for _ in range(max_rounds):
+        pts = b.points(V)
+        t0 = time.perf_counter()
+        hull = ConvexHull(pts)                                    # Qhull's own errors for a degenerate set, as on the host path
+        qhull_s = time.perf_counter() - t0
+        V = V[np.sort(hull.vertices)]
+        planes = np.ascontiguousarray(hull.equations)
+        cand, count, far_id, _ = b.classify(cand, planes, eps)
+        stats.append((V, planes, count, far_id, qhull_s))
+        if count == 0:
+            return V, b.points(V), stats
+        V = np.union1d(V, far_id[far_id >= 0])
+    raise RuntimeError(f'depth_hull: points remain outside the hull after {max_rounds} rounds; no partial hull is returned')
+
+
+def _no_keyframes(depth):
+    if int(depth.shape[0]) == 0:
+        raise ValueError('depth_hull: need at least one keyframe')
+
+
+def depth_hull_host(depth, c2w, fx, fy, cx, cy, directions=None, return_stats=False, max_rounds=BOUND_MAX_ROUNDS):
+    """depth_hull in numpy, round for round: the same support points, survivors, farthest ids and vertex ids, bit for bit."""
+    _no_keyframes(depth)
+    ids, pts, stats = _hull_rounds(_HostBound(depth, c2w, fx, fy, cx, cy), directions, max_rounds)
+    return (ids, pts, stats) if return_stats else (ids, pts)
+
+
+def depth_hull(depth, c2w, fx, fy, cx, cy, directions=None, return_stats=False, max_rounds=BOUND_MAX_ROUNDS):
+    """The vertices of the convex hull of the scene's points -- device tensors depth [K,H,W] f32, c2w [K,4,4] f32 (est_c2w as
+    KeyframeStore.poses() holds it) -- as (ids int64 ascending, points f64 [n,3]) numpy arrays.  Rounds: the support points of
+    `directions` (default bound_directions()) start the vertex set; each round Qhull hulls the set on the host, the device drops
+    every candidate within eps = 1e-12 x the largest AABB extent of the hull's planes, compacts the rest in id order and reports
+    each facet's farthest point, which joins the set; one synchronisation per round, until nothing remains outside.  More than
+    max_rounds rounds raise RuntimeError; non-finite points ValueError.  return_stats: also the per-round list of (vertex ids,
+    planes, survivors, farthest id per facet, seconds in Qhull)."""
+    _no_keyframes(depth)
+    ids, pts, stats = _hull_rounds(_DeviceBound(depth, c2w, fx, fy, cx, cy), directions, max_rounds)
+    return (ids, pts, stats) if return_stats else (ids, pts)
 
 
 def write_ply(path, verts, faces, colors=None, normals=None, ascii=False):

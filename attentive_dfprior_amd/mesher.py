@@ -7,9 +7,12 @@ Where the work runs: the lattice is formed on the device chunk by chunk and quer
 (libadfp.so); the convex-hull mask is one kernel (``adfp_lattice_hull_fill``); marching cubes is ``mesh.marching_cubes``
 (``adfp_mc_count`` / ``adfp_mc_emit``); the seen mask is one launch over all poses (``seen_mask``, ``adfp_mesh_seen_mask``); the
 component culling, the colour bytes and the merge of coincident vertices are ``mesh.clean_components`` / ``color_bytes`` /
-``merge_coincident`` (csrc/adfp_meshclean.h).  The host keeps the mesh bound (scipy ConvexHull) and the file.  ``point_masks``
-(the reference's torch code, the only source of the forecast / unseen masks), ``clean`` (scipy.sparse.csgraph) and the module's
-``merge_coincident`` remain as the host statements of the same steps: the tests compare the device path against them.
+``merge_coincident`` (csrc/adfp_meshclean.h); the mesh bound is ``bound_planes`` (``mesh.depth_hull``: a quickhull in rounds whose
+point work -- support pass, classification, ordered compaction, per-facet farthest -- runs over the resident depth block,
+csrc/adfp_bound.h, while Qhull keeps the facets of the few hundred hull vertices).  The host keeps those small hulls and the file.
+``point_masks`` (the reference's torch code, the only source of the forecast / unseen masks), ``clean`` (scipy.sparse.csgraph),
+``get_bound_planes`` (numpy and Qhull over every point) and the module's ``merge_coincident`` remain as the host statements of the
+same steps: the tests compare the device path against them.
 
 Deviations, both documented in INTEGRATION.md:
   * the mesh bound (``get_bound_from_frames``) is the convex hull of the keyframes' camera centres and back-projected valid
@@ -204,6 +207,32 @@ class Mesher(object):
         verts = center + self.clean_mesh_bound_scale * (verts - center)
         return ConvexHull(verts).equations
 
+    def bound_planes(self, keyframe_dict, scale=1, device='cuda:0', keyframe_store=None):
+        """get_bound_planes with the point work on the device (mesh.depth_hull: a quickhull in rounds over the resident depth
+        block, csrc/adfp_bound.h): the same bound, facet planes [F,4].  Depths and poses come from ``keyframe_store`` (a
+        keyframes.KeyframeStore of the same keyframes in the same order, read in place) or are stacked from ``keyframe_dict`` once.
+        The tail is the host path's: the mean of the hull's vertices in id order (the order the per-frame-then-union hull yields
+        them in), the scale by clean_mesh_bound_scale, Qhull's equations of the scaled vertices.  The vertex set is that of the
+        hull over ALL points, which the per-frame-then-union route also yields; coordinates differ from get_bound_planes' within
+        the rounding of its BLAS product (include/adfp.h fixes the order of operations here)."""
+        from scipy.spatial import ConvexHull
+        dev = torch.device(device)
+        K = len(keyframe_dict)
+        if K == 0:
+            raise ValueError('bound_planes: need at least one keyframe')
+        if keyframe_store is not None:
+            if len(keyframe_store) < K:
+                raise ValueError(f'bound_planes: the store holds {len(keyframe_store)} keyframes, keyframe_dict {K}')
+            depth, poses = keyframe_store.depths(K), keyframe_store.poses(K)
+        else:
+            depth = torch.stack([keyframe['depth'] for keyframe in keyframe_dict]).to(dev, torch.float32)
+            poses = torch.stack([keyframe['est_c2w'].detach() for keyframe in keyframe_dict]).to(dev, torch.float32)
+        depth = depth.reshape(K, self.H, self.W)
+        _, verts = M.depth_hull(depth, poses.reshape(K, 4, 4), self.fx, self.fy, self.cx, self.cy)
+        center = verts.mean(0)
+        verts = center + self.clean_mesh_bound_scale * (verts - center)
+        return ConvexHull(verts).equations
+
     def get_grid_uniform(self, resolution):
         """The lattice axes of Mesher.py:365-393 (float64 np.linspace over the marching-cubes bound + 0.05).  The [P,3] point
         list is not formed on the host: get_mesh builds it on the device chunk by chunk."""
@@ -305,7 +334,8 @@ class Mesher(object):
         """Extract the mesh of the scene representation and write it to mesh_out_file (.ply); returns z_uni_m (Mesher.py:395-544).
         From marching cubes to the file everything stays on the device (seen_mask, mesh.clean_components' kernels, the colour
         query and bytes, mesh.merge_coincident's kernels); the host receives the final vertices, faces and colours, one copy each.
-        keyframe_store: a keyframes.KeyframeStore of the same keyframes, whose resident depth block seen_mask then reads."""
+        keyframe_store: a keyframes.KeyframeStore of the same keyframes, whose resident depth block bound_planes and seen_mask
+        then read."""
         if not str(mesh_out_file).lower().endswith('.ply'):
             raise NotImplementedError(f'{mesh_out_file}: only .ply output is supported')
         if color and self.color_mesh_extraction_method != 'direct_point_query':
@@ -313,7 +343,7 @@ class Mesher(object):
         with torch.no_grad():
             xyz = self.get_grid_uniform(self.resolution)['xyz']
             z, ax = self.lattice(c, decoders, tsdf_volume, xyz, device)
-            planes = self.get_bound_planes(keyframe_dict, self.scale)
+            planes = self.bound_planes(keyframe_dict, self.scale, device, keyframe_store)
             M.hull_fill(z, ax, planes, 100.)
             z_uni_m = z.cpu().numpy()
             spacing, origin = self.marching_cubes_geometry(xyz)

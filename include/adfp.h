@@ -1011,6 +1011,49 @@ int adfp_mesh_merge_emit(const float* verts, const unsigned char* colors, long l
  * first three are used); NaN gives 0. */
 int adfp_mesh_color_bytes(const float* rgb, long long n, int stride, unsigned char* out, void* stream);
 
+/* ---- mesh bound (mesher.Mesher.get_bound_planes: the hull of the keyframes' camera centres and back-projected depth pixels) ----
+ * The point work of a quickhull in rounds (mesh.depth_hull keeps the facets of the few hundred hull vertices with Qhull on the
+ * host).  The scene: depth [K][H][W] (f32, device), poses [K][16] (f32, device; row-major [4,4] est_c2w), fx, fy, cx, cy (f64, host).
+ * The points are never stored.  A point is named by an id (int64): id = k (H W + 1) + j; j = 0 is keyframe k's camera centre,
+ * j = 1 + row W + col its pixel (row, col).  Every kernel recomputes a point from its id, all in f64, every product and sum rounded
+ * on its own (no FMA), in exactly this order:
+ *   pose      M = poses[k] widened to f64, columns 1 and 2 negated (the OpenCV camera of Mesher.py:250-251): R_c0 = M[c][0],
+ *             R_c1 = -M[c][1], R_c2 = -M[c][2], t_c = M[c][3];
+ *   validity  d = depth[k][row][col] widened to f64; the pixel is a point iff d > 0 && d < 1000 (NaN and inf fail);
+ *   camera    x = ((col - cx) / fx) d,  y = ((row - cy) / fy) d,  z = d;
+ *   world     p_c = ((R_c0 x + R_c1 y) + R_c2 z) + t_c;   a centre is p_c = t_c, and always a point.
+ * An id outside [0, K (H W + 1)) on the device is never dereferenced: it names no point.  Plane evaluation, the same everywhere:
+ * s_f = ((n_x p_x + n_y p_y) + n_z p_z) + d_f for planes [F][4] (f64, device; n, d; inside: s <= 0), and m = max_f s_f formed by
+ * `s > m` from -inf in facet order.  No result depends on the order atomics land in (they are integer max / min); the same input
+ * gives the same bits.  Errors: ADFP_E_ARG for a null pointer, K < 0, H or W < 1, fx or fy 0 or non-finite, cx or cy non-finite,
+ * a negative count, D outside [1, ADFP_BOUND_MAX_DIRECTIONS], F < 1; ADFP_E_UNSUPPORTED for H or W > 32768 or more than 2^40 ids;
+ * ADFP_E_WORKSPACE.  K = 0 (support) and n = 0 do nothing. */
+#define ADFP_BOUND_MAX_DIRECTIONS 1024
+/* Support pass, one pass over all ids: best_id[i] (int64, device, [D]) = the point with the largest ((u_x p_x + u_y p_y) + u_z p_z)
+ * for directions[i] = u ([D][3] f64, device), the lowest id among equals, -1 when there is no point.  aabb [6] (f64, device) = the
+ * minimum (x, y, z) then the maximum (x, y, z) of the points; counts [2] (device long long) = the number of points and the number
+ * of NON-FINITE points (a pose with a NaN or inf produces them): those take no part in best_id, aabb or counts[0].  Workspace:
+ * adfp_bound_support_workspace_bytes (per-workgroup partials, at most 1024 workgroups per 256 directions). */
+size_t adfp_bound_support_workspace_bytes(long long K, int H, int W, int D);
+int adfp_bound_support(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                       const double* directions, int D, void* workspace, size_t workspace_bytes, long long* best_id, double* aabb,
+                       long long* counts, void* stream);
+/* One round: candidate i of n_in is ids_in[i] (int64, device, ascending), or id i itself when ids_in is NULL (then n_in must be
+ * K (H W + 1)).  A candidate that is no point, or whose m <= eps, is dropped.  The others (the survivors) go to ids_out in
+ * ascending position (so ascending id); *count (device long long) = their number, of which only the first ids_cap are written: the
+ * caller compares.  Each survivor is assigned to the LOWEST facet that attains its m; far_dist[f] (f64, device) = the largest m
+ * over the survivors assigned to f among the first ids_cap (0 when none), far_id[f] (int64) the lowest id that attains it (-1 when
+ * none).  Planes beyond what the LDS of a workgroup holds are taken in chunks inside the launch.  eps must be finite and >= 0.
+ * Workspace: adfp_bound_classify_workspace_bytes(n_in) = one bit per candidate and 12 bytes per tile of 1024. */
+size_t adfp_bound_classify_workspace_bytes(long long n_in);
+int adfp_bound_classify(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                        const long long* ids_in, long long n_in, const double* planes, int F, double eps, void* workspace,
+                        size_t workspace_bytes, long long* ids_out, long long ids_cap, long long* count, long long* far_id, double* far_dist,
+                        void* stream);
+/* out [n][3] (f64, device) = the points of ids [n] (int64, device); NaN for an id that names no point. */
+int adfp_bound_points(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                      const long long* ids, long long n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,44 @@ def main(template, d):
     v['mt_rep_hi'] = '%.2f' % max(rep['clean']['device']['all_ms'])
     v['mt_rep_tail'] = '%.2f' % rep['whole_tail']['device']['median_ms']
     v['mt_getmesh512'] = '%.0f' % (mt['512']['get_mesh_total']['median_s'] * 1e3)
+    # the mesh bound: host route against device route (tools/bound_bench.py) and the kernel trace of the device route
+    mb = json.load(open(P('mesh_bound_bench.json')))
+    cell = lambda s, f='%.1f': (f + ' (' + f + ', ' + f + ')') % (s['median_ms'], s['min_ms'], s['spread_ms'])
+    rows = []
+    for name, w in sorted(mb['workloads'].items()):
+        rows.append('| (%s) %d × %d × %d | %s | %s | %s | %.0f× | %d | %s |' % (
+            name, w['keyframes'], w['frame'][0], w['frame'][1], thousands(w['points']), cell(w['host']), cell(w['device'], '%.2f'),
+            w['host_over_device_median'], w['rounds'], ', '.join(thousands(n) for n in w['survivors_per_round'])))
+        v['mb_qhull_' + name] = '%.1f' % sum(w['qhull_ms_per_round'])
+        v['mb_dict_' + name] = '%.1f' % w['device_from_keyframe_dict']['median_ms']
+        v['mb_vertices_' + name] = str(w['vertices'])
+    v['mb_table'] = '\n'.join(rows)
+    ds = sorted(mb['workloads']['a']['by_directions'], key=int)
+    v['mb_d_table'] = '\n'.join('| %s | %s |' % (D, ' | '.join('%.2f, %s' % (w['by_directions'][D]['depth_hull']['median_ms'],
+                                                                              thousands(w['by_directions'][D]['survivors_per_round'][0]))
+                                                               for _, w in sorted(mb['workloads'].items()))) for D in ds)
+    v['mb_D'] = str(mb['D'])
+    v['mb_single'] = 'wins' if mb['single_routing'] else 'does NOT win'
+    for res in ('256', '512'):
+        g = mb['get_mesh'][res]
+        v['mb_gm' + res] = '%.1f' % g['get_mesh']['median_ms']
+        v['mb_gmb' + res] = '%.2f' % g['bound_planes']['median_ms']
+        v['mb_gmh' + res] = '%.0f' % g['get_bound_planes_host']['median_ms']
+        v['mb_share' + res] = '%.1f' % (100 * g['bound_share_of_get_mesh'])
+    ks = stats(P('mesh_bound_kernels.csv'))
+    for name in ('k_bnd_support(', 'k_bnd_support_fold', 'k_bnd_flag', 'k_bnd_emit', 'k_bnd_far<0>', 'k_bnd_far<1>', 'k_mcl_tile_scan'):
+        r = next((r for k, r in ks.items() if name in k), None)
+        if r:
+            key = 'mbk_' + re.sub(r'\W', '', name)
+            v[key + '_max'] = '%.0f' % float(r['max_us']); v[key + '_avg'] = '%.1f' % float(r['avg_us']); v[key + '_calls'] = r['calls']
+    wb = mb['workloads']['b']
+    n_ids = wb['keyframes'] * (wb['frame'][0] * wb['frame'][1] + 1)
+    v['mbk_ids'] = thousands(n_ids); v['mbk_F'] = str(wb['planes_per_round'][0])
+    v['mbk_hbm_us'] = '%.0f' % (4.0 * n_ids / 6.29e12 * 1e6)            # the depth block once at the measured HBM rate
+    if 'mbk_k_bnd_flag_max' in v:
+        v['mbk_flag_tops'] = '%.1f' % (7.0 * n_ids * wb['planes_per_round'][0] / (float(v['mbk_k_bnd_flag_max']) * 1e-6) / 1e12)
+    if 'mbk_k_bnd_support_max' in v:
+        v['mbk_support_tops'] = '%.1f' % (5.0 * n_ids * mb['D'] / (float(v['mbk_k_bnd_support_max']) * 1e-6) / 1e12)
     # ---- parity / gradient stats
     t = open(P('r06_parity_stats.txt')).read()
     m = re.search(r'tol 0\.0001: (\d+) tensors, worst (\S+) of the limit', t)
