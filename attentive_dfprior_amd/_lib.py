@@ -73,6 +73,20 @@ class AdfpKeyframe(C.Structure):
 KEYFRAMES_MAX = 16
 
 
+class AdfpIngestGeom(C.Structure):
+    _fields_ = [('color_h', C.c_int), ('color_w', C.c_int), ('depth_h', C.c_int), ('depth_w', C.c_int), ('crop_h', C.c_int), ('crop_w', C.c_int),
+                ('crop_edge', C.c_int), ('color_order', C.c_int), ('depth_kind', C.c_int), ('color_out', C.c_int),
+                ('png_depth_scale', C.c_float), ('scale', C.c_float)]
+
+
+class AdfpIngestJob(C.Structure):
+    _fields_ = [('color', C.c_void_p), ('depth', C.c_void_p), ('color_out', C.c_void_p), ('depth_out', C.c_void_p)]
+
+
+INGEST_MAX_JOBS = 16              # ADFP_INGEST_MAX_JOBS
+COLOR_ORDER = {'bgr': 0, 'rgb': 1}
+
+
 class AdfpScene(C.Structure):
     _fields_ = [('bound', (C.c_double * 2) * 3), ('tsdf_bnds', (C.c_double * 2) * 3),
                 ('low', AdfpGrid), ('high', AdfpGrid), ('color', AdfpGrid), ('tsdf', AdfpTsdf),
@@ -331,6 +345,9 @@ SYMBOLS = [
     ('adfp_bound_classify', C.c_int, _BOUND_SCENE + [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_size_t,
                                                      C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('adfp_bound_points', C.c_int, _BOUND_SCENE + [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    # frame ingestion
+    ('adfp_ingest_frames', C.c_int, [C.POINTER(AdfpIngestGeom), C.c_int, C.POINTER(AdfpIngestJob), C.c_void_p]),
+    ('adfp_ingest_out_shape', C.c_int, [C.POINTER(AdfpIngestGeom), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER

@@ -4237,3 +4237,6 @@ int adfp_bound_points(const float* depth, const float* poses, long long K, int H
 }
 
 }   // extern "C"
+
+// ---- frame ingestion (adfp_ingest.h) ----
+#include "adfp_ingest.h"

@@ -1054,6 +1054,45 @@ int adfp_bound_classify(const float* depth, const float* poses, long long K, int
 int adfp_bound_points(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
                       const long long* ids, long long n, double* out, void* stream);
 
+/* ---- frame ingestion (datasets.FrameIngest: the reference's BaseDataset.__getitem__, src/utils/datasets.py:77-113) ----
+ * The decoded images go in as they are -- colour [color_h][color_w][3] uint8, depth [depth_h][depth_w] uint16 or f32, both on the
+ * device -- and ONE launch writes, for each of n_jobs frames, color_out [H][W][3] (f32 or f64) and depth_out [H][W] (f32), H and W
+ * as adfp_ingest_out_shape gives them.  Per output pixel, nothing rounded that the reference does not round, no FMA:
+ *   A  colour   c = byte / 255 in f64; channel order RGB (color_order 0 reads the bytes as B, G, R).
+ *   B  resize   only when (color_h, color_w) != (depth_h, depth_w): cv2.resize(img_f64, (depth_w, depth_h)), i.e. bilinear with
+ *               half-pixel centres and float coefficients: fx = (float)((dx + 0.5) * (double)color_w / depth_w - 0.5), sx = floor(fx),
+ *               fx -= sx (float); sx < 0 gives sx = 0, fx = 0; sx >= color_w - 1 gives sx = color_w - 1, fx = 0; weights 1.f - fx and
+ *               fx widened to f64.  In y the same coefficients, the two rows sy and sy + 1 clamped into the image and their weights
+ *               kept.  OpenCV itself forms scale = 1. / ((double)depth_w / color_w) and (dx + 0.5) * scale - 0.5; the float
+ *               coefficients of the two forms are equal for 1296 -> 640, 968 -> 480 and the tests' shapes (compared on the
+ *               host), and a last-bit f64 difference survives the rounding to float only at a rounding tie; parity with
+ *               cv2.resize itself is checked only where cv2 is installed (tests/test_ingest_host.py).  Horizontal pass first: h_r = S[r][sx] w0 + S[r][sx + 1] w1 for both rows, then h_0 b0 + h_1 b1, all f64.
+ *   C  crop_size  only when crop_h, crop_w != 0, on the result of B: colour as F.interpolate(bilinear, align_corners=True) forms
+ *               it for f64 on the CPU (ratio = (in - 1) / (out - 1) in f64, i0 = (int)(ratio d), l1 = ratio d - i0, l0 = 1 - l1,
+ *               ((w00 v00 + w01 v01) + w10 v10) + w11 v11 with w_ab = l_a(y) l_b(x); equal sizes copy); depth as
+ *               F.interpolate(nearest): src = min((int)floorf(d * ((float)in / out)), in - 1).
+ *   D  edge     [crop_edge : -crop_edge] in both axes of the result of C.
+ *   depth       ((float)raw / png_depth_scale) * scale: two f32 roundings; depth_kind 1 takes raw as the f32 it is.
+ *   colour out  the f64 value, or its single rounding to f32.
+ * The jobs are a HOST array (copied into the kernel's arguments, like adfp_sample_keyframes' frames).  Errors, before any launch:
+ * ADFP_E_ARG for a null geom / jobs / job pointer, a size < 1, crop_h or crop_w negative or only one of them 0, crop_edge < 0 or
+ * 2 crop_edge >= the height or width it crops, png_depth_scale 0 or non-finite, an unknown color_order / depth_kind / color_out,
+ * n_jobs < 0; ADFP_E_UNSUPPORTED for n_jobs > ADFP_INGEST_MAX_JOBS or a size above 32768.  n_jobs = 0 launches nothing. */
+#define ADFP_INGEST_MAX_JOBS 16
+typedef struct adfp_ingest_geom {           /* host */
+    int color_h, color_w;                   /* decoded colour image */
+    int depth_h, depth_w;                   /* decoded depth image */
+    int crop_h, crop_w;                     /* cfg cam.crop_size, 0 0 = none */
+    int crop_edge;                          /* cfg cam.crop_edge */
+    int color_order;                        /* 0 = BGR (cv2.imread), 1 = RGB (PIL) */
+    int depth_kind;                         /* 0 = uint16, 1 = float32 */
+    int color_out;                          /* 0 = float32, 1 = float64 (the reference's dtype) */
+    float png_depth_scale, scale;
+} adfp_ingest_geom;
+typedef struct adfp_ingest_job { const unsigned char* color; const void* depth; void* color_out; float* depth_out; } adfp_ingest_job;
+int adfp_ingest_frames(const adfp_ingest_geom* geom, int n_jobs, const adfp_ingest_job* jobs /*host*/, void* stream);
+int adfp_ingest_out_shape(const adfp_ingest_geom* geom, int* H, int* W);    /* host only */
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,25 @@ def main(template, d):
         v['mbk_flag_tops'] = '%.1f' % (7.0 * n_ids * wb['planes_per_round'][0] / (float(v['mbk_k_bnd_flag_max']) * 1e-6) / 1e12)
     if 'mbk_k_bnd_support_max' in v:
         v['mbk_support_tops'] = '%.1f' % (5.0 * n_ids * mb['D'] / (float(v['mbk_k_bnd_support_max']) * 1e-6) / 1e12)
+    # frame ingestion: host chain against device route (tools/ingest_bench.py)
+    ib = json.load(open(P('ingest_bench.json')))
+    v['ing_cpus'], v['ing_threads'] = str(ib['host']['cpus']), str(ib['host']['torch_threads'])
+    v['ing_reps'], v['ing_iters'] = str(ib['reps']), str(ib['iters'])
+    ik = {n: stats(P('ingest_kernels_%d.csv' % n)) for n in (1, ib['frames_per_batch'])}
+    v['ing_hbm'] = '6.3'
+    rows, lrows = [], []
+    for name, g in sorted(ib['geometries'].items()):
+        shape = '%s: %d × %d → %d × %d' % (name, g['color'][0], g['color'][1], g['out'][0], g['out'][1])
+        rows.append('| %s | %s | %s | %s | %.0f× | %s → %s |' % (
+            shape, cell(g['host_chain'], '%.2f'), cell(g['device_1_frame'], '%.3f'), cell(g['device_8_frames_per_frame'], '%.3f'),
+            g['host_over_device_median'], thousands(g['upload_bytes_host_route']), thousands(g['upload_bytes_device_route'])))
+        la = g['launch']
+        k1, k8 = (next(r for k, r in ik[n].items() if 'k_ingest<%d, float>' % (0 if g['color'] == g['depth'] else 1) in k)
+                  for n in (1, ib['frames_per_batch']))
+        lrows.append('| %s | %s | %.1f µs | %.1f µs | %.1f µs | %.1f µs | %.1f TB/s |' % (
+            shape, thousands(la['bytes_per_frame']), la['ms_1_frame'] * 1e3, la['ms_per_frame_of_8'] * 1e3, float(k1['avg_us']), float(k8['avg_us']),
+            ib['frames_per_batch'] * la['bytes_per_frame'] / (float(k8['avg_us']) * 1e-6) / 1e12))
+    v['ing_table'], v['ing_launch_table'] = '\n'.join(rows), '\n'.join(lrows)
     # ---- parity / gradient stats
     t = open(P('r06_parity_stats.txt')).read()
     m = re.search(r'tol 0\.0001: (\d+) tensors, worst (\S+) of the limit', t)
