@@ -87,6 +87,13 @@ INGEST_MAX_JOBS = 16              # ADFP_INGEST_MAX_JOBS
 COLOR_ORDER = {'bgr': 0, 'rgb': 1}
 
 
+class AdfpVisGeom(C.Structure):
+    _fields_ = [('H', C.c_int), ('W', C.c_int), ('stride', C.c_int), ('gap', C.c_int), ('gt_color_f64', C.c_int)]
+
+
+VIS_STATS = 6                     # ADFP_VIS_STATS
+
+
 class AdfpScene(C.Structure):
     _fields_ = [('bound', (C.c_double * 2) * 3), ('tsdf_bnds', (C.c_double * 2) * 3),
                 ('low', AdfpGrid), ('high', AdfpGrid), ('color', AdfpGrid), ('tsdf', AdfpTsdf),
@@ -348,6 +355,11 @@ SYMBOLS = [
     # frame ingestion
     ('adfp_ingest_frames', C.c_int, [C.POINTER(AdfpIngestGeom), C.c_int, C.POINTER(AdfpIngestJob), C.c_void_p]),
     ('adfp_ingest_out_shape', C.c_int, [C.POINTER(AdfpIngestGeom), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    # visualisation
+    ('adfp_vis_canvas_shape', C.c_int, [C.POINTER(AdfpVisGeom), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ('adfp_vis_workspace_bytes', C.c_size_t, [C.POINTER(AdfpVisGeom)]),
+    ('adfp_vis_panels', C.c_int, [C.POINTER(AdfpVisGeom), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER

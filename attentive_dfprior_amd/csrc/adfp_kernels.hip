@@ -4240,3 +4240,6 @@ int adfp_bound_points(const float* depth, const float* poses, long long K, int H
 
 // ---- frame ingestion (adfp_ingest.h) ----
 #include "adfp_ingest.h"
+
+// ---- visualisation (adfp_vis.h) ----
+#include "adfp_vis.h"

@@ -1093,6 +1093,45 @@ typedef struct adfp_ingest_job { const unsigned char* color; const void* depth; 
 int adfp_ingest_frames(const adfp_ingest_geom* geom, int n_jobs, const adfp_ingest_job* jobs /*host*/, void* stream);
 int adfp_ingest_out_shape(const adfp_ingest_geom* geom, int* H, int* W);    /* host only */
 
+/* ---- visualisation (visualizer.Visualizer: the reference's src/utils/Visualizer.py:71-114, everything after render_img) ----
+ * The frame's input images -- gt_depth [H][W] f32, gt_color [H][W][3] f32 or f64 (gt_color_f64) -- and the rendered ones -- depth
+ * [H][W] f64, color [H][W][3] f32 -- go in as they lie in device memory, and two launches write the uint8 canvas [rows][cols][3]
+ * of six panels and stats [ADFP_VIS_STATS] (f64, device).  The contract is what matplotlib maps a data array to (Normalize,
+ * Colormap.__call__, the float-RGB rule of imshow), not what imshow resamples into a figure; tests/vis_ref.py states it in numpy.
+ *   layout     h = ceil(H / stride), w = ceil(W / stride); rows = 2 h + 3 gap, cols = 3 w + 4 gap; the background is white (255).
+ *              Panel (r, k) has its top-left corner at (gap + r (h + gap), gap + k (w + gap)); its pixel (i, j) shows source
+ *              pixel (i stride, j stride).  Row 0: input depth, generated depth, depth residual; row 1: input RGB, generated
+ *              RGB, RGB residual.
+ *   residuals  depth: |(double)gt_depth - depth|, 0 where gt_depth == 0.  RGB: |gt_color - color| in the promoted dtype (f32 with
+ *              f32 gt_color, f64 with f64), all three channels 0 where gt_depth == 0.
+ *   depth panels  vmax = max(gt_depth), an f32 (gt_depth is taken to be free of NaN).  x = v / vmax, in f32 for the input-depth
+ *              panel and in f64 with (double)vmax for the other two; the division is IEEE.  index = 255 if 256 x == 256, else
+ *              trunc(256 x) clamped to [0, 255]; the colour is entry `index` of matplotlib's 'plasma' as bytes.  NaN is white.
+ *              vmax == 0 maps every value to index 0.  (vmax < 0, where matplotlib raises, takes the same formula.)
+ *   RGB panels    byte = trunc(255 clip(v, 0, 1)), the product in the array's own dtype; NaN is 0.
+ *   stats      over the full-resolution frame whatever the stride: [0] vmax; [1] n_valid, the pixels with gt_depth > 0 and finite
+ *              rendered depth and colour (all three channels); [2] depth_abs_sum, the depth residual summed over those; [3]
+ *              color_sq_sum, ((double)gt_color - (double)color)^2 summed over the three channels of every pixel with finite
+ *              rendered colour; [4] n_nonfinite, the pixels whose rendered depth or colour is not finite; [5] n_color, the
+ *              pixels color_sq_sum counted (a pixel may have a finite colour beside a NaN depth, so [4] does not give it).
+ *              Sums are f64; per-workgroup partials over a grid that depends on H W alone, then one fixed-order pass: no float
+ *              atomics, the same bits on every call.
+ * Asynchronous on `stream`, no allocation, no pointer kept; nothing is read back between the two launches (vmax reaches the
+ * second through the workspace).  Workspace: adfp_vis_workspace_bytes(geom) (0 for a bad geometry), 8-byte aligned.  Errors,
+ * before any launch: ADFP_E_ARG for a null pointer, H, W or stride < 1, gap < 0, gt_color_f64 outside {0, 1}, a workspace that is
+ * too small or misaligned; ADFP_E_UNSUPPORTED for H, W or gap above 32768. */
+#define ADFP_VIS_STATS 6
+typedef struct adfp_vis_geom {              /* host */
+    int H, W;                               /* the frame */
+    int stride;                             /* every stride-th source pixel in both axes */
+    int gap;                                /* gutter and margin, canvas pixels */
+    int gt_color_f64;                       /* gt_color: 0 = float32, 1 = float64 (the reference's dtype) */
+} adfp_vis_geom;
+int adfp_vis_canvas_shape(const adfp_vis_geom* geom, int* rows, int* cols);    /* host only */
+size_t adfp_vis_workspace_bytes(const adfp_vis_geom* geom);
+int adfp_vis_panels(const adfp_vis_geom* geom, const float* gt_depth, const void* gt_color, const double* depth, const float* color,
+                    unsigned char* canvas, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

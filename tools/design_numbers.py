@@ -107,6 +107,35 @@ def main(template, d):
             shape, thousands(la['bytes_per_frame']), la['ms_1_frame'] * 1e3, la['ms_per_frame_of_8'] * 1e3, float(k1['avg_us']), float(k8['avg_us']),
             ib['frames_per_batch'] * la['bytes_per_frame'] / (float(k8['avg_us']) * 1e-6) / 1e12))
     v['ing_table'], v['ing_launch_table'] = '\n'.join(rows), '\n'.join(lrows)
+    # the Visualizer after render_img: host chain against device route (tools/vis_bench.py) and the per-configuration kernel trace
+    vb = json.load(open(P('vis_bench.json')))
+    v['vis_cpus'], v['vis_threads'] = str(vb['host']['cpus']), str(vb['host']['torch_threads'])
+    v['vis_reps'], v['vis_iters'], v['vis_mpl'] = str(vb['reps']), str(vb['iters']), str(vb['host']['matplotlib'])
+    with open(P('vis_kernels.csv')) as f:
+        vk = {(r['frame'], r['stride'], r['kernel']): r for r in csv.DictReader(l for l in f if not l.startswith('#'))}
+    rows, krows = [], []
+    for name, g in sorted(vb['frames'].items()):
+        shape = '%s: %d × %d' % (name, g['frame'][0], g['frame'][1])
+        s1, s2 = g['by_stride']['1'], g['by_stride']['2']
+        fig = cell(g['matplotlib_figure'], '%.0f') if g['matplotlib_figure'] else 'no matplotlib'
+        rows.append('| %s | %s | %s | %s | %s | %.0f× | %.0f× | %s |' % (
+            shape, cell(g['host_chain'], '%.2f'), cell(g['host_downloads_alone'], '%.2f'), cell(s1['device'], '%.3f'), cell(s2['device'], '%.3f'),
+            s1['host_over_device_median'], s1['host_numpy_over_device_median'], fig))
+        v['vis_numpy_' + name] = '%.1f' % (g['host_chain']['median_ms'] - g['host_downloads_alone']['median_ms'])
+        for st, r in sorted(g['by_stride'].items()):
+            kr, kp = vk[(name, st, 'k_vis_reduce')], vk[(name, st, 'k_vis_panels')]
+            krows.append('| %s, stride %s | %d × %d | %s | %s | %.1f µs | %.1f (%.1f) | %.1f (%.1f) |' % (
+                shape, st, r['canvas'][0], r['canvas'][1], thousands(g['input_bytes']), thousands(r['canvas_bytes']), r['launches_ms'] * 1e3,
+                float(kr['avg_us']), float(kr['max_us']), float(kp['avg_us']), float(kp['max_us'])))
+            v['vis_dev_%s%s' % (name, st)] = '%.2f' % r['device']['median_ms']
+    v['vis_table'], v['vis_kernel_table'] = '\n'.join(rows), '\n'.join(krows)
+    g = vb['frames']['replica']
+    kp, kr = vk[('replica', '1', 'k_vis_panels')], vk[('replica', '1', 'k_vis_reduce')]
+    moved = g['input_bytes'] + g['by_stride']['1']['canvas_bytes']
+    v['vis_panels_replica1'] = '%.0f' % float(kp['avg_us'])
+    v['vis_mb_replica1'] = '%.0f' % (moved / 1e6)
+    v['vis_tbps_replica1'] = '%.1f' % (moved / (float(kp['avg_us']) * 1e-6) / 1e12)
+    v['vis_launch_share_replica1'] = '%.0f' % (100 * (float(kp['avg_us']) + float(kr['avg_us'])) * 1e-3 / g['by_stride']['1']['device']['median_ms'])
     # ---- parity / gradient stats
     t = open(P('r06_parity_stats.txt')).read()
     m = re.search(r'tol 0\.0001: (\d+) tensors, worst (\S+) of the limit', t)
