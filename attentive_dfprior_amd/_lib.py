@@ -309,6 +309,9 @@ SYMBOLS = [
                                     C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     ('adfp_views_in_sight', C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float,
                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ('adfp_points_visible', C.c_int, [C.c_void_p, C.c_size_t, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                      C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_double,
+                                      C.c_double, C.c_void_p, C.c_void_p]),
     ('adfp_depth_l1_workspace_bytes', C.c_size_t, [C.c_longlong, C.c_longlong]),
     ('adfp_depth_l1_sums', C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ('adfp_render_depth_cull', C.c_int, [C.c_void_p, C.c_size_t, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_double,

@@ -3633,6 +3633,31 @@ int adfp_views_in_sight(const double* points, long long n_points, const float* w
     return 0;
 }
 
+int adfp_points_visible(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* points, long long n_points,
+                        const float* w2c, const double* c2w, long long n_poses, float fx, float fy, float cx, float cy, int W, int H,
+                        double near, double eps, unsigned char* seen, void* stream) {
+    if (n_faces < 0 || n_points < 0 || n_poses < 0 || !tri_leaf_ok(leaf)) return ADFP_E_ARG;
+    if (!(eps >= 0.0) || !isfinite(eps) || !(near >= 0.0) || !isfinite(near) || !(fx != 0.f) || !(fy != 0.f)) return ADFP_E_ARG;
+    if (n_points == 0) return 0;
+    if (!points || !seen || (n_poses > 0 && !w2c) || (n_poses > 0 && n_faces > 0 && (!bvh || !c2w))) return ADFP_E_ARG;
+    if (n_faces > RECON_MAX_N || n_points > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
+    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
+    if (n_faces == 0 || n_poses == 0)                     // nothing occludes (or nothing looks): the frustum-only kernel itself
+        return adfp_cull_vertices(points, n_points, w2c, n_poses, fx, fy, cx, cy, W, H, seen, stream);
+    const TriLayout L = tri_layout(n_faces, leaf);
+    VisibleArgs a;
+    a.tri = (const double*)bvh;
+    a.box = (const double*)((const char*)bvh + L.off_box);
+    a.nf = (int)n_faces; a.leaf = leaf; a.P = L.P; a.D = L.D;
+    a.pts = points; a.n = (int)n_points; a.w2c = w2c; a.c2w = c2w; a.np = (int)n_poses;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H;
+    a.near = near; a.eps = eps; a.seen = seen;
+    hipLaunchKernelGGL(k_points_visible, dim3((unsigned)((n_points + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0,
+                       (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
 size_t adfp_depth_l1_workspace_bytes(long long n_views, long long n_pixels) {
     if (n_views < 0 || n_pixels < 0 || n_pixels > RECON_MAX_N || n_views > RECON_MAX_N) return 0;
     return (size_t)n_views * red_blocks(n_pixels) * 8;

@@ -8,14 +8,18 @@ cam = w2c [p, 1], cam.x *= -1, uv = K cam, z = uv.z + 1e-5, uv /= z, seen iff 0 
 dropped iff all three of its vertices are unseen in every pose.  Like trimesh's update_faces, the output keeps every vertex and
 its properties and only the kept faces.
 
-    python -m attentive_dfprior_amd.cull_mesh --input_mesh MESH.ply --traj traj.txt --output_mesh CULLED.ply
+    python -m attentive_dfprior_amd.cull_mesh --input_mesh MESH.ply --traj traj.txt --output_mesh CULLED.ply [--remove_occlusion]
+
+--remove_occlusion (not in the reference) is the occlusion-aware cull: a vertex counts as seen only where a pose also sees it
+unoccluded by the mesh itself (visibility.points_visible), so a face behind a wall goes although it lies inside a frustum.
 """
 import argparse
 
 import numpy as np
 import torch
 
-from . import mesh
+from . import mesh, visibility
+from .raycast import MeshBVH
 from .recon import device_of, frustum_seen, faces_kept
 
 H, W = 680, 1200                      # cull_mesh.py:31-37 (Replica)
@@ -37,10 +41,15 @@ def load_poses(path):
     return poses
 
 
-def cull_mesh(verts, faces, c2w_list, H=H, W=W, fx=FX, fy=FY, cx=CX, cy=CY):
-    """Boolean numpy mask [F] of the faces to keep: a face goes iff none of its vertices lies in any pose's viewing frustum."""
+def cull_mesh(verts, faces, c2w_list, H=H, W=W, fx=FX, fy=FY, cx=CX, cy=CY, occlusion=False, eps=visibility.OCCLUSION_EPS):
+    """Boolean numpy mask [F] of the faces to keep: a face goes iff none of its vertices lies in any pose's viewing frustum.
+    occlusion=True (not in the reference): a vertex also has to be seen unoccluded by the mesh itself from such a pose, no face
+    nearer to the camera than the vertex by more than `eps` metres (visibility.points_visible against the mesh's own BVH)."""
     dev = device_of(verts, faces)
-    seen = frustum_seen(verts, c2w_list, H, W, fx, fy, cx, cy, device=dev)
+    if occlusion:
+        seen = visibility.points_visible(MeshBVH(verts, faces, dev), verts, c2w_list, H, W, fx, fy, cx, cy, eps=eps)
+    else:
+        seen = frustum_seen(verts, c2w_list, H, W, fx, fy, cx, cy, device=dev)
     return faces_kept(seen, faces).cpu().numpy().astype(bool)
 
 
@@ -71,10 +80,13 @@ def main(argv=None):
     parser.add_argument('--input_mesh', type=str, help='path to the mesh to be culled')
     parser.add_argument('--traj', type=str, help='path to the trajectory')
     parser.add_argument('--output_mesh', type=str, help='path to the output mesh')
+    parser.add_argument('--remove_occlusion', action='store_true',
+                        help='also drop faces whose vertices the mesh itself hides from every pose (not in the reference)')
+    parser.add_argument('--eps', type=float, default=visibility.OCCLUSION_EPS, help='occlusion margin in metres')
     args = parser.parse_args(argv)
     poses = load_poses(args.traj)
     m = mesh.read_ply(args.input_mesh)
-    keep = cull_mesh(m.verts, m.faces, poses)
+    keep = cull_mesh(m.verts, m.faces, poses, occlusion=args.remove_occlusion, eps=args.eps)
     _write_like(args.output_mesh, m, m.faces[keep])
     return keep
 

@@ -858,6 +858,27 @@ int adfp_render_depth_cull(const void* bvh, size_t bvh_bytes, long long n_faces,
  * no points gives all zeros. */
 int adfp_views_in_sight(const double* points, long long n_points, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
                         int W, int H, int* any, void* stream);
+/* Occlusion-aware visibility of points from a batch of poses in one launch (no workspace): seen[i] (device) = 1 iff some pose k
+ * both (a) has point i in its frustum and (b) sees it unoccluded by the mesh of `bvh` (adfp_tri_bvh_build's, with its n_faces and
+ * leaf), else 0.
+ *   (a) is adfp_cull_vertices's test bit for bit: w2c [n_poses][12] (f32, device) are its rows, the point (f64) is rounded to f32.
+ *   (b) is a shadow ray in adfp_render_depth's arithmetic: c2w [n_poses][12] (f64, device) = the top three rows [R | o] of the same
+ *     pose in OpenCV axes.  The point p goes to camera space as a mesh vertex does, e = p - o, cam_c = ((R0c e0 + R1c e1) + R2c e2),
+ *     and z_p = cam_z.  The pair is not visible when z_p <= 0 or is not finite, when d = (cam_x / z_p, cam_y / z_p, 1) is not
+ *     finite, or when the pose's c2w row holds a non-finite entry.  Else the triangle test is the one above verbatim with that d
+ *     (the shear, U, V, W; mixed signs or det = 0 miss; z = ((U Az + V Bz) + W Cz) / det; edges inside, back faces count), and the
+ *     point is occluded iff some triangle is hit with near <= z && z < z_p - eps.  eps keeps a surface point from being occluded
+ *     by the face it lies on.  The decision is existence over a set of hits: independent of the traversal order, equal to a brute
+ *     force over all faces (tests/visible_ref.py), two runs give the same bytes.
+ *   The walk is the renderer's with the bound fixed at z_p - eps: boxes padded as there, a box pruned when its entry t is at or
+ *     beyond the bound or its exit t lies below near, left at the first qualifying hit.  Only pairs that pass (a) are walked, and
+ *     a point that some pose has seen is not tested against the poses after it.
+ * n_faces = 0 returns exactly what adfp_cull_vertices returns (bvh and c2w may be NULL).  n_points = 0 returns 0; n_poses = 0
+ * writes zeros.  ADFP_E_ARG: a NULL pointer, a negative count, a leaf other than 4, 8, 16, eps or near negative or not finite,
+ * fx or fy zero. */
+int adfp_points_visible(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* points, long long n_points,
+                        const float* w2c, const double* c2w, long long n_poses, float fx, float fy, float cx, float cy, int W, int H,
+                        double near, double eps, unsigned char* seen, void* stream);
 /* Per view p: out[p] (f64, device) = sum over n_pixels of (double)|a - b|, the f32 difference widened, for a, b [n_views][n_pixels]
  * (f32, device); per-workgroup partials over min(max(ceil(n_pixels / 256), 1), 1024) workgroups, then one fixed-order pass.
  * Workspace: adfp_depth_l1_workspace_bytes = 8 n_views times that workgroup count.  n_views = 0 does nothing. */

@@ -136,6 +136,31 @@ def main(template, d):
     v['vis_mb_replica1'] = '%.0f' % (moved / 1e6)
     v['vis_tbps_replica1'] = '%.1f' % (moved / (float(kp['avg_us']) * 1e-6) / 1e12)
     v['vis_launch_share_replica1'] = '%.0f' % (100 * (float(kp['avg_us']) + float(kr['avg_us'])) * 1e-3 / g['by_stride']['1']['device']['median_ms'])
+    # occlusion-aware visibility against the frustum-only cull (tools/recon_bench.py --visible)
+    pv = json.load(open(P('visible_bench.json')))
+    q = pv['visible']
+    mmm = lambda t, f='%.1f': (f + ' (' + f + ', ' + f + ')') % (t['median_ms'], t['min_ms'], t['max_ms'])
+    v['pv_reps'] = str(pv['reps'])
+    v['pv_faces'], v['pv_verts'] = thousands(q['faces']), thousands(q['verts'])
+    v['pv_points'], v['pv_poses'] = thousands(q['points']), thousands(q['poses'])
+    v['pv_visible'], v['pv_frustum'], v['pv_cull_leg'] = mmm(q['points_visible']), mmm(q['frustum_only_same_inputs'], '%.2f'), mmm(q['frustum_only_cull_leg'], '%.2f')
+    qr = json.load(open(P('visible_bench_runahead.json')))['visible']
+    v['pv_runahead'] = mmm(qr['points_visible'])
+    v['pv_runahead_ratio'] = '%.2f' % (qr['points_visible']['median_ms'] / q['points_visible']['median_ms'])
+    v['pv_runahead_again'] = '%.1f' % qr['repeat_in_the_same_run']['median_ms']
+    if (qr['seen_visible'], qr['pairs_walked_share']) != (q['seen_visible'], q['pairs_walked_share']):
+        v['pv_runahead'] += ' (MASKS DIFFER)'
+    v['pv_never'] = thousands(q['points'] - q['seen_visible'])
+    v['pv_ratio_same'], v['pv_ratio_leg'] = '%.1f' % q['visible_over_frustum_same_inputs'], '%.1f' % q['visible_over_frustum_cull_leg']
+    v['pv_seen_visible'], v['pv_seen_frustum'] = thousands(q['seen_visible']), thousands(q['seen_frustum'])
+    v['pv_in_frustum_share'] = '%.2f' % (100 * q['pairs_in_frustum_share'])
+    v['pv_walked_share'] = '%.3f' % (100 * q['pairs_walked_share'])
+    v['pv_walks_per_point'] = '%.1f' % q['walks_per_point']
+    v['pv_mrays'] = '%.0f' % (q['pairs_walked_share'] * q['pairs'] / (q['points_visible']['median_ms'] * 1e-3) / 1e6)
+    v['pv_same'] = 'equal' if q['pose_by_pose_equals_one_launch'] and q['visible_not_in_frustum'] == 0 else 'NOT equal'
+    u = q['unseen_points']
+    v['pv_unseen_ms'] = '%.1f (%.1f)' % (u['median_ms'], u['min_ms'])
+    v['pv_unseen_samples'], v['pv_unseen_n'] = thousands(u['samples']), thousands(u['unseen'])
     # ---- parity / gradient stats
     t = open(P('r06_parity_stats.txt')).read()
     m = re.search(r'tol 0\.0001: (\d+) tensors, worst (\S+) of the limit', t)

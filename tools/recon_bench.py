@@ -8,11 +8,14 @@
   * --2d: the 2D metric alone -- the triangle BVH build over the 512^3 room (~1 M faces) and the depth render of one chunk of
     100 views at 500 x 500 (M rays/s), for each leaf size, and the whole metric_2d for 1 000 views on two synthetic 512^3 rooms
     (no ICP); median and range.
+  * --visible: occlusion-aware visibility alone -- adfp_points_visible for 1 M surface points x 2 000 poses inside the 512^3 room
+    (~1 M faces) next to the frustum-only cull (adfp_cull_vertices) of the same points and poses and of the default run's cull
+    leg, the share of point/pose pairs that reach the shadow-ray walk, and visibility.unseen_points at 200 000 samples.
 ADFP_LIB_PATH selects another build of the library (an A/B of leaf sizes: --nn_only runs the 3D-metric legs alone).
 Device legs: warm-up, then `--reps` repetitions between torch.cuda events (host clock around a synchronised call where the leg
 reads results back), min and median.
 
-    python tools/recon_bench.py [--reps 5] [--2d]
+    python tools/recon_bench.py [--reps 5] [--2d | --visible]
 """
 import argparse
 import json
@@ -167,6 +170,100 @@ def leg_2d(reps, res, n_imgs, chunk):
     return out
 
 
+def cull_leg_inputs(n_verts, n_poses):
+    """The cull leg's inputs: uniform points in a box, poses turned about z at uniform positions (load_poses's convention)."""
+    rng = np.random.default_rng(0)
+    pc = torch.from_numpy(rng.uniform([-4, -3, -2], [4, 3, 2], (n_verts, 3))).to(DEV)
+    poses = []
+    for _ in range(n_poses):
+        yaw = rng.uniform(-np.pi, np.pi)
+        c2w = np.eye(4)
+        c2w[:3, :3] = [[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0, 0, 1]]
+        c2w[:3, 3] = rng.uniform(-2, 2, 3)
+        poses.append(torch.from_numpy(c2w).float())
+    return pc, poses
+
+
+def leg_visible(reps, res, n_points, n_poses, count):
+    """adfp_points_visible against the frustum-only cull on the same inputs: n_points points on the room's surface (its vertices,
+    then area-weighted samples), n_poses poses at uniform positions in the room's free space looking in uniform directions."""
+    from attentive_dfprior_amd import _lib, raycast, visibility
+    from attentive_dfprior_amd.cull_mesh import H, W, FX, FY, CX, CY
+    out = {}
+    v, f = room(res)
+    out['faces'], out['verts'] = int(f.shape[0]), int(v.shape[0])
+    g = torch.Generator().manual_seed(0)
+    pts = v[:n_points]
+    if pts.shape[0] < n_points:
+        pts = torch.cat([pts, recon.sample_surface(v, f, n_points - int(pts.shape[0]), generator=g)[0]])
+    pts = pts.contiguous()
+    rng = np.random.default_rng(0)
+    poses = []
+    while len(poses) < n_poses:
+        eye = rng.uniform([-1.4, -0.9, -0.6], [1.4, 0.9, 0.7])           # the room's walls are 0.4 inside BOUND
+        if np.linalg.norm(eye - [0.6, -0.3, -0.2]) < 0.55:                # inside the ball
+            continue
+        d = rng.normal(size=3)
+        m = np.eye(4)
+        m[:3, :] = recon_eval.viewmatrix(d, recon_eval.UP_2D, eye)
+        if not np.isfinite(m).all():
+            continue
+        m[:3, 1] *= -1
+        m[:3, 2] *= -1
+        poses.append(torch.from_numpy(m).float())
+    out['points'], out['poses'] = int(pts.shape[0]), len(poses)
+    dev = torch.device(DEV)
+    h = {}
+    out['bvh_build'] = timed(lambda: h.__setitem__('b', raycast.MeshBVH(v, f, DEV)), reps)
+    bvh = h['b']
+    w = torch.from_numpy(recon.w2c_rows(poses)).to(DEV)
+    m = torch.from_numpy(visibility.opencv_rows(poses)).to(DEV)
+    seen_v = torch.empty(n_points, dtype=torch.uint8, device=DEV)
+    seen_f = torch.empty(n_points, dtype=torch.uint8, device=DEV)
+    L = _lib.lib()
+
+    def visible():
+        _lib.check(L.adfp_points_visible(_lib.ptr(bvh.bvh), bvh.bvh.numel(), bvh.n_faces, bvh.leaf, _lib.ptr(pts), n_points, _lib.ptr(w),
+                                         _lib.ptr(m), len(poses), FX, FY, CX, CY, W, H, 0.0, visibility.OCCLUSION_EPS, _lib.ptr(seen_v),
+                                         _lib.current_stream(dev)), 'adfp_points_visible')
+
+    def frustum(p=pts, rows=w, dst=seen_f):
+        _lib.check(L.adfp_cull_vertices(_lib.ptr(p), n_points, _lib.ptr(rows), int(rows.shape[0]), FX, FY, CX, CY, W, H, _lib.ptr(dst),
+                                        _lib.current_stream(dev)), 'adfp_cull_vertices')
+    out['points_visible'] = timed(visible, reps)
+    out['frustum_only_same_inputs'] = timed(frustum, reps)
+    pc, cposes = cull_leg_inputs(n_points, n_poses)
+    cw = torch.from_numpy(recon.w2c_rows(cposes)).to(DEV)
+    scratch = torch.empty(n_points, dtype=torch.uint8, device=DEV)
+    out['frustum_only_cull_leg'] = timed(lambda: frustum(pc, cw, scratch), reps)
+    out['visible_over_frustum_same_inputs'] = round(out['points_visible']['median_ms'] / out['frustum_only_same_inputs']['median_ms'], 2)
+    out['visible_over_frustum_cull_leg'] = round(out['points_visible']['median_ms'] / out['frustum_only_cull_leg']['median_ms'], 2)
+    out['seen_visible'], out['seen_frustum'] = int(seen_v.sum()), int(seen_f.sum())
+    out['visible_not_in_frustum'] = int((seen_v & (1 - seen_f)).sum())     # 0: occlusion only removes
+    # the pairs that reach the walk, counted pose by pose as the kernel meets them: in the frustum, the point not yet seen
+    done = torch.zeros(n_points, dtype=torch.bool, device=DEV)
+    walked = torch.zeros((), dtype=torch.int64, device=DEV)
+    in_frustum = torch.zeros((), dtype=torch.int64, device=DEV)
+    for c in poses:
+        fr = recon.frustum_seen(pts, [c], H, W, FX, FY, CX, CY, device=DEV).bool()
+        in_frustum += fr.sum()
+        walked += (fr & ~done).sum()
+        done |= visibility.points_visible(bvh, pts, [c], H, W, FX, FY, CX, CY).bool()
+    out['pose_by_pose_equals_one_launch'] = bool(torch.equal(done, seen_v.bool()))
+    pairs = n_points * len(poses)
+    out['pairs'] = pairs
+    out['pairs_in_frustum_share'] = round(int(in_frustum) / pairs, 5)
+    out['pairs_walked_share'] = round(int(walked) / pairs, 5)
+    out['walks_per_point'] = round(int(walked) / n_points, 2)
+    gu = torch.Generator().manual_seed(1)
+    res_u = {}
+    out['unseen_points'] = wall(lambda: res_u.__setitem__('u', visibility.unseen_points(v, f, poses, count=count, generator=gu)), reps)
+    out['unseen_points']['samples'], out['unseen_points']['unseen'] = count, int(len(res_u['u']))
+    out['unseen_points']['note'] = 'BVH build + draws + sampling + points_visible + read-back'
+    out['morton_ordered_points'] = 'not run'
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
@@ -176,6 +273,8 @@ def main():
     ap.add_argument('--cull_poses', type=int, default=2000)
     ap.add_argument('--nn_only', action='store_true', help='only the two 3D-metric legs (for an A/B of library builds)')
     ap.add_argument('--2d', dest='two_d', action='store_true', help='only the 2D-metric legs (BVH build, render, metric_2d)')
+    ap.add_argument('--visible', action='store_true', help='only the occlusion-aware visibility legs')
+    ap.add_argument('--unseen_count', type=int, default=200000)
     ap.add_argument('--res_2d', type=int, default=512)
     ap.add_argument('--n_imgs', type=int, default=1000)
     a = ap.parse_args()
@@ -183,6 +282,10 @@ def main():
     out = {'device': torch.cuda.get_device_name(0), 'reps': a.reps, 'lib': os.path.basename(_lib.LIB_PATH)}
     if a.two_d:
         out['metric_2d'] = leg_2d(a.reps, a.res_2d, a.n_imgs, 100)
+        print(json.dumps(out))
+        return
+    if a.visible:
+        out['visible'] = leg_visible(a.reps, a.res_2d, a.cull_verts, a.cull_poses, a.unseen_count)
         print(json.dumps(out))
         return
     v, f = room(256)
@@ -213,15 +316,7 @@ def main():
                   'note': 'per iteration = total / (iterations + 1) correspondence passes, index build included in total'}
     del src, tgt
 
-    rng = np.random.default_rng(0)
-    pc = torch.from_numpy(rng.uniform([-4, -3, -2], [4, 3, 2], (a.cull_verts, 3))).to(DEV)
-    poses = []
-    for _ in range(a.cull_poses):
-        yaw = rng.uniform(-np.pi, np.pi)
-        c2w = np.eye(4)
-        c2w[:3, :3] = [[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0, 0, 1]]
-        c2w[:3, 3] = rng.uniform(-2, 2, 3)
-        poses.append(torch.from_numpy(c2w).float())
+    pc, poses = cull_leg_inputs(a.cull_verts, a.cull_poses)
     w = torch.from_numpy(recon.w2c_rows(poses)).to(DEV)
     seen = torch.empty(a.cull_verts, dtype=torch.uint8, device=DEV)
     L = _lib.lib()
