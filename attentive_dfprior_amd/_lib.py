@@ -94,6 +94,13 @@ class AdfpVisGeom(C.Structure):
 VIS_STATS = 6                     # ADFP_VIS_STATS
 
 
+class AdfpMetricsGeom(C.Structure):
+    _fields_ = [('H', C.c_int), ('W', C.c_int), ('levels', C.c_int), ('gt_color_f64', C.c_int)]
+
+
+FRAME_METRICS = 35                # ADFP_FRAME_METRICS
+
+
 class AdfpScene(C.Structure):
     _fields_ = [('bound', (C.c_double * 2) * 3), ('tsdf_bnds', (C.c_double * 2) * 3),
                 ('low', AdfpGrid), ('high', AdfpGrid), ('color', AdfpGrid), ('tsdf', AdfpTsdf),
@@ -363,6 +370,11 @@ SYMBOLS = [
     ('adfp_vis_workspace_bytes', C.c_size_t, [C.POINTER(AdfpVisGeom)]),
     ('adfp_vis_panels', C.c_int, [C.POINTER(AdfpVisGeom), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    # rendering metrics
+    ('adfp_frame_metrics_workspace_bytes', C.c_size_t, [C.POINTER(AdfpMetricsGeom)]),
+    ('adfp_frame_metrics_windows', C.c_int, [C.POINTER(AdfpMetricsGeom), C.POINTER(C.c_longlong)]),
+    ('adfp_frame_metrics', C.c_int, [C.POINTER(AdfpMetricsGeom), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER

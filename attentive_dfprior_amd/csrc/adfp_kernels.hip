@@ -4268,3 +4268,6 @@ int adfp_bound_points(const float* depth, const float* poses, long long K, int H
 
 // ---- visualisation (adfp_vis.h) ----
 #include "adfp_vis.h"
+
+// ---- rendering metrics (adfp_metrics.h) ----
+#include "adfp_metrics.h"

@@ -1153,6 +1153,51 @@ size_t adfp_vis_workspace_bytes(const adfp_vis_geom* geom);
 int adfp_vis_panels(const adfp_vis_geom* geom, const float* gt_depth, const void* gt_color, const double* depth, const float* color,
                     unsigned char* canvas, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- rendering metrics (render_eval.FrameMetrics: PSNR, SSIM, MS-SSIM and depth L1 of a rendered frame; no counterpart in the
+ * reference) ----
+ * One frame's inputs are adfp_vis_panels' -- gt_depth [H][W] f32, gt_color [H][W][3] f32 or f64 (gt_color_f64), and the rendered
+ * depth [H][W] f64 and color [H][W][3] f32 as render_img returns them -- read as they lie in device memory.  The output is one
+ * row of ADFP_FRAME_METRICS doubles at a device address the caller chooses, so that a run fills a table [n_frames][35] without a
+ * read-back per frame.  tests/render_ref.py states the contract in numpy.
+ *   row[0..4]  n_valid, depth_abs_sum, color_sq_sum, n_color, n_nonfinite: over the full-resolution frame; n_valid, the pixels with
+ *              gt_depth > 0 and finite rendered depth and colour (all three channels); depth_abs_sum, the depth residual
+ *              |(double)gt_depth - depth| summed over those; color_sq_sum, ((double)gt_color - (double)color)^2 summed over the
+ *              three channels of every pixel with finite rendered colour; n_color, the pixels color_sq_sum counted; n_nonfinite,
+ *              the pixels whose rendered depth or colour is not finite.  These are adfp_vis_panels' stats of the same names, over
+ *              the same reduction grid and in the same order: the same bits.
+ *   row[5 + 6 k + 2 c], row[5 + 6 k + 2 c + 1]   for level k in 0..4 and channel c in 0..2: the sum over all window positions of
+ *              the SSIM map and of the contrast-structure map of that level and channel.  Levels at or beyond geom.levels hold
+ *              exactly 0.
+ *   images     the whole image; gt_depth plays no part.  x = gt_color, y = clip(color, 0, 1) with NaN mapped to 0 (the RGB
+ *              panel's rule), both taken to double.
+ *   level 0    window: 11 taps, Gaussian, sigma 1.5, normalised to sum 1 in f64, applied separably with no padding: level k of
+ *              size Hk x Wk has (Hk - 10)(Wk - 10) positions.  Per position mx, my, sxx = E[x^2] - mx^2, syy, sxy; C1 = 1e-4,
+ *              C2 = 9e-4 (data range 1); cs = (2 sxy + C2) / (sxx + syy + C2); ssim = (2 mx my + C1) / (mx^2 + my^2 + C1) * cs.
+ *              All arithmetic is f64.
+ *   level k+1  level k averaged over 2 x 2 blocks with stride 2 after zero padding of Hk mod 2 rows and Wk mod 2 columns on each
+ *              side; the padded zeros count in the average (torch's avg_pool2d(x, 2, padding=(Hk % 2, Wk % 2))), so the size is
+ *              floor((Hk + 2 (Hk mod 2) - 2) / 2) + 1.  The pooled images are f64.
+ *   This is the convention of the pytorch_msssim package.  The numbers are held to the formula as restated in
+ *   tests/render_ref.py (and, independently, in torch f64 by tests/test_render_ref_host.py), NOT to that package or to skimage:
+ *   neither has been compared with.
+ *   sums       f64; per-workgroup partials over grids that depend on the geometry alone, then one pass in fixed order: no float
+ *              atomics, the same bits on every call.
+ * Asynchronous on `stream`, no allocation, no pointer kept, nothing read back between the launches (2 + 2 levels - 1 of them for
+ * levels >= 1); capturable in a graph.  Workspace: adfp_frame_metrics_workspace_bytes(geom) (0 for a bad geometry).  Errors, all
+ * before any launch: ADFP_E_ARG for a null pointer, H or W < 1, levels outside 0..5, gt_color_f64 outside {0, 1}, a level
+ * k < levels whose image is smaller than 11 on a side, a row or workspace that is not 8-byte aligned, a workspace that is too
+ * small; ADFP_E_UNSUPPORTED for H or W above 32768. */
+#define ADFP_FRAME_METRICS 35
+typedef struct adfp_metrics_geom {          /* host */
+    int H, W;                               /* the frame */
+    int levels;                             /* 0..5; 0 = entries [0..4] only */
+    int gt_color_f64;                       /* gt_color: 0 = float32, 1 = float64 (the reference's dtype) */
+} adfp_metrics_geom;
+size_t adfp_frame_metrics_workspace_bytes(const adfp_metrics_geom* geom);      /* 0 for a bad geometry */
+int adfp_frame_metrics_windows(const adfp_metrics_geom* geom, long long windows[5]);   /* host only: positions per level, 0 beyond levels */
+int adfp_frame_metrics(const adfp_metrics_geom* geom, const float* gt_depth, const void* gt_color, const double* depth,
+                       const float* color, double* row /* device [ADFP_FRAME_METRICS] */, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

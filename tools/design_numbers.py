@@ -136,6 +136,40 @@ def main(template, d):
     v['vis_mb_replica1'] = '%.0f' % (moved / 1e6)
     v['vis_tbps_replica1'] = '%.1f' % (moved / (float(kp['avg_us']) * 1e-6) / 1e12)
     v['vis_launch_share_replica1'] = '%.0f' % (100 * (float(kp['avg_us']) + float(kr['avg_us'])) * 1e-3 / g['by_stride']['1']['device']['median_ms'])
+    # rendering metrics of a run: host route against device route (tools/render_eval_bench.py) and the kernel trace
+    rb = json.load(open(P('render_eval_bench.json')))
+    v['re_cpus'], v['re_threads'] = str(rb['host']['cpus']), str(rb['host']['torch_threads'])
+    v['re_numpy'], v['re_scipy'] = rb['host']['numpy'], rb['host']['scipy']
+    v['re_reps'], v['re_iters'] = str(rb['reps']), str(rb['iters'])
+    with open(P('render_eval_kernels.csv')) as f:
+        rk = {(r['frame'], r['kernel']): r for r in csv.DictReader(l for l in f if not l.startswith('#'))}
+    rows, prows, brows = [], [], []
+    for name, g in sorted(rb['frames'].items()):
+        nf = g['frames_per_table']
+        many = g['device_%d_frames_per_frame' % nf]
+        shape = '%s: %d × %d' % (name, g['frame'][0], g['frame'][1])
+        rows.append('| %s | %s | %s | %s | %s | %.0f×, %.0f× | %s |' % (
+            shape, cell(g['host_scipy'], '%.1f'), cell(g['host_downloads_alone'], '%.2f'), cell(g['device_1_frame'], '%.3f'), cell(many, '%.3f'),
+            g['host_over_device_1_median'], g['host_over_device_many_median'], cell(g['host_numpy_statement'], '%.1f')))
+        pr = g['pair']
+        k = lambda n, c='avg_us_per_add': float(rk[(name, n)][c])
+        prows.append('| %s | %.1f µs | %.1f | %.1f (%.1f) | %.1f | %.1f | %.2f (%.2f) ms | %.2f ms | %.1f %% |' % (
+            shape, g['launches_ms'] * 1e3, k('k_vis_reduce'), k('k_met_ssim'), k('k_met_ssim', 'max_us_per_launch'), k('k_met_pool'), k('k_met_final'),
+            pr['render_img_ms'], pr['render_img_again_ms'], pr['render_img_and_add_ms'], 100 * pr['add_share_of_pair_by_launches']))
+        brows.append('%s %.1f MB read (%.1f MB of them the four inputs), %.1f MB written (the pooled levels), %.2f G f64 operations, %.1f MB of workspace, %d bytes downloaded per frame'
+                     % (shape, g['bytes_read'] / 1e6, g['input_bytes'] / 1e6, g['bytes_written'] / 1e6, g['f64_operations'] / 1e9, g['workspace_bytes'] / 1e6,
+                        g['download_bytes_device_route']))
+        v['re_share_' + name] = '%.1f' % (100 * pr['add_share_of_pair_by_launches'])
+        v['re_diff_' + name] = '%.2f' % pr['add_ms_by_difference']
+        v['re_frames'], v['re_pair_iters'] = str(nf), str(pr['iters'])
+    v['re_table'], v['re_pair_table'], v['re_table_bytes'] = '\n'.join(rows), '\n'.join(prows), '; '.join(brows) + '.'
+    v['re_parity'] = '%.0e' % max(g['worst_mean_difference'] for g in rb['frames'].values())
+    g = rb['frames']['replica']
+    v['re_ssim0_replica'] = '%.0f' % float(rk[('replica', 'k_met_ssim')]['max_us_per_launch'])
+    v['re_enqueue_replica'] = '%.0f' % (g['launches_ms'] * 1e3)
+    w = g['windows']
+    v['re_gflops'] = '%.2f' % (g['f64_operations'] * w[0] / sum(w) / 1e9)
+    v['re_tflops'] = '%.0f' % (g['f64_operations'] * w[0] / sum(w) / (float(rk[('replica', 'k_met_ssim')]['max_us_per_launch']) * 1e-6) / 1e12)
     # occlusion-aware visibility against the frustum-only cull (tools/recon_bench.py --visible)
     pv = json.load(open(P('visible_bench.json')))
     q = pv['visible']
