@@ -90,6 +90,64 @@ def test_nn_radius(radius):
     assert (i >= 0).any() and (i < 0).any() or radius == 0.3
 
 
+def adversarial_cloud(case):
+    """(ref, query), about 20 000 each: clouds on which the Morton order says little about where a point's neighbours are."""
+    rng = np.random.default_rng(31)
+    n = 20000
+    if case == 'duplicates':                                                 # 5 000 copies of one point: many leaves hold nothing else
+        p = np.array([0.25, -0.5, 0.75])
+        ref = np.concatenate([np.repeat(p[None], 5000, 0), rng.uniform(-2, 2, (15000, 3))])[rng.permutation(n)]
+        return ref, np.concatenate([np.repeat(p[None], 10, 0), ref[:1990], rng.uniform(-2, 2, (n - 2000, 3))])
+    if case == 'cluster':                                                    # 15 000 points in one cell of the 1024^3 lattice
+        c = np.array([0.3, 0.3, 0.3])
+        ref = np.concatenate([c + rng.uniform(-1e-6, 1e-6, (15000, 3)), rng.uniform(-1000, 1000, (5000, 3))])[rng.permutation(n)]
+        lo, side = ref.min(0), np.ptp(ref, 0)                                # k_nn_morton's lattice over the box of the references
+        cell = np.floor(np.clip((ref - lo) * (1024.0 / side), 0.0, 1023.0))
+        assert len(np.unique(cell[np.abs(ref - c).max(1) <= 1e-6], axis=0)) == 1 and len(np.unique(cell, axis=0)) > 4000
+        # half of the queries near the cluster (inside it and about it, a ten-thousandth of a cell away), half uniform
+        near = np.concatenate([c + rng.uniform(-2e-6, 2e-6, (n // 4, 3)), c + rng.normal(0, 2e-4, (n // 4, 3))])
+        return ref, np.concatenate([near, rng.uniform(-1000, 1000, (n // 2, 3))])
+    if case == 'line':                                                       # leaf boxes are thin diagonal slivers
+        t = rng.uniform(-2, 2, n)
+        ref = np.array([0.1, -0.2, 0.3]) + t[:, None] * np.array([1.0, 0.5, -0.25])
+        return ref, rng.uniform(-2, 2, (n, 3))
+    if case == 'plane':                                                      # z = const exactly: leaf boxes of zero thickness
+        ref = np.concatenate([rng.uniform(-2, 2, (n, 2)), np.full((n, 1), 0.375)], 1)
+        q = rng.uniform(-2, 2, (n, 3))
+        q[np.abs(q[:, 2] - 0.375) < 1e-3, 2] += 0.01                         # every query off the plane
+        return ref, q
+    raise KeyError(case)
+
+
+@pytest.mark.parametrize('sort_queries', [True, False])
+@pytest.mark.parametrize('case', ['duplicates', 'cluster', 'line', 'plane'])
+def test_nn_adversarial_clouds(case, sort_queries):
+    ref, q = adversarial_cloud(case)
+    d, i, rd = check_nn(ref, q, sort_queries=sort_queries)
+    if case == 'duplicates':
+        assert (d[:2000] == 0).all() and (ref[i[:10]] == q[:10]).all()       # the point itself; any of its copies will do
+    if case == 'line':
+        assert (d > 0).all()
+    if case == 'plane':
+        assert (d >= 1e-3).all()
+
+
+@pytest.mark.parametrize('sort_queries', [True, False])
+def test_nn_cluster_radius(sort_queries):
+    ref, q = adversarial_cloud('cluster')
+    _, i, _ = check_nn(ref, q, radius=50.0, sort_queries=sort_queries)
+    assert (i[:10000] >= 0).all() and (i[10000:] >= 0).any() and (i[10000:] < 0).any()
+
+
+@pytest.mark.parametrize('n', [1, 15, 16, 17, 31, 32, 33, 16 * 1024 + 1])
+def test_nn_reference_counts(n):
+    """Around one and two leaves of ADFP_NN_LEAF = 16 points, and one point more than a full last level of 1024 leaves."""
+    rng = np.random.default_rng(100 + n)
+    ref, q = rng.uniform(-1, 1, (n, 3)), rng.uniform(-1.2, 1.2, (1000, 3))
+    for sort_queries in (True, False):
+        check_nn(ref, q, sort_queries=sort_queries)
+
+
 def test_nn_transform_on_the_fly():
     rng = np.random.default_rng(2)
     ref, q = rng.random((5000, 3)), rng.random((4000, 3))
