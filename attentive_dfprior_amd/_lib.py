@@ -375,6 +375,12 @@ SYMBOLS = [
     ('adfp_frame_metrics_windows', C.c_int, [C.POINTER(AdfpMetricsGeom), C.POINTER(C.c_longlong)]),
     ('adfp_frame_metrics', C.c_int, [C.POINTER(AdfpMetricsGeom), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
+    # TSDF raycast
+    ('adfp_tsdf_bricks_bytes', C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ('adfp_tsdf_bricks_build', C.c_int, [C.POINTER(AdfpTsdf), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ('adfp_tsdf_raycast', C.c_int, [C.POINTER(AdfpTsdf), C.POINTER(Bound), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
 ]
 
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER
@@ -387,6 +393,7 @@ CULL = {'none': 0, 'back': 1, 'front': 2}     # ADFP_CULL_NONE / ADFP_CULL_BACK 
 UNIT_VOXELS = 16                        # ADFP_UNIT_VOXELS
 SEEN_RULE = {'frustum': 0, 'max_depth': 1, 'depth_test': 2}     # ADFP_SEEN_FRUSTUM / _MAX_DEPTH / _DEPTH_TEST
 BOUND_MAX_DIRECTIONS = 1024             # ADFP_BOUND_MAX_DIRECTIONS
+CAST_NO_SKIP = 1                       # ADFP_CAST_NO_SKIP
 LABEL_ROUNDS_MAX = 128                # above the worst case of adfp_mesh_face_labels_rounds (2 log2(F) + 2 < 66)
 
 _lib = None

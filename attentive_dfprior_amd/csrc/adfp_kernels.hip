@@ -4271,3 +4271,6 @@ int adfp_bound_points(const float* depth, const float* poses, long long K, int H
 
 // ---- rendering metrics (adfp_metrics.h) ----
 #include "adfp_metrics.h"
+
+// ---- TSDF raycast (adfp_tsdfcast.h) ----
+#include "adfp_tsdfcast.h"

@@ -2,7 +2,11 @@
 papers of this family of methods report.  The reference has no counterpart (it publishes no render-quality figure).
 
     python -m attentive_dfprior_amd.render_eval CONFIG [--input_folder ..] [--output ..] [--ckpt PATH] [--every N] [--gt_pose]
-                                                       [--tsdf_volume PATH --tsdf_bounds PATH]
+                                                       [--tsdf_volume PATH --tsdf_bounds PATH] [--guide sensor|tsdf]
+
+--guide tsdf renders every frame as a NOVEL view (Renderer.render_novel: the raycast of the TSDF prior takes the sensor depth
+image's place as the sampler's guide), scores it against the same ground truth and writes eval_render_tsdf_guide.json beside
+eval_render.json: the difference is what the rendering metrics owe to the sensor's depth guide.
 
 Each chosen frame is rendered with Renderer.render_img and handed, still on the device, to adfp_frame_metrics
 (csrc/adfp_metrics.h), which writes one row of 35 doubles into a device table; the table comes down once, at the end.
@@ -143,19 +147,23 @@ def newest_checkpoint(output):
     return paths[-1]
 
 
-def eval_render(cfg, args, ckpt, every=5, gt_pose=False, levels=None, device='cuda:0'):
+def eval_render(cfg, args, ckpt, every=5, gt_pose=False, levels=None, device='cuda:0', guide='sensor'):
     """Renders frames 0, every, 2 every, ... <= idx of a checkpoint and returns (summary, per-frame dict of lists, frame indices).
 
     cfg: the loaded config; args: input_folder / tsdf_volume / tsdf_bounds (paths or None); ckpt: the dict src/utils/Logger.py
     saves, or its path.  The decoders come from get_model, the bound is built the way get_tsdf.init_tsdf_volume builds it, the
     camera is get_tsdf.update_cam's and the frames are datasets.get_dataset(...).frames(...) in chunks.  The pose is the estimated
     one, or the ground-truth one with gt_pose; frames whose ground-truth pose holds a non-finite entry are skipped, as
-    eval_ate.convert_poses skips them.  One synchronisation, at the end."""
+    eval_ate.convert_poses skips them.  One synchronisation, at the end.
+    guide: 'sensor' renders with the frame's depth image as the sampler's guide (render_img); 'tsdf' with the raycast of the TSDF
+    prior instead (render_novel), as a pose without a sensor image would be rendered.  The ground truth is the same."""
     from . import Renderer, get_model
     from .datasets import get_dataset
     from .get_tsdf import update_cam
     if every < 1:
         raise ValueError(f'every {every} must be >= 1')
+    if guide not in ('sensor', 'tsdf'):
+        raise ValueError(f"guide {guide!r}: 'sensor' or 'tsdf'")
     if not isinstance(ckpt, dict):
         ckpt = torch.load(ckpt, map_location='cpu', weights_only=False)
     scale = cfg['scale']
@@ -189,7 +197,10 @@ def eval_render(cfg, args, ckpt, every=5, gt_pose=False, levels=None, device='cu
         colors, depths, _ = frames.frames(chunk)
         for i, gt_color, gt_depth in zip(chunk, colors, depths):
             c2w = torch.as_tensor(poses[i]).to(device=device, dtype=torch.float32)
-            depth, _, color = renderer.render_img(c, decoders, c2w, device, tsdf_volume, tsdf_bnds, stage='color', gt_depth=gt_depth)
+            if guide == 'tsdf':
+                depth, _, color, _ = renderer.render_novel(c, decoders, c2w, device, tsdf_volume, tsdf_bnds, stage='color')
+            else:
+                depth, _, color = renderer.render_img(c, decoders, c2w, device, tsdf_volume, tsdf_bnds, stage='color', gt_depth=gt_depth)
             fm.add(gt_depth, gt_color, depth, color)
     pf = fm.per_frame()                                # the one synchronisation
     summary = {k: (float(np.mean(pf[k])) if chosen else float('nan')) for k in PER_FRAME}
@@ -199,7 +210,7 @@ def eval_render(cfg, args, ckpt, every=5, gt_pose=False, levels=None, device='cu
 
 def main(argv=None):
     """Write {output}/eval_render.json (summary, per-frame lists, frame indices) for the newest checkpoint of a run and print the
-    summary (also returned)."""
+    summary (also returned); with --guide tsdf, {output}/eval_render_tsdf_guide.json."""
     from .get_tsdf import load_config, update_cam
     parser = argparse.ArgumentParser(description='Rendering metrics (PSNR, SSIM, MS-SSIM, depth L1) of a finished run.')
     parser.add_argument('config', type=str, help='YAML config of the scene')
@@ -210,17 +221,21 @@ def main(argv=None):
     parser.add_argument('--gt_pose', action='store_true', help='render from the ground-truth poses instead of the estimated ones')
     parser.add_argument('--tsdf_volume', type=str, help="prior TSDF volume file (default: the checkpoint's)")
     parser.add_argument('--tsdf_bounds', type=str, help='bounds file of the TSDF volume (default: <dataset>_tsdf_volume/<scene>_bounds.pt)')
+    parser.add_argument('--guide', choices=('sensor', 'tsdf'), default='sensor',
+                        help="the sampler's depth guide: the sensor's depth image, or the raycast of the TSDF prior (a novel view)")
     parser.add_argument('--default_config', type=str, default='configs/df_prior.yaml', help='the config every other one inherits from')
     parser.add_argument('--device', type=str, default='cuda:0')
     args = parser.parse_args(argv)
     cfg = load_config(args.config, args.default_config if os.path.exists(args.default_config) else None)
     output = args.output or cfg['data']['output']
     ckpt = args.ckpt or newest_checkpoint(output)
-    summary, frames, indices = eval_render(cfg, args, ckpt, every=args.every, gt_pose=args.gt_pose, device=args.device)
+    summary, frames, indices = eval_render(cfg, args, ckpt, every=args.every, gt_pose=args.gt_pose, device=args.device, guide=args.guide)
     result = {'checkpoint': os.path.basename(ckpt), 'every': args.every, 'gt_pose': bool(args.gt_pose), 'levels': max_levels(*update_cam(cfg)[:2]),
               'summary': summary, 'frames': frames, 'frame_indices': indices}
+    if args.guide == 'tsdf':
+        result['guide'] = 'tsdf'
     os.makedirs(output, exist_ok=True)
-    with open(os.path.join(output, 'eval_render.json'), 'w') as f:
+    with open(os.path.join(output, 'eval_render_tsdf_guide.json' if args.guide == 'tsdf' else 'eval_render.json'), 'w') as f:
         json.dump(result, f, indent=1)
         f.write('\n')
     print(summary)

@@ -10,6 +10,7 @@ same return dtypes -- implemented on the MI355X by libadfp.so.
                    stage, gt_depth) -> (depth f64, uncertainty f64, color, weight[N,S,1])
                                                                                 Renderer.py:110-255
   render_img(c, decoders, c2w, device, tsdf_volume, tsdf_bnds, stage, gt_depth)  Renderer.py:258-327
+  render_novel(c, decoders, c2w, device, tsdf_volume, tsdf_bnds, stage)          not in the reference: a frame without sensor depth
 """
 import torch
 
@@ -305,3 +306,19 @@ class Renderer(object):
             uncertainty = torch.cat(us, dim=0).reshape(H, W)
             color = torch.cat(cs, dim=0).reshape(H, W, 3)
             return depth, uncertainty, color
+
+    def render_novel(self, c, decoders, c2w, device, tsdf_volume, tsdf_bnds, stage):
+        """Not in the reference, whose render_img needs a sensor depth image (Renderer.py:292): a full frame from a pose that has
+        none -> (depth [H,W] f64, uncertainty [H,W] f64, color [H,W,3] f32, guide [H,W] f32).  The guide is the raycast of the
+        TSDF prior (tsdf_raycast.TsdfRaycaster: the first + -> - crossing along every pixel's ray, 0 where there is none) and
+        takes gt_depth's place in render_img: 16 of a ray's samples sit within 5 % of it, and a pixel whose ray meets no surface
+        is sampled like a pixel without sensor depth.  The raycaster shares this Renderer's engine: invalidate_tsdf() drops its
+        empty-space bitmap together with the corner-block copy."""
+        from .tsdf_raycast import TsdfRaycaster
+        rc = getattr(self, '_novel', None)
+        if rc is None or rc.tsdf_volume is not tsdf_volume or rc.tsdf_bnds is not tsdf_bnds:
+            rc = self._novel = TsdfRaycaster(tsdf_volume, tsdf_bnds, engine=self._engine)
+        with torch.no_grad():
+            guide = rc.render_depth(c2w, self.H, self.W, self.fx, self.fy, self.cx, self.cy)
+        depth, uncertainty, color = self.render_img(c, decoders, c2w, device, tsdf_volume, tsdf_bnds, stage, gt_depth=guide)
+        return depth, uncertainty, color, guide

@@ -1198,6 +1198,37 @@ int adfp_frame_metrics_windows(const adfp_metrics_geom* geom, long long windows[
 int adfp_frame_metrics(const adfp_metrics_geom* geom, const float* gt_depth, const void* gt_color, const double* depth,
                        const float* color, double* row /* device [ADFP_FRAME_METRICS] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- TSDF raycast (tsdf_raycast.TsdfRaycaster, Renderer.render_novel: the depth image of the TSDF prior from any pose; no
+ * counterpart in the reference, whose render_img needs a sensor depth image, src/utils/Renderer.py:292) ----
+ * depth [V][H][W] f32: per pixel the z-depth of the first + -> - crossing of the TSDF along the pixel's ray, 0 where there is none
+ * (what the sampler reads as "no sensor depth").  tests/tsdfcast_ref.py states the rule in torch:
+ *   ray      adfp_get_rays' (f32, direction with camera z = -1, so the ray parameter is the sensor depth), promoted to f64.
+ *   interval tn, tf = the slab entry and exit against tsdf_bnds in f64 (an axis with d = 0 only says inside or outside);
+ *            tn = max(tn, near, 0); tf = min(tf, far) when far > 0; tf < tn gives 0.
+ *   march    dt = step / |d| (step in metres); sample k at t_k = tn + k dt, computed and not accumulated, while t_k <= tf; position
+ *            o + d t_k in f64, normalised into tsdf_bnds in f64, then .float(), then the trilinear lookup of adfp_sample_tsdf
+ *            (grid_sample, border padding, align_corners).  tsdf->corner_blocks, when given, is read instead: the same bits.
+ *   hit      the first sample with f <= 0 ends the ray: depth 0 if k = 0 (the ray starts behind a surface), else
+ *            t_{k-1} + dt f_{k-1} / (f_{k-1} - f_k) in f64, stored as f32.  No band test on f_{k-1}: the rule is on interpolated
+ *            values, as KinectFusion's is, so a ray that reaches a surface from behind through unobserved space (f = -1) reports
+ *            a crossing at the truncation boundary.
+ * Empty-space skip: adfp_tsdf_bricks_build writes a bitmap with one bit per brick of 8^3 voxels (brick (bx nby + by) nbz + bz with
+ * nb = ceil(size / 8), 32 per word), set when any voxel of the brick -- padded by one voxel on every side, clipped to the volume --
+ * is not >= 2^-100 (every value <= 0, and NaN).  The march passes over samples whose eight corners are vouched positive without
+ * looking them up; because t_k is computed from k, the image is byte for byte the image with ADFP_CAST_NO_SKIP
+ * (csrc/adfp_tsdfcast.h argues it).  Build the bitmap once per volume and again after the volume changes.
+ * lookups (device, or NULL): the number of trilinear lookups of the call is ADDED to it (a diagnostic: one atomic per pixel).
+ * Asynchronous on `stream`, no allocation, no pointer kept; one launch each.  Errors, all before any launch: ADFP_E_ARG for a null
+ * pointer (bricks may be NULL with ADFP_CAST_NO_SKIP), a size or V, H, W < 1, step <= 0 or NaN, NaN near or far, an empty bound, an
+ * unknown option bit, a bitmap that is unaligned or smaller than adfp_tsdf_bricks_bytes; ADFP_E_UNSUPPORTED for a volume side, H or
+ * W above 32768, V above 65535, or a step below 2^-24 of the bound's diagonal.  adfp_tsdf_bricks_bytes is 0 for a bad size. */
+#define ADFP_CAST_NO_SKIP 1      /* options bit: look every sample up */
+size_t adfp_tsdf_bricks_bytes(int Z, int Y, int X);
+int adfp_tsdf_bricks_build(const adfp_tsdf* tsdf /*host*/, void* bricks, size_t bricks_bytes, void* stream);
+int adfp_tsdf_raycast(const adfp_tsdf* tsdf /*host*/, const double tsdf_bnds[3][2] /*host*/, const void* bricks, size_t bricks_bytes,
+                      const float* c2w /*[V][4][4]*/, int V, int H, int W, float fx, float fy, float cx, float cy, double near, double far,
+                      double step, int options, float* depth /*[V][H][W]*/, unsigned long long* lookups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

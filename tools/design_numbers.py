@@ -297,6 +297,36 @@ def main(template, d):
             b5, b6 = d[('round 5', 'loss.backward()')], d[('round 6', 'loss.backward()')]
             v['host_ab'] = ('`render_batch_ray` forward %.0f → %.0f µs of host time (its share above the allocation-only floor %.0f → %.0f), `loss.backward()` %.0f → %.0f (share %.0f → %.0f)'
                             % (f5[0], f6[0], f5[2], f6[2], b5[0], b6[0], b5[2], b6[2]))
+    # ---- the TSDF raycast (tools/tsdfcast_bench.py)
+    Q = lambda n: os.path.join(os.path.dirname(hp), n)          # (`d` is the host A/B table by now)
+    tp = Q('tsdfcast_bench.json')
+    if os.path.exists(tp):
+        tc = json.load(open(tp))
+        cell3 = lambda s, f='%.2f': (f + ' (' + f + ', ' + f + ')') % (s['median_ms'], s['min_ms'], s['max_ms'])
+        rows, vols, bitmaps, worst, one_sided, samples = [], [], [], 0.0, 0, []
+        for name, sc in tc['scenes'].items():
+            X, Y, Z = sc['volume']
+            vols.append('%s: %d × %d × %d voxels (%.2f GB), %s of %s bricks set, bitmap %.0f KB, built in %s ms.' % (
+                name, X, Y, Z, sc['volume_bytes'] / 1e9, thousands(sc['bricks_set']), thousands(sc['bricks']), sc['bitmap_bytes'] / 1e3,
+                cell3(sc['bricks_build'], '%.3f')))
+            bitmaps.append('%.0f KB for %s' % (sc['bitmap_bytes'] / 1e3, name))
+            for fname, fr in sc['frames'].items():
+                at = fr.get('against_torch', {})
+                worst = max(worst, at.get('max_abs_diff_m', 0.0)); one_sided = max(one_sided, at.get('one_sided_pixels', 0))
+                samples.append(fr['lookups_per_ray_noskip'])
+                rows.append('| %s, %d × %d | %s | %s | %s | %s | %.2f× | %s | %.1f %% of %.0f per ray | %.1f %% |' % (
+                    name, fr['frame'][0], fr['frame'][1], cell3(fr['skip'], '%.3f'), cell3(fr['noskip'], '%.3f'),
+                    cell3(fr['torch'], '%.0f') if 'torch' in fr else 'not measured', cell3(fr['render']), fr['noskip_over_skip'],
+                    ('%.0f×' % fr['torch_over_skip']) if 'torch' in fr else 'not measured', 100 * fr['share_looked_up'], fr['lookups_per_ray_noskip'],
+                    100 * fr['guide_share_of_novel_view']))
+        v['tc_table'] = '\n'.join(rows); v['tc_volumes'] = '  '.join(vols); v['tc_bitmaps'] = 'It is ' + ', '.join(bitmaps)
+        v['tc_reps'] = str(tc['reps']); v['tc_samples'] = '%.0f – %.0f' % (min(samples), max(samples))
+        v['tc_parity'] = 'largest difference where both report a hit %.1e m, at most %d pixels of a frame hit on one side only' % (worst, one_sided)
+    else:                                            # no run of tools/tsdfcast_bench.py is in the collection
+        v['tc_table'] = '| not measured | | | | | | | | |'
+        v['tc_volumes'] = 'No run of `tools/tsdfcast_bench.py` is in `profiles/`: none of these times has been measured.'
+        v['tc_bitmaps'] = 'It is 49 KB for room0 and 93 KB for office0 (one bit per 8³ voxels of 758 × 574 × 451 and 738 × 779 × 656)'
+        v['tc_reps'] = '5'; v['tc_samples'] = 'about 1 300'; v['tc_parity'] = 'not measured'
     s = open(template).read()
     out = re.sub(r'@@(\w+)@@', lambda m: v.get(m.group(1), m.group(0)), s)
     sys.stdout.write(out)
