@@ -3338,6 +3338,17 @@ static int morton_order(const double* p, int n, void* ws, const int** perm, hipS
     return radix_sort_pairs(key, val, key2, val2, n, 30, (int*)w, &kf, perm, st);
 }
 
+// the boxes of an index over the sorted points sp[0, n): leaves of B points each at the nodes [P, 2 P), then every level above
+static int nn_boxes(const double* sp, long long n, int B, long long P, double* box, hipStream_t st) {
+    hipLaunchKernelGGL(k_nn_leaves, dim3((unsigned)((P + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, sp, n, B, P, box);
+    ADFP_CHECK_LAUNCH();
+    for (long long first = P >> 1; first >= 1; first >>= 1) {
+        hipLaunchKernelGGL(k_nn_level, dim3((unsigned)((first + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, first, box);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
 size_t adfp_nn_index_bytes(long long n_ref) { return n_ref <= 0 || n_ref > RECON_MAX_N ? 0 : nn_layout(n_ref).bytes; }
 size_t adfp_nn_build_workspace_bytes(long long n_ref) { return n_ref <= 0 || n_ref > RECON_MAX_N ? 0 : morton_ws_bytes(n_ref); }
 
@@ -3359,13 +3370,7 @@ int adfp_nn_build(const double* ref, long long n_ref, void* index, size_t index_
     const unsigned nb = (unsigned)((n + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS);
     hipLaunchKernelGGL(k_nn_gather, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, ref, n, perm, sp, orig);
     ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_nn_leaves, dim3((unsigned)((L.P + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, sp, n, L.P, box);
-    ADFP_CHECK_LAUNCH();
-    for (long long first = L.P >> 1; first >= 1; first >>= 1) {
-        hipLaunchKernelGGL(k_nn_level, dim3((unsigned)((first + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, first, box);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
+    return nn_boxes(sp, n, ADFP_NN_LEAF, L.P, box, st);
 }
 
 size_t adfp_nn_query_workspace_bytes(long long n_query, int flags) {
@@ -3523,6 +3528,13 @@ static TriLayout tri_layout(long long nf, int leaf) {
     return L;
 }
 
+static TriDev make_tri(const void* bvh, long long n_faces, int leaf) {
+    const TriLayout L = tri_layout(n_faces, leaf);
+    TriDev d; d.tri = (const double*)bvh; d.box = (const double*)((const char*)bvh + L.off_box);
+    d.nf = (int)n_faces; d.leaf = leaf; d.P = L.P; d.D = L.D;
+    return d;
+}
+
 size_t adfp_tri_bvh_bytes(long long n_faces, int leaf) {
     return n_faces <= 0 || n_faces > RECON_MAX_N || !tri_leaf_ok(leaf) ? 0 : tri_layout(n_faces, leaf).bytes;
 }
@@ -3552,14 +3564,7 @@ int adfp_tri_bvh_build(const double* verts, long long n_verts, const int* faces,
     double* box = (double*)((char*)bvh + L.off_box);
     hipLaunchKernelGGL(k_tri_gather, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, verts, nv, faces, nf, perm, tri, orig);
     ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_tri_leaves, dim3((unsigned)((L.P + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, tri, nf,
-                       leaf, L.P, box);
-    ADFP_CHECK_LAUNCH();
-    for (long long first = L.P >> 1; first >= 1; first >>= 1) {
-        hipLaunchKernelGGL(k_nn_level, dim3((unsigned)((first + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, first, box);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
+    return nn_boxes(tri, 3ll * nf, 3 * leaf, L.P, box, st);      // a triangle is three consecutive points
 }
 
 #define RT_MAX_SIDE 32768
@@ -3580,24 +3585,18 @@ static int render_depth_launch(const void* bvh, size_t bvh_bytes, long long n_fa
         hipError_t e = hipMemsetAsync(depth, 0, (size_t)n_views * H * W * sizeof(float), st);
         return e == hipSuccess ? 0 : (int)e;
     }
-    const TriLayout L = tri_layout(n_faces, leaf);
     RenderArgs a;
-    a.tri = (const double*)bvh;
-    a.box = (const double*)((const char*)bvh + L.off_box);
-    a.nf = (int)n_faces; a.leaf = leaf; a.P = L.P; a.D = L.D;
+    a.t = make_tri(bvh, n_faces, leaf);
     a.c2w = c2w; a.near = near; a.far = far;
     a.H = H; a.W = W; a.nbx = (W + 15) / 16; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
     a.depth = depth;
     const unsigned nblk = (unsigned)a.nbx * (unsigned)((H + 15) / 16);
+    void (*const kern)(RenderArgs) = cull == ADFP_CULL_BACK ? k_render_depth<ADFP_CULL_BACK>
+                                     : cull == ADFP_CULL_FRONT ? k_render_depth<ADFP_CULL_FRONT> : k_render_depth<ADFP_CULL_NONE>;
     for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
         const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
         a.view0 = (int)v0;
-        if (cull == ADFP_CULL_BACK)
-            hipLaunchKernelGGL(k_render_depth_cull<ADFP_CULL_BACK>, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
-        else if (cull == ADFP_CULL_FRONT)
-            hipLaunchKernelGGL(k_render_depth_cull<ADFP_CULL_FRONT>, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
-        else
-            hipLaunchKernelGGL(k_render_depth, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
+        hipLaunchKernelGGL(kern, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
         ADFP_CHECK_LAUNCH();
     }
     return 0;
@@ -3644,11 +3643,8 @@ int adfp_points_visible(const void* bvh, size_t bvh_bytes, long long n_faces, in
     if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
     if (n_faces == 0 || n_poses == 0)                     // nothing occludes (or nothing looks): the frustum-only kernel itself
         return adfp_cull_vertices(points, n_points, w2c, n_poses, fx, fy, cx, cy, W, H, seen, stream);
-    const TriLayout L = tri_layout(n_faces, leaf);
     VisibleArgs a;
-    a.tri = (const double*)bvh;
-    a.box = (const double*)((const char*)bvh + L.off_box);
-    a.nf = (int)n_faces; a.leaf = leaf; a.P = L.P; a.D = L.D;
+    a.t = make_tri(bvh, n_faces, leaf);
     a.pts = points; a.n = (int)n_points; a.w2c = w2c; a.c2w = c2w; a.np = (int)n_poses;
     a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H;
     a.near = near; a.eps = eps; a.seen = seen;

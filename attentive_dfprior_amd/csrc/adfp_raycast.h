@@ -3,12 +3,15 @@
 //   triangle BVH (f64)      the NN index's construction over triangles: Morton codes of the centroids (adfp_recon.h's box and
 //                           code kernels, the radix sort), leaves of `leaf` triangles holding their nine vertex coordinates and
 //                           original face indices, an implicit complete binary tree of leaf boxes (padding leaves inverted)
-//   depth render (f64)      one lane per pixel, a wave per 8x8 tile, four tiles per workgroup, views along grid y; the stackless
-//                           trail-bit walk of k_nn_query ordered by entry t; Woop, Benthin & Wald's watertight test in f64
+//   ray (f64)               RtRay, filled from a pose and an image-plane point by rt_ray; rt_box, the slab test against a padded
+//                           box; rt_tri, Woop, Benthin & Wald's watertight test.  Both walks below are adfp_recon.h's bvh_walk
+//                           with a visitor made of these: RtNearest (closed, shrinking bound) and RtAny (open, fixed bound)
+//   depth render (f64)      one lane per pixel, a wave per 8x8 tile, four tiles per workgroup, views along grid y; the walk
+//                           ordered by entry t, the nearest hit
 //   views in sight (f32)    check_proj of eval_recon.py:70-96 for a batch of poses: k_cull_seen's test, a wave ballot per pose
 //                           and one integer atomic OR
 //   points visible          points x poses: k_cull_seen's f32 frustum test per pair, then for the pairs that pass an any-hit shadow
-//                           ray in the renderer's f64 arithmetic (one lane per point, poses through LDS)
+//                           ray in the renderer's f64 arithmetic (one lane per point, poses through LDS), the left child first
 //   depth L1 sums (f64)     per view, sum |a - b| of two f32 depth images, reduced as k_metric_partial / k_red_final do
 //
 // The exact contract (camera, intersection, clipping, pruning) is stated in include/adfp.h; tests/depth_ref.py restates it in numpy.
@@ -53,46 +56,46 @@ __global__ __launch_bounds__(ADFP_NN_THREADS) void k_tri_gather(const double* __
     orig[s] = j;
 }
 
-// leaf j of [0, P): the box of the vertices of sorted triangles [j leaf, min(j leaf + leaf, nf)), inverted when it holds none
-__global__ __launch_bounds__(ADFP_NN_THREADS) void k_tri_leaves(const double* __restrict__ tri, int nf, int leaf, long long P,
-                                                                  double* __restrict__ box) {
-    const long long j = (long long)blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
-    if (j >= P) return;
-    double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    const long long a = j * leaf, e = a + leaf < nf ? a + leaf : nf;
-    for (long long s = a; s < e; ++s) {
-        for (int c = 0; c < 9; ++c) {                      // fmin / fmax drop the NaN of an out-of-range face
-            const double x = tri[9 * s + c];
-            m[c % 3] = fmin(m[c % 3], x);
-            m[3 + c % 3] = fmax(m[3 + c % 3], x);
-        }
-    }
+// where the pieces of a triangle BVH live (the host's make_tri): sorted triangles, node boxes, the leaves [P, 2 P) at depth D
+struct TriDev { const double* tri; const double* box; int nf; int leaf; long long P; int D; };
+
+// the ray o + t Dw, Dw = R (dx, dy, 1), of pose [R | o] through the image-plane point (dx, dy); inv = 1 / Dw, or 0 on an axis the
+// ray is parallel to; pad = what the boxes grow by
+struct RtRay { double R[9], o[3], dx, dy, Dw[3], inv[3], pad; };
+
+// m: 12 f64, [R | o] row-major; rb: the root box (the mesh's)
+ADFP_DEV void rt_ray(RtRay& r, const double* m, double dx, double dy, const double* rb) {
 #pragma unroll
-    for (int c = 0; c < 6; ++c) box[6 * (P + j) + c] = m[c];
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r.R[3 * i + c] = m[4 * i + c];
+        r.o[i] = m[4 * i + 3];
+    }
+    r.dx = dx; r.dy = dy;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double t = (r.R[3 * i] * dx + r.R[3 * i + 1] * dy) + r.R[3 * i + 2];
+        if (fabs(t) < 1e-200) t = 0.0;                       // parallel to the axis: a containment test, never 0 x inf
+        r.Dw[i] = t;
+        r.inv[i] = t != 0.0 ? 1.0 / t : 0.0;
+    }
+    const double M = fmax(fmax(fmax(fabs(rb[0]), fabs(rb[3])), fmax(fabs(rb[1]), fabs(rb[4]))), fmax(fabs(rb[2]), fabs(rb[5])));
+    r.pad = ADFP_RT_BOX_PAD * (M + fmax(fmax(fabs(r.o[0]), fabs(r.o[1])), fabs(r.o[2])));
 }
 
-struct RenderArgs {
-    const double* tri; const double* box; int nf; int leaf; long long P; int D;
-    const double* c2w; const double* near; double far;       // c2w [views][12] (3x4 row-major), near [views]
-    int H, W, nbx; double fx, fy, cx, cy;
-    int view0;                                                // first view of this launch
-    float* depth;                                             // [views][H][W]
-};
-
-// Does the ray o + t D meet box b, grown by pad, at some t in [near, best]?  Inverted boxes never do.  An axis with D = 0 is a
+// Does the ray meet box b, grown by pad, at some t in [near, best]?  Inverted boxes never do.  An axis with Dw = 0 is a
 // containment test (no 0 x inf); elsewhere the slab of each axis is [(lo - o) inv, (hi - o) inv] sorted, with finite factors.
 // *tin = the entry t.  The pad is far above the rounding of both this test and the triangle test (include/adfp.h).
-ADFP_DEV bool rt_box(const double* b, double pad, const double* o, const double* D, const double* inv, double near, double best,
-                     double* tin) {
+ADFP_DEV bool rt_box(const RtRay& r, const double* b, double near, double best, double* tin) {
     if (!(b[0] <= b[3])) return false;
     double tn = -INFINITY, tf = INFINITY;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const double lo = b[c] - pad, hi = b[3 + c] + pad;
-        if (D[c] == 0.0) {
-            if (o[c] < lo || o[c] > hi) return false;
+        const double lo = b[c] - r.pad, hi = b[3 + c] + r.pad;
+        if (r.Dw[c] == 0.0) {
+            if (r.o[c] < lo || r.o[c] > hi) return false;
         } else {
-            const double t0 = (lo - o[c]) * inv[c], t1 = (hi - o[c]) * inv[c];
+            const double t0 = (lo - r.o[c]) * r.inv[c], t1 = (hi - r.o[c]) * r.inv[c];
             tn = fmax(tn, fmin(t0, t1));
             tf = fmin(tf, fmax(t0, t1));
         }
@@ -101,14 +104,77 @@ ADFP_DEV bool rt_box(const double* b, double pad, const double* o, const double*
     return tn <= tf && tn <= best && tf >= near;
 }
 
-// One lane, one pixel (row i, col j) of view p.  d = ((j - cx) / fx, (i - cy) / fy, 1); a vertex goes to camera space as
-// cam_c = ((R0c e0 + R1c e1) + R2c e2), e = v - o; the shear A' = (Ax - dx Az, Ay - dy Az); U = Cx By - Cy Bx, V = Ax Cy - Ay Cx,
-// W = Bx Ay - By Ax; a miss when their signs are mixed or det = (U + V) + W is 0; z = ((U Az + V Bz) + W Cz) / det; the depth is
-// the least z with near <= z <= far, rounded to f32, or 0.  CULL (ADFP_CULL_*): BACK keeps only hits with det > 0, FRONT only hits
-// with det < 0 (det = -(n . R d), n = (v1 - v0) x (v2 - v0): det > 0 is a face whose normal points toward the camera); the culled
-// modes write 0 for a view whose pose holds a non-finite entry.  CULL = NONE is k_render_depth, instruction for instruction.
+// Does the ray's line meet triangle t (v0, v1, v2)?  A vertex goes to camera space as cam_c = ((R0c e0 + R1c e1) + R2c e2),
+// e = v - o; the shear A' = (Ax - dx Az, Ay - dy Az); U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax; a miss when their
+// signs are mixed or det = (U + V) + W is 0; *z = ((U Az + V Bz) + W Cz) / det, NaN for an out-of-range face: it fails the caller's
+// range test.  CULL (ADFP_CULL_*): BACK keeps only det > 0, FRONT only det < 0 (det = -(n . R d), n = (v1 - v0) x (v2 - v0):
+// det > 0 is a face whose normal points toward the camera).
 template <int CULL>
-ADFP_DEV void render_depth_body(const RenderArgs& a) {
+ADFP_DEV bool rt_tri(const RtRay& r, const double* t, double* z) {
+    double cam[9];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const double e0 = t[3 * q] - r.o[0], e1 = t[3 * q + 1] - r.o[1], e2 = t[3 * q + 2] - r.o[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cam[3 * q + c] = (r.R[c] * e0 + r.R[3 + c] * e1) + r.R[6 + c] * e2;
+    }
+    const double Ax = cam[0] - r.dx * cam[2], Ay = cam[1] - r.dy * cam[2];
+    const double Bx = cam[3] - r.dx * cam[5], By = cam[4] - r.dy * cam[5];
+    const double Cx = cam[6] - r.dx * cam[8], Cy = cam[7] - r.dy * cam[8];
+    const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) return false;
+    const double det = (U + V) + W;
+    if (det == 0.0) return false;
+    if (CULL == ADFP_CULL_BACK && !(det > 0.0)) return false;
+    if (CULL == ADFP_CULL_FRONT && !(det < 0.0)) return false;
+    *z = ((U * cam[2] + V * cam[5]) + W * cam[8]) / det;
+    return true;
+}
+
+// bvh_walk's visitor for the nearest hit: the least z in [near, best], best shrinking with every hit (a closed bound: an equal
+// z is a hit again, and a box entered exactly at best is still walked)
+template <int CULL>
+struct RtNearest {
+    const RtRay& r; const TriDev& t; double near, best; bool found;
+    ADFP_DEV bool enter(const double* b, double* tin) { return rt_box(r, b, near, best, tin); }
+    ADFP_DEV bool leaf(long long j) {
+        const long long s0 = j * t.leaf, s1 = s0 + t.leaf < t.nf ? s0 + t.leaf : t.nf;
+        for (long long s = s0; s < s1; ++s) {
+            double z;
+            if (rt_tri<CULL>(r, t.tri + 9 * s, &z) && z >= near && z <= best) { best = z; found = true; }
+        }
+        return false;
+    }
+};
+
+// bvh_walk's visitor for a shadow ray: is there any hit (back faces included) with near <= z < best?  The bound is open and fixed,
+// so a box entered at or beyond it is pruned too, and the first hit ends the walk: existence over a set does not depend on order
+struct RtAny {
+    const RtRay& r; const TriDev& t; double near, best;
+    ADFP_DEV bool enter(const double* b, double* tin) { return rt_box(r, b, near, best, tin) && *tin < best; }
+    ADFP_DEV bool leaf(long long j) {
+        const long long s0 = j * t.leaf, s1 = s0 + t.leaf < t.nf ? s0 + t.leaf : t.nf;
+        for (long long s = s0; s < s1; ++s) {
+            double z;
+            if (rt_tri<ADFP_CULL_NONE>(r, t.tri + 9 * s, &z) && z >= near && z < best) return true;
+        }
+        return false;
+    }
+};
+
+struct RenderArgs {
+    TriDev t;
+    const double* c2w; const double* near; double far;       // c2w [views][12] (3x4 row-major), near [views]
+    int H, W, nbx; double fx, fy, cx, cy;
+    int view0;                                                // first view of this launch
+    float* depth;                                             // [views][H][W]
+};
+
+// One lane, one pixel (row i, col j) of view p: the ray through d = ((j - cx) / fx, (i - cy) / fy, 1); the depth is the least z of
+// a hit (rt_tri<CULL>) with near <= z <= far, rounded to f32, or 0.  The culled modes write 0 for a view whose pose holds a
+// non-finite entry.
+template <int CULL>
+__global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int bx = (int)(blockIdx.x % (unsigned)a.nbx), by = (int)(blockIdx.x / (unsigned)a.nbx);
     const int col = bx * 16 + (w & 1) * 8 + (lane & 7);
@@ -116,94 +182,19 @@ ADFP_DEV void render_depth_body(const RenderArgs& a) {
     if (row >= a.H || col >= a.W) return;                   // no barrier below
     const long long p = (long long)a.view0 + blockIdx.y;
     const double* m = a.c2w + 12 * p;
+    float* out = a.depth + (p * a.H + row) * (long long)a.W + col;
     if (CULL != ADFP_CULL_NONE) {                           // uniform over the workgroup: one view per grid row
         bool fin = true;
 #pragma unroll
         for (int e = 0; e < 12; ++e) fin = fin && isfinite(m[e]);
-        if (!fin) { a.depth[(p * a.H + row) * (long long)a.W + col] = 0.f; return; }
+        if (!fin) { *out = 0.f; return; }
     }
-    double R[9], o[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) R[3 * r + c] = m[4 * r + c];
-        o[r] = m[4 * r + 3];
-    }
-    const double near = a.near[p], far = a.far;
-    const double dx = ((double)col - a.cx) / a.fx, dy = ((double)row - a.cy) / a.fy;
-    double Dw[3], inv[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        double t = (R[3 * r] * dx + R[3 * r + 1] * dy) + R[3 * r + 2];
-        if (fabs(t) < 1e-200) t = 0.0;                       // parallel to the axis: a containment test, never 0 x inf
-        Dw[r] = t;
-        inv[r] = t != 0.0 ? 1.0 / t : 0.0;
-    }
-    const double* rb = a.box + 6;                           // the root: the mesh's box
-    const double M = fmax(fmax(fmax(fabs(rb[0]), fabs(rb[3])), fmax(fabs(rb[1]), fabs(rb[4]))), fmax(fabs(rb[2]), fabs(rb[5])));
-    const double pad = ADFP_RT_BOX_PAD * (M + fmax(fmax(fabs(o[0]), fabs(o[1])), fabs(o[2])));
-    double best = far;
-    bool found = false;
-    unsigned long long k = 1;
-    int depth = 0;
-    unsigned trail = 0;
-    double tin;
-    bool alive = a.nf > 0 && rt_box(rb, pad, o, Dw, inv, near, best, &tin);
-    while (alive) {
-        bool up = true;
-        if (depth == a.D) {                                  // a leaf: test its triangles
-            const long long s0 = (long long)(k - (unsigned long long)a.P) * a.leaf;
-            const long long s1 = s0 + a.leaf < a.nf ? s0 + a.leaf : a.nf;
-            for (long long s = s0; s < s1; ++s) {
-                const double* t = a.tri + 9 * s;
-                double cam[9];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const double e0 = t[3 * q] - o[0], e1 = t[3 * q + 1] - o[1], e2 = t[3 * q + 2] - o[2];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) cam[3 * q + c] = (R[c] * e0 + R[3 + c] * e1) + R[6 + c] * e2;
-                }
-                const double Ax = cam[0] - dx * cam[2], Ay = cam[1] - dy * cam[2];
-                const double Bx = cam[3] - dx * cam[5], By = cam[4] - dy * cam[5];
-                const double Cx = cam[6] - dx * cam[8], Cy = cam[7] - dy * cam[8];
-                const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-                if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) continue;
-                const double det = (U + V) + W;
-                if (det == 0.0) continue;
-                if (CULL == ADFP_CULL_BACK && !(det > 0.0)) continue;
-                if (CULL == ADFP_CULL_FRONT && !(det < 0.0)) continue;
-                const double z = ((U * cam[2] + V * cam[5]) + W * cam[8]) / det;
-                if (z >= near && z <= best) { best = z; found = true; }     // NaN (an out-of-range face) fails here
-            }
-        } else {
-            double t0, t1;
-            const bool h0 = rt_box(a.box + 12 * k, pad, o, Dw, inv, near, best, &t0);
-            const bool h1 = rt_box(a.box + 12 * k + 6, pad, o, Dw, inv, near, best, &t1);
-            if (h0 || h1) {
-                const bool first = h0 && (!h1 || t0 <= t1);
-                k = 2 * k + (first ? 0 : 1);
-                ++depth;
-                const bool other = first ? h1 : h0;
-                trail = other ? (trail & ~(1u << depth)) : (trail | (1u << depth));
-                up = false;
-            }
-        }
-        if (up) {
-            for (;;) {
-                while (depth > 0 && ((trail >> depth) & 1u)) { k >>= 1; --depth; }
-                if (depth == 0) { alive = false; break; }
-                k ^= 1ull;
-                trail |= 1u << depth;
-                if (rt_box(a.box + 6 * k, pad, o, Dw, inv, near, best, &tin)) break;
-            }
-        }
-    }
-    a.depth[(p * a.H + row) * (long long)a.W + col] = found ? (float)best : 0.f;
+    RtRay r;
+    rt_ray(r, m, ((double)col - a.cx) / a.fx, ((double)row - a.cy) / a.fy, a.t.box + 6);
+    RtNearest<CULL> v = {r, a.t, a.near[p], a.far, false};
+    if (a.t.nf > 0) bvh_walk<true>(a.t.box, a.t.P, a.t.D, v);
+    *out = v.found ? (float)v.best : 0.f;
 }
-
-__global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) { render_depth_body<ADFP_CULL_NONE>(a); }
-template <int CULL>
-__global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth_cull(RenderArgs a) { render_depth_body<CULL>(a); }
 
 // any[p] |= 1 iff pose p projects some point into the image (k_cull_seen's f32 test, cull_mesh.py:49-71 = eval_recon.py:70-96);
 // any[] is zeroed by the entry before the launch
@@ -234,7 +225,7 @@ __global__ __launch_bounds__(ADFP_NN_THREADS) void k_views_in_sight(SightArgs a)
 
 // ---- occlusion-aware visibility: points x poses ----
 struct VisibleArgs {
-    const double* tri; const double* box; int nf; int leaf; long long P; int D;
+    TriDev t;
     const double* pts; int n;                                 // [n][3] f64
     const float* w2c; const double* c2w; int np;              // [np][12] f32 (k_cull_seen's rows) / [np][12] f64 (k_render_depth's rows)
     float fx, fy, cx, cy, W, H;
@@ -242,100 +233,26 @@ struct VisibleArgs {
     unsigned char* seen;                                      // [n]
 };
 
-// rt_box for the shadow ray: the bound is open (a hit needs z < best), so a box entered at or beyond it is pruned too
-ADFP_DEV bool vis_box(const double* b, double pad, const double* o, const double* D, const double* inv, double near, double best) {
-    double tin;
-    return rt_box(b, pad, o, D, inv, near, best, &tin) && tin < best;
-}
-
 // Does pose m (12 f64, [R | o] row-major, here in LDS) see the point p unoccluded?  p goes to camera space as a mesh vertex does;
 // z_p = cam z; not seen when m holds a non-finite entry, when z_p <= 0 or is not finite, or when d = (cam x / z_p, cam y / z_p)
-// is not finite.  Else the ray o + t R (d, 1) is walked as render_depth_body walks a pixel's, with the bound fixed at
-// best = z_p - eps: occluded iff some triangle is hit (that body's test, back faces included) at near <= z < best.  The walk
-// leaves at the first such hit; existence over a set does not depend on the order.
+// is not finite.  Else occluded iff the ray through d has a hit (RtAny) at near <= z < z_p - eps.
 ADFP_DEV bool vis_unoccluded(const VisibleArgs& a, const double* m, double px, double py, double pz) {
     bool fin = true;
 #pragma unroll
     for (int e = 0; e < 12; ++e) fin = fin && isfinite(m[e]);
     if (!fin) return false;
-    double R[9], o[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) R[3 * r + c] = m[4 * r + c];
-        o[r] = m[4 * r + 3];
-    }
-    const double e0 = px - o[0], e1 = py - o[1], e2 = pz - o[2];
+    const double e0 = px - m[3], e1 = py - m[7], e2 = pz - m[11];
     double pc[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) pc[c] = (R[c] * e0 + R[3 + c] * e1) + R[6 + c] * e2;
+    for (int c = 0; c < 3; ++c) pc[c] = (m[c] * e0 + m[4 + c] * e1) + m[8 + c] * e2;
     const double zp = pc[2];
     if (!(zp > 0.0) || !isfinite(zp)) return false;
     const double dx = pc[0] / zp, dy = pc[1] / zp;
     if (!isfinite(dx) || !isfinite(dy)) return false;
-    const double near = a.near, best = zp - a.eps;
-    double Dw[3], inv[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        double t = (R[3 * r] * dx + R[3 * r + 1] * dy) + R[3 * r + 2];
-        if (fabs(t) < 1e-200) t = 0.0;
-        Dw[r] = t;
-        inv[r] = t != 0.0 ? 1.0 / t : 0.0;
-    }
-    const double* rb = a.box + 6;
-    const double M = fmax(fmax(fmax(fabs(rb[0]), fabs(rb[3])), fmax(fabs(rb[1]), fabs(rb[4]))), fmax(fabs(rb[2]), fabs(rb[5])));
-    const double pad = ADFP_RT_BOX_PAD * (M + fmax(fmax(fabs(o[0]), fabs(o[1])), fabs(o[2])));
-    bool hit = false;
-    unsigned long long k = 1;
-    int depth = 0;
-    unsigned trail = 0;
-    bool alive = vis_box(rb, pad, o, Dw, inv, near, best);
-    while (alive) {
-        bool up = true;
-        if (depth == a.D) {                                  // a leaf: any qualifying triangle ends the walk
-            const long long s0 = (long long)(k - (unsigned long long)a.P) * a.leaf;
-            const long long s1 = s0 + a.leaf < a.nf ? s0 + a.leaf : a.nf;
-            for (long long s = s0; s < s1; ++s) {
-                const double* t = a.tri + 9 * s;
-                double cam[9];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const double f0 = t[3 * q] - o[0], f1 = t[3 * q + 1] - o[1], f2 = t[3 * q + 2] - o[2];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) cam[3 * q + c] = (R[c] * f0 + R[3 + c] * f1) + R[6 + c] * f2;
-                }
-                const double Ax = cam[0] - dx * cam[2], Ay = cam[1] - dy * cam[2];
-                const double Bx = cam[3] - dx * cam[5], By = cam[4] - dy * cam[5];
-                const double Cx = cam[6] - dx * cam[8], Cy = cam[7] - dy * cam[8];
-                const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-                if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) continue;
-                const double det = (U + V) + W;
-                if (det == 0.0) continue;
-                const double z = ((U * cam[2] + V * cam[5]) + W * cam[8]) / det;
-                if (z >= near && z < best) { hit = true; break; }           // NaN (an out-of-range face) fails here
-            }
-            if (hit) break;
-        } else {
-            const bool h0 = vis_box(a.box + 12 * k, pad, o, Dw, inv, near, best);
-            const bool h1 = vis_box(a.box + 12 * k + 6, pad, o, Dw, inv, near, best);
-            if (h0 || h1) {                                  // any hit will do: the left child first
-                k = 2 * k + (h0 ? 0 : 1);
-                ++depth;
-                trail = h0 && h1 ? (trail & ~(1u << depth)) : (trail | (1u << depth));
-                up = false;
-            }
-        }
-        if (up) {
-            for (;;) {
-                while (depth > 0 && ((trail >> depth) & 1u)) { k >>= 1; --depth; }
-                if (depth == 0) { alive = false; break; }
-                k ^= 1ull;
-                trail |= 1u << depth;
-                if (vis_box(a.box + 6 * k, pad, o, Dw, inv, near, best)) break;
-            }
-        }
-    }
-    return !hit;
+    RtRay r;
+    rt_ray(r, m, dx, dy, a.t.box + 6);
+    RtAny v = {r, a.t, a.near, zp - a.eps};
+    return !bvh_walk<false>(a.t.box, a.t.P, a.t.D, v);
 }
 
 // seen[i] = 1 iff some pose k has point i in its frustum (cull_sees on the f32 rounding of the point: k_cull_seen's test) and sees

@@ -120,12 +120,14 @@ __global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_gather(const double* __r
     orig[i] = j;
 }
 
-// leaf j of [0, P): the box of sorted points [j B, min(j B + B, n)), inverted when empty; written at node P + j
-__global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_leaves(const double* __restrict__ sp, int n, long long P, double* __restrict__ box) {
+// leaf j of [0, P): the box of sorted points [j B, min(j B + B, n)), inverted when empty; written at node P + j.  fmin / fmax drop a
+// NaN coordinate.  A triangle index calls it on its 3 nf vertices with B = 3 leaf.
+__global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_leaves(const double* __restrict__ sp, long long n, int B, long long P,
+                                                                double* __restrict__ box) {
     const long long j = (long long)blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
     if (j >= P) return;
     double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    const long long a = j * ADFP_NN_LEAF, e = a + ADFP_NN_LEAF < n ? a + ADFP_NN_LEAF : n;
+    const long long a = j * B, e = a + B < n ? a + B : n;
     for (long long s = a; s < e; ++s) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -150,6 +152,48 @@ __global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_level(long long first, d
     }
 }
 
+// The stackless walk of an implicit tree of boxes (the root is node 1, the leaves are the nodes [P, 2 P) at depth D), shared by
+// the NN query and the two ray walks of adfp_raycast.h.  The visitor says what a box and a leaf mean:
+//   v.enter(box6, &key) -> bool   may the walk enter this box, by the visitor's bound as it stands now; key orders two children
+//   v.leaf(j) -> bool             visit leaf j of [0, P); true ends the walk (any-hit), and bvh_walk returns true
+// `trail` bit d = the sibling of the current node at depth d is done (visited or pruned).  Descend into an enterable child, of two
+// the one with the smaller key when ORDERED (the left one on a tie, and always when not); on the way up, climb past every level
+// whose bit is set, then step to the sibling and test its box again, against the bound the visitor has reached by then.
+template <bool ORDERED, class V>
+ADFP_DEV bool bvh_walk(const double* box, long long P, int D, V& v) {
+    unsigned long long k = 1;
+    int depth = 0;
+    unsigned trail = 0;
+    double key0, key1;
+    bool alive = v.enter(box + 6, &key0);
+    while (alive) {
+        bool up = true;
+        if (depth == D) {
+            if (v.leaf((long long)(k - (unsigned long long)P))) return true;
+        } else {
+            const bool h0 = v.enter(box + 12 * k, &key0);          // children 2k and 2k + 1 are adjacent
+            const bool h1 = v.enter(box + 12 * k + 6, &key1);
+            if (h0 || h1) {
+                const bool first = h0 && (!ORDERED || !h1 || key0 <= key1);
+                k = 2 * k + (first ? 0 : 1);
+                ++depth;
+                trail = h0 && h1 ? (trail & ~(1u << depth)) : (trail | (1u << depth));
+                up = false;
+            }
+        }
+        if (up) {
+            for (;;) {
+                while (depth > 0 && ((trail >> depth) & 1u)) { k >>= 1; --depth; }
+                if (depth == 0) { alive = false; break; }
+                k ^= 1ull;
+                trail |= 1u << depth;
+                if (v.enter(box + 6 * k, &key0)) break;
+            }
+        }
+    }
+    return false;
+}
+
 struct NnQueryArgs {
     const double* sp; const int* orig; const double* box; int n_ref; long long P; int D;
     const double* q; int nq; const int* order;            // order: lane i takes query order[i] (Morton order), or NULL
@@ -158,9 +202,22 @@ struct NnQueryArgs {
     double* dist; int* idx;
 };
 
-// One lane, one query.  Walks the implicit tree without a stack: `trail` bit d = the sibling of the current node at depth d is
-// done (visited or pruned); descend into the nearer child first, prune a box whose squared distance is >= the best so far;
-// on the way up, climb past every level whose bit is set, then step to the sibling and re-test its box against the best.
+// the nearest point so far: a box is entered while its squared distance is below `best`, the nearer child first
+struct NnNearest {
+    const double* sp; int n_ref; double x, y, z, best; long long bi;
+    ADFP_DEV bool enter(const double* b, double* d2) { *d2 = nn_box_d2(b, x, y, z); return *d2 < best; }
+    ADFP_DEV bool leaf(long long j) {
+        const long long s0 = j * ADFP_NN_LEAF, s1 = s0 + ADFP_NN_LEAF < n_ref ? s0 + ADFP_NN_LEAF : n_ref;
+        for (long long s = s0; s < s1; ++s) {
+            const double dx = sp[3 * s] - x, dy = sp[3 * s + 1] - y, dz = sp[3 * s + 2] - z;
+            const double d = (dx * dx + dy * dy) + dz * dz;
+            if (d < best) { best = d; bi = s; }
+        }
+        return false;
+    }
+};
+
+// One lane, one query: bvh_walk with the NnNearest visitor
 __global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_query(NnQueryArgs a) {
     const int i = blockIdx.x * ADFP_NN_THREADS + threadIdx.x;
     if (i >= a.nq) return;
@@ -172,46 +229,10 @@ __global__ __launch_bounds__(ADFP_NN_THREADS) void k_nn_query(NnQueryArgs a) {
         const double tz = ((a.t[8] * x + a.t[9] * y) + a.t[10] * z) + a.t[11];
         x = tx; y = ty; z = tz;
     }
-    double best = a.best0;
-    long long bi = -1;
-    unsigned long long k = 1;
-    int depth = 0;
-    unsigned trail = 0;
-    bool alive = nn_box_d2(a.box + 6, x, y, z) < best;
-    while (alive) {
-        bool up = true;
-        if (depth == a.D) {                                          // a leaf: scan its points
-            const long long s0 = (long long)(k - (unsigned long long)a.P) * ADFP_NN_LEAF;
-            const long long s1 = s0 + ADFP_NN_LEAF < a.n_ref ? s0 + ADFP_NN_LEAF : a.n_ref;
-            for (long long s = s0; s < s1; ++s) {
-                const double dx = a.sp[3 * s] - x, dy = a.sp[3 * s + 1] - y, dz = a.sp[3 * s + 2] - z;
-                const double d = (dx * dx + dy * dy) + dz * dz;
-                if (d < best) { best = d; bi = s; }
-            }
-        } else {
-            const double d0 = nn_box_d2(a.box + 12 * k, x, y, z);
-            const double d1 = nn_box_d2(a.box + 12 * k + 6, x, y, z);
-            const bool first = d0 <= d1;
-            const double dn = first ? d0 : d1, df = first ? d1 : d0;
-            if (dn < best) {
-                k = 2 * k + (first ? 0 : 1);
-                ++depth;
-                trail = df < best ? (trail & ~(1u << depth)) : (trail | (1u << depth));
-                up = false;
-            }
-        }
-        if (up) {
-            for (;;) {
-                while (depth > 0 && ((trail >> depth) & 1u)) { k >>= 1; --depth; }
-                if (depth == 0) { alive = false; break; }
-                k ^= 1ull;
-                trail |= 1u << depth;
-                if (nn_box_d2(a.box + 6 * k, x, y, z) < best) break;
-            }
-        }
-    }
-    a.dist[qi] = bi >= 0 ? sqrt(best) : INFINITY;
-    a.idx[qi] = bi >= 0 ? a.orig[bi] : -1;
+    NnNearest v = {a.sp, a.n_ref, x, y, z, a.best0, -1};
+    bvh_walk<true>(a.box, a.P, a.D, v);
+    a.dist[qi] = v.bi >= 0 ? sqrt(v.best) : INFINITY;
+    a.idx[qi] = v.bi >= 0 ? a.orig[v.bi] : -1;
 }
 
 // ---- deterministic f64 reductions ----

@@ -833,8 +833,8 @@ int adfp_tri_bvh_build(const double* verts, long long n_verts, const int* faces,
  *     force over all faces bit for bit (tests/depth_ref.py), two runs give the same bits.
  *   Pruning is conservative: every box tested is first grown by 2^-24 (max |coordinate| of the mesh's box + max |o|), a margin
  *     far above the rounding of both the slab test and the triangle test, so boxes of zero thickness keep a width; an axis along
- *     which R d is 0 (|R d| < 1e-200) is a containment test instead of a slab, so no 0 x inf arises.  The walk is k_nn_query's
- *     stackless trail-bit walk: the child with the smaller entry t first, a box pruned when its entry t exceeds the best z or its
+ *     which R d is 0 (|R d| < 1e-200) is a containment test instead of a slab, so no 0 x inf arises.  The walk is the stackless
+ *     trail-bit walk that k_nn_query runs (bvh_walk, csrc/adfp_recon.h): the child with the smaller entry t first, a box pruned when its entry t exceeds the best z or its
  *     exit t lies below near.
  * n_faces = 0 writes zeros (bvh, c2w and near may be NULL); n_views = 0 does nothing.  far must be positive and finite, fx, fy
  * nonzero; H, W in [1, 32768]. */

@@ -1,4 +1,4 @@
-"""GPU: the two ray walks over the triangle BVH (render_depth_body, vis_unoccluded in csrc/adfp_raycast.h) on the triangle soups of
+"""GPU: the two ray walks over the triangle BVH (bvh_walk under RtNearest and RtAny in csrc/adfp_raycast.h) on the triangle soups of
 tests/soup_meshes.py, against the brute-force numpy oracles bit for bit: triangles of every size, leaf boxes that cover the whole
 soup, dozens of surfaces along a ray, more copies of a triangle than a leaf holds, zero-thickness boxes seen edge on, a soup
 3 000 units from the origin, and face counts around every full and nearly empty last level.  On the room meshes of the other tests
