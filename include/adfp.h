@@ -499,7 +499,7 @@ int adfp_prefilter_mask(const float* rays_o, const float* rays_d, const float* g
 /* The Mapper's loss (src/Mapper.py:457-469) and its cotangents w.r.t. the renderer's outputs:
  *   sum_{gt_depth > 0} |gt_depth - depth|  [+ sum |weight - 1| when `warmup`]  [+ w_color_loss * sum |gt_color - color| in stage color]
  * g_* = d loss / d output (sign functions, 0 at 0 like torch.abs's backward), zero for rays with keep == 0.
- * loss (device double, may be NULL) is ACCUMULATED: zero it first. */
+ * loss (device double, REQUIRED: a NULL loss is ADFP_E_ARG) is ACCUMULATED by adfp_mapper_loss: zero it first. */
 typedef struct adfp_loss_args {
     int n_rays, S;
     int stage;                   /* ADFP_STAGE_*; the colour term exists in stage color only */
@@ -511,7 +511,7 @@ typedef struct adfp_loss_args {
     const float* gt_depth;       /* [N]   */
     const float* gt_color;       /* [N,3] (stage color) */
     const unsigned char* keep;   /* [N] or NULL */
-    double* loss;                /* device double or NULL */
+    double* loss;                /* device double, required */
     double* g_depth;             /* [N]   out */
     float* g_color;              /* [N,3] out (stage color; may be NULL otherwise) */
     float* g_weight;             /* [N,S] out (warm-up; may be NULL otherwise) */
