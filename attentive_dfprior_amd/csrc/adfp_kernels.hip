@@ -1070,7 +1070,7 @@ __global__ __launch_bounds__(256) void k_ray_order_probe(const float* __restrict
     __shared__ int s_cnt;
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
-    const int pairs = n - 1 < 2048 ? n - 1 : 2048;
+    const int pairs = n < 1 ? 0 : (n - 1 < 2048 ? n - 1 : 2048);       // an empty batch: 0 pairs, not -1
     const int stride = pairs > 0 ? (n - 1) / pairs : 1;
     int far = 0;
     for (int k = threadIdx.x; k < pairs; k += 256) {

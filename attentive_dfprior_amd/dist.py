@@ -12,6 +12,8 @@ flat-bucket all-reduce (SUM) of the loss gradients per iteration; because the Ma
 plain sums (src/Mapper.py:457-469) the summed shard gradients equal the single-GPU gradient
 (up to fp32 summation order) with no rescaling.
 """
+import math
+
 import torch
 import torch.distributed as dist
 
@@ -44,7 +46,7 @@ def _all_gather_packed(outs, sizes, group):
     the two sides are ONE kernel each (adfp_gather_pack straight into the send buffer, adfp_gather_unpack out of the gathered
     one; no zero fill, no per-output slice copies, no torch.cat); host tensors (the gloo tests) take the torch composition."""
     world, pad = len(sizes), max(sizes)
-    rows = [o.contiguous().reshape(o.shape[0], -1) for o in outs]
+    rows = [o.contiguous().reshape(o.shape[0], math.prod(o.shape[1:])) for o in outs]      # (-1 cannot be inferred for a rank without rows)
     widths = [r.shape[1] * r.element_size() for r in rows]
     dev = outs[0].device
     if dev.type == 'cuda' and all(wd % 4 == 0 for wd in widths) and len(outs) <= 8 and world <= 64:
@@ -59,13 +61,15 @@ def _all_gather_packed(outs, sizes, group):
             send = torch.empty((pad, W), dtype=torch.uint8, device=dev)        # rows beyond the shard: never read by unpack
             gathered = torch.empty((world * pad, W), dtype=torch.uint8, device=dev)
             src = (C.c_void_p * n)(*[r.data_ptr() for r in rows])
-            _lib.check(L.adfp_gather_pack(n, src, words, rows[0].shape[0], _lib.ptr(send), st), 'adfp_gather_pack')
+            if rows[0].shape[0]:                                               # a rank without rows: empty tensors have no address
+                _lib.check(L.adfp_gather_pack(n, src, words, rows[0].shape[0], _lib.ptr(send), st), 'adfp_gather_pack')
             dist.all_gather_into_tensor(gathered, send, group=group)
             total = sum(sizes)
             res = [torch.empty((total,) + tuple(o.shape[1:]), dtype=o.dtype, device=dev) for o in outs]
             dst = (C.c_void_p * n)(*[r.data_ptr() for r in res])
             per = (C.c_longlong * world)(*sizes)
-            _lib.check(L.adfp_gather_unpack(n, dst, words, world, pad, per, _lib.ptr(gathered), st), 'adfp_gather_unpack')
+            if total:
+                _lib.check(L.adfp_gather_unpack(n, dst, words, world, pad, per, _lib.ptr(gathered), st), 'adfp_gather_unpack')
         return tuple(res)
     buf = torch.zeros((pad, sum(widths)), dtype=torch.uint8, device=dev)
     off = 0
