@@ -3614,6 +3614,44 @@ int adfp_render_depth_cull(const void* bvh, size_t bvh_bytes, long long n_faces,
     return render_depth_launch(bvh, bvh_bytes, n_faces, leaf, c2w, near, far, n_views, H, W, fx, fy, cx, cy, cull, depth, stream);
 }
 
+int adfp_render_hits(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
+                     long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull, float* depth, int* face,
+                     float* bary, void* stream) {
+    if (n_faces < 0 || n_views < 0 || !tri_leaf_ok(leaf) || H <= 0 || W <= 0) return ADFP_E_ARG;
+    if (cull != ADFP_CULL_NONE && cull != ADFP_CULL_BACK && cull != ADFP_CULL_FRONT) return ADFP_E_ARG;
+    if (!(far > 0.0) || !(fx != 0.0) || !(fy != 0.0) || !isfinite(far) || !isfinite(fx) || !isfinite(fy) ||
+        !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    if (n_views == 0) return 0;
+    if ((!depth && !face && !bary) || (n_faces > 0 && (!bvh || !c2w || !near))) return ADFP_E_ARG;
+    if (n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_faces == 0) {                                  // no hit anywhere: 0 / -1 / (0, 0)
+        const size_t npix = (size_t)n_views * H * W;
+        hipError_t e = hipSuccess;
+        if (depth) e = hipMemsetAsync(depth, 0, npix * sizeof(float), st);
+        if (e == hipSuccess && face) e = hipMemsetAsync(face, 0xff, npix * sizeof(int), st);
+        if (e == hipSuccess && bary) e = hipMemsetAsync(bary, 0, npix * 2 * sizeof(float), st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    HitArgs a;
+    a.t = make_tri(bvh, n_faces, leaf);
+    a.orig = (const int*)((const char*)bvh + tri_layout(n_faces, leaf).off_orig);
+    a.c2w = c2w; a.near = near; a.far = far;
+    a.H = H; a.W = W; a.nbx = (W + 15) / 16; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.depth = depth; a.face = face; a.bary = bary;
+    const unsigned nblk = (unsigned)a.nbx * (unsigned)((H + 15) / 16);
+    void (*const kern)(HitArgs) = cull == ADFP_CULL_BACK ? k_render_hits<ADFP_CULL_BACK>
+                                  : cull == ADFP_CULL_FRONT ? k_render_hits<ADFP_CULL_FRONT> : k_render_hits<ADFP_CULL_NONE>;
+    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
+        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
+        a.view0 = (int)v0;
+        hipLaunchKernelGGL(kern, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
 int adfp_views_in_sight(const double* points, long long n_points, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
                         int W, int H, int* any, void* stream) {
     if (n_points < 0 || n_poses < 0) return ADFP_E_ARG;
@@ -4132,6 +4170,77 @@ int adfp_mesh_color_bytes(const float* rgb, long long n, int stride, unsigned ch
     if (!rgb || !out) return ADFP_E_ARG;
     if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
     hipLaunchKernelGGL(k_mcl_color_bytes, dim3(mcl_blocks(n)), dim3(ADFP_MCL_THREADS), 0, (hipStream_t)stream, rgb, n, stride, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+}   // extern "C"
+
+// ---- mesh views: vertex normals and the shading pass (adfp_meshshade.h) ----
+#include "adfp_meshshade.h"
+
+#define SHADE_MAX_PIXELS (1ll << 38)                    // the grid's x stays below 2^31
+static unsigned shade_blocks(long long n) { return (unsigned)((n + ADFP_SHADE_THREADS - 1) / ADFP_SHADE_THREADS); }
+
+extern "C" {
+
+size_t adfp_vertex_normals_workspace_bytes(long long n_faces) {
+    if (n_faces <= 0 || n_faces > RECON_MAX_N / 3) return 0;
+    const size_t e = (size_t)n_faces * 3;
+    return al256((size_t)n_faces * 24) + 4 * al256(e * 4) + al256(adfp_sort_workspace_bytes((long long)e));
+}
+
+int adfp_vertex_normals(const double* verts, long long n_verts, const int* faces, long long n_faces, void* workspace,
+                        size_t workspace_bytes, double* normals, void* stream) {
+    if (n_verts < 0 || n_faces < 0) return ADFP_E_ARG;
+    if (n_verts == 0) return 0;
+    if (!verts || !normals || (n_faces > 0 && (!faces || !workspace))) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (n_faces > 0 && workspace_bytes < adfp_vertex_normals_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_faces == 0) {
+        hipError_t e = hipMemsetAsync(normals, 0, (size_t)n_verts * 24, st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    const long long ne = 3 * n_faces;
+    char* w = (char*)workspace;
+    double* fn = (double*)mcl_take(w, (size_t)n_faces * 24);
+    int* key = (int*)mcl_take(w, (size_t)ne * 4);
+    int* val = (int*)mcl_take(w, (size_t)ne * 4);
+    int* key_tmp = (int*)mcl_take(w, (size_t)ne * 4);
+    int* val_tmp = (int*)mcl_take(w, (size_t)ne * 4);
+    hipLaunchKernelGGL(k_vn_faces, dim3(shade_blocks(n_faces)), dim3(ADFP_SHADE_THREADS), 0, st, verts, (int)n_verts, faces, (int)n_faces,
+                       fn, key, val);
+    ADFP_CHECK_LAUNCH();
+    int rc = adfp_sort_pairs(key, val, key_tmp, val_tmp, ne, mcl_bits(n_verts), w, adfp_sort_workspace_bytes(ne), stream);   // keys in [0, n_verts]
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_vn_sum, dim3(shade_blocks(n_verts)), dim3(ADFP_SHADE_THREADS), 0, st, key, val, ne, fn, (int)n_verts, normals);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_shade_hits(const int* face, const float* bary, long long n_views, int H, int W, const double* verts, long long n_verts,
+                    const int* faces, long long n_faces, const double* c2w, double fx, double fy, double cx, double cy,
+                    const double* vertex_normals, const unsigned char* vertex_colors, const float albedo[3], double ambient,
+                    const unsigned char background[3], int mode, float* normal, unsigned char* rgb, void* stream) {
+    if (n_views < 0 || n_verts < 0 || n_faces < 0 || H <= 0 || W <= 0) return ADFP_E_ARG;
+    if (mode != ADFP_SHADE_COLOR && mode != ADFP_SHADE_SHADED && mode != ADFP_SHADE_NORMAL) return ADFP_E_ARG;
+    if (!(ambient >= 0.0) || !(ambient <= 1.0)) return ADFP_E_ARG;
+    if (!(fx != 0.0) || !(fy != 0.0) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    if (!background || (!vertex_colors && !albedo)) return ADFP_E_ARG;
+    if (n_views == 0 || (!normal && !rgb)) return 0;
+    if (!face || !bary || !c2w || (n_faces > 0 && (!faces || (n_verts > 0 && !verts)))) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    const long long npix = n_views * H * W;
+    if (npix > SHADE_MAX_PIXELS) return ADFP_E_UNSUPPORTED;
+    ShadeArgs a;
+    a.face = face; a.bary = bary; a.npix = npix; a.H = H; a.W = W;
+    a.v = verts; a.nv = (int)n_verts; a.f = faces; a.nf = (int)n_faces;
+    a.c2w = c2w; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.vn = vertex_normals; a.vc = vertex_colors;
+    for (int c = 0; c < 3; ++c) { a.albedo[c] = albedo ? (double)albedo[c] : 0.0; a.bg[c] = background[c]; }
+    a.ambient = ambient; a.mode = mode; a.normal = normal; a.rgb = rgb;
+    hipLaunchKernelGGL(k_shade_hits, dim3(shade_blocks(npix)), dim3(ADFP_SHADE_THREADS), 0, (hipStream_t)stream, a);
     ADFP_CHECK_LAUNCH();
     return 0;
 }

@@ -196,6 +196,90 @@ __global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_depth(RenderArgs a) 
     *out = v.found ? (float)v.best : 0.f;
 }
 
+// ---- hit render: the nearest hit's depth, original face index and barycentric weights ----
+// bvh_walk's visitor for the nearest hit and its identity: RtNearest's closed, shrinking bound, so every triangle whose z equals
+// the least one is visited, and among those the smallest original face index wins -- a function of the set of hits, not of the
+// walk.  The winner travels as its sorted slot and its original index (two 32-bit registers, the slot doubling as RtNearest's
+// `found`); U, V, W are not kept but formed once more after the walk (rt_bary).
+template <int CULL>
+struct RtHit {
+    const RtRay& r; const TriDev& t; const int* orig; double near, best; int slot, face;      // slot < 0: no hit yet
+    ADFP_DEV bool enter(const double* b, double* tin) { return rt_box(r, b, near, best, tin); }
+    ADFP_DEV bool leaf(long long j) {
+        const long long s0 = j * t.leaf, s1 = s0 + t.leaf < t.nf ? s0 + t.leaf : t.nf;
+        for (long long s = s0; s < s1; ++s) {
+            double z;
+            if (rt_tri<CULL>(r, t.tri + 9 * s, &z) && z >= near && z <= best) {
+                const int o = orig[s];
+                if (slot < 0 || z < best || o < face) { slot = (int)s; face = o; }
+                best = z;
+            }
+        }
+        return false;
+    }
+};
+
+// (V / det, W / det) of triangle t for ray r, rounded to f32: rt_tri's arithmetic again, operation for operation, for a
+// triangle that rt_tri has accepted (det != 0)
+ADFP_DEV void rt_bary(const RtRay& r, const double* t, float* b1, float* b2) {
+    double cam[9];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const double e0 = t[3 * q] - r.o[0], e1 = t[3 * q + 1] - r.o[1], e2 = t[3 * q + 2] - r.o[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cam[3 * q + c] = (r.R[c] * e0 + r.R[3 + c] * e1) + r.R[6 + c] * e2;
+    }
+    const double Ax = cam[0] - r.dx * cam[2], Ay = cam[1] - r.dy * cam[2];
+    const double Bx = cam[3] - r.dx * cam[5], By = cam[4] - r.dy * cam[5];
+    const double Cx = cam[6] - r.dx * cam[8], Cy = cam[7] - r.dy * cam[8];
+    const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    const double det = (U + V) + W;
+    *b1 = (float)(V / det);
+    *b2 = (float)(W / det);
+}
+
+struct HitArgs {
+    TriDev t; const int* orig;                                // orig [nf]: the original face index of each sorted slot
+    const double* c2w; const double* near; double far;
+    int H, W, nbx; double fx, fy, cx, cy;
+    int view0;
+    float* depth; int* face; float* bary;                     // [views][H][W], [views][H][W], [views][H][W][2]; each may be NULL
+};
+
+// k_render_depth's lane, pixel and ray; depth is its value bit for bit, face the original index of the nearest hit (the smallest
+// among hits of equal z) or -1, bary = (V / det, W / det) of that triangle or (0, 0)
+template <int CULL>
+__global__ __launch_bounds__(ADFP_RT_THREADS) void k_render_hits(HitArgs a) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int bx = (int)(blockIdx.x % (unsigned)a.nbx), by = (int)(blockIdx.x / (unsigned)a.nbx);
+    const int col = bx * 16 + (w & 1) * 8 + (lane & 7);
+    const int row = by * 16 + (w >> 1) * 8 + (lane >> 3);
+    if (row >= a.H || col >= a.W) return;                   // no barrier below
+    const long long p = (long long)a.view0 + blockIdx.y;
+    const double* m = a.c2w + 12 * p;
+    const long long px = (p * a.H + row) * (long long)a.W + col;
+    float z = 0.f, b1 = 0.f, b2 = 0.f;
+    int face = -1;
+    bool fin = true;
+    if (CULL != ADFP_CULL_NONE) {                           // uniform over the workgroup: one view per grid row
+#pragma unroll
+        for (int e = 0; e < 12; ++e) fin = fin && isfinite(m[e]);
+    }
+    if (fin) {
+        RtRay r;
+        rt_ray(r, m, ((double)col - a.cx) / a.fx, ((double)row - a.cy) / a.fy, a.t.box + 6);
+        RtHit<CULL> v = {r, a.t, a.orig, a.near[p], a.far, -1, -1};
+        bvh_walk<true>(a.t.box, a.t.P, a.t.D, v);
+        if (v.slot >= 0) {
+            z = (float)v.best; face = v.face;
+            if (a.bary) rt_bary(r, a.t.tri + 9 * (long long)v.slot, &b1, &b2);
+        }
+    }
+    if (a.depth) a.depth[px] = z;
+    if (a.face) a.face[px] = face;
+    if (a.bary) { a.bary[2 * px] = b1; a.bary[2 * px + 1] = b2; }
+}
+
 // any[p] |= 1 iff pose p projects some point into the image (k_cull_seen's f32 test, cull_mesh.py:49-71 = eval_recon.py:70-96);
 // any[] is zeroed by the entry before the launch
 struct SightArgs {

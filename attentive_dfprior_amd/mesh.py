@@ -237,6 +237,33 @@ def color_bytes(rgb):
     return out
 
 
+def vertex_normals(verts, faces, device=None):
+    """Area-weighted vertex normals on the device (adfp_vertex_normals; open3d's compute_vertex_normals as we read it): f64 [V,3],
+    per vertex the sum of (v1 - v0) x (v2 - v0) over its faces in ascending face index, normalised; zeros for a vertex that no
+    face uses or whose sum has no direction.  A face with an index outside [0, V) is skipped.  The same bits every run.  verts,
+    faces: tensors or arrays (f64 and int32 on the device are used as they are).  write_ply(path, verts, faces, colors,
+    normals=vertex_normals(verts, faces)) saves the mesh with its normals."""
+    v = verts if torch.is_tensor(verts) else torch.from_numpy(np.asarray(verts, dtype=np.float64))
+    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.asarray(faces, dtype=np.int64))
+    dev = torch.device(device) if device is not None else (v.device if v.is_cuda else f.device)
+    v = v.detach().reshape(-1, 3).to(dev, torch.float64).contiguous()
+    f = f.detach().reshape(-1, 3).to(dev, torch.int32).contiguous()
+    require_cuda(v, 'vertex_normals verts')
+    V, F = int(v.shape[0]), int(f.shape[0])
+    out = torch.empty((V, 3), dtype=torch.float64, device=dev)
+    if V == 0:
+        return out
+    L = lib()
+    nbytes = L.adfp_vertex_normals_workspace_bytes(F)
+    if F and nbytes == 0:
+        raise RuntimeError(f'vertex_normals: {F} faces are more than the int32 sort carries')
+    ws = _ws(nbytes, dev) if F else None
+    with _lib.device_guard(dev):
+        check(L.adfp_vertex_normals(ptr(v), V, ptr(f) if F else None, F, ptr(ws), nbytes, ptr(out), _lib.current_stream(dev)),
+              'adfp_vertex_normals')
+    return out
+
+
 def _np(x):
     if x is None:
         return None

@@ -82,6 +82,37 @@ class MeshBVH(object):
                       'adfp_render_depth_cull')
         return depth
 
+    def render_hits(self, c2w, H, W, fx, fy, cx, cy, near, far, cull='none', want=('depth', 'face', 'bary')):
+        """What each pixel sees (adfp_render_hits), a dict of device tensors with the keys of `want`: 'depth' f32 [P,H,W],
+        render_depth's image bit for bit; 'face' int32 [P,H,W], the row of `faces` of the nearest hit (the smallest row among hits
+        of equal z), -1 where there is none; 'bary' f32 [P,H,W,2], the weights of that face's v1 and v2 (v0 has the rest), 0
+        where there is none.  The arguments are render_depth's."""
+        if cull not in _lib.CULL:
+            raise ValueError(f"render_hits: cull must be one of {tuple(_lib.CULL)}, got {cull!r}")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in ('depth', 'face', 'bary') for k in want):
+            raise ValueError(f"render_hits: want must name some of 'depth', 'face', 'bary', got {want!r}")
+        dev = self.device
+        m = _c2w_rows(c2w, dev)
+        P = int(m.shape[0])
+        nr = torch.as_tensor(near, dtype=torch.float64).reshape(-1).to(dev)
+        if nr.numel() == 1:
+            nr = nr.expand(P)
+        if nr.numel() != P:
+            raise ValueError(f'render_hits: {nr.numel()} near values for {P} views')
+        nr = nr.contiguous()
+        H, W = int(H), int(W)
+        shapes = {'depth': ((P, H, W), torch.float32), 'face': ((P, H, W), torch.int32), 'bary': ((P, H, W, 2), torch.float32)}
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
+        if P == 0:
+            return out
+        with _lib.device_guard(dev):
+            check(lib().adfp_render_hits(ptr(self.bvh) if self.n_faces else None, self.bvh.numel(), self.n_faces, self.leaf, ptr(m),
+                                         ptr(nr), float(far), P, H, W, float(fx), float(fy), float(cx), float(cy), _lib.CULL[cull],
+                                         ptr(out.get('depth')), ptr(out.get('face')), ptr(out.get('bary')),
+                                         _lib.current_stream(dev)), 'adfp_render_hits')
+        return out
+
 
 def proj_rows(c2w_list):
     """[P,12] float32: the top three rows of inv(c2w') for each pose, c2w' = c2w with columns 1 and 2 negated, inverted in f64

@@ -852,6 +852,71 @@ int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int 
 int adfp_render_depth_cull(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near,
                            double far, long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull,
                            float* depth, void* stream);
+/* ---- mesh views: which triangle a pixel sees, where on it, and what it looks like ----
+ * The hit render: adfp_render_depth_cull's arguments, argument checks, errors, launch geometry and walk, with three outputs (device),
+ * each of which may be NULL but not all three (ADFP_E_ARG):
+ *   depth [n_views][H][W] f32     adfp_render_depth_cull's image for the same arguments bit for bit (the culled modes' all-zero view
+ *                                 for a pose with a non-finite entry included).
+ *   face  [n_views][H][W] int32   the ORIGINAL index (row of the faces given to adfp_tri_bvh_build) of the nearest hit; -1 exactly
+ *                                 where no triangle passes the test above with near <= z <= far (a hit at z = 0 with near = 0 has
+ *                                 depth 0 and a face).  The nearest hit is the one of least f64 z, z as stated above; among hits
+ *                                 whose z are equal as doubles the smallest original index wins.  The walk's bound is closed (a
+ *                                 triangle at exactly the best z is tested, a box entered at exactly the best z is walked), so every
+ *                                 tied triangle is visited: face is a function of the set of hits, not of the traversal, the leaf
+ *                                 size or the run, and equals a brute force over all faces (tests/hits_ref.py).
+ *   bary  [n_views][H][W][2] f32  (V / det, W / det) of the winning triangle, the weights of its v1 and v2 (U belongs to v0:
+ *                                 z = ((U Az + V Bz) + W Cz) / det), each divided in f64 and then rounded to f32; (0, 0) where
+ *                                 face is -1.
+ * n_faces = 0 writes 0 / -1 / (0, 0); n_views = 0 does nothing. */
+int adfp_render_hits(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
+                     long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull, float* depth, int* face,
+                     float* bary, void* stream);
+/* Area-weighted vertex normals (open3d's TriangleMesh.compute_vertex_normals as we read it -- unnormalised triangle normals summed
+ * per vertex, then normalised; unpinned: there is no open3d to compare against), deterministic, no float atomics.  verts
+ * [n_verts][3] f64, faces [n_faces][3] int32, normals [n_verts][3] f64 (device).  Per face, in f64, every difference and product
+ * rounded on its own: e1 = v1 - v0, e2 = v2 - v0, n_f = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x); a face with an
+ * index outside [0, n_verts) is skipped.  Per vertex: s = 0, then s += n_f (per component) over its incident face corners in
+ * ascending face index (a face that names the vertex twice adds twice); len = sqrt((sx sx + sy sy) + sz sz); normal = s / len
+ * (per component), or (0, 0, 0) when len is 0 or not finite (an unreferenced vertex among them).  Workspace:
+ * adfp_vertex_normals_workspace_bytes(n_faces) = 24 n_faces and four times 12 n_faces, each rounded up to 256, plus
+ * adfp_sort_workspace_bytes(3 n_faces) rounded up to 256 (0 for n_faces <= 0 or beyond the limit).  n_verts = 0 does nothing;
+ * n_faces = 0 writes zeros (faces and workspace may be NULL).  n_verts or 3 n_faces above 2^31 - 1025 is ADFP_E_UNSUPPORTED. */
+size_t adfp_vertex_normals_workspace_bytes(long long n_faces);
+int adfp_vertex_normals(const double* verts, long long n_verts, const int* faces, long long n_faces, void* workspace,
+                        size_t workspace_bytes, double* normals, void* stream);
+/* The shading pass over adfp_render_hits's face and bary images (device; a caller may also make them): one lane per pixel, every
+ * operation below in f64 in the order written, no contraction.  verts, faces: the mesh given to adfp_tri_bvh_build; c2w
+ * [n_views][12] and fx, fy, cx, cy: the render's.  vertex_normals [n_verts][3] f64 (device) or NULL = flat shading;
+ * vertex_colors [n_verts][3] u8 (device) or NULL = the uniform `albedo` (HOST, three floats, widened to f64); `background` (HOST,
+ * three bytes).  Outputs (device), each may be NULL: normal [n_views][H][W][3] f32, rgb [n_views][H][W][3] u8.
+ *   No hit: face < 0, face >= n_faces, or a face with a vertex index outside [0, n_verts) (the last two cannot come from
+ *     adfp_render_hits).  normal = (0, 0, 0), rgb = background.
+ *   Weights: b1, b2 = the f32 bary values widened; b0 = (1 - b1) - b2.
+ *   Geometric normal: g = (v1 - v0) x (v2 - v0) as in adfp_vertex_normals.
+ *   Shading normal: n = g when vertex_normals is NULL, else s_c = (b0 n0_c + b1 n1_c) + b2 n2_c with n0, n1, n2 the normals of
+ *     v0, v1, v2, and n = s unless all three components of s equal 0, then n = g.
+ *   Camera space, in the vertex transform's order: m_c = (R0c n_0 + R1c n_1) + R2c n_2 (R transposed).  len = sqrt((m_0 m_0 +
+ *     m_1 m_1) + m_2 m_2); m = m / len per component, or (0, 0, 0) when len is 0 or not finite.  With d = (dx, dy, 1) the pixel's
+ *     direction as in the render, t = (m_0 dx + m_1 dy) + m_2; when t > 0 both m and t are negated: every normal faces the camera.
+ *   normal = m rounded to f32.
+ *   Intensity: I = ambient + (1 - ambient) * (-t / sqrt((dx dx + dy dy) + 1)): a light at the camera.
+ *   Base colour: ((b0 c0 + b1 c1) + b2 c2) / 255 per channel with c0, c1, c2 the bytes of v0, v1, v2 widened, or the albedo.
+ *   rgb, by mode: ADFP_SHADE_COLOR x = base; ADFP_SHADE_SHADED x = base * I; ADFP_SHADE_NORMAL x = ((m_0 + 1) / 2,
+ *     (-m_1 + 1) / 2, (-m_2 + 1) / 2) (the OpenGL-axes normal map).  byte = floor(y * 255 + 0.5) with y = x when x > 0 else 0
+ *     (NaN goes to 0), then y = y when y < 1 else 1.
+ * A byte whose y * 255 lies within rounding of a half-integer may differ by one from another correctly rounded evaluation only if
+ * sqrt or division were not correctly rounded; they are (tests/test_gpu_mesh_shade.py compares against numpy).
+ * ADFP_E_ARG: a NULL face, bary, c2w or background, NULL albedo without vertex_colors, NULL verts or faces with n_faces > 0, a
+ * negative count, H or W < 1, a mode other than the three, ambient outside [0, 1] or NaN, fx or fy zero or an intrinsic not finite.
+ * ADFP_E_UNSUPPORTED: H or W above 32768, a count above 2^31 - 1025, more than 2^38 pixels.  n_views = 0, or both outputs NULL,
+ * does nothing. */
+#define ADFP_SHADE_COLOR  0
+#define ADFP_SHADE_SHADED 1
+#define ADFP_SHADE_NORMAL 2
+int adfp_shade_hits(const int* face, const float* bary, long long n_views, int H, int W, const double* verts, long long n_verts,
+                    const int* faces, long long n_faces, const double* c2w, double fx, double fy, double cx, double cy,
+                    const double* vertex_normals, const unsigned char* vertex_colors, const float albedo[3] /*host*/, double ambient,
+                    const unsigned char background[3] /*host*/, int mode, float* normal, unsigned char* rgb, void* stream);
 /* check_proj (eval_recon.py:70-96) for a batch of poses: any[p] (int32, device) = 1 iff pose p projects some point into the
  * image, else 0.  w2c [n_poses][12] (f32, device) = the top three rows of inv(c2w'), c2w' = c2w with columns 1 and 2 negated,
  * inverted in f64 and rounded to f32 by the caller; the per-point test is adfp_cull_vertices's.  n_poses = 0 does nothing;
