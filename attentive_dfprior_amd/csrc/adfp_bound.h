@@ -9,18 +9,19 @@
 //               a second launch folds them in a fixed order: no atomics.
 //   classify    count / scan / emit: one pass evaluates every candidate against the planes (planes in LDS in chunks of 512, four
 //               candidates per lane per plane read) and leaves one bit per candidate and a count per tile of 1024; one workgroup
-//               scans the tile counts (k_mcl_tile_scan); the emit pass writes the surviving ids in ascending position.  The
+//               scans the tile counts (adfp_scan.h: k_tile_scan); the emit pass writes the surviving ids in ascending position.  The
 //               per-facet farthest is two passes over the survivors: the distance's bit pattern (positive, so monotone as an
 //               integer) through an LDS max per workgroup and one 64-bit vector atomic max per touched facet per workgroup, then
 //               the lowest id among the survivors that attain it (atomic min).  Max and min of integers: the order the atomics
 //               land in decides nothing.
 #pragma once
 #include "adfp_device.h"
-#include "adfp_meshclean.h"
+#include "adfp_scan.h"
 
 #define ADFP_BND_THREADS 256
 #define ADFP_BND_PER 4
 #define ADFP_BND_TILE (ADFP_BND_THREADS * ADFP_BND_PER)
+#define ADFP_BND_SCAN_PER 8           // tile counts per lane and round of the one-workgroup scan (adfp_scan.h: k_tile_scan)
 #define ADFP_BND_PLANES 512              // planes per LDS chunk (16 KB)
 #define ADFP_BND_FARS 4096               // facets whose farthest distance is reduced in LDS first (32 KB); the rest go to memory directly
 #define ADFP_BND_SUP_BLOCKS 1024         // workgroups (per 256 directions) of the support pass
@@ -295,3 +296,132 @@ __global__ __launch_bounds__(ADFP_BND_THREADS) void k_bnd_points(BndScene s, con
     if (!bnd_point(s, ids[i], p)) p[0] = p[1] = p[2] = (double)NAN;
     out[3 * i] = p[0]; out[3 * i + 1] = p[1]; out[3 * i + 2] = p[2];
 }
+
+// ---- host side: the launchers ----
+static const long long BND_MAX_IDS = 1ll << 40;                    // tile numbers stay int
+static long long bnd_tiles(long long n) { return ceil_div(n, ADFP_BND_TILE); }
+static bool bnd_finite_host(double x) { return x == x && x - x == 0.0; }
+// 0, or the error of a scene description; fills s
+static int bnd_scene(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy, BndScene& s) {
+    if (K < 0 || H < 1 || W < 1) return ADFP_E_ARG;
+    if (!bnd_finite_host(fx) || !bnd_finite_host(fy) || fx == 0.0 || fy == 0.0 || !bnd_finite_host(cx) || !bnd_finite_host(cy)) return ADFP_E_ARG;
+    if (K > 0 && (!depth || !poses)) return ADFP_E_ARG;
+    if (H > 32768 || W > 32768) return ADFP_E_UNSUPPORTED;
+    s.depth = depth; s.poses = poses; s.K = K; s.H = H; s.W = W; s.HW1 = (long long)H * W + 1;
+    if (K > BND_MAX_IDS / s.HW1) return ADFP_E_UNSUPPORTED;
+    s.n_ids = K * s.HW1; s.fx = fx; s.fy = fy; s.cx = cx; s.cy = cy;
+    return 0;
+}
+static int bnd_sup_blocks(long long n_ids) { const long long t = bnd_tiles(n_ids); return (int)(t < ADFP_BND_SUP_BLOCKS ? t : ADFP_BND_SUP_BLOCKS); }
+
+extern "C" {
+
+// the partials of the support pass's a.nbx workgroups
+static void bnd_support_layout(Arena& A, BndSupport& a) {
+    const size_t nb = (size_t)a.nbx;
+    a.part_dot = A.take<double>(nb * a.D);
+    a.part_id = A.take<long long>(nb * a.D);
+    a.part_box = A.take<double>(nb * 6);
+    a.part_cnt = A.take<long long>(nb * 2);
+}
+size_t adfp_bound_support_workspace_bytes(long long K, int H, int W, int D) {
+    if (K <= 0 || H < 1 || W < 1 || H > 32768 || W > 32768 || D < 1 || D > ADFP_BOUND_MAX_DIRECTIONS) return 0;
+    if (K > BND_MAX_IDS / ((long long)H * W + 1)) return 0;
+    BndSupport a;
+    a.D = D; a.nbx = bnd_sup_blocks(K * ((long long)H * W + 1));
+    return layout_bytes(bnd_support_layout, a);
+}
+
+int adfp_bound_support(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                       const double* directions, int D, void* workspace, size_t workspace_bytes, long long* best_id, double* aabb,
+                       long long* counts, void* stream) {
+    BndSupport a;
+    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, a.s);
+    if (rc) return rc;
+    if (D < 1 || D > ADFP_BOUND_MAX_DIRECTIONS || !directions || !best_id || !aabb || !counts) return ADFP_E_ARG;
+    if (K == 0) return 0;
+    if (!workspace) return ADFP_E_ARG;
+    if (workspace_bytes < adfp_bound_support_workspace_bytes(K, H, W, D)) return ADFP_E_WORKSPACE;
+    a.dirs = directions; a.D = D; a.n_tiles = bnd_tiles(a.s.n_ids); a.nbx = bnd_sup_blocks(a.s.n_ids);
+    Arena A(workspace);
+    bnd_support_layout(A, a);
+    a.best_id = best_id; a.aabb = aabb; a.counts = counts;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_bnd_support, dim3((unsigned)a.nbx, (unsigned)ceil_div(D, ADFP_BND_THREADS)), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_bnd_support_fold, dim3((unsigned)D + 1), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+// the inside mask (a bit per id), the tile counts and their exclusive prefix; returns the prefix, which the kernels only read
+static long long* bnd_classify_layout(Arena& A, long long n_in, BndClassify& a) {
+    const size_t T = (size_t)bnd_tiles(n_in);
+    a.mask = A.take<unsigned long long>(T * (ADFP_BND_TILE / 64));
+    a.tile_counts = A.take<unsigned>(T);
+    long long* tile_offsets = A.take<long long>(T);
+    a.tile_offsets = tile_offsets;
+    return tile_offsets;
+}
+size_t adfp_bound_classify_workspace_bytes(long long n_in) {
+    BndClassify a;
+    return n_in <= 0 || n_in > BND_MAX_IDS ? 0 : layout_bytes(bnd_classify_layout, n_in, a);
+}
+
+int adfp_bound_classify(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                        const long long* ids_in, long long n_in, const double* planes, int F, double eps, void* workspace,
+                        size_t workspace_bytes, long long* ids_out, long long ids_cap, long long* count, long long* far_id, double* far_dist,
+                        void* stream) {
+    BndClassify a;
+    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, a.s);
+    if (rc) return rc;
+    if (n_in < 0 || ids_cap < 0 || F < 1 || !planes || !count || !far_id || !far_dist || !(eps >= 0.0) || !bnd_finite_host(eps)) return ADFP_E_ARG;
+    if (!ids_in && n_in != a.s.n_ids) return ADFP_E_ARG;                // NULL: all ids of the scene
+    if (n_in > BND_MAX_IDS) return ADFP_E_UNSUPPORTED;
+    if (n_in > 0 && (!workspace || (ids_cap > 0 && !ids_out))) return ADFP_E_ARG;
+    if (n_in > 0 && workspace_bytes < adfp_bound_classify_workspace_bytes(n_in)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(far_id, 0xff, (size_t)F * 8, st);     // -1: no point
+    if (e != hipSuccess) return (int)e;
+    e = hipMemsetAsync(far_dist, 0, (size_t)F * 8, st);
+    if (e != hipSuccess) return (int)e;
+    if (n_in == 0) { e = hipMemsetAsync(count, 0, sizeof(long long), st); return e == hipSuccess ? 0 : (int)e; }
+    const long long T = bnd_tiles(n_in);
+    Arena A(workspace);
+    long long* tile_offsets = bnd_classify_layout(A, n_in, a);
+    a.ids_in = ids_in; a.n_in = n_in; a.planes = planes; a.F = F; a.eps = eps;
+    a.ids_out = ids_out; a.ids_cap = ids_cap; a.count = count;
+    a.far_bits = (unsigned long long*)far_dist; a.far_id = (unsigned long long*)far_id;
+    hipLaunchKernelGGL(k_bnd_flag, dim3((unsigned)T), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL((k_tile_scan<ADFP_BND_THREADS, ADFP_BND_SCAN_PER>), dim3(1), dim3(ADFP_BND_THREADS), 0, st, a.tile_counts, T, tile_offsets, count);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_bnd_emit, dim3((unsigned)T), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    if (ids_cap == 0) return 0;
+    const long long cap_tiles = bnd_tiles(n_in < ids_cap ? n_in : ids_cap);
+    const unsigned fb = (unsigned)(cap_tiles < ADFP_BND_FAR_BLOCKS ? cap_tiles : ADFP_BND_FAR_BLOCKS);
+    a.ids_in = nullptr;                                                  // the farthest passes read ids_out
+    hipLaunchKernelGGL(k_bnd_far<0>, dim3(fb), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_bnd_far<1>, dim3(fb), dim3(ADFP_BND_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_bound_points(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
+                      const long long* ids, long long n, double* out, void* stream) {
+    BndScene s;
+    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, s);
+    if (rc) return rc;
+    if (n < 0) return ADFP_E_ARG;
+    if (n == 0) return 0;
+    if (!ids || !out) return ADFP_E_ARG;
+    if (n > BND_MAX_IDS) return ADFP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_bnd_points, dim3((unsigned)ceil_div(n, ADFP_BND_THREADS)), dim3(ADFP_BND_THREADS), 0, (hipStream_t)stream,
+                       s, ids, n, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+}   // extern "C"

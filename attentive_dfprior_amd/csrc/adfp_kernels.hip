@@ -1113,6 +1113,8 @@ __global__ __launch_bounds__(256) void k_gather_rows(GatherJobs j, unsigned* __r
 // =====================================================================================
 // host side: C ABI
 // =====================================================================================
+#include "adfp_host.h"
+
 // compute units of the CURRENT device (launch geometry of the persistent kernels).  Asked per call: the library keeps no global
 // mutable state, and a process may drive GPUs of different sizes.  hipDeviceGetAttribute is a table lookup (no device round trip).
 // t_cu_reserve: compute units the calling thread's CURRENT entry point leaves to its side lane (adfp_backward_args.side_stream): the
@@ -1165,7 +1167,7 @@ struct Workspace {
     unsigned* segparts;          // [SEGMAX_SEGS][SEGMAX_PARTS] ordered-uint partial maxima of gt_depth (k_forward_head -> k_sample)
     size_t bytes;
 };
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+static size_t align256(size_t x) { return al256(x); }
 // (offsets are formed as integers: the size queries carve a NULL base, and pointer arithmetic on NULL is undefined)
 template <typename T> static T* at(void* base, size_t o) { return (T*)((uintptr_t)base + o); }
 static Workspace carve(void* base, long long P) {
@@ -3203,1179 +3205,16 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
     return 0;
 }
 
-// ---- mesh extraction (adfp_mesh.h) ----
-#include "adfp_mesh.h"
-
-static long long mc_tiles(int nx, int ny, int nz) {
-    return ((long long)nx * ny * nz + ADFP_MC_TILE - 1) / ADFP_MC_TILE;
-}
-static size_t mc_counts_bytes(long long ntiles) { return (((size_t)ntiles * 8) + 255) & ~(size_t)255; }
-size_t adfp_mc_workspace_bytes(int nx, int ny, int nz) {
-    if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
-    const long long nt = mc_tiles(nx, ny, nz);
-    return mc_counts_bytes(nt) + (size_t)(nt + 1) * 16;
-}
-static McLattice mc_lattice(const float* values, int nx, int ny, int nz, float level) {
-    McLattice L;
-    L.v = values; L.nx = nx; L.ny = ny; L.nz = nz;
-    L.sy = nz; L.sx = (long long)ny * nz; L.n = L.sx * nx; L.level = level;
-    return L;
-}
-static McWork mc_carve(const void* workspace, int nx, int ny, int nz) {
-    McWork W;
-    W.ntiles = mc_tiles(nx, ny, nz);
-    W.tile_counts = (unsigned*)workspace;
-    W.tile_offsets = (long long*)((char*)workspace + mc_counts_bytes(W.ntiles));
-    return W;
-}
-
-int adfp_mc_count(const float* values, int nx, int ny, int nz, float level, void* workspace, size_t workspace_bytes,
-                  long long* totals, void* stream) {
-    if (!values || !workspace || !totals || nx <= 0 || ny <= 0 || nz <= 0) return ADFP_E_ARG;
-    if (workspace_bytes < adfp_mc_workspace_bytes(nx, ny, nz)) return ADFP_E_WORKSPACE;
-    const McLattice L = mc_lattice(values, nx, ny, nz, level);
-    const McWork W = mc_carve(workspace, nx, ny, nz);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_mc_count, dim3((unsigned)W.ntiles), dim3(ADFP_MC_THREADS), 0, st, L, W);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(ADFP_MC_SCAN_THREADS), 0, st, W, totals);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_mc_emit(const float* values, int nx, int ny, int nz, float level, const float origin[3], const float spacing[3], int outward,
-                 const void* workspace, size_t workspace_bytes, long long n_verts, long long n_faces, float* verts, float* normals,
-                 long long* keys, long long vert_capacity, int* faces, long long face_capacity, void* stream) {
-    if (!values || !workspace || !origin || !spacing || nx <= 0 || ny <= 0 || nz <= 0) return ADFP_E_ARG;
-    if (outward != ADFP_MC_OUT_LOWER && outward != ADFP_MC_OUT_HIGHER) return ADFP_E_ARG;
-    if (n_verts < 0 || n_faces < 0 || vert_capacity < 0 || face_capacity < 0) return ADFP_E_ARG;
-    if (n_verts > 0 && (!verts || !keys)) return ADFP_E_ARG;
-    if (n_faces > 0 && !faces) return ADFP_E_ARG;
-    if (workspace_bytes < adfp_mc_workspace_bytes(nx, ny, nz)) return ADFP_E_WORKSPACE;
-    if (n_verts >= 0x80000000ll) return ADFP_E_UNSUPPORTED;                 // faces index vertices as int32
-    if (vert_capacity < n_verts || face_capacity < n_faces) return ADFP_E_WORKSPACE;
-    if (n_verts == 0 && n_faces == 0) return 0;
-    McEmit e;
-    e.L = mc_lattice(values, nx, ny, nz, level);
-    e.W = mc_carve(workspace, nx, ny, nz);
-    for (int k = 0; k < 3; ++k) { e.org[k] = origin[k]; e.sp[k] = spacing[k]; }
-    e.outward = outward;
-    e.verts = verts; e.normals = normals; e.keys = keys; e.vcap = vert_capacity;
-    e.faces = faces; e.fcap = face_capacity;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_verts > 0) {
-        hipLaunchKernelGGL(k_mc_emit_verts, dim3((unsigned)e.W.ntiles), dim3(ADFP_MC_THREADS), 0, st, e);
-        ADFP_CHECK_LAUNCH();
-    }
-    if (n_faces > 0) {
-        hipLaunchKernelGGL(k_mc_emit_faces, dim3((unsigned)e.W.ntiles), dim3(ADFP_MC_THREADS), 0, st, e);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-int adfp_mc_table(int mc_case, signed char* out) {
-    if (mc_case < 0 || mc_case > 255 || !out) return ADFP_E_ARG;
-    memcpy(out, mc_tri_host[mc_case], 3 * ADFP_MC_MAX_TRI);
-    return (int)mc_count_host[mc_case];
-}
-
-int adfp_lattice_hull_fill(float* values, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz,
-                           const double* planes, int n_planes, float fill, void* stream) {
-    if (!values || !xs || !ys || !zs || nx <= 0 || ny <= 0 || nz <= 0 || n_planes < 0 || (n_planes > 0 && !planes)) return ADFP_E_ARG;
-    if (n_planes == 0) return 0;
-    HullFill h;
-    h.v = values; h.ax[0] = xs; h.ax[1] = ys; h.ax[2] = zs; h.nx = nx; h.ny = ny; h.nz = nz;
-    h.n = (long long)nx * ny * nz; h.planes = planes; h.n_planes = n_planes; h.fill = fill;
-    hipLaunchKernelGGL(k_hull_fill, dim3((unsigned)((h.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_mesh_unpack_colors(const float* verts, long long n_verts, const float* color_vol, int nx, int ny, int nz,
-                            unsigned char* colors, void* stream) {
-    if (n_verts < 0 || nx <= 0 || ny <= 0 || nz <= 0 || !color_vol || (n_verts > 0 && (!verts || !colors))) return ADFP_E_ARG;
-    if (n_verts == 0) return 0;
-    hipLaunchKernelGGL(k_unpack_colors, dim3((unsigned)((n_verts + 255) / 256)), dim3(256), 0, (hipStream_t)stream, verts, n_verts,
-                       color_vol, nx, ny, nz, colors);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---- reconstruction evaluation (adfp_recon.h) ----
-#include "adfp_recon.h"
-
-static const long long RECON_MAX_N = 0x7fffffffll - ADFP_RS_TILE;       // the sort's tile arithmetic is int
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-static NnLayout nn_layout(long long n) {
-    NnLayout L;
-    L.n = n;
-    L.nleaves = (n + ADFP_NN_LEAF - 1) / ADFP_NN_LEAF;
-    L.P = 1; L.D = 0;
-    while (L.P < L.nleaves) { L.P <<= 1; ++L.D; }
-    L.off_orig = al256((size_t)n * 24);
-    L.off_box = L.off_orig + al256((size_t)n * 4);
-    L.bytes = L.off_box + (size_t)(2 * L.P) * 48;
-    return L;
-}
-// the Morton ordering of a cloud: bounding-box partials, codes, the stable radix sort; perm <- the sorted order
-static size_t morton_ws_bytes(long long n) {
-    return al256(ADFP_NN_BB_BLOCKS * 48) + 4 * al256((size_t)n * 4) + al256(adfp_sort_workspace_bytes(n));
-}
-static int morton_order(const double* p, int n, void* ws, const int** perm, hipStream_t st) {
-    char* w = (char*)ws;
-    double* part = (double*)w; w += al256(ADFP_NN_BB_BLOCKS * 48);
-    int* key = (int*)w; w += al256((size_t)n * 4);
-    int* val = (int*)w; w += al256((size_t)n * 4);
-    int* key2 = (int*)w; w += al256((size_t)n * 4);
-    int* val2 = (int*)w; w += al256((size_t)n * 4);
-    hipLaunchKernelGGL(k_nn_bbox_partial, dim3(ADFP_NN_BB_BLOCKS), dim3(ADFP_NN_THREADS), 0, st, p, n, part);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_nn_morton, dim3((unsigned)((n + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, p, n, part,
-                       key, val);
-    ADFP_CHECK_LAUNCH();
-    const int* kf;
-    return radix_sort_pairs(key, val, key2, val2, n, 30, (int*)w, &kf, perm, st);
-}
-
-// the boxes of an index over the sorted points sp[0, n): leaves of B points each at the nodes [P, 2 P), then every level above
-static int nn_boxes(const double* sp, long long n, int B, long long P, double* box, hipStream_t st) {
-    hipLaunchKernelGGL(k_nn_leaves, dim3((unsigned)((P + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, sp, n, B, P, box);
-    ADFP_CHECK_LAUNCH();
-    for (long long first = P >> 1; first >= 1; first >>= 1) {
-        hipLaunchKernelGGL(k_nn_level, dim3((unsigned)((first + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, first, box);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-size_t adfp_nn_index_bytes(long long n_ref) { return n_ref <= 0 || n_ref > RECON_MAX_N ? 0 : nn_layout(n_ref).bytes; }
-size_t adfp_nn_build_workspace_bytes(long long n_ref) { return n_ref <= 0 || n_ref > RECON_MAX_N ? 0 : morton_ws_bytes(n_ref); }
-
-int adfp_nn_build(const double* ref, long long n_ref, void* index, size_t index_bytes, void* workspace, size_t workspace_bytes, void* stream) {
-    if (n_ref < 0) return ADFP_E_ARG;
-    if (n_ref == 0) return 0;
-    if (!ref || !index || !workspace) return ADFP_E_ARG;
-    if (n_ref > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (index_bytes < adfp_nn_index_bytes(n_ref) || workspace_bytes < adfp_nn_build_workspace_bytes(n_ref)) return ADFP_E_WORKSPACE;
-    const NnLayout L = nn_layout(n_ref);
-    const int n = (int)n_ref;
-    hipStream_t st = (hipStream_t)stream;
-    const int* perm;
-    int rc = morton_order(ref, n, workspace, &perm, st);
-    if (rc) return rc;
-    double* sp = (double*)index;
-    int* orig = (int*)((char*)index + L.off_orig);
-    double* box = (double*)((char*)index + L.off_box);
-    const unsigned nb = (unsigned)((n + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS);
-    hipLaunchKernelGGL(k_nn_gather, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, ref, n, perm, sp, orig);
-    ADFP_CHECK_LAUNCH();
-    return nn_boxes(sp, n, ADFP_NN_LEAF, L.P, box, st);
-}
-
-size_t adfp_nn_query_workspace_bytes(long long n_query, int flags) {
-    if (n_query <= 0 || n_query > RECON_MAX_N || !(flags & ADFP_NN_SORT_QUERIES)) return 0;
-    return morton_ws_bytes(n_query);
-}
-
-int adfp_nn_query(const void* index, size_t index_bytes, long long n_ref, const double* query, long long n_query, const double* transform,
-                  double radius, int flags, void* workspace, size_t workspace_bytes, double* dist, int* idx, void* stream) {
-    if (n_ref < 0 || n_query < 0 || (flags & ~ADFP_NN_SORT_QUERIES)) return ADFP_E_ARG;
-    if (!(radius > 0.0)) return ADFP_E_ARG;                                // NaN, zero or negative
-    if (n_query == 0) return 0;
-    if (n_ref == 0 || !index || !query || !dist || !idx) return ADFP_E_ARG;
-    if ((flags & ADFP_NN_SORT_QUERIES) && !workspace) return ADFP_E_ARG;
-    if (n_ref > RECON_MAX_N || n_query > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (index_bytes < adfp_nn_index_bytes(n_ref) || workspace_bytes < adfp_nn_query_workspace_bytes(n_query, flags)) return ADFP_E_WORKSPACE;
-    const NnLayout L = nn_layout(n_ref);
-    hipStream_t st = (hipStream_t)stream;
-    NnQueryArgs a;
-    a.sp = (const double*)index;
-    a.orig = (const int*)((const char*)index + L.off_orig);
-    a.box = (const double*)((const char*)index + L.off_box);
-    a.n_ref = (int)n_ref; a.P = L.P; a.D = L.D;
-    a.q = query; a.nq = (int)n_query; a.order = nullptr;
-    a.has_t = transform != nullptr;
-    for (int k = 0; k < 12; ++k) a.t[k] = transform ? transform[k] : 0.0;
-    a.best0 = radius * radius;                              // +inf stays +inf
-    a.dist = dist; a.idx = idx;
-    if (flags & ADFP_NN_SORT_QUERIES) {
-        int rc = morton_order(query, (int)n_query, workspace, &a.order, st);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_nn_query, dim3((unsigned)((n_query + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-static int red_blocks(long long n) {
-    const long long b = (n + ADFP_RED_THREADS - 1) / ADFP_RED_THREADS;
-    return (int)(b < 1 ? 1 : (b > ADFP_RED_MAX_BLOCKS ? ADFP_RED_MAX_BLOCKS : b));
-}
-size_t adfp_recon_reduce_workspace_bytes(long long n) {
-    if (n < 0 || n > RECON_MAX_N) return 0;
-    return (size_t)red_blocks(n) * ADFP_ICP_MOMENTS * 8;
-}
-
-int adfp_nn_metric_sums(const double* dist, long long n, double threshold, void* workspace, size_t workspace_bytes, double* out, void* stream) {
-    if (n < 0 || !out || !workspace || (n > 0 && !dist)) return ADFP_E_ARG;
-    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_recon_reduce_workspace_bytes(n)) return ADFP_E_WORKSPACE;
-    MetricArgs a;
-    a.d = dist; a.n = (int)n; a.th = threshold; a.nblk = red_blocks(n); a.part = (double*)workspace; a.out = out;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_metric_partial, dim3((unsigned)a.nblk), dim3(ADFP_RED_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_red_final<2>, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a.part, a.nblk, out);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_icp_moments(const double* src, long long n_src, const double* transform, const double* origin, const double* tgt, long long n_tgt,
-                     const int* idx, void* workspace, size_t workspace_bytes, double* out, void* stream) {
-    if (n_src < 0 || n_tgt < 0 || !transform || !origin || !out || !workspace) return ADFP_E_ARG;
-    if (n_src > 0 && (!src || !idx || (n_tgt > 0 && !tgt))) return ADFP_E_ARG;
-    if (n_src > RECON_MAX_N || n_tgt > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_recon_reduce_workspace_bytes(n_src)) return ADFP_E_WORKSPACE;
-    IcpArgs a;
-    a.src = src; a.n_src = (int)n_src; a.tgt = tgt; a.n_tgt = (int)n_tgt; a.idx = idx;
-    for (int k = 0; k < 12; ++k) a.t[k] = transform[k];
-    for (int k = 0; k < 3; ++k) a.org[k] = origin[k];
-    a.nblk = red_blocks(n_src); a.part = (double*)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_icp_partial, dim3((unsigned)a.nblk), dim3(ADFP_RED_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_red_final<ADFP_ICP_MOMENTS>, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a.part, a.nblk, out);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-static long long scan_tiles(long long n_faces) { return (n_faces + ADFP_SCAN_TILE - 1) / ADFP_SCAN_TILE; }
-size_t adfp_sample_surface_workspace_bytes(long long n_faces) {
-    if (n_faces <= 0 || n_faces > RECON_MAX_N) return 0;
-    return al256((size_t)n_faces * 8) + (size_t)(2 * scan_tiles(n_faces) + 1) * 8;
-}
-
-int adfp_sample_surface(const double* verts, long long n_verts, const int* faces, long long n_faces, const double* u_face, const double* u_bary,
-                        long long count, void* workspace, size_t workspace_bytes, double* points, int* face_index, void* stream) {
-    if (n_verts < 0 || n_faces < 0 || count < 0) return ADFP_E_ARG;
-    if (count == 0) return 0;
-    if (n_faces == 0 || n_verts == 0 || !verts || !faces || !u_face || !u_bary || !workspace || !points || !face_index) return ADFP_E_ARG;
-    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N || count > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_sample_surface_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
-    SurfSampleArgs a;
-    a.v = verts; a.nv = (int)n_verts; a.f = faces; a.nf = (int)n_faces;
-    a.u_face = u_face; a.u_bary = u_bary; a.count = (int)count;
-    a.cum = (double*)workspace;
-    a.tile_sum = (double*)((char*)workspace + al256((size_t)n_faces * 8));
-    a.ntiles = (int)scan_tiles(n_faces);
-    a.tile_max = a.tile_sum + a.ntiles + 1;
-    a.pts = points; a.face_index = face_index;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_area_tiles, dim3((unsigned)a.ntiles), dim3(ADFP_RED_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_area_tile_scan, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_area_apply, dim3((unsigned)a.ntiles), dim3(ADFP_RED_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_area_tile_max, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_sample, dim3((unsigned)((count + ADFP_RED_THREADS - 1) / ADFP_RED_THREADS)), dim3(ADFP_RED_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_cull_vertices(const double* verts, long long n_verts, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
-                       int W, int H, unsigned char* seen, void* stream) {
-    if (n_verts < 0 || n_poses < 0) return ADFP_E_ARG;
-    if (n_verts == 0) return 0;
-    if (!verts || !seen || (n_poses > 0 && !w2c)) return ADFP_E_ARG;
-    if (n_verts > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
-    CullArgs a;
-    a.v = verts; a.nv = (int)n_verts; a.w2c = w2c; a.np = (int)n_poses;
-    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.seen = seen;
-    a.vf = nullptr; a.depth = nullptr; a.dmax = nullptr; a.Wi = W; a.Hi = H; a.rW = 0.f; a.rH = 0.f;
-    hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_CULL_MESH>, dim3((unsigned)((n_verts + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0,
-                       (hipStream_t)stream, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_cull_faces(const unsigned char* seen, long long n_verts, const int* faces, long long n_faces, unsigned char* keep, void* stream) {
-    if (n_verts < 0 || n_faces < 0) return ADFP_E_ARG;
-    if (n_faces == 0) return 0;
-    if (!faces || !keep || (n_verts > 0 && !seen)) return ADFP_E_ARG;
-    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_cull_faces, dim3((unsigned)((n_faces + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0,
-                       (hipStream_t)stream, seen, (int)n_verts, faces, (int)n_faces, keep);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---- mesh depth rendering (adfp_raycast.h) ----
-#include "adfp_raycast.h"
-
-static bool tri_leaf_ok(int leaf) { return leaf == 4 || leaf == 8 || leaf == 16; }
-struct TriLayout { long long nleaves, P; int D; size_t off_orig, off_box, bytes; };
-static TriLayout tri_layout(long long nf, int leaf) {
-    TriLayout L;
-    L.nleaves = (nf + leaf - 1) / leaf;
-    L.P = 1; L.D = 0;
-    while (L.P < L.nleaves) { L.P <<= 1; ++L.D; }
-    L.off_orig = al256((size_t)nf * 72);
-    L.off_box = L.off_orig + al256((size_t)nf * 4);
-    L.bytes = L.off_box + (size_t)(2 * L.P) * 48;
-    return L;
-}
-
-static TriDev make_tri(const void* bvh, long long n_faces, int leaf) {
-    const TriLayout L = tri_layout(n_faces, leaf);
-    TriDev d; d.tri = (const double*)bvh; d.box = (const double*)((const char*)bvh + L.off_box);
-    d.nf = (int)n_faces; d.leaf = leaf; d.P = L.P; d.D = L.D;
-    return d;
-}
-
-size_t adfp_tri_bvh_bytes(long long n_faces, int leaf) {
-    return n_faces <= 0 || n_faces > RECON_MAX_N || !tri_leaf_ok(leaf) ? 0 : tri_layout(n_faces, leaf).bytes;
-}
-size_t adfp_tri_bvh_build_workspace_bytes(long long n_faces) {
-    return n_faces <= 0 || n_faces > RECON_MAX_N ? 0 : al256((size_t)n_faces * 24) + morton_ws_bytes(n_faces);
-}
-
-int adfp_tri_bvh_build(const double* verts, long long n_verts, const int* faces, long long n_faces, int leaf, void* bvh, size_t bvh_bytes,
-                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (n_verts < 0 || n_faces < 0 || !tri_leaf_ok(leaf)) return ADFP_E_ARG;
-    if (n_faces == 0) return 0;
-    if (!faces || !bvh || !workspace || (n_verts > 0 && !verts)) return ADFP_E_ARG;
-    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf) || workspace_bytes < adfp_tri_bvh_build_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
-    const TriLayout L = tri_layout(n_faces, leaf);
-    const int nf = (int)n_faces, nv = (int)n_verts;
-    hipStream_t st = (hipStream_t)stream;
-    double* cen = (double*)workspace;
-    const unsigned nb = (unsigned)((nf + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS);
-    hipLaunchKernelGGL(k_tri_centroids, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, verts, nv, faces, nf, cen);
-    ADFP_CHECK_LAUNCH();
-    const int* perm;
-    int rc = morton_order(cen, nf, (char*)workspace + al256((size_t)nf * 24), &perm, st);
-    if (rc) return rc;
-    double* tri = (double*)bvh;
-    int* orig = (int*)((char*)bvh + L.off_orig);
-    double* box = (double*)((char*)bvh + L.off_box);
-    hipLaunchKernelGGL(k_tri_gather, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, verts, nv, faces, nf, perm, tri, orig);
-    ADFP_CHECK_LAUNCH();
-    return nn_boxes(tri, 3ll * nf, 3 * leaf, L.P, box, st);      // a triangle is three consecutive points
-}
-
-#define RT_MAX_SIDE 32768
-#define RT_VIEWS_PER_LAUNCH 32768                    // grid y
-static int render_depth_launch(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near,
-                               double far, long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull,
-                               float* depth, void* stream) {
-    if (n_faces < 0 || n_views < 0 || !tri_leaf_ok(leaf) || H <= 0 || W <= 0) return ADFP_E_ARG;
-    if (cull != ADFP_CULL_NONE && cull != ADFP_CULL_BACK && cull != ADFP_CULL_FRONT) return ADFP_E_ARG;
-    if (!(far > 0.0) || !(fx != 0.0) || !(fy != 0.0) || !isfinite(far) || !isfinite(fx) || !isfinite(fy) ||
-        !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
-    if (n_views == 0) return 0;
-    if (!depth || (n_faces > 0 && (!bvh || !c2w || !near))) return ADFP_E_ARG;
-    if (n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_faces == 0) {
-        hipError_t e = hipMemsetAsync(depth, 0, (size_t)n_views * H * W * sizeof(float), st);
-        return e == hipSuccess ? 0 : (int)e;
-    }
-    RenderArgs a;
-    a.t = make_tri(bvh, n_faces, leaf);
-    a.c2w = c2w; a.near = near; a.far = far;
-    a.H = H; a.W = W; a.nbx = (W + 15) / 16; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
-    a.depth = depth;
-    const unsigned nblk = (unsigned)a.nbx * (unsigned)((H + 15) / 16);
-    void (*const kern)(RenderArgs) = cull == ADFP_CULL_BACK ? k_render_depth<ADFP_CULL_BACK>
-                                     : cull == ADFP_CULL_FRONT ? k_render_depth<ADFP_CULL_FRONT> : k_render_depth<ADFP_CULL_NONE>;
-    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
-        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
-        a.view0 = (int)v0;
-        hipLaunchKernelGGL(kern, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
-                      long long n_views, int H, int W, double fx, double fy, double cx, double cy, float* depth, void* stream) {
-    return render_depth_launch(bvh, bvh_bytes, n_faces, leaf, c2w, near, far, n_views, H, W, fx, fy, cx, cy, ADFP_CULL_NONE, depth,
-                               stream);
-}
-
-int adfp_render_depth_cull(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near,
-                           double far, long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull,
-                           float* depth, void* stream) {
-    return render_depth_launch(bvh, bvh_bytes, n_faces, leaf, c2w, near, far, n_views, H, W, fx, fy, cx, cy, cull, depth, stream);
-}
-
-int adfp_render_hits(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
-                     long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull, float* depth, int* face,
-                     float* bary, void* stream) {
-    if (n_faces < 0 || n_views < 0 || !tri_leaf_ok(leaf) || H <= 0 || W <= 0) return ADFP_E_ARG;
-    if (cull != ADFP_CULL_NONE && cull != ADFP_CULL_BACK && cull != ADFP_CULL_FRONT) return ADFP_E_ARG;
-    if (!(far > 0.0) || !(fx != 0.0) || !(fy != 0.0) || !isfinite(far) || !isfinite(fx) || !isfinite(fy) ||
-        !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
-    if (n_views == 0) return 0;
-    if ((!depth && !face && !bary) || (n_faces > 0 && (!bvh || !c2w || !near))) return ADFP_E_ARG;
-    if (n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_faces == 0) {                                  // no hit anywhere: 0 / -1 / (0, 0)
-        const size_t npix = (size_t)n_views * H * W;
-        hipError_t e = hipSuccess;
-        if (depth) e = hipMemsetAsync(depth, 0, npix * sizeof(float), st);
-        if (e == hipSuccess && face) e = hipMemsetAsync(face, 0xff, npix * sizeof(int), st);
-        if (e == hipSuccess && bary) e = hipMemsetAsync(bary, 0, npix * 2 * sizeof(float), st);
-        return e == hipSuccess ? 0 : (int)e;
-    }
-    HitArgs a;
-    a.t = make_tri(bvh, n_faces, leaf);
-    a.orig = (const int*)((const char*)bvh + tri_layout(n_faces, leaf).off_orig);
-    a.c2w = c2w; a.near = near; a.far = far;
-    a.H = H; a.W = W; a.nbx = (W + 15) / 16; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
-    a.depth = depth; a.face = face; a.bary = bary;
-    const unsigned nblk = (unsigned)a.nbx * (unsigned)((H + 15) / 16);
-    void (*const kern)(HitArgs) = cull == ADFP_CULL_BACK ? k_render_hits<ADFP_CULL_BACK>
-                                  : cull == ADFP_CULL_FRONT ? k_render_hits<ADFP_CULL_FRONT> : k_render_hits<ADFP_CULL_NONE>;
-    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
-        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
-        a.view0 = (int)v0;
-        hipLaunchKernelGGL(kern, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-int adfp_views_in_sight(const double* points, long long n_points, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
-                        int W, int H, int* any, void* stream) {
-    if (n_points < 0 || n_poses < 0) return ADFP_E_ARG;
-    if (n_poses == 0) return 0;
-    if (!w2c || !any || (n_points > 0 && !points)) return ADFP_E_ARG;
-    if (n_points > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(any, 0, (size_t)n_poses * sizeof(int), st);
-    if (e != hipSuccess) return (int)e;
-    if (n_points == 0) return 0;
-    SightArgs a;
-    a.v = points; a.nv = (int)n_points; a.w2c = w2c; a.np = (int)n_poses;
-    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.any = any;
-    hipLaunchKernelGGL(k_views_in_sight, dim3((unsigned)((n_points + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_points_visible(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* points, long long n_points,
-                        const float* w2c, const double* c2w, long long n_poses, float fx, float fy, float cx, float cy, int W, int H,
-                        double near, double eps, unsigned char* seen, void* stream) {
-    if (n_faces < 0 || n_points < 0 || n_poses < 0 || !tri_leaf_ok(leaf)) return ADFP_E_ARG;
-    if (!(eps >= 0.0) || !isfinite(eps) || !(near >= 0.0) || !isfinite(near) || !(fx != 0.f) || !(fy != 0.f)) return ADFP_E_ARG;
-    if (n_points == 0) return 0;
-    if (!points || !seen || (n_poses > 0 && !w2c) || (n_poses > 0 && n_faces > 0 && (!bvh || !c2w))) return ADFP_E_ARG;
-    if (n_faces > RECON_MAX_N || n_points > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
-    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
-    if (n_faces == 0 || n_poses == 0)                     // nothing occludes (or nothing looks): the frustum-only kernel itself
-        return adfp_cull_vertices(points, n_points, w2c, n_poses, fx, fy, cx, cy, W, H, seen, stream);
-    VisibleArgs a;
-    a.t = make_tri(bvh, n_faces, leaf);
-    a.pts = points; a.n = (int)n_points; a.w2c = w2c; a.c2w = c2w; a.np = (int)n_poses;
-    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H;
-    a.near = near; a.eps = eps; a.seen = seen;
-    hipLaunchKernelGGL(k_points_visible, dim3((unsigned)((n_points + ADFP_NN_THREADS - 1) / ADFP_NN_THREADS)), dim3(ADFP_NN_THREADS), 0,
-                       (hipStream_t)stream, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-size_t adfp_depth_l1_workspace_bytes(long long n_views, long long n_pixels) {
-    if (n_views < 0 || n_pixels < 0 || n_pixels > RECON_MAX_N || n_views > RECON_MAX_N) return 0;
-    return (size_t)n_views * red_blocks(n_pixels) * 8;
-}
-
-int adfp_depth_l1_sums(const float* a, const float* b, long long n_views, long long n_pixels, void* workspace, size_t workspace_bytes,
-                       double* out, void* stream) {
-    if (n_views < 0 || n_pixels < 0) return ADFP_E_ARG;
-    if (n_views == 0) return 0;
-    if (!out || !workspace || (n_pixels > 0 && (!a || !b))) return ADFP_E_ARG;
-    if (n_pixels > RECON_MAX_N || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_depth_l1_workspace_bytes(n_views, n_pixels)) return ADFP_E_WORKSPACE;
-    L1Args r;
-    r.a = a; r.b = b; r.n = n_pixels; r.nblk = red_blocks(n_pixels); r.part = (double*)workspace; r.out = out;
-    hipStream_t st = (hipStream_t)stream;
-    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
-        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
-        L1Args c = r;
-        c.a = a + v0 * n_pixels; c.b = b + v0 * n_pixels; c.part = r.part + v0 * r.nblk;
-        hipLaunchKernelGGL(k_l1_partial, dim3((unsigned)r.nblk, (unsigned)nv), dim3(ADFP_RED_THREADS), 0, st, c);
-        ADFP_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_l1_final, dim3((unsigned)n_views), dim3(ADFP_RED_THREADS), 0, st, r.part, r.nblk, out);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---- ScanNet mesh evaluation (adfp_refuse.h) ----
-#include "adfp_refuse.h"
-
-static bool box_ok(const int lo[3], const int dim[3], long long* nunits) {
-    long long n = 1;
-    for (int c = 0; c < 3; ++c) {
-        if (dim[c] <= 0) return false;
-        n *= dim[c];
-        if (n > 0x7fffffffll) { *nunits = -1; return true; }
-    }
-    *nunits = n;
-    return true;
-}
-
-int adfp_refuse_touch(const float* depth, long long n_views, int H, int W, const double* c2w, double fx, double fy, double cx, double cy,
-                      int stride, float depth_trunc, double sdf_trunc, double unit_length, const int unit_lo[3], const int unit_dim[3],
-                      unsigned char* touched, int* outside, void* stream) {
-    if (n_views < 0 || H <= 0 || W <= 0 || stride < 1 || !unit_lo || !unit_dim) return ADFP_E_ARG;
-    if (!(fx != 0.0) || !(fy != 0.0) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
-    if (!(sdf_trunc >= 0.0) || !isfinite(sdf_trunc) || !(unit_length > 0.0) || !isfinite(unit_length) || !(depth_trunc > 0.f))
-        return ADFP_E_ARG;
-    long long nunits = 0;
-    if (!box_ok(unit_lo, unit_dim, &nunits)) return ADFP_E_ARG;
-    if (n_views == 0) return 0;
-    if (!depth || !c2w || !touched || !outside) return ADFP_E_ARG;
-    if (nunits < 0 || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(touched, 0, (size_t)n_views * (size_t)nunits, st);
-    if (e != hipSuccess) return (int)e;
-    TouchArgs a;
-    a.depth = depth; a.H = H; a.W = W; a.stride = stride; a.nsx = (W + stride - 1) / stride; a.nsy = (H + stride - 1) / stride;
-    a.c2w = c2w; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
-    a.depth_trunc = depth_trunc; a.trunc = sdf_trunc; a.unit = unit_length;
-    for (int c = 0; c < 3; ++c) { a.lo[c] = unit_lo[c]; a.dim[c] = unit_dim[c]; }
-    a.nunits = nunits; a.touched = touched; a.outside = outside;
-    const unsigned nblk = (unsigned)(((long long)a.nsx * a.nsy + ADFP_TOUCH_THREADS - 1) / ADFP_TOUCH_THREADS);
-    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
-        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
-        a.view0 = (int)v0;
-        hipLaunchKernelGGL(k_refuse_touch, dim3(nblk, (unsigned)nv), dim3(ADFP_TOUCH_THREADS), 0, st, a);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-#define FUSE_MAX_VIEWS 65536
-int adfp_refuse_integrate(float* tsdf, float* weight, const int unit_lo[3], const int unit_dim[3], double voxel, const int* units,
-                          long long n_units, const float* depth, const float* w2c, const unsigned char* touched, long long n_views, int H,
-                          int W, float fx, float fy, float cx, float cy, float sdf_trunc, float depth_trunc, void* stream) {
-    if (n_units < 0 || n_views < 0 || H <= 0 || W <= 0 || !unit_lo || !unit_dim) return ADFP_E_ARG;
-    if (!(voxel > 0.0) || !isfinite(voxel) || !(sdf_trunc > 0.f) || !isfinite(sdf_trunc) || !(depth_trunc > 0.f)) return ADFP_E_ARG;
-    if (!(fx != 0.f) || !(fy != 0.f) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
-    long long nunits = 0;
-    if (!box_ok(unit_lo, unit_dim, &nunits)) return ADFP_E_ARG;
-    if (n_units == 0 || n_views == 0) return 0;
-    if (!tsdf || !weight || !units || !depth || !w2c || !touched) return ADFP_E_ARG;
-    if (nunits < 0 || n_units > nunits || n_views > FUSE_MAX_VIEWS || H > RT_MAX_SIDE || W > RT_MAX_SIDE) return ADFP_E_UNSUPPORTED;
-    FuseArgs a;
-    a.tsdf = tsdf; a.weight = weight;
-    for (int c = 0; c < 3; ++c) { a.dim[c] = unit_dim[c]; a.org[c] = (long long)unit_lo[c] * ADFP_UNIT; }
-    a.ny = (long long)unit_dim[1] * ADFP_UNIT; a.nz = (long long)unit_dim[2] * ADFP_UNIT; a.nunits = nunits;
-    a.units = units; a.depth = depth; a.w2c = w2c; a.touched = touched; a.n_views = (int)n_views; a.H = H; a.W = W;
-    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.trunc = sdf_trunc; a.inv_trunc = 1.0f / sdf_trunc; a.depth_trunc = depth_trunc;
-    a.safe_w = (float)W - 0.0001f; a.safe_h = (float)H - 0.0001f; a.voxel = voxel;
-    hipLaunchKernelGGL(k_refuse_integrate, dim3((unsigned)n_units), dim3(ADFP_FUSE_THREADS), 0, (hipStream_t)stream, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-#define VDS_MAX_CELLS_PER_AXIS (1ll << 21)
-static long long vds_tiles(long long n) { return (n + ADFP_VDS_TILE - 1) / ADFP_VDS_TILE; }
-size_t adfp_voxel_down_sample_workspace_bytes(long long n) {
-    if (n <= 0 || n > RECON_MAX_N) return 0;
-    const long long T = vds_tiles(n);
-    return al256((size_t)n * 8) + 5 * al256((size_t)n * 4) + al256((size_t)T * 4) + al256((size_t)T * 8) + al256(adfp_sort_workspace_bytes(n));
-}
-
-int adfp_voxel_down_sample(const double* points, long long n, double voxel_size, const double min_bound[3], const double max_bound[3],
-                           void* workspace, size_t workspace_bytes, double* out, int* counts, long long* total, void* stream) {
-    if (n < 0 || !(voxel_size > 0.0) || !isfinite(voxel_size) || !total) return ADFP_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) {
-        hipError_t e = hipMemsetAsync(total, 0, sizeof(long long), st);
-        return e == hipSuccess ? 0 : (int)e;
-    }
-    if (!points || !min_bound || !max_bound || !workspace || !out || !counts) return ADFP_E_ARG;
-    VdsArgs a;
-    unsigned long long ncell = 1;
-    for (int c = 0; c < 3; ++c) {
-        if (!isfinite(min_bound[c]) || !isfinite(max_bound[c]) || !(min_bound[c] <= max_bound[c])) return ADFP_E_ARG;
-        a.vmin[c] = min_bound[c] - voxel_size * 0.5;
-        const double f = floor((max_bound[c] - a.vmin[c]) / voxel_size);
-        if (!(f < (double)VDS_MAX_CELLS_PER_AXIS)) return ADFP_E_UNSUPPORTED;
-        a.dim[c] = (long long)f + 1;
-        ncell *= (unsigned long long)a.dim[c];
-    }
-    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_voxel_down_sample_workspace_bytes(n)) return ADFP_E_WORKSPACE;
-    const long long T = vds_tiles(n);
-    char* w = (char*)workspace;
-    a.key64 = (unsigned long long*)w; w += al256((size_t)n * 8);
-    a.key = (int*)w; w += al256((size_t)n * 4);
-    int* key_tmp = (int*)w; w += al256((size_t)n * 4);
-    a.perm = (int*)w; w += al256((size_t)n * 4);
-    int* perm_tmp = (int*)w; w += al256((size_t)n * 4);
-    a.start = (int*)w; w += al256((size_t)n * 4);
-    a.tile_counts = (unsigned*)w; w += al256((size_t)T * 4);
-    a.tile_offsets = (long long*)w; w += al256((size_t)T * 8);
-    void* sort_ws = w;
-    const size_t sort_wsb = adfp_sort_workspace_bytes(n);
-    a.p = points; a.n = (int)n; a.vs = voxel_size; a.ntiles = (int)T; a.total = total; a.out = out; a.counts = counts;
-    int bits = 0;
-    while (bits < 64 && ((ncell - 1) >> bits) != 0ull) ++bits;
-    if (bits == 0) bits = 1;
-    const unsigned nb = (unsigned)((n + ADFP_VDS_THREADS - 1) / ADFP_VDS_THREADS);
-    hipLaunchKernelGGL(k_vds_keys, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    for (int shift = 0; shift < bits; shift += 31) {                     // LSD: low segment first, every pass stable
-        hipLaunchKernelGGL(k_vds_segment, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a, shift);
-        ADFP_CHECK_LAUNCH();
-        const int kb = bits - shift < 31 ? bits - shift : 31;
-        int rc = adfp_sort_pairs(a.key, a.perm, key_tmp, perm_tmp, n, kb, sort_ws, sort_wsb, stream);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_vds_tile_heads, dim3((unsigned)T), dim3(ADFP_VDS_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_vds_tile_scan, dim3(1), dim3(ADFP_VDS_SCAN_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_vds_starts, dim3((unsigned)T), dim3(ADFP_VDS_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_vds_mean, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---- the Mapper's keyframe selection (adfp_keyframes.h) ----
-#include "adfp_keyframes.h"
-
-// ---- mesh clean-up (adfp_meshclean.h; the seen mask is adfp_recon.h's k_cull_seen) ----
-#include "adfp_meshclean.h"
-
-static unsigned mcl_blocks(long long n) { return (unsigned)((n + ADFP_MCL_THREADS - 1) / ADFP_MCL_THREADS); }
-static long long mcl_tiles(long long n) { return (n + ADFP_MCL_TILE - 1) / ADFP_MCL_TILE; }
-static int mcl_bits(long long top) { int b = 1; while (b < 31 && (top >> b) != 0) ++b; return b; }     // top < 2^bits
-static char* mcl_take(char*& w, size_t bytes) { char* p = w; w += al256(bytes); return p; }
-// pos[i] = set flags before i, total[0] = their number; tc / to: mcl_tiles(n) entries each
-static int mcl_scan(const unsigned char* flag, long long n, unsigned* tc, long long* to, int* pos, long long* total, hipStream_t st) {
-    if (n == 0) { hipError_t e = hipMemsetAsync(total, 0, sizeof(long long), st); return e == hipSuccess ? 0 : (int)e; }
-    MclScan s; s.flag = flag; s.n = (int)n; s.ntiles = (int)mcl_tiles(n); s.tile_counts = tc; s.tile_offsets = to; s.pos = pos; s.total = total;
-    hipLaunchKernelGGL(k_mcl_tile_count, dim3((unsigned)s.ntiles), dim3(ADFP_MCL_THREADS), 0, st, s);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mcl_tile_scan, dim3(1), dim3(ADFP_MCL_THREADS), 0, st, s);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mcl_positions, dim3((unsigned)s.ntiles), dim3(ADFP_MCL_THREADS), 0, st, s);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" {
-
-int adfp_mesh_seen_mask(const float* verts, long long n_verts, const float* w2c, long long n_poses, int rule, const float* depth,
-                        const float* depth_max, float fx, float fy, float cx, float cy, int W, int H, unsigned char* seen, void* stream) {
-    if (n_verts < 0 || n_poses < 0 || W < 1 || H < 1) return ADFP_E_ARG;
-    if (rule != ADFP_SEEN_FRUSTUM && rule != ADFP_SEEN_MAX_DEPTH && rule != ADFP_SEEN_DEPTH_TEST) return ADFP_E_ARG;
-    if (n_verts == 0) return 0;
-    if (!verts || !seen || (n_poses > 0 && !w2c)) return ADFP_E_ARG;
-    if (n_poses > 0 && ((rule == ADFP_SEEN_MAX_DEPTH && !depth_max) || (rule == ADFP_SEEN_DEPTH_TEST && !depth))) return ADFP_E_ARG;
-    if (n_verts > RECON_MAX_N || n_poses > RECON_MAX_N / 12 || W > 32768 || H > 32768) return ADFP_E_UNSUPPORTED;
-    if (rule == ADFP_SEEN_DEPTH_TEST && (W < 2 || H < 2)) return ADFP_E_UNSUPPORTED;       // the sample grid divides by W - 1, H - 1
-    CullArgs a;
-    a.v = nullptr; a.vf = verts; a.nv = (int)n_verts; a.w2c = w2c; a.np = (int)n_poses;
-    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.seen = seen;
-    a.depth = depth; a.dmax = depth_max; a.Wi = W; a.Hi = H;
-    a.rW = W > 1 ? 1.0f / (float)(W - 1) : 0.f; a.rH = H > 1 ? 1.0f / (float)(H - 1) : 0.f;
-    const dim3 grid(mcl_blocks(n_verts)), block(ADFP_NN_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (rule == ADFP_SEEN_FRUSTUM) hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_FRUSTUM>, grid, block, 0, st, a);
-    else if (rule == ADFP_SEEN_MAX_DEPTH) hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_MAX_DEPTH>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_DEPTH_TEST>, grid, block, 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-static bool mcl_mesh_too_large(long long n_verts, long long n_faces) { return n_verts > RECON_MAX_N || n_faces > RECON_MAX_N / 3; }
-
-size_t adfp_mesh_face_labels_workspace_bytes(long long n_faces) {
-    if (n_faces <= 0 || n_faces > RECON_MAX_N / 3) return 0;
-    const size_t e = (size_t)n_faces * 3;
-    return 6 * al256(e * 4) + al256(adfp_sort_workspace_bytes((long long)e));
-}
-
-int adfp_mesh_face_labels_begin(const int* faces, long long n_faces, long long n_verts, const unsigned char* keep, int* mate, int* labels,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-    if (n_faces < 0 || n_verts < 0) return ADFP_E_ARG;
-    if (n_faces == 0) return 0;
-    if (!faces || !mate || !labels || !workspace) return ADFP_E_ARG;
-    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_mesh_face_labels_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
-    const long long ne = 3 * n_faces;
-    char* w = (char*)workspace;
-    int* lo = (int*)mcl_take(w, (size_t)ne * 4);
-    int* hi = (int*)mcl_take(w, (size_t)ne * 4);
-    int* key = (int*)mcl_take(w, (size_t)ne * 4);
-    int* key_tmp = (int*)mcl_take(w, (size_t)ne * 4);
-    int* perm = (int*)mcl_take(w, (size_t)ne * 4);
-    int* perm_tmp = (int*)mcl_take(w, (size_t)ne * 4);
-    const size_t swb = adfp_sort_workspace_bytes(ne);
-    hipStream_t st = (hipStream_t)stream;
-    const int bits = mcl_bits(n_verts);                                     // keys lie in [0, n_verts]
-    hipLaunchKernelGGL(k_mcl_edges, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, (int)n_verts, keep, lo, hi,
-                       perm, labels);
-    ADFP_CHECK_LAUNCH();
-    const int* src[2] = {hi, lo};                                          // by the larger vertex, then (stable) by the smaller
-    for (int ps = 0; ps < 2; ++ps) {
-        hipLaunchKernelGGL(k_mcl_gather, dim3(mcl_blocks(ne)), dim3(ADFP_MCL_THREADS), 0, st, src[ps], perm, (int)ne, key);
-        ADFP_CHECK_LAUNCH();
-        int rc = adfp_sort_pairs(key, perm, key_tmp, perm_tmp, ne, bits, w, swb, stream);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_mcl_mates, dim3(mcl_blocks(ne)), dim3(ADFP_MCL_THREADS), 0, st, lo, hi, perm, (int)ne, (int)n_verts, mate);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_mesh_face_labels_rounds(const int* mate, int* labels, long long n_faces, int rounds, int* changed, void* stream) {
-    if (n_faces < 0 || rounds < 1 || !changed) return ADFP_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_faces == 0) { hipError_t e = hipMemsetAsync(changed, 0, sizeof(int), st); return e == hipSuccess ? 0 : (int)e; }
-    if (!mate || !labels) return ADFP_E_ARG;
-    if (n_faces > RECON_MAX_N / 3) return ADFP_E_UNSUPPORTED;
-    for (int r = 0; r < rounds; ++r) {
-        hipError_t e = hipMemsetAsync(changed, 0, sizeof(int), st);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k_mcl_hook, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, mate, labels, (int)n_faces, changed);
-        ADFP_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_mcl_compress, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, labels, (int)n_faces);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-#define MCL_BEST_BLOCKS 1024
-size_t adfp_mesh_component_keep_workspace_bytes(long long n_faces) {
-    if (n_faces <= 0 || n_faces > RECON_MAX_N / 3) return 0;
-    const size_t f = (size_t)n_faces, T = (size_t)mcl_tiles(n_faces);
-    return 2 * al256(f * 8) + 4 * al256(f * 4) + al256(T) + 2 * al256(T * 8) + al256(MCL_BEST_BLOCKS * 8) + al256(MCL_BEST_BLOCKS * 4) + 2 * 256 +
-           al256(adfp_sort_workspace_bytes(n_faces));
-}
-
-int adfp_mesh_component_keep(const float* verts, long long n_verts, const int* faces, long long n_faces, const int* labels, int largest,
-                             double threshold, unsigned char* keep, void* workspace, size_t workspace_bytes, void* stream) {
-    if (n_faces < 0 || n_verts < 0 || (largest != 0 && largest != 1) || (!largest && threshold != threshold)) return ADFP_E_ARG;
-    if (n_faces == 0) return 0;
-    if (!faces || !labels || !keep || !workspace || (n_verts > 0 && !verts)) return ADFP_E_ARG;
-    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_mesh_component_keep_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
-    const size_t f = (size_t)n_faces, T = (size_t)mcl_tiles(n_faces);
-    char* w = (char*)workspace;
-    double* area = (double*)mcl_take(w, f * 8);
-    double* comp_area = (double*)mcl_take(w, f * 8);
-    int* key = (int*)mcl_take(w, f * 4);
-    int* key_tmp = (int*)mcl_take(w, f * 4);
-    int* perm = (int*)mcl_take(w, f * 4);
-    int* perm_tmp = (int*)mcl_take(w, f * 4);
-    MclSeg s;
-    s.tile_flag = (unsigned char*)mcl_take(w, T);
-    s.tile_sum = (double*)mcl_take(w, T * 8);
-    s.carry = (double*)mcl_take(w, T * 8);
-    double* part_val = (double*)mcl_take(w, MCL_BEST_BLOCKS * 8);
-    int* part_lab = (int*)mcl_take(w, MCL_BEST_BLOCKS * 4);
-    double* best_val = (double*)mcl_take(w, 8);
-    int* best_lab = (int*)mcl_take(w, 4);
-    hipStream_t st = (hipStream_t)stream;
-    const int nf = (int)n_faces;
-    const dim3 grid(mcl_blocks(n_faces)), block(ADFP_MCL_THREADS);
-    hipLaunchKernelGGL(k_mcl_areas, grid, block, 0, st, verts, faces, nf, labels, area, key, perm);
-    ADFP_CHECK_LAUNCH();
-    int rc = adfp_sort_pairs(key, perm, key_tmp, perm_tmp, n_faces, mcl_bits(n_faces), w, adfp_sort_workspace_bytes(n_faces), stream);
-    if (rc) return rc;
-    s.key = key; s.perm = perm; s.area = area; s.n = nf; s.nf = nf; s.ntiles = (int)T; s.comp_area = comp_area;
-    hipLaunchKernelGGL(k_mcl_seg<0>, dim3((unsigned)T), block, 0, st, s);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mcl_seg_carry, dim3(1), dim3(64), 0, st, s);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mcl_seg<1>, dim3((unsigned)T), block, 0, st, s);
-    ADFP_CHECK_LAUNCH();
-    if (largest) {
-        MclBest b;
-        const unsigned nb = grid.x < MCL_BEST_BLOCKS ? grid.x : MCL_BEST_BLOCKS;
-        b.labels = labels; b.val = comp_area; b.lab = nullptr; b.n = nf; b.out_val = part_val; b.out_lab = part_lab;
-        hipLaunchKernelGGL(k_mcl_best, dim3(nb), block, 0, st, b);
-        ADFP_CHECK_LAUNCH();
-        b.labels = nullptr; b.val = part_val; b.lab = part_lab; b.n = (int)nb; b.out_val = best_val; b.out_lab = best_lab;
-        hipLaunchKernelGGL(k_mcl_best, dim3(1), block, 0, st, b);
-        ADFP_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_mcl_keep, grid, block, 0, st, labels, nf, comp_area, largest ? best_lab : (const int*)nullptr, threshold, keep);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-// compaction workspace: fkeep [F], used [V] (bytes), fpos [F], vpos [V] (ints), tile counts / offsets for the longer of the two
-struct MclCompact { unsigned char* fkeep; unsigned char* used; int* fpos; int* vpos; unsigned* tc; long long* to; };
-static MclCompact mcl_compact_carve(void* workspace, long long nv, long long nf) {
-    MclCompact c;
-    char* w = (char*)workspace;
-    const size_t T = (size_t)mcl_tiles(nv > nf ? nv : nf);
-    c.fkeep = (unsigned char*)mcl_take(w, (size_t)nf);
-    c.used = (unsigned char*)mcl_take(w, (size_t)nv);
-    c.fpos = (int*)mcl_take(w, (size_t)nf * 4);
-    c.vpos = (int*)mcl_take(w, (size_t)nv * 4);
-    c.tc = (unsigned*)mcl_take(w, T * 4);
-    c.to = (long long*)mcl_take(w, T * 8);
-    return c;
-}
-size_t adfp_mesh_compact_workspace_bytes(long long n_verts, long long n_faces) {
-    if (n_verts < 0 || n_faces < 0 || mcl_mesh_too_large(n_verts, n_faces)) return 0;
-    const size_t T = (size_t)mcl_tiles(n_verts > n_faces ? n_verts : n_faces);
-    return al256((size_t)n_faces) + al256((size_t)n_verts) + al256((size_t)n_faces * 4) + al256((size_t)n_verts * 4) + al256(T * 4) + al256(T * 8);
-}
-
-int adfp_mesh_compact_plan(const int* faces, long long n_faces, long long n_verts, const unsigned char* keep, void* workspace,
-                           size_t workspace_bytes, long long* totals, void* stream) {
-    if (n_faces < 0 || n_verts < 0 || !totals) return ADFP_E_ARG;
-    if (n_faces > 0 && (!faces || !keep)) return ADFP_E_ARG;
-    if ((n_faces > 0 || n_verts > 0) && !workspace) return ADFP_E_ARG;
-    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_mesh_compact_workspace_bytes(n_verts, n_faces)) return ADFP_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const MclCompact c = mcl_compact_carve(workspace, n_verts, n_faces);
-    if (n_verts > 0) { hipError_t e = hipMemsetAsync(c.used, 0, (size_t)n_verts, st); if (e != hipSuccess) return (int)e; }
-    if (n_faces > 0) {
-        hipLaunchKernelGGL(k_mcl_mark, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, (int)n_verts, keep, c.fkeep,
-                           c.used);
-        ADFP_CHECK_LAUNCH();
-    }
-    int rc = mcl_scan(c.used, n_verts, c.tc, c.to, c.vpos, totals, st);
-    if (rc) return rc;
-    return mcl_scan(c.fkeep, n_faces, c.tc, c.to, c.fpos, totals + 1, st);
-}
-
-int adfp_mesh_compact_emit(const float* verts, long long n_verts, const int* faces, long long n_faces, const void* workspace,
-                           size_t workspace_bytes, float* verts_out, long long n_verts_out, int* faces_out, long long n_faces_out, void* stream) {
-    if (n_faces < 0 || n_verts < 0 || n_verts_out < 0 || n_faces_out < 0 || n_verts_out > n_verts || n_faces_out > n_faces) return ADFP_E_ARG;
-    if (n_verts_out == 0 && n_faces_out == 0) return 0;
-    if (!workspace || !verts || (n_faces_out > 0 && (!faces || !faces_out)) || (n_verts_out > 0 && !verts_out)) return ADFP_E_ARG;
-    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_mesh_compact_workspace_bytes(n_verts, n_faces)) return ADFP_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const MclCompact c = mcl_compact_carve((void*)workspace, n_verts, n_faces);
-    if (n_verts_out > 0) {
-        hipLaunchKernelGGL(k_mcl_take_rows, dim3(mcl_blocks(n_verts)), dim3(ADFP_MCL_THREADS), 0, st, verts, (const unsigned char*)nullptr,
-                           (int)n_verts, c.used, c.vpos, verts_out, (unsigned char*)nullptr);
-        ADFP_CHECK_LAUNCH();
-    }
-    if (n_faces_out > 0) {
-        hipLaunchKernelGGL(k_mcl_take_faces, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, c.fkeep, c.fpos, c.vpos,
-                           (int)n_verts, faces_out);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-// merge workspace: key, key_tmp, perm, perm_tmp, gid, first, rep, pos, vmap [V] ints, head, survive [V] bytes, tiles, the sort's
-struct MclMerge { int* key; int* key_tmp; int* perm; int* perm_tmp; int* gid; int* first; int* rep; int* pos; int* vmap;
-                  unsigned char* head; unsigned char* survive; unsigned* tc; long long* to; void* sort_ws; };
-static MclMerge mcl_merge_carve(void* workspace, long long nv) {
-    MclMerge m;
-    char* w = (char*)workspace;
-    int** ints[9] = {&m.key, &m.key_tmp, &m.perm, &m.perm_tmp, &m.gid, &m.first, &m.rep, &m.pos, &m.vmap};
-    for (int k = 0; k < 9; ++k) *ints[k] = (int*)mcl_take(w, (size_t)nv * 4);
-    m.head = (unsigned char*)mcl_take(w, (size_t)nv);
-    m.survive = (unsigned char*)mcl_take(w, (size_t)nv);
-    m.tc = (unsigned*)mcl_take(w, (size_t)mcl_tiles(nv) * 4);
-    m.to = (long long*)mcl_take(w, (size_t)mcl_tiles(nv) * 8);
-    m.sort_ws = w;
-    return m;
-}
-size_t adfp_mesh_merge_workspace_bytes(long long n_verts) {
-    if (n_verts <= 0 || n_verts > RECON_MAX_N) return 0;
-    const size_t v = (size_t)n_verts, T = (size_t)mcl_tiles(n_verts);
-    return 9 * al256(v * 4) + 2 * al256(v) + al256(T * 4) + al256(T * 8) + al256(adfp_sort_workspace_bytes(n_verts));
-}
-
-int adfp_mesh_merge_plan(const float* verts, long long n_verts, void* workspace, size_t workspace_bytes, long long* total, void* stream) {
-    if (n_verts < 0 || !total) return ADFP_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_verts == 0) { hipError_t e = hipMemsetAsync(total, 0, sizeof(long long), st); return e == hipSuccess ? 0 : (int)e; }
-    if (!verts || !workspace) return ADFP_E_ARG;
-    if (n_verts > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_mesh_merge_workspace_bytes(n_verts)) return ADFP_E_WORKSPACE;
-    const MclMerge m = mcl_merge_carve(workspace, n_verts);
-    const int n = (int)n_verts;
-    const dim3 grid(mcl_blocks(n_verts)), block(ADFP_MCL_THREADS);
-    const unsigned* bits = (const unsigned*)verts;
-    const size_t swb = adfp_sort_workspace_bytes(n_verts);
-    hipLaunchKernelGGL(k_mcl_iota, grid, block, 0, st, m.perm, n);
-    ADFP_CHECK_LAUNCH();
-    for (int ps = 0; ps < 6; ++ps) {                       // 96 key bits in stable passes of 16, the lowest first
-        hipLaunchKernelGGL(k_mcl_bits_key, grid, block, 0, st, bits, m.perm, n, 2 - ps / 2, 16 * (ps & 1), m.key);
-        ADFP_CHECK_LAUNCH();
-        int rc = adfp_sort_pairs(m.key, m.perm, m.key_tmp, m.perm_tmp, n_verts, 16, m.sort_ws, swb, stream);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_mcl_heads, grid, block, 0, st, bits, m.perm, n, m.head);
-    ADFP_CHECK_LAUNCH();
-    int rc = mcl_scan(m.head, n_verts, m.tc, m.to, m.gid, total, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_mcl_group_first, grid, block, 0, st, m.perm, n, m.head, m.gid, m.first);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mcl_rep, grid, block, 0, st, m.perm, n, m.head, m.gid, m.first, m.rep, m.survive);
-    ADFP_CHECK_LAUNCH();
-    rc = mcl_scan(m.survive, n_verts, m.tc, m.to, m.pos, total, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_mcl_vmap, grid, block, 0, st, m.rep, m.pos, n, m.vmap);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_mesh_merge_emit(const float* verts, const unsigned char* colors, long long n_verts, const int* faces, long long n_faces,
-                         const void* workspace, size_t workspace_bytes, float* verts_out, unsigned char* colors_out, long long n_verts_out,
-                         int* faces_out, void* stream) {
-    if (n_verts < 0 || n_faces < 0 || n_verts_out < 0 || n_verts_out > n_verts) return ADFP_E_ARG;
-    if (n_verts == 0 && n_faces == 0) return 0;
-    if ((n_verts > 0 && (!workspace || !verts || !verts_out)) || (n_faces > 0 && (!faces || !faces_out))) return ADFP_E_ARG;
-    if ((colors != nullptr) != (colors_out != nullptr)) return ADFP_E_ARG;
-    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
-    if (workspace_bytes < adfp_mesh_merge_workspace_bytes(n_verts)) return ADFP_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    MclMerge m;
-    memset(&m, 0, sizeof(m));
-    if (n_verts > 0) {
-        m = mcl_merge_carve((void*)workspace, n_verts);
-        hipLaunchKernelGGL(k_mcl_take_rows, dim3(mcl_blocks(n_verts)), dim3(ADFP_MCL_THREADS), 0, st, verts, colors, (int)n_verts, m.survive, m.pos,
-                           verts_out, colors_out);
-        ADFP_CHECK_LAUNCH();
-    }
-    if (n_faces > 0) {
-        hipLaunchKernelGGL(k_mcl_take_faces, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces,
-                           (const unsigned char*)nullptr, (const int*)nullptr, m.vmap, (int)n_verts, faces_out);
-        ADFP_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-int adfp_mesh_color_bytes(const float* rgb, long long n, int stride, unsigned char* out, void* stream) {
-    if (n < 0 || stride < 3) return ADFP_E_ARG;
-    if (n == 0) return 0;
-    if (!rgb || !out) return ADFP_E_ARG;
-    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_mcl_color_bytes, dim3(mcl_blocks(n)), dim3(ADFP_MCL_THREADS), 0, (hipStream_t)stream, rgb, n, stride, out);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-}   // extern "C"
-
-// ---- mesh views: vertex normals and the shading pass (adfp_meshshade.h) ----
-#include "adfp_meshshade.h"
-
-#define SHADE_MAX_PIXELS (1ll << 38)                    // the grid's x stays below 2^31
-static unsigned shade_blocks(long long n) { return (unsigned)((n + ADFP_SHADE_THREADS - 1) / ADFP_SHADE_THREADS); }
-
-extern "C" {
-
-size_t adfp_vertex_normals_workspace_bytes(long long n_faces) {
-    if (n_faces <= 0 || n_faces > RECON_MAX_N / 3) return 0;
-    const size_t e = (size_t)n_faces * 3;
-    return al256((size_t)n_faces * 24) + 4 * al256(e * 4) + al256(adfp_sort_workspace_bytes((long long)e));
-}
-
-int adfp_vertex_normals(const double* verts, long long n_verts, const int* faces, long long n_faces, void* workspace,
-                        size_t workspace_bytes, double* normals, void* stream) {
-    if (n_verts < 0 || n_faces < 0) return ADFP_E_ARG;
-    if (n_verts == 0) return 0;
-    if (!verts || !normals || (n_faces > 0 && (!faces || !workspace))) return ADFP_E_ARG;
-    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
-    if (n_faces > 0 && workspace_bytes < adfp_vertex_normals_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_faces == 0) {
-        hipError_t e = hipMemsetAsync(normals, 0, (size_t)n_verts * 24, st);
-        return e == hipSuccess ? 0 : (int)e;
-    }
-    const long long ne = 3 * n_faces;
-    char* w = (char*)workspace;
-    double* fn = (double*)mcl_take(w, (size_t)n_faces * 24);
-    int* key = (int*)mcl_take(w, (size_t)ne * 4);
-    int* val = (int*)mcl_take(w, (size_t)ne * 4);
-    int* key_tmp = (int*)mcl_take(w, (size_t)ne * 4);
-    int* val_tmp = (int*)mcl_take(w, (size_t)ne * 4);
-    hipLaunchKernelGGL(k_vn_faces, dim3(shade_blocks(n_faces)), dim3(ADFP_SHADE_THREADS), 0, st, verts, (int)n_verts, faces, (int)n_faces,
-                       fn, key, val);
-    ADFP_CHECK_LAUNCH();
-    int rc = adfp_sort_pairs(key, val, key_tmp, val_tmp, ne, mcl_bits(n_verts), w, adfp_sort_workspace_bytes(ne), stream);   // keys in [0, n_verts]
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_vn_sum, dim3(shade_blocks(n_verts)), dim3(ADFP_SHADE_THREADS), 0, st, key, val, ne, fn, (int)n_verts, normals);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_shade_hits(const int* face, const float* bary, long long n_views, int H, int W, const double* verts, long long n_verts,
-                    const int* faces, long long n_faces, const double* c2w, double fx, double fy, double cx, double cy,
-                    const double* vertex_normals, const unsigned char* vertex_colors, const float albedo[3], double ambient,
-                    const unsigned char background[3], int mode, float* normal, unsigned char* rgb, void* stream) {
-    if (n_views < 0 || n_verts < 0 || n_faces < 0 || H <= 0 || W <= 0) return ADFP_E_ARG;
-    if (mode != ADFP_SHADE_COLOR && mode != ADFP_SHADE_SHADED && mode != ADFP_SHADE_NORMAL) return ADFP_E_ARG;
-    if (!(ambient >= 0.0) || !(ambient <= 1.0)) return ADFP_E_ARG;
-    if (!(fx != 0.0) || !(fy != 0.0) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
-    if (!background || (!vertex_colors && !albedo)) return ADFP_E_ARG;
-    if (n_views == 0 || (!normal && !rgb)) return 0;
-    if (!face || !bary || !c2w || (n_faces > 0 && (!faces || (n_verts > 0 && !verts)))) return ADFP_E_ARG;
-    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
-    const long long npix = n_views * H * W;
-    if (npix > SHADE_MAX_PIXELS) return ADFP_E_UNSUPPORTED;
-    ShadeArgs a;
-    a.face = face; a.bary = bary; a.npix = npix; a.H = H; a.W = W;
-    a.v = verts; a.nv = (int)n_verts; a.f = faces; a.nf = (int)n_faces;
-    a.c2w = c2w; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
-    a.vn = vertex_normals; a.vc = vertex_colors;
-    for (int c = 0; c < 3; ++c) { a.albedo[c] = albedo ? (double)albedo[c] : 0.0; a.bg[c] = background[c]; }
-    a.ambient = ambient; a.mode = mode; a.normal = normal; a.rgb = rgb;
-    hipLaunchKernelGGL(k_shade_hits, dim3(shade_blocks(npix)), dim3(ADFP_SHADE_THREADS), 0, (hipStream_t)stream, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-}   // extern "C"
-
-// ---- mesh bound (adfp_bound.h) ----
-#include "adfp_bound.h"
-
-static const long long BND_MAX_IDS = 1ll << 40;                    // tile numbers stay int
-static long long bnd_tiles(long long n) { return (n + ADFP_BND_TILE - 1) / ADFP_BND_TILE; }
-static bool bnd_finite_host(double x) { return x == x && x - x == 0.0; }
-// 0, or the error of a scene description; fills s
-static int bnd_scene(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy, BndScene& s) {
-    if (K < 0 || H < 1 || W < 1) return ADFP_E_ARG;
-    if (!bnd_finite_host(fx) || !bnd_finite_host(fy) || fx == 0.0 || fy == 0.0 || !bnd_finite_host(cx) || !bnd_finite_host(cy)) return ADFP_E_ARG;
-    if (K > 0 && (!depth || !poses)) return ADFP_E_ARG;
-    if (H > 32768 || W > 32768) return ADFP_E_UNSUPPORTED;
-    s.depth = depth; s.poses = poses; s.K = K; s.H = H; s.W = W; s.HW1 = (long long)H * W + 1;
-    if (K > BND_MAX_IDS / s.HW1) return ADFP_E_UNSUPPORTED;
-    s.n_ids = K * s.HW1; s.fx = fx; s.fy = fy; s.cx = cx; s.cy = cy;
-    return 0;
-}
-static int bnd_sup_blocks(long long n_ids) { const long long t = bnd_tiles(n_ids); return (int)(t < ADFP_BND_SUP_BLOCKS ? t : ADFP_BND_SUP_BLOCKS); }
-
-extern "C" {
-
-size_t adfp_bound_support_workspace_bytes(long long K, int H, int W, int D) {
-    if (K <= 0 || H < 1 || W < 1 || H > 32768 || W > 32768 || D < 1 || D > ADFP_BOUND_MAX_DIRECTIONS) return 0;
-    if (K > BND_MAX_IDS / ((long long)H * W + 1)) return 0;
-    const size_t nb = (size_t)bnd_sup_blocks(K * ((long long)H * W + 1));
-    return 2 * al256(nb * (size_t)D * 8) + al256(nb * 48) + al256(nb * 16);
-}
-
-int adfp_bound_support(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
-                       const double* directions, int D, void* workspace, size_t workspace_bytes, long long* best_id, double* aabb,
-                       long long* counts, void* stream) {
-    BndSupport a;
-    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, a.s);
-    if (rc) return rc;
-    if (D < 1 || D > ADFP_BOUND_MAX_DIRECTIONS || !directions || !best_id || !aabb || !counts) return ADFP_E_ARG;
-    if (K == 0) return 0;
-    if (!workspace) return ADFP_E_ARG;
-    if (workspace_bytes < adfp_bound_support_workspace_bytes(K, H, W, D)) return ADFP_E_WORKSPACE;
-    a.dirs = directions; a.D = D; a.n_tiles = bnd_tiles(a.s.n_ids); a.nbx = bnd_sup_blocks(a.s.n_ids);
-    char* w = (char*)workspace;
-    a.part_dot = (double*)mcl_take(w, (size_t)a.nbx * D * 8);
-    a.part_id = (long long*)mcl_take(w, (size_t)a.nbx * D * 8);
-    a.part_box = (double*)mcl_take(w, (size_t)a.nbx * 48);
-    a.part_cnt = (long long*)mcl_take(w, (size_t)a.nbx * 16);
-    a.best_id = best_id; a.aabb = aabb; a.counts = counts;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_bnd_support, dim3((unsigned)a.nbx, (unsigned)((D + ADFP_BND_THREADS - 1) / ADFP_BND_THREADS)), dim3(ADFP_BND_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_bnd_support_fold, dim3((unsigned)D + 1), dim3(ADFP_BND_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-size_t adfp_bound_classify_workspace_bytes(long long n_in) {
-    if (n_in <= 0 || n_in > BND_MAX_IDS) return 0;
-    const size_t T = (size_t)bnd_tiles(n_in);
-    return al256(T * (ADFP_BND_TILE / 64) * 8) + al256(T * 4) + al256(T * 8);
-}
-
-int adfp_bound_classify(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
-                        const long long* ids_in, long long n_in, const double* planes, int F, double eps, void* workspace,
-                        size_t workspace_bytes, long long* ids_out, long long ids_cap, long long* count, long long* far_id, double* far_dist,
-                        void* stream) {
-    BndClassify a;
-    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, a.s);
-    if (rc) return rc;
-    if (n_in < 0 || ids_cap < 0 || F < 1 || !planes || !count || !far_id || !far_dist || !(eps >= 0.0) || !bnd_finite_host(eps)) return ADFP_E_ARG;
-    if (!ids_in && n_in != a.s.n_ids) return ADFP_E_ARG;                // NULL: all ids of the scene
-    if (n_in > BND_MAX_IDS) return ADFP_E_UNSUPPORTED;
-    if (n_in > 0 && (!workspace || (ids_cap > 0 && !ids_out))) return ADFP_E_ARG;
-    if (n_in > 0 && workspace_bytes < adfp_bound_classify_workspace_bytes(n_in)) return ADFP_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(far_id, 0xff, (size_t)F * 8, st);     // -1: no point
-    if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(far_dist, 0, (size_t)F * 8, st);
-    if (e != hipSuccess) return (int)e;
-    if (n_in == 0) { e = hipMemsetAsync(count, 0, sizeof(long long), st); return e == hipSuccess ? 0 : (int)e; }
-    const long long T = bnd_tiles(n_in);
-    char* w = (char*)workspace;
-    a.mask = (unsigned long long*)mcl_take(w, (size_t)T * (ADFP_BND_TILE / 64) * 8);
-    a.tile_counts = (unsigned*)mcl_take(w, (size_t)T * 4);
-    long long* tile_offsets = (long long*)mcl_take(w, (size_t)T * 8);
-    a.tile_offsets = tile_offsets;
-    a.ids_in = ids_in; a.n_in = n_in; a.planes = planes; a.F = F; a.eps = eps;
-    a.ids_out = ids_out; a.ids_cap = ids_cap; a.count = count;
-    a.far_bits = (unsigned long long*)far_dist; a.far_id = (unsigned long long*)far_id;
-    hipLaunchKernelGGL(k_bnd_flag, dim3((unsigned)T), dim3(ADFP_BND_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    MclScan s; s.flag = nullptr; s.n = 0; s.ntiles = (int)T; s.tile_counts = a.tile_counts; s.tile_offsets = tile_offsets; s.pos = nullptr; s.total = count;
-    hipLaunchKernelGGL(k_mcl_tile_scan, dim3(1), dim3(ADFP_MCL_THREADS), 0, st, s);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_bnd_emit, dim3((unsigned)T), dim3(ADFP_BND_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    if (ids_cap == 0) return 0;
-    const long long cap_tiles = bnd_tiles(n_in < ids_cap ? n_in : ids_cap);
-    const unsigned fb = (unsigned)(cap_tiles < ADFP_BND_FAR_BLOCKS ? cap_tiles : ADFP_BND_FAR_BLOCKS);
-    a.ids_in = nullptr;                                                  // the farthest passes read ids_out
-    hipLaunchKernelGGL(k_bnd_far<0>, dim3(fb), dim3(ADFP_BND_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_bnd_far<1>, dim3(fb), dim3(ADFP_BND_THREADS), 0, st, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-int adfp_bound_points(const float* depth, const float* poses, long long K, int H, int W, double fx, double fy, double cx, double cy,
-                      const long long* ids, long long n, double* out, void* stream) {
-    BndScene s;
-    const int rc = bnd_scene(depth, poses, K, H, W, fx, fy, cx, cy, s);
-    if (rc) return rc;
-    if (n < 0) return ADFP_E_ARG;
-    if (n == 0) return 0;
-    if (!ids || !out) return ADFP_E_ARG;
-    if (n > BND_MAX_IDS) return ADFP_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_bnd_points, dim3((unsigned)((n + ADFP_BND_THREADS - 1) / ADFP_BND_THREADS)), dim3(ADFP_BND_THREADS), 0, (hipStream_t)stream,
-                       s, ids, n, out);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-}   // extern "C"
-
-// ---- frame ingestion (adfp_ingest.h) ----
-#include "adfp_ingest.h"
-
-// ---- visualisation (adfp_vis.h) ----
-#include "adfp_vis.h"
-
-// ---- rendering metrics (adfp_metrics.h) ----
-#include "adfp_metrics.h"
-
-// ---- TSDF raycast (adfp_tsdfcast.h) ----
-#include "adfp_tsdfcast.h"
+// ---- the tools: every header holds its kernels and, at its foot, its layouts and launchers ----
+#include "adfp_mesh.h"          // mesh extraction
+#include "adfp_recon.h"         // reconstruction evaluation
+#include "adfp_raycast.h"       // mesh depth rendering
+#include "adfp_refuse.h"        // ScanNet mesh evaluation
+#include "adfp_keyframes.h"     // the Mapper's keyframe selection
+#include "adfp_meshclean.h"     // mesh clean-up (the seen mask is adfp_recon.h's k_cull_seen)
+#include "adfp_meshshade.h"     // mesh views: vertex normals and the shading pass
+#include "adfp_bound.h"         // mesh bound
+#include "adfp_ingest.h"        // frame ingestion
+#include "adfp_vis.h"           // visualisation
+#include "adfp_metrics.h"       // rendering metrics
+#include "adfp_tsdfcast.h"      // TSDF raycast

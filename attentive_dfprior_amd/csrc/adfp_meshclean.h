@@ -11,72 +11,15 @@
 //                2 log2(F) + 2 rounds are the worst case: the host caps at 128.
 //   areas        f64 as numpy forms them; faces ordered by label (one more sort), a segmented scan of fixed shape (8 items per
 //                lane in order, 256 lanes by doubling steps, the tiles in order) sums each component: no float atomics.
-//   compaction   flags -> exclusive scan (tile counts, one workgroup over the tiles, positions) -> gathers.
+//   compaction   flags -> exclusive scan (adfp_scan.h: k_scan_count, k_tile_scan, k_scan_place) -> gathers.
 #pragma once
 #include "adfp_device.h"
+#include "adfp_scan.h"
 
 #define ADFP_MCL_THREADS 256
 #define ADFP_MCL_PER 8
 #define ADFP_MCL_TILE (ADFP_MCL_THREADS * ADFP_MCL_PER)
-
-// ---- exclusive scan of byte flags: pos[i] = number of set flags before i; total[0] = their number (long long) ----
-struct MclScan { const unsigned char* flag; int n; int ntiles; unsigned* tile_counts; long long* tile_offsets; int* pos; long long* total; };
-
-__global__ __launch_bounds__(ADFP_MCL_THREADS) void k_mcl_tile_count(MclScan a) {
-    __shared__ unsigned lds[ADFP_MCL_THREADS / 64];
-    const long long first = (long long)blockIdx.x * ADFP_MCL_TILE + (long long)threadIdx.x * ADFP_MCL_PER;
-    unsigned c = 0;
-#pragma unroll
-    for (int q = 0; q < ADFP_MCL_PER; ++q) c += (first + q < a.n && a.flag[first + q]) ? 1u : 0u;
-    unsigned tot;
-    mc_block_scan<unsigned, ADFP_MCL_THREADS>(c, tot, lds);
-    if (threadIdx.x == 0) a.tile_counts[blockIdx.x] = tot;
-}
-
-// one workgroup: exclusive prefix of the tile counts
-__global__ __launch_bounds__(ADFP_MCL_THREADS) void k_mcl_tile_scan(MclScan a) {
-    __shared__ unsigned long long lds[ADFP_MCL_THREADS / 64];
-    unsigned long long carry = 0;
-    const long long per_round = (long long)ADFP_MCL_THREADS * ADFP_MCL_PER;
-    for (long long t0 = 0; t0 < a.ntiles; t0 += per_round) {
-        const long long first = t0 + (long long)threadIdx.x * ADFP_MCL_PER;
-        unsigned cv[ADFP_MCL_PER];
-        unsigned long long s = 0;
-#pragma unroll
-        for (int q = 0; q < ADFP_MCL_PER; ++q) {
-            cv[q] = first + q < a.ntiles ? a.tile_counts[first + q] : 0u;
-            s += cv[q];
-        }
-        unsigned long long tot;
-        unsigned long long o = carry + mc_block_scan<unsigned long long, ADFP_MCL_THREADS>(s, tot, lds);
-#pragma unroll
-        for (int q = 0; q < ADFP_MCL_PER; ++q) {
-            if (first + q < a.ntiles) a.tile_offsets[first + q] = (long long)o;
-            o += cv[q];
-        }
-        carry += tot;
-    }
-    if (threadIdx.x == 0) a.total[0] = (long long)carry;
-}
-
-__global__ __launch_bounds__(ADFP_MCL_THREADS) void k_mcl_positions(MclScan a) {
-    __shared__ unsigned lds[ADFP_MCL_THREADS / 64];
-    const long long first = (long long)blockIdx.x * ADFP_MCL_TILE + (long long)threadIdx.x * ADFP_MCL_PER;
-    bool h[ADFP_MCL_PER];
-    unsigned c = 0;
-#pragma unroll
-    for (int q = 0; q < ADFP_MCL_PER; ++q) {
-        h[q] = first + q < a.n && a.flag[first + q];
-        c += h[q] ? 1u : 0u;
-    }
-    unsigned tot;
-    long long p = a.tile_offsets[blockIdx.x] + mc_block_scan<unsigned, ADFP_MCL_THREADS>(c, tot, lds);
-#pragma unroll
-    for (int q = 0; q < ADFP_MCL_PER; ++q) {
-        if (first + q < a.n) a.pos[first + q] = (int)p;
-        p += h[q] ? 1 : 0;
-    }
-}
+static_assert(ADFP_MCL_THREADS == ADFP_SCAN_THREADS, "flags are scanned in tiles of ADFP_MCL_TILE items");
 
 // ---- components ----
 ADFP_DEV bool mcl_face_ok(const int* f, int i, int nv, const unsigned char* keep) {
@@ -401,3 +344,312 @@ __global__ __launch_bounds__(ADFP_MCL_THREADS) void k_mcl_color_bytes(const floa
         out[3 * i + c] = y == y ? (unsigned char)(int)(y * 255.f) : (unsigned char)0;
     }
 }
+
+// ---- host side: the launchers ----
+static unsigned mcl_blocks(long long n) { return (unsigned)ceil_div(n, ADFP_MCL_THREADS); }
+static size_t mcl_tiles(long long n) { return (size_t)ceil_div(n, ADFP_MCL_TILE); }
+static int mcl_bits(long long top) { int b = 1; while (b < 31 && (top >> b) != 0) ++b; return b; }     // top < 2^bits
+// pos[i] = set flags before i, total[0] = their number; tc / to: mcl_tiles(n) entries each
+static int mcl_scan(const unsigned char* flag, long long n, unsigned* tc, long long* to, int* pos, long long* total, hipStream_t st) {
+    return scan_items<ADFP_MCL_PER, ADFP_MCL_THREADS, ADFP_MCL_PER, false>(FlagSet{flag}, n, tc, to, pos, total, st);
+}
+
+extern "C" {
+
+int adfp_mesh_seen_mask(const float* verts, long long n_verts, const float* w2c, long long n_poses, int rule, const float* depth,
+                        const float* depth_max, float fx, float fy, float cx, float cy, int W, int H, unsigned char* seen, void* stream) {
+    if (n_verts < 0 || n_poses < 0 || W < 1 || H < 1) return ADFP_E_ARG;
+    if (rule != ADFP_SEEN_FRUSTUM && rule != ADFP_SEEN_MAX_DEPTH && rule != ADFP_SEEN_DEPTH_TEST) return ADFP_E_ARG;
+    if (n_verts == 0) return 0;
+    if (!verts || !seen || (n_poses > 0 && !w2c)) return ADFP_E_ARG;
+    if (n_poses > 0 && ((rule == ADFP_SEEN_MAX_DEPTH && !depth_max) || (rule == ADFP_SEEN_DEPTH_TEST && !depth))) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_poses > RECON_MAX_N / 12 || W > 32768 || H > 32768) return ADFP_E_UNSUPPORTED;
+    if (rule == ADFP_SEEN_DEPTH_TEST && (W < 2 || H < 2)) return ADFP_E_UNSUPPORTED;       // the sample grid divides by W - 1, H - 1
+    CullArgs a;
+    a.v = nullptr; a.vf = verts; a.nv = (int)n_verts; a.w2c = w2c; a.np = (int)n_poses;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.seen = seen;
+    a.depth = depth; a.dmax = depth_max; a.Wi = W; a.Hi = H;
+    a.rW = W > 1 ? 1.0f / (float)(W - 1) : 0.f; a.rH = H > 1 ? 1.0f / (float)(H - 1) : 0.f;
+    const dim3 grid(mcl_blocks(n_verts)), block(ADFP_NN_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (rule == ADFP_SEEN_FRUSTUM) hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_FRUSTUM>, grid, block, 0, st, a);
+    else if (rule == ADFP_SEEN_MAX_DEPTH) hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_MAX_DEPTH>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_DEPTH_TEST>, grid, block, 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+static bool mcl_mesh_too_large(long long n_verts, long long n_faces) { return n_verts > RECON_MAX_N || n_faces > RECON_MAX_N / 3; }
+
+// half-edge workspace: lo, hi, key, key_tmp, perm, perm_tmp [3 F] ints, the sort's
+struct MclEdges { int* lo; int* hi; int* key; int* key_tmp; int* perm; int* perm_tmp; void* sort_ws; };
+static MclEdges mcl_edges_layout(Arena& A, long long nf) {
+    MclEdges m;
+    int** ints[6] = {&m.lo, &m.hi, &m.key, &m.key_tmp, &m.perm, &m.perm_tmp};
+    for (int k = 0; k < 6; ++k) *ints[k] = A.take<int>(3 * (size_t)nf);
+    m.sort_ws = A.take<char>(adfp_sort_workspace_bytes(3 * nf));
+    return m;
+}
+size_t adfp_mesh_face_labels_workspace_bytes(long long n_faces) {
+    return n_faces <= 0 || n_faces > RECON_MAX_N / 3 ? 0 : layout_bytes(mcl_edges_layout, n_faces);
+}
+
+int adfp_mesh_face_labels_begin(const int* faces, long long n_faces, long long n_verts, const unsigned char* keep, int* mate, int* labels,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_faces < 0 || n_verts < 0) return ADFP_E_ARG;
+    if (n_faces == 0) return 0;
+    if (!faces || !mate || !labels || !workspace) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_face_labels_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    const long long ne = 3 * n_faces;
+    Arena A(workspace);
+    const MclEdges m = mcl_edges_layout(A, n_faces);
+    const size_t swb = adfp_sort_workspace_bytes(ne);
+    hipStream_t st = (hipStream_t)stream;
+    const int bits = mcl_bits(n_verts);                                     // keys lie in [0, n_verts]
+    hipLaunchKernelGGL(k_mcl_edges, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, (int)n_verts, keep, m.lo, m.hi,
+                       m.perm, labels);
+    ADFP_CHECK_LAUNCH();
+    const int* src[2] = {m.hi, m.lo};                                         // by the larger vertex, then (stable) by the smaller
+    for (int ps = 0; ps < 2; ++ps) {
+        hipLaunchKernelGGL(k_mcl_gather, dim3(mcl_blocks(ne)), dim3(ADFP_MCL_THREADS), 0, st, src[ps], m.perm, (int)ne, m.key);
+        ADFP_CHECK_LAUNCH();
+        int rc = adfp_sort_pairs(m.key, m.perm, m.key_tmp, m.perm_tmp, ne, bits, m.sort_ws, swb, stream);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_mcl_mates, dim3(mcl_blocks(ne)), dim3(ADFP_MCL_THREADS), 0, st, m.lo, m.hi, m.perm, (int)ne, (int)n_verts, mate);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_mesh_face_labels_rounds(const int* mate, int* labels, long long n_faces, int rounds, int* changed, void* stream) {
+    if (n_faces < 0 || rounds < 1 || !changed) return ADFP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_faces == 0) { hipError_t e = hipMemsetAsync(changed, 0, sizeof(int), st); return e == hipSuccess ? 0 : (int)e; }
+    if (!mate || !labels) return ADFP_E_ARG;
+    if (n_faces > RECON_MAX_N / 3) return ADFP_E_UNSUPPORTED;
+    for (int r = 0; r < rounds; ++r) {
+        hipError_t e = hipMemsetAsync(changed, 0, sizeof(int), st);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(k_mcl_hook, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, mate, labels, (int)n_faces, changed);
+        ADFP_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_mcl_compress, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, labels, (int)n_faces);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+#define MCL_BEST_BLOCKS 1024
+// component workspace: area, comp_area [F] doubles, key, key_tmp, perm, perm_tmp [F] ints, the segmented scan's tiles, the partials
+// and the result of the largest-component search, the sort's
+struct MclKeep { double* area; double* comp_area; int* key; int* key_tmp; int* perm; int* perm_tmp; unsigned char* tile_flag; double* tile_sum;
+                 double* carry; double* part_val; int* part_lab; double* best_val; int* best_lab; void* sort_ws; };
+static MclKeep mcl_keep_layout(Arena& A, long long nf) {
+    MclKeep m;
+    const size_t f = (size_t)nf, T = mcl_tiles(nf);
+    m.area = A.take<double>(f); m.comp_area = A.take<double>(f);
+    m.key = A.take<int>(f); m.key_tmp = A.take<int>(f); m.perm = A.take<int>(f); m.perm_tmp = A.take<int>(f);
+    m.tile_flag = A.take<unsigned char>(T); m.tile_sum = A.take<double>(T); m.carry = A.take<double>(T);
+    m.part_val = A.take<double>(MCL_BEST_BLOCKS); m.part_lab = A.take<int>(MCL_BEST_BLOCKS);
+    m.best_val = A.take<double>(1); m.best_lab = A.take<int>(1);
+    m.sort_ws = A.take<char>(adfp_sort_workspace_bytes(nf));
+    return m;
+}
+size_t adfp_mesh_component_keep_workspace_bytes(long long n_faces) {
+    return n_faces <= 0 || n_faces > RECON_MAX_N / 3 ? 0 : layout_bytes(mcl_keep_layout, n_faces);
+}
+
+int adfp_mesh_component_keep(const float* verts, long long n_verts, const int* faces, long long n_faces, const int* labels, int largest,
+                             double threshold, unsigned char* keep, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_faces < 0 || n_verts < 0 || (largest != 0 && largest != 1) || (!largest && threshold != threshold)) return ADFP_E_ARG;
+    if (n_faces == 0) return 0;
+    if (!faces || !labels || !keep || !workspace || (n_verts > 0 && !verts)) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_component_keep_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    Arena A(workspace);
+    const MclKeep m = mcl_keep_layout(A, n_faces);
+    const unsigned T = (unsigned)mcl_tiles(n_faces);
+    hipStream_t st = (hipStream_t)stream;
+    const int nf = (int)n_faces;
+    const dim3 grid(mcl_blocks(n_faces)), block(ADFP_MCL_THREADS);
+    hipLaunchKernelGGL(k_mcl_areas, grid, block, 0, st, verts, faces, nf, labels, m.area, m.key, m.perm);
+    ADFP_CHECK_LAUNCH();
+    int rc = adfp_sort_pairs(m.key, m.perm, m.key_tmp, m.perm_tmp, n_faces, mcl_bits(n_faces), m.sort_ws, adfp_sort_workspace_bytes(n_faces), stream);
+    if (rc) return rc;
+    MclSeg s;
+    s.key = m.key; s.perm = m.perm; s.area = m.area; s.n = nf; s.nf = nf; s.ntiles = (int)T; s.comp_area = m.comp_area;
+    s.tile_flag = m.tile_flag; s.tile_sum = m.tile_sum; s.carry = m.carry;
+    hipLaunchKernelGGL(k_mcl_seg<0>, dim3(T), block, 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mcl_seg_carry, dim3(1), dim3(64), 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mcl_seg<1>, dim3(T), block, 0, st, s);
+    ADFP_CHECK_LAUNCH();
+    if (largest) {
+        MclBest b;
+        const unsigned nb = grid.x < MCL_BEST_BLOCKS ? grid.x : MCL_BEST_BLOCKS;
+        b.labels = labels; b.val = m.comp_area; b.lab = nullptr; b.n = nf; b.out_val = m.part_val; b.out_lab = m.part_lab;
+        hipLaunchKernelGGL(k_mcl_best, dim3(nb), block, 0, st, b);
+        ADFP_CHECK_LAUNCH();
+        b.labels = nullptr; b.val = m.part_val; b.lab = m.part_lab; b.n = (int)nb; b.out_val = m.best_val; b.out_lab = m.best_lab;
+        hipLaunchKernelGGL(k_mcl_best, dim3(1), block, 0, st, b);
+        ADFP_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_mcl_keep, grid, block, 0, st, labels, nf, m.comp_area, largest ? m.best_lab : (const int*)nullptr, threshold, keep);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+// compaction workspace: fkeep [F], used [V] (bytes), fpos [F], vpos [V] (ints), tile counts / offsets for the longer of the two
+struct MclCompact { unsigned char* fkeep; unsigned char* used; int* fpos; int* vpos; unsigned* tc; long long* to; };
+static MclCompact mcl_compact_layout(Arena& A, long long nv, long long nf) {
+    MclCompact c;
+    const size_t T = mcl_tiles(nv > nf ? nv : nf);
+    c.fkeep = A.take<unsigned char>((size_t)nf);
+    c.used = A.take<unsigned char>((size_t)nv);
+    c.fpos = A.take<int>((size_t)nf);
+    c.vpos = A.take<int>((size_t)nv);
+    c.tc = A.take<unsigned>(T);
+    c.to = A.take<long long>(T);
+    return c;
+}
+size_t adfp_mesh_compact_workspace_bytes(long long n_verts, long long n_faces) {
+    return n_verts < 0 || n_faces < 0 || mcl_mesh_too_large(n_verts, n_faces) ? 0 : layout_bytes(mcl_compact_layout, n_verts, n_faces);
+}
+
+int adfp_mesh_compact_plan(const int* faces, long long n_faces, long long n_verts, const unsigned char* keep, void* workspace,
+                           size_t workspace_bytes, long long* totals, void* stream) {
+    if (n_faces < 0 || n_verts < 0 || !totals) return ADFP_E_ARG;
+    if (n_faces > 0 && (!faces || !keep)) return ADFP_E_ARG;
+    if ((n_faces > 0 || n_verts > 0) && !workspace) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_compact_workspace_bytes(n_verts, n_faces)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    Arena A(workspace);
+    const MclCompact c = mcl_compact_layout(A, n_verts, n_faces);
+    if (n_verts > 0) { hipError_t e = hipMemsetAsync(c.used, 0, (size_t)n_verts, st); if (e != hipSuccess) return (int)e; }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_mcl_mark, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, (int)n_verts, keep, c.fkeep,
+                           c.used);
+        ADFP_CHECK_LAUNCH();
+    }
+    int rc = mcl_scan(c.used, n_verts, c.tc, c.to, c.vpos, totals, st);
+    if (rc) return rc;
+    return mcl_scan(c.fkeep, n_faces, c.tc, c.to, c.fpos, totals + 1, st);
+}
+
+int adfp_mesh_compact_emit(const float* verts, long long n_verts, const int* faces, long long n_faces, const void* workspace,
+                           size_t workspace_bytes, float* verts_out, long long n_verts_out, int* faces_out, long long n_faces_out, void* stream) {
+    if (n_faces < 0 || n_verts < 0 || n_verts_out < 0 || n_faces_out < 0 || n_verts_out > n_verts || n_faces_out > n_faces) return ADFP_E_ARG;
+    if (n_verts_out == 0 && n_faces_out == 0) return 0;
+    if (!workspace || !verts || (n_faces_out > 0 && (!faces || !faces_out)) || (n_verts_out > 0 && !verts_out)) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_compact_workspace_bytes(n_verts, n_faces)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    Arena A(workspace);
+    const MclCompact c = mcl_compact_layout(A, n_verts, n_faces);
+    if (n_verts_out > 0) {
+        hipLaunchKernelGGL(k_mcl_take_rows, dim3(mcl_blocks(n_verts)), dim3(ADFP_MCL_THREADS), 0, st, verts, (const unsigned char*)nullptr,
+                           (int)n_verts, c.used, c.vpos, verts_out, (unsigned char*)nullptr);
+        ADFP_CHECK_LAUNCH();
+    }
+    if (n_faces_out > 0) {
+        hipLaunchKernelGGL(k_mcl_take_faces, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces, c.fkeep, c.fpos, c.vpos,
+                           (int)n_verts, faces_out);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// merge workspace: key, key_tmp, perm, perm_tmp, gid, first, rep, pos, vmap [V] ints, head, survive [V] bytes, tiles, the sort's
+struct MclMerge { int* key; int* key_tmp; int* perm; int* perm_tmp; int* gid; int* first; int* rep; int* pos; int* vmap;
+                  unsigned char* head; unsigned char* survive; unsigned* tc; long long* to; void* sort_ws; };
+static MclMerge mcl_merge_layout(Arena& A, long long nv) {
+    MclMerge m;
+    int** ints[9] = {&m.key, &m.key_tmp, &m.perm, &m.perm_tmp, &m.gid, &m.first, &m.rep, &m.pos, &m.vmap};
+    for (int k = 0; k < 9; ++k) *ints[k] = A.take<int>((size_t)nv);
+    m.head = A.take<unsigned char>((size_t)nv);
+    m.survive = A.take<unsigned char>((size_t)nv);
+    m.tc = A.take<unsigned>(mcl_tiles(nv));
+    m.to = A.take<long long>(mcl_tiles(nv));
+    m.sort_ws = A.take<char>(adfp_sort_workspace_bytes(nv));
+    return m;
+}
+size_t adfp_mesh_merge_workspace_bytes(long long n_verts) {
+    return n_verts <= 0 || n_verts > RECON_MAX_N ? 0 : layout_bytes(mcl_merge_layout, n_verts);
+}
+
+int adfp_mesh_merge_plan(const float* verts, long long n_verts, void* workspace, size_t workspace_bytes, long long* total, void* stream) {
+    if (n_verts < 0 || !total) return ADFP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_verts == 0) { hipError_t e = hipMemsetAsync(total, 0, sizeof(long long), st); return e == hipSuccess ? 0 : (int)e; }
+    if (!verts || !workspace) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_merge_workspace_bytes(n_verts)) return ADFP_E_WORKSPACE;
+    Arena A(workspace);
+    const MclMerge m = mcl_merge_layout(A, n_verts);
+    const int n = (int)n_verts;
+    const dim3 grid(mcl_blocks(n_verts)), block(ADFP_MCL_THREADS);
+    const unsigned* bits = (const unsigned*)verts;
+    const size_t swb = adfp_sort_workspace_bytes(n_verts);
+    hipLaunchKernelGGL(k_mcl_iota, grid, block, 0, st, m.perm, n);
+    ADFP_CHECK_LAUNCH();
+    for (int ps = 0; ps < 6; ++ps) {                       // 96 key bits in stable passes of 16, the lowest first
+        hipLaunchKernelGGL(k_mcl_bits_key, grid, block, 0, st, bits, m.perm, n, 2 - ps / 2, 16 * (ps & 1), m.key);
+        ADFP_CHECK_LAUNCH();
+        int rc = adfp_sort_pairs(m.key, m.perm, m.key_tmp, m.perm_tmp, n_verts, 16, m.sort_ws, swb, stream);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_mcl_heads, grid, block, 0, st, bits, m.perm, n, m.head);
+    ADFP_CHECK_LAUNCH();
+    int rc = mcl_scan(m.head, n_verts, m.tc, m.to, m.gid, total, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mcl_group_first, grid, block, 0, st, m.perm, n, m.head, m.gid, m.first);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mcl_rep, grid, block, 0, st, m.perm, n, m.head, m.gid, m.first, m.rep, m.survive);
+    ADFP_CHECK_LAUNCH();
+    rc = mcl_scan(m.survive, n_verts, m.tc, m.to, m.pos, total, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mcl_vmap, grid, block, 0, st, m.rep, m.pos, n, m.vmap);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_mesh_merge_emit(const float* verts, const unsigned char* colors, long long n_verts, const int* faces, long long n_faces,
+                         const void* workspace, size_t workspace_bytes, float* verts_out, unsigned char* colors_out, long long n_verts_out,
+                         int* faces_out, void* stream) {
+    if (n_verts < 0 || n_faces < 0 || n_verts_out < 0 || n_verts_out > n_verts) return ADFP_E_ARG;
+    if (n_verts == 0 && n_faces == 0) return 0;
+    if ((n_verts > 0 && (!workspace || !verts || !verts_out)) || (n_faces > 0 && (!faces || !faces_out))) return ADFP_E_ARG;
+    if ((colors != nullptr) != (colors_out != nullptr)) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_mesh_merge_workspace_bytes(n_verts)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    MclMerge m;
+    memset(&m, 0, sizeof(m));
+    if (n_verts > 0) {
+        Arena A(workspace);
+        m = mcl_merge_layout(A, n_verts);
+        hipLaunchKernelGGL(k_mcl_take_rows, dim3(mcl_blocks(n_verts)), dim3(ADFP_MCL_THREADS), 0, st, verts, colors, (int)n_verts, m.survive, m.pos,
+                           verts_out, colors_out);
+        ADFP_CHECK_LAUNCH();
+    }
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_mcl_take_faces, dim3(mcl_blocks(n_faces)), dim3(ADFP_MCL_THREADS), 0, st, faces, (int)n_faces,
+                           (const unsigned char*)nullptr, (const int*)nullptr, m.vmap, (int)n_verts, faces_out);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int adfp_mesh_color_bytes(const float* rgb, long long n, int stride, unsigned char* out, void* stream) {
+    if (n < 0 || stride < 3) return ADFP_E_ARG;
+    if (n == 0) return 0;
+    if (!rgb || !out) return ADFP_E_ARG;
+    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_mcl_color_bytes, dim3(mcl_blocks(n)), dim3(ADFP_MCL_THREADS), 0, (hipStream_t)stream, rgb, n, stride, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+}   // extern "C"

@@ -149,3 +149,76 @@ __global__ __launch_bounds__(ADFP_SHADE_THREADS) void k_shade_hits(ShadeArgs a) 
 #pragma unroll
     for (int c = 0; c < 3; ++c) a.rgb[3 * px + c] = shade_byte(x[c]);
 }
+
+// ---- host side: the launchers ----
+#define SHADE_MAX_PIXELS (1ll << 38)                    // the grid's x stays below 2^31
+static unsigned shade_blocks(long long n) { return (unsigned)ceil_div(n, ADFP_SHADE_THREADS); }
+
+extern "C" {
+
+// face normals [F][3] doubles; key, val, key_tmp, val_tmp [3 F] ints (the corners by vertex); the sort's
+struct VnWork { double* fn; int* key; int* val; int* key_tmp; int* val_tmp; void* sort_ws; };
+static VnWork vn_layout(Arena& A, long long nf) {
+    VnWork w;
+    const size_t ne = 3 * (size_t)nf;
+    w.fn = A.take<double>(ne);
+    w.key = A.take<int>(ne); w.val = A.take<int>(ne); w.key_tmp = A.take<int>(ne); w.val_tmp = A.take<int>(ne);
+    w.sort_ws = A.take<char>(adfp_sort_workspace_bytes((long long)ne));
+    return w;
+}
+size_t adfp_vertex_normals_workspace_bytes(long long n_faces) {
+    return n_faces <= 0 || n_faces > RECON_MAX_N / 3 ? 0 : layout_bytes(vn_layout, n_faces);
+}
+
+int adfp_vertex_normals(const double* verts, long long n_verts, const int* faces, long long n_faces, void* workspace,
+                        size_t workspace_bytes, double* normals, void* stream) {
+    if (n_verts < 0 || n_faces < 0) return ADFP_E_ARG;
+    if (n_verts == 0) return 0;
+    if (!verts || !normals || (n_faces > 0 && (!faces || !workspace))) return ADFP_E_ARG;
+    if (mcl_mesh_too_large(n_verts, n_faces)) return ADFP_E_UNSUPPORTED;
+    if (n_faces > 0 && workspace_bytes < adfp_vertex_normals_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_faces == 0) {
+        hipError_t e = hipMemsetAsync(normals, 0, (size_t)n_verts * 24, st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    const long long ne = 3 * n_faces;
+    Arena A(workspace);
+    const VnWork w = vn_layout(A, n_faces);
+    hipLaunchKernelGGL(k_vn_faces, dim3(shade_blocks(n_faces)), dim3(ADFP_SHADE_THREADS), 0, st, verts, (int)n_verts, faces, (int)n_faces,
+                       w.fn, w.key, w.val);
+    ADFP_CHECK_LAUNCH();
+    int rc = adfp_sort_pairs(w.key, w.val, w.key_tmp, w.val_tmp, ne, mcl_bits(n_verts), w.sort_ws, adfp_sort_workspace_bytes(ne), stream);   // keys in [0, n_verts]
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_vn_sum, dim3(shade_blocks(n_verts)), dim3(ADFP_SHADE_THREADS), 0, st, w.key, w.val, ne, w.fn, (int)n_verts, normals);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_shade_hits(const int* face, const float* bary, long long n_views, int H, int W, const double* verts, long long n_verts,
+                    const int* faces, long long n_faces, const double* c2w, double fx, double fy, double cx, double cy,
+                    const double* vertex_normals, const unsigned char* vertex_colors, const float albedo[3], double ambient,
+                    const unsigned char background[3], int mode, float* normal, unsigned char* rgb, void* stream) {
+    if (n_views < 0 || n_verts < 0 || n_faces < 0 || H <= 0 || W <= 0) return ADFP_E_ARG;
+    if (mode != ADFP_SHADE_COLOR && mode != ADFP_SHADE_SHADED && mode != ADFP_SHADE_NORMAL) return ADFP_E_ARG;
+    if (!(ambient >= 0.0) || !(ambient <= 1.0)) return ADFP_E_ARG;
+    if (!(fx != 0.0) || !(fy != 0.0) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    if (!background || (!vertex_colors && !albedo)) return ADFP_E_ARG;
+    if (n_views == 0 || (!normal && !rgb)) return 0;
+    if (!face || !bary || !c2w || (n_faces > 0 && (!faces || (n_verts > 0 && !verts)))) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    const long long npix = n_views * H * W;
+    if (npix > SHADE_MAX_PIXELS) return ADFP_E_UNSUPPORTED;
+    ShadeArgs a;
+    a.face = face; a.bary = bary; a.npix = npix; a.H = H; a.W = W;
+    a.v = verts; a.nv = (int)n_verts; a.f = faces; a.nf = (int)n_faces;
+    a.c2w = c2w; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.vn = vertex_normals; a.vc = vertex_colors;
+    for (int c = 0; c < 3; ++c) { a.albedo[c] = albedo ? (double)albedo[c] : 0.0; a.bg[c] = background[c]; }
+    a.ambient = ambient; a.mode = mode; a.normal = normal; a.rgb = rgb;
+    hipLaunchKernelGGL(k_shade_hits, dim3(shade_blocks(npix)), dim3(ADFP_SHADE_THREADS), 0, (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+}   // extern "C"

@@ -12,7 +12,7 @@
 //                           and one integer atomic OR
 //   points visible          points x poses: k_cull_seen's f32 frustum test per pair, then for the pairs that pass an any-hit shadow
 //                           ray in the renderer's f64 arithmetic (one lane per point, poses through LDS), the left child first
-//   depth L1 sums (f64)     per view, sum |a - b| of two f32 depth images, reduced as k_metric_partial / k_red_final do
+//   depth L1 sums (f64)     per view, sum |a - b| of two f32 depth images: k_l1_partial, then k_red_final<1> with a view per workgroup
 //
 // The exact contract (camera, intersection, clipping, pruning) is stated in include/adfp.h; tests/depth_ref.py restates it in numpy.
 #pragma once
@@ -384,12 +384,202 @@ __global__ __launch_bounds__(ADFP_RED_THREADS) void k_l1_partial(L1Args a) {
     if (threadIdx.x == 0) a.part[(long long)blockIdx.y * a.nblk + blockIdx.x] = sum;
 }
 
-// out[p] = the partials of view p (grid x) summed in k_red_final's fixed order
-__global__ __launch_bounds__(ADFP_RED_THREADS) void k_l1_final(const double* __restrict__ part, int nblk, double* __restrict__ out) {
-    __shared__ double s_wave[ADFP_RED_THREADS / 64];
-    const double* q = part + (long long)blockIdx.x * nblk;
-    double v = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += ADFP_RED_THREADS) v += q[b];
-    v = red_block_sum(v, s_wave);
-    if (threadIdx.x == 0) out[blockIdx.x] = v;
+// ---- host side: the launchers ----
+static bool tri_leaf_ok(int leaf) { return leaf == 4 || leaf == 8 || leaf == 16; }
+// a triangle is nine doubles (adfp_recon.h: bvh_layout)
+static BvhLayout tri_layout(Arena& A, long long nf, int leaf) { return bvh_layout(A, nf, 9, leaf); }
+
+static TriDev make_tri(const void* bvh, long long n_faces, int leaf, const int** orig = nullptr) {
+    Arena A(bvh);
+    const BvhLayout L = tri_layout(A, n_faces, leaf);
+    TriDev d; d.tri = L.sorted; d.box = L.box;
+    d.nf = (int)n_faces; d.leaf = leaf; d.P = L.P; d.D = L.D;
+    if (orig) *orig = L.orig;
+    return d;
+}
+
+size_t adfp_tri_bvh_bytes(long long n_faces, int leaf) {
+    return n_faces <= 0 || n_faces > RECON_MAX_N || !tri_leaf_ok(leaf) ? 0 : layout_bytes(tri_layout, n_faces, leaf);
+}
+// the face centroids [F][3], then the Morton workspace
+size_t adfp_tri_bvh_build_workspace_bytes(long long n_faces) {
+    if (n_faces <= 0 || n_faces > RECON_MAX_N) return 0;
+    Arena A;
+    A.take<double>(3 * (size_t)n_faces);
+    morton_layout(A, n_faces);
+    return A.bytes();
+}
+
+int adfp_tri_bvh_build(const double* verts, long long n_verts, const int* faces, long long n_faces, int leaf, void* bvh, size_t bvh_bytes,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_verts < 0 || n_faces < 0 || !tri_leaf_ok(leaf)) return ADFP_E_ARG;
+    if (n_faces == 0) return 0;
+    if (!faces || !bvh || !workspace || (n_verts > 0 && !verts)) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf) || workspace_bytes < adfp_tri_bvh_build_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    Arena I(bvh), A(workspace);
+    const BvhLayout L = tri_layout(I, n_faces, leaf);
+    const int nf = (int)n_faces, nv = (int)n_verts;
+    hipStream_t st = (hipStream_t)stream;
+    double* cen = A.take<double>(3 * (size_t)nf);
+    const unsigned nb = nn_blocks(nf);
+    hipLaunchKernelGGL(k_tri_centroids, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, verts, nv, faces, nf, cen);
+    ADFP_CHECK_LAUNCH();
+    const int* perm;
+    int rc = morton_order(cen, nf, A, &perm, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_tri_gather, dim3(nb), dim3(ADFP_NN_THREADS), 0, st, verts, nv, faces, nf, perm, L.sorted, L.orig);
+    ADFP_CHECK_LAUNCH();
+    return nn_boxes(L.sorted, 3ll * nf, 3 * leaf, L.P, L.box, st);      // a triangle is three consecutive points
+}
+
+#define RT_MAX_SIDE 32768
+#define RT_VIEWS_PER_LAUNCH 32768                    // grid y
+static int render_depth_launch(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near,
+                               double far, long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull,
+                               float* depth, void* stream) {
+    if (n_faces < 0 || n_views < 0 || !tri_leaf_ok(leaf) || H <= 0 || W <= 0) return ADFP_E_ARG;
+    if (cull != ADFP_CULL_NONE && cull != ADFP_CULL_BACK && cull != ADFP_CULL_FRONT) return ADFP_E_ARG;
+    if (!(far > 0.0) || !(fx != 0.0) || !(fy != 0.0) || !isfinite(far) || !isfinite(fx) || !isfinite(fy) ||
+        !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    if (n_views == 0) return 0;
+    if (!depth || (n_faces > 0 && (!bvh || !c2w || !near))) return ADFP_E_ARG;
+    if (n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_faces == 0) {
+        hipError_t e = hipMemsetAsync(depth, 0, (size_t)n_views * H * W * sizeof(float), st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    RenderArgs a;
+    a.t = make_tri(bvh, n_faces, leaf);
+    a.c2w = c2w; a.near = near; a.far = far;
+    a.H = H; a.W = W; a.nbx = (int)ceil_div(W, 16); a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.depth = depth;
+    const unsigned nblk = (unsigned)a.nbx * (unsigned)ceil_div(H, 16);
+    void (*const kern)(RenderArgs) = cull == ADFP_CULL_BACK ? k_render_depth<ADFP_CULL_BACK>
+                                     : cull == ADFP_CULL_FRONT ? k_render_depth<ADFP_CULL_FRONT> : k_render_depth<ADFP_CULL_NONE>;
+    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
+        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
+        a.view0 = (int)v0;
+        hipLaunchKernelGGL(kern, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int adfp_render_depth(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
+                      long long n_views, int H, int W, double fx, double fy, double cx, double cy, float* depth, void* stream) {
+    return render_depth_launch(bvh, bvh_bytes, n_faces, leaf, c2w, near, far, n_views, H, W, fx, fy, cx, cy, ADFP_CULL_NONE, depth,
+                               stream);
+}
+
+int adfp_render_depth_cull(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near,
+                           double far, long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull,
+                           float* depth, void* stream) {
+    return render_depth_launch(bvh, bvh_bytes, n_faces, leaf, c2w, near, far, n_views, H, W, fx, fy, cx, cy, cull, depth, stream);
+}
+
+int adfp_render_hits(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* c2w, const double* near, double far,
+                     long long n_views, int H, int W, double fx, double fy, double cx, double cy, int cull, float* depth, int* face,
+                     float* bary, void* stream) {
+    if (n_faces < 0 || n_views < 0 || !tri_leaf_ok(leaf) || H <= 0 || W <= 0) return ADFP_E_ARG;
+    if (cull != ADFP_CULL_NONE && cull != ADFP_CULL_BACK && cull != ADFP_CULL_FRONT) return ADFP_E_ARG;
+    if (!(far > 0.0) || !(fx != 0.0) || !(fy != 0.0) || !isfinite(far) || !isfinite(fx) || !isfinite(fy) ||
+        !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    if (n_views == 0) return 0;
+    if ((!depth && !face && !bary) || (n_faces > 0 && (!bvh || !c2w || !near))) return ADFP_E_ARG;
+    if (n_faces > RECON_MAX_N || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_faces == 0) {                                  // no hit anywhere: 0 / -1 / (0, 0)
+        const size_t npix = (size_t)n_views * H * W;
+        hipError_t e = hipSuccess;
+        if (depth) e = hipMemsetAsync(depth, 0, npix * sizeof(float), st);
+        if (e == hipSuccess && face) e = hipMemsetAsync(face, 0xff, npix * sizeof(int), st);
+        if (e == hipSuccess && bary) e = hipMemsetAsync(bary, 0, npix * 2 * sizeof(float), st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    HitArgs a;
+    a.t = make_tri(bvh, n_faces, leaf, &a.orig);
+    a.c2w = c2w; a.near = near; a.far = far;
+    a.H = H; a.W = W; a.nbx = (int)ceil_div(W, 16); a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.depth = depth; a.face = face; a.bary = bary;
+    const unsigned nblk = (unsigned)a.nbx * (unsigned)ceil_div(H, 16);
+    void (*const kern)(HitArgs) = cull == ADFP_CULL_BACK ? k_render_hits<ADFP_CULL_BACK>
+                                  : cull == ADFP_CULL_FRONT ? k_render_hits<ADFP_CULL_FRONT> : k_render_hits<ADFP_CULL_NONE>;
+    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
+        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
+        a.view0 = (int)v0;
+        hipLaunchKernelGGL(kern, dim3(nblk, (unsigned)nv), dim3(ADFP_RT_THREADS), 0, st, a);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int adfp_views_in_sight(const double* points, long long n_points, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
+                        int W, int H, int* any, void* stream) {
+    if (n_points < 0 || n_poses < 0) return ADFP_E_ARG;
+    if (n_poses == 0) return 0;
+    if (!w2c || !any || (n_points > 0 && !points)) return ADFP_E_ARG;
+    if (n_points > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(any, 0, (size_t)n_poses * sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+    if (n_points == 0) return 0;
+    SightArgs a;
+    a.v = points; a.nv = (int)n_points; a.w2c = w2c; a.np = (int)n_poses;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.any = any;
+    hipLaunchKernelGGL(k_views_in_sight, dim3(nn_blocks(n_points)), dim3(ADFP_NN_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_points_visible(const void* bvh, size_t bvh_bytes, long long n_faces, int leaf, const double* points, long long n_points,
+                        const float* w2c, const double* c2w, long long n_poses, float fx, float fy, float cx, float cy, int W, int H,
+                        double near, double eps, unsigned char* seen, void* stream) {
+    if (n_faces < 0 || n_points < 0 || n_poses < 0 || !tri_leaf_ok(leaf)) return ADFP_E_ARG;
+    if (!(eps >= 0.0) || !isfinite(eps) || !(near >= 0.0) || !isfinite(near) || !(fx != 0.f) || !(fy != 0.f)) return ADFP_E_ARG;
+    if (n_points == 0) return 0;
+    if (!points || !seen || (n_poses > 0 && !w2c) || (n_poses > 0 && n_faces > 0 && (!bvh || !c2w))) return ADFP_E_ARG;
+    if (n_faces > RECON_MAX_N || n_points > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
+    if (n_faces > 0 && bvh_bytes < adfp_tri_bvh_bytes(n_faces, leaf)) return ADFP_E_WORKSPACE;
+    if (n_faces == 0 || n_poses == 0)                     // nothing occludes (or nothing looks): the frustum-only kernel itself
+        return adfp_cull_vertices(points, n_points, w2c, n_poses, fx, fy, cx, cy, W, H, seen, stream);
+    VisibleArgs a;
+    a.t = make_tri(bvh, n_faces, leaf);
+    a.pts = points; a.n = (int)n_points; a.w2c = w2c; a.c2w = c2w; a.np = (int)n_poses;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H;
+    a.near = near; a.eps = eps; a.seen = seen;
+    hipLaunchKernelGGL(k_points_visible, dim3(nn_blocks(n_points)), dim3(ADFP_NN_THREADS), 0,
+                       (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+size_t adfp_depth_l1_workspace_bytes(long long n_views, long long n_pixels) {
+    if (n_views < 0 || n_pixels < 0 || n_pixels > RECON_MAX_N || n_views > RECON_MAX_N) return 0;
+    return (size_t)n_views * red_blocks(n_pixels) * 8;
+}
+
+int adfp_depth_l1_sums(const float* a, const float* b, long long n_views, long long n_pixels, void* workspace, size_t workspace_bytes,
+                       double* out, void* stream) {
+    if (n_views < 0 || n_pixels < 0) return ADFP_E_ARG;
+    if (n_views == 0) return 0;
+    if (!out || !workspace || (n_pixels > 0 && (!a || !b))) return ADFP_E_ARG;
+    if (n_pixels > RECON_MAX_N || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_depth_l1_workspace_bytes(n_views, n_pixels)) return ADFP_E_WORKSPACE;
+    L1Args r;
+    r.a = a; r.b = b; r.n = n_pixels; r.nblk = red_blocks(n_pixels); r.part = (double*)workspace; r.out = out;
+    hipStream_t st = (hipStream_t)stream;
+    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
+        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
+        L1Args c = r;
+        c.a = a + v0 * n_pixels; c.b = b + v0 * n_pixels; c.part = r.part + v0 * r.nblk;
+        hipLaunchKernelGGL(k_l1_partial, dim3((unsigned)r.nblk, (unsigned)nv), dim3(ADFP_RED_THREADS), 0, st, c);
+        ADFP_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_red_final<1>, dim3((unsigned)n_views), dim3(ADFP_RED_THREADS), 0, st, r.part, r.nblk, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
 }

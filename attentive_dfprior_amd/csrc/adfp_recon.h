@@ -24,11 +24,6 @@
 #define ADFP_SCAN_TILE 2048        // elements per workgroup of the area scan (256 threads x 8)
 #define ADFP_CULL_CHUNK 256        // poses per LDS stage of the cull
 
-struct NnLayout {                  // where the pieces of an index live; the same arithmetic on both sides of the ABI
-    long long n; long long nleaves; long long P; int D;
-    size_t off_orig, off_box, bytes;
-};
-
 // squared distance of (x, y, z) to an axis-aligned box [lo, hi]; +inf for an inverted (empty) box.  Never above the squared
 // distance, computed the same way, to any point inside the box: rounding is monotone.
 ADFP_DEV double nn_box_d2(const double* b, double x, double y, double z) {
@@ -263,10 +258,13 @@ __global__ __launch_bounds__(ADFP_RED_THREADS) void k_metric_partial(MetricArgs 
     if (threadIdx.x == 0) { a.part[2 * blockIdx.x] = sum; a.part[2 * blockIdx.x + 1] = cnt; }
 }
 
-// the fixed-order pass over the partials of a reduction of `width` doubles each: out[c] = sum_b part[width b + c]
+// the fixed-order pass over the partials of a reduction of `width` doubles each: out[c] = sum_b part[width b + c].  Workgroup g
+// (grid x) reduces batch g: nblk partials from part + g * WIDTH * nblk into out + g * WIDTH.
 template <int WIDTH>
 __global__ __launch_bounds__(ADFP_RED_THREADS) void k_red_final(const double* __restrict__ part, int nblk, double* __restrict__ out) {
     __shared__ double s_wave[ADFP_RED_THREADS / 64];
+    part += (long long)blockIdx.x * WIDTH * nblk;
+    out += (long long)blockIdx.x * WIDTH;
     for (int c = 0; c < WIDTH; ++c) {
         double v = 0.0;
         for (int b = threadIdx.x; b < nblk; b += ADFP_RED_THREADS) v += part[WIDTH * b + c];
@@ -581,4 +579,213 @@ __global__ __launch_bounds__(ADFP_NN_THREADS) void k_cull_faces(const unsigned c
         k |= ((unsigned)j < (unsigned)nv) ? seen[j] : (unsigned char)0;
     }
     keep[i] = k;
+}
+
+// ---- host side: the launchers ----
+// An index (the NN index over points, the BVH over triangles in adfp_raycast.h): `items` objects of `width` doubles in Morton order,
+// each one's position in the caller's order, and the boxes of a complete binary tree over leaves of `leaf` objects (P leaves, depth D).
+struct BvhLayout { long long P; int D; double* sorted; int* orig; double* box; };
+static BvhLayout bvh_layout(Arena& A, long long items, int width, int leaf) {
+    BvhLayout L;
+    L.P = 1; L.D = 0;
+    while (L.P < ceil_div(items, leaf)) { L.P <<= 1; ++L.D; }
+    L.sorted = A.take<double>((size_t)items * width);
+    L.orig = A.take<int>((size_t)items);
+    L.box = A.take_tail<double>((size_t)(2 * L.P) * 6);
+    return L;
+}
+static unsigned nn_blocks(long long n) { return (unsigned)ceil_div(n, ADFP_NN_THREADS); }
+
+// the Morton ordering of a cloud: bounding-box partials, codes, the stable radix sort; perm <- the sorted order
+struct MortonWork { double* part; int* key; int* val; int* key2; int* val2; int* table; };
+static MortonWork morton_layout(Arena& A, long long n) {
+    MortonWork m;
+    m.part = A.take<double>(ADFP_NN_BB_BLOCKS * 6);
+    m.key = A.take<int>((size_t)n); m.val = A.take<int>((size_t)n); m.key2 = A.take<int>((size_t)n); m.val2 = A.take<int>((size_t)n);
+    m.table = (int*)A.take<char>(adfp_sort_workspace_bytes(n));
+    return m;
+}
+static int morton_order(const double* p, int n, Arena& A, const int** perm, hipStream_t st) {
+    const MortonWork m = morton_layout(A, n);
+    hipLaunchKernelGGL(k_nn_bbox_partial, dim3(ADFP_NN_BB_BLOCKS), dim3(ADFP_NN_THREADS), 0, st, p, n, m.part);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_nn_morton, dim3(nn_blocks(n)), dim3(ADFP_NN_THREADS), 0, st, p, n, m.part, m.key, m.val);
+    ADFP_CHECK_LAUNCH();
+    const int* kf;
+    return radix_sort_pairs(m.key, m.val, m.key2, m.val2, n, 30, m.table, &kf, perm, st);
+}
+static size_t morton_ws_bytes(long long n) { return layout_bytes(morton_layout, n); }
+
+// the boxes of an index over the sorted points sp[0, n): leaves of B points each at the nodes [P, 2 P), then every level above
+static int nn_boxes(const double* sp, long long n, int B, long long P, double* box, hipStream_t st) {
+    hipLaunchKernelGGL(k_nn_leaves, dim3(nn_blocks(P)), dim3(ADFP_NN_THREADS), 0, st, sp, n, B, P, box);
+    ADFP_CHECK_LAUNCH();
+    for (long long first = P >> 1; first >= 1; first >>= 1) {
+        hipLaunchKernelGGL(k_nn_level, dim3(nn_blocks(first)), dim3(ADFP_NN_THREADS), 0, st, first, box);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+size_t adfp_nn_index_bytes(long long n_ref) { return n_ref <= 0 || n_ref > RECON_MAX_N ? 0 : layout_bytes(bvh_layout, n_ref, 3, ADFP_NN_LEAF); }
+size_t adfp_nn_build_workspace_bytes(long long n_ref) { return n_ref <= 0 || n_ref > RECON_MAX_N ? 0 : morton_ws_bytes(n_ref); }
+
+int adfp_nn_build(const double* ref, long long n_ref, void* index, size_t index_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_ref < 0) return ADFP_E_ARG;
+    if (n_ref == 0) return 0;
+    if (!ref || !index || !workspace) return ADFP_E_ARG;
+    if (n_ref > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (index_bytes < adfp_nn_index_bytes(n_ref) || workspace_bytes < adfp_nn_build_workspace_bytes(n_ref)) return ADFP_E_WORKSPACE;
+    Arena I(index), A(workspace);
+    const BvhLayout L = bvh_layout(I, n_ref, 3, ADFP_NN_LEAF);
+    const int n = (int)n_ref;
+    hipStream_t st = (hipStream_t)stream;
+    const int* perm;
+    int rc = morton_order(ref, n, A, &perm, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_nn_gather, dim3(nn_blocks(n)), dim3(ADFP_NN_THREADS), 0, st, ref, n, perm, L.sorted, L.orig);
+    ADFP_CHECK_LAUNCH();
+    return nn_boxes(L.sorted, n, ADFP_NN_LEAF, L.P, L.box, st);
+}
+
+size_t adfp_nn_query_workspace_bytes(long long n_query, int flags) {
+    if (n_query <= 0 || n_query > RECON_MAX_N || !(flags & ADFP_NN_SORT_QUERIES)) return 0;
+    return morton_ws_bytes(n_query);
+}
+
+int adfp_nn_query(const void* index, size_t index_bytes, long long n_ref, const double* query, long long n_query, const double* transform,
+                  double radius, int flags, void* workspace, size_t workspace_bytes, double* dist, int* idx, void* stream) {
+    if (n_ref < 0 || n_query < 0 || (flags & ~ADFP_NN_SORT_QUERIES)) return ADFP_E_ARG;
+    if (!(radius > 0.0)) return ADFP_E_ARG;                                // NaN, zero or negative
+    if (n_query == 0) return 0;
+    if (n_ref == 0 || !index || !query || !dist || !idx) return ADFP_E_ARG;
+    if ((flags & ADFP_NN_SORT_QUERIES) && !workspace) return ADFP_E_ARG;
+    if (n_ref > RECON_MAX_N || n_query > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (index_bytes < adfp_nn_index_bytes(n_ref) || workspace_bytes < adfp_nn_query_workspace_bytes(n_query, flags)) return ADFP_E_WORKSPACE;
+    Arena I(index), A(workspace);
+    const BvhLayout L = bvh_layout(I, n_ref, 3, ADFP_NN_LEAF);
+    hipStream_t st = (hipStream_t)stream;
+    NnQueryArgs a;
+    a.sp = L.sorted; a.orig = L.orig; a.box = L.box;
+    a.n_ref = (int)n_ref; a.P = L.P; a.D = L.D;
+    a.q = query; a.nq = (int)n_query; a.order = nullptr;
+    a.has_t = transform != nullptr;
+    for (int k = 0; k < 12; ++k) a.t[k] = transform ? transform[k] : 0.0;
+    a.best0 = radius * radius;                              // +inf stays +inf
+    a.dist = dist; a.idx = idx;
+    if (flags & ADFP_NN_SORT_QUERIES) {
+        int rc = morton_order(query, (int)n_query, A, &a.order, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_nn_query, dim3(nn_blocks(n_query)), dim3(ADFP_NN_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+static int red_blocks(long long n) {
+    const long long b = ceil_div(n, ADFP_RED_THREADS);
+    return (int)(b < 1 ? 1 : (b > ADFP_RED_MAX_BLOCKS ? ADFP_RED_MAX_BLOCKS : b));
+}
+size_t adfp_recon_reduce_workspace_bytes(long long n) {
+    if (n < 0 || n > RECON_MAX_N) return 0;
+    return (size_t)red_blocks(n) * ADFP_ICP_MOMENTS * 8;
+}
+
+int adfp_nn_metric_sums(const double* dist, long long n, double threshold, void* workspace, size_t workspace_bytes, double* out, void* stream) {
+    if (n < 0 || !out || !workspace || (n > 0 && !dist)) return ADFP_E_ARG;
+    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_recon_reduce_workspace_bytes(n)) return ADFP_E_WORKSPACE;
+    MetricArgs a;
+    a.d = dist; a.n = (int)n; a.th = threshold; a.nblk = red_blocks(n); a.part = (double*)workspace; a.out = out;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_metric_partial, dim3((unsigned)a.nblk), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_red_final<2>, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a.part, a.nblk, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_icp_moments(const double* src, long long n_src, const double* transform, const double* origin, const double* tgt, long long n_tgt,
+                     const int* idx, void* workspace, size_t workspace_bytes, double* out, void* stream) {
+    if (n_src < 0 || n_tgt < 0 || !transform || !origin || !out || !workspace) return ADFP_E_ARG;
+    if (n_src > 0 && (!src || !idx || (n_tgt > 0 && !tgt))) return ADFP_E_ARG;
+    if (n_src > RECON_MAX_N || n_tgt > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_recon_reduce_workspace_bytes(n_src)) return ADFP_E_WORKSPACE;
+    IcpArgs a;
+    a.src = src; a.n_src = (int)n_src; a.tgt = tgt; a.n_tgt = (int)n_tgt; a.idx = idx;
+    for (int k = 0; k < 12; ++k) a.t[k] = transform[k];
+    for (int k = 0; k < 3; ++k) a.org[k] = origin[k];
+    a.nblk = red_blocks(n_src); a.part = (double*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_icp_partial, dim3((unsigned)a.nblk), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_red_final<ADFP_ICP_MOMENTS>, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a.part, a.nblk, out);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+// cum [F]; then tile_sum [tiles + 1] and tile_max [tiles] in one block
+static void surf_layout(Arena& A, long long n_faces, SurfSampleArgs& a) {
+    a.ntiles = (int)ceil_div(n_faces, ADFP_SCAN_TILE);
+    a.cum = A.take<double>((size_t)n_faces);
+    a.tile_sum = A.take_tail<double>(2 * (size_t)a.ntiles + 1);
+    a.tile_max = a.tile_sum + a.ntiles + 1;
+}
+size_t adfp_sample_surface_workspace_bytes(long long n_faces) {
+    SurfSampleArgs a;
+    return n_faces <= 0 || n_faces > RECON_MAX_N ? 0 : layout_bytes(surf_layout, n_faces, a);
+}
+
+int adfp_sample_surface(const double* verts, long long n_verts, const int* faces, long long n_faces, const double* u_face, const double* u_bary,
+                        long long count, void* workspace, size_t workspace_bytes, double* points, int* face_index, void* stream) {
+    if (n_verts < 0 || n_faces < 0 || count < 0) return ADFP_E_ARG;
+    if (count == 0) return 0;
+    if (n_faces == 0 || n_verts == 0 || !verts || !faces || !u_face || !u_bary || !workspace || !points || !face_index) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N || count > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_sample_surface_workspace_bytes(n_faces)) return ADFP_E_WORKSPACE;
+    SurfSampleArgs a;
+    a.v = verts; a.nv = (int)n_verts; a.f = faces; a.nf = (int)n_faces;
+    a.u_face = u_face; a.u_bary = u_bary; a.count = (int)count;
+    Arena A(workspace);
+    surf_layout(A, n_faces, a);
+    a.pts = points; a.face_index = face_index;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_area_tiles, dim3((unsigned)a.ntiles), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_area_tile_scan, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_area_apply, dim3((unsigned)a.ntiles), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_area_tile_max, dim3(1), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sample, dim3((unsigned)ceil_div(count, ADFP_RED_THREADS)), dim3(ADFP_RED_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_cull_vertices(const double* verts, long long n_verts, const float* w2c, long long n_poses, float fx, float fy, float cx, float cy,
+                       int W, int H, unsigned char* seen, void* stream) {
+    if (n_verts < 0 || n_poses < 0) return ADFP_E_ARG;
+    if (n_verts == 0) return 0;
+    if (!verts || !seen || (n_poses > 0 && !w2c)) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_poses > RECON_MAX_N / 12) return ADFP_E_UNSUPPORTED;
+    CullArgs a;
+    a.v = verts; a.nv = (int)n_verts; a.w2c = w2c; a.np = (int)n_poses;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.W = (float)W; a.H = (float)H; a.seen = seen;
+    a.vf = nullptr; a.depth = nullptr; a.dmax = nullptr; a.Wi = W; a.Hi = H; a.rW = 0.f; a.rH = 0.f;
+    hipLaunchKernelGGL(k_cull_seen<ADFP_CULL_RULE_CULL_MESH>, dim3(nn_blocks(n_verts)), dim3(ADFP_NN_THREADS), 0,
+                       (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+int adfp_cull_faces(const unsigned char* seen, long long n_verts, const int* faces, long long n_faces, unsigned char* keep, void* stream) {
+    if (n_verts < 0 || n_faces < 0) return ADFP_E_ARG;
+    if (n_faces == 0) return 0;
+    if (!faces || !keep || (n_verts > 0 && !seen)) return ADFP_E_ARG;
+    if (n_verts > RECON_MAX_N || n_faces > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_cull_faces, dim3(nn_blocks(n_faces)), dim3(ADFP_NN_THREADS), 0,
+                       (hipStream_t)stream, seen, (int)n_verts, faces, (int)n_faces, keep);
+    ADFP_CHECK_LAUNCH();
+    return 0;
 }

@@ -11,6 +11,7 @@
 // include/adfp.h; tests/refuse_ref.py restates it in numpy.
 #pragma once
 #include "adfp_raycast.h"
+#include "adfp_scan.h"
 
 #define ADFP_UNIT 16               // voxels per unit edge (open3d's ScalableTSDFVolume volume_unit_resolution)
 #define ADFP_TOUCH_THREADS 256
@@ -18,6 +19,7 @@
 #define ADFP_VDS_THREADS 256
 #define ADFP_VDS_PER_THREAD 4
 #define ADFP_VDS_TILE (ADFP_VDS_THREADS * ADFP_VDS_PER_THREAD)
+static_assert(ADFP_VDS_THREADS == ADFP_SCAN_THREADS, "the cells are scanned in tiles of ADFP_VDS_TILE points");
 #define ADFP_VDS_SCAN_THREADS 1024
 #define ADFP_VDS_SCAN_PER_THREAD 8
 
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(ADFP_FUSE_THREADS) void k_refuse_integrate(FuseArgs
 struct VdsArgs {
     const double* p; int n; double vmin[3]; double vs; long long dim[3];
     unsigned long long* key64; int* key; int* perm;
-    unsigned* tile_counts; long long* tile_offsets; int ntiles; int* start; long long* total;
+    int* start; long long* total;                  // start[cell] = the sorted position of the cell's first point, total[0] = the cells
     double* out; int* counts;
 };
 
@@ -154,63 +156,11 @@ __global__ __launch_bounds__(ADFP_VDS_THREADS) void k_vds_segment(VdsArgs a, int
     a.key[i] = (int)((a.key64[a.perm[i]] >> shift) & 0x7fffffffull);
 }
 
-ADFP_DEV bool vds_head(const VdsArgs& a, int i) { return i == 0 || a.key64[a.perm[i]] != a.key64[a.perm[i - 1]]; }
-
-// heads (first point of a cell in sorted order) per tile of ADFP_VDS_TILE sorted points
-__global__ __launch_bounds__(ADFP_VDS_THREADS) void k_vds_tile_heads(VdsArgs a) {
-    __shared__ unsigned lds[ADFP_VDS_THREADS / 64];
-    const long long first = (long long)blockIdx.x * ADFP_VDS_TILE + (long long)threadIdx.x * ADFP_VDS_PER_THREAD;
-    unsigned c = 0;
-#pragma unroll
-    for (int q = 0; q < ADFP_VDS_PER_THREAD; ++q) c += (first + q < a.n && vds_head(a, (int)(first + q))) ? 1u : 0u;
-    unsigned tot;
-    mc_block_scan<unsigned, ADFP_VDS_THREADS>(c, tot, lds);
-    if (threadIdx.x == 0) a.tile_counts[blockIdx.x] = tot;
-}
-
-// one workgroup: exclusive prefix of the tile counts; total[0] = the number of cells
-__global__ __launch_bounds__(ADFP_VDS_SCAN_THREADS) void k_vds_tile_scan(VdsArgs a) {
-    __shared__ unsigned long long lds[ADFP_VDS_SCAN_THREADS / 64];
-    unsigned long long carry = 0;
-    const long long per_round = (long long)ADFP_VDS_SCAN_THREADS * ADFP_VDS_SCAN_PER_THREAD;
-    for (long long t0 = 0; t0 < a.ntiles; t0 += per_round) {
-        const long long first = t0 + (long long)threadIdx.x * ADFP_VDS_SCAN_PER_THREAD;
-        unsigned cv[ADFP_VDS_SCAN_PER_THREAD];
-        unsigned long long s = 0;
-#pragma unroll
-        for (int q = 0; q < ADFP_VDS_SCAN_PER_THREAD; ++q) {
-            cv[q] = first + q < a.ntiles ? a.tile_counts[first + q] : 0u;
-            s += cv[q];
-        }
-        unsigned long long tot;
-        unsigned long long o = carry + mc_block_scan<unsigned long long, ADFP_VDS_SCAN_THREADS>(s, tot, lds);
-#pragma unroll
-        for (int q = 0; q < ADFP_VDS_SCAN_PER_THREAD; ++q) {
-            if (first + q < a.ntiles) a.tile_offsets[first + q] = (long long)o;
-            o += cv[q];
-        }
-        carry += tot;
-    }
-    if (threadIdx.x == 0) a.total[0] = (long long)carry;
-}
-
-// start[cell] = the sorted position of the cell's first point
-__global__ __launch_bounds__(ADFP_VDS_THREADS) void k_vds_starts(VdsArgs a) {
-    __shared__ unsigned lds[ADFP_VDS_THREADS / 64];
-    const long long first = (long long)blockIdx.x * ADFP_VDS_TILE + (long long)threadIdx.x * ADFP_VDS_PER_THREAD;
-    bool h[ADFP_VDS_PER_THREAD];
-    unsigned c = 0;
-#pragma unroll
-    for (int q = 0; q < ADFP_VDS_PER_THREAD; ++q) {
-        h[q] = first + q < a.n && vds_head(a, (int)(first + q));
-        c += h[q] ? 1u : 0u;
-    }
-    unsigned tot;
-    long long cell = a.tile_offsets[blockIdx.x] + mc_block_scan<unsigned, ADFP_VDS_THREADS>(c, tot, lds);
-#pragma unroll
-    for (int q = 0; q < ADFP_VDS_PER_THREAD; ++q)
-        if (h[q]) a.start[cell++] = (int)(first + q);
-}
+// the scan's predicate (adfp_scan.h): sorted position i is the first point of its cell
+struct VdsHead {
+    const unsigned long long* key64; const int* perm;
+    ADFP_DEV bool operator()(long long i) const { return i == 0 || key64[perm[i]] != key64[perm[i - 1]]; }
+};
 
 // one lane per cell c < total: the f64 sum of its points in sorted (= input, the sort is stable) order over the count
 __global__ __launch_bounds__(ADFP_VDS_THREADS) void k_vds_mean(VdsArgs a) {
@@ -226,4 +176,137 @@ __global__ __launch_bounds__(ADFP_VDS_THREADS) void k_vds_mean(VdsArgs a) {
     const double k = (double)(e - s);
     a.out[3 * c] = sx / k; a.out[3 * c + 1] = sy / k; a.out[3 * c + 2] = sz / k;
     a.counts[c] = e - s;
+}
+
+// ---- host side: the launchers ----
+static bool box_ok(const int lo[3], const int dim[3], long long* nunits) {
+    long long n = 1;
+    for (int c = 0; c < 3; ++c) {
+        if (dim[c] <= 0) return false;
+        n *= dim[c];
+        if (n > 0x7fffffffll) { *nunits = -1; return true; }
+    }
+    *nunits = n;
+    return true;
+}
+
+int adfp_refuse_touch(const float* depth, long long n_views, int H, int W, const double* c2w, double fx, double fy, double cx, double cy,
+                      int stride, float depth_trunc, double sdf_trunc, double unit_length, const int unit_lo[3], const int unit_dim[3],
+                      unsigned char* touched, int* outside, void* stream) {
+    if (n_views < 0 || H <= 0 || W <= 0 || stride < 1 || !unit_lo || !unit_dim) return ADFP_E_ARG;
+    if (!(fx != 0.0) || !(fy != 0.0) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    if (!(sdf_trunc >= 0.0) || !isfinite(sdf_trunc) || !(unit_length > 0.0) || !isfinite(unit_length) || !(depth_trunc > 0.f))
+        return ADFP_E_ARG;
+    long long nunits = 0;
+    if (!box_ok(unit_lo, unit_dim, &nunits)) return ADFP_E_ARG;
+    if (n_views == 0) return 0;
+    if (!depth || !c2w || !touched || !outside) return ADFP_E_ARG;
+    if (nunits < 0 || H > RT_MAX_SIDE || W > RT_MAX_SIDE || n_views > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(touched, 0, (size_t)n_views * (size_t)nunits, st);
+    if (e != hipSuccess) return (int)e;
+    TouchArgs a;
+    a.depth = depth; a.H = H; a.W = W; a.stride = stride; a.nsx = (int)ceil_div(W, stride); a.nsy = (int)ceil_div(H, stride);
+    a.c2w = c2w; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.depth_trunc = depth_trunc; a.trunc = sdf_trunc; a.unit = unit_length;
+    for (int c = 0; c < 3; ++c) { a.lo[c] = unit_lo[c]; a.dim[c] = unit_dim[c]; }
+    a.nunits = nunits; a.touched = touched; a.outside = outside;
+    const unsigned nblk = (unsigned)ceil_div((long long)a.nsx * a.nsy, ADFP_TOUCH_THREADS);
+    for (long long v0 = 0; v0 < n_views; v0 += RT_VIEWS_PER_LAUNCH) {
+        const long long nv = n_views - v0 < RT_VIEWS_PER_LAUNCH ? n_views - v0 : RT_VIEWS_PER_LAUNCH;
+        a.view0 = (int)v0;
+        hipLaunchKernelGGL(k_refuse_touch, dim3(nblk, (unsigned)nv), dim3(ADFP_TOUCH_THREADS), 0, st, a);
+        ADFP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+#define FUSE_MAX_VIEWS 65536
+int adfp_refuse_integrate(float* tsdf, float* weight, const int unit_lo[3], const int unit_dim[3], double voxel, const int* units,
+                          long long n_units, const float* depth, const float* w2c, const unsigned char* touched, long long n_views, int H,
+                          int W, float fx, float fy, float cx, float cy, float sdf_trunc, float depth_trunc, void* stream) {
+    if (n_units < 0 || n_views < 0 || H <= 0 || W <= 0 || !unit_lo || !unit_dim) return ADFP_E_ARG;
+    if (!(voxel > 0.0) || !isfinite(voxel) || !(sdf_trunc > 0.f) || !isfinite(sdf_trunc) || !(depth_trunc > 0.f)) return ADFP_E_ARG;
+    if (!(fx != 0.f) || !(fy != 0.f) || !isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return ADFP_E_ARG;
+    long long nunits = 0;
+    if (!box_ok(unit_lo, unit_dim, &nunits)) return ADFP_E_ARG;
+    if (n_units == 0 || n_views == 0) return 0;
+    if (!tsdf || !weight || !units || !depth || !w2c || !touched) return ADFP_E_ARG;
+    if (nunits < 0 || n_units > nunits || n_views > FUSE_MAX_VIEWS || H > RT_MAX_SIDE || W > RT_MAX_SIDE) return ADFP_E_UNSUPPORTED;
+    FuseArgs a;
+    a.tsdf = tsdf; a.weight = weight;
+    for (int c = 0; c < 3; ++c) { a.dim[c] = unit_dim[c]; a.org[c] = (long long)unit_lo[c] * ADFP_UNIT; }
+    a.ny = (long long)unit_dim[1] * ADFP_UNIT; a.nz = (long long)unit_dim[2] * ADFP_UNIT; a.nunits = nunits;
+    a.units = units; a.depth = depth; a.w2c = w2c; a.touched = touched; a.n_views = (int)n_views; a.H = H; a.W = W;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.trunc = sdf_trunc; a.inv_trunc = 1.0f / sdf_trunc; a.depth_trunc = depth_trunc;
+    a.safe_w = (float)W - 0.0001f; a.safe_h = (float)H - 0.0001f; a.voxel = voxel;
+    hipLaunchKernelGGL(k_refuse_integrate, dim3((unsigned)n_units), dim3(ADFP_FUSE_THREADS), 0, (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
+#define VDS_MAX_CELLS_PER_AXIS (1ll << 21)
+struct VdsWork { int* key_tmp; int* perm_tmp; unsigned* tile_counts; long long* tile_offsets; void* sort_ws; };
+static VdsWork vds_layout(Arena& A, long long n, VdsArgs& a) {
+    VdsWork w;
+    const size_t N = (size_t)n, T = (size_t)ceil_div(n, ADFP_VDS_TILE);
+    a.key64 = A.take<unsigned long long>(N);
+    a.key = A.take<int>(N); w.key_tmp = A.take<int>(N);
+    a.perm = A.take<int>(N); w.perm_tmp = A.take<int>(N);
+    a.start = A.take<int>(N);
+    w.tile_counts = A.take<unsigned>(T);
+    w.tile_offsets = A.take<long long>(T);
+    w.sort_ws = A.take<char>(adfp_sort_workspace_bytes(n));
+    return w;
+}
+size_t adfp_voxel_down_sample_workspace_bytes(long long n) {
+    VdsArgs a;
+    return n <= 0 || n > RECON_MAX_N ? 0 : layout_bytes(vds_layout, n, a);
+}
+
+int adfp_voxel_down_sample(const double* points, long long n, double voxel_size, const double min_bound[3], const double max_bound[3],
+                           void* workspace, size_t workspace_bytes, double* out, int* counts, long long* total, void* stream) {
+    if (n < 0 || !(voxel_size > 0.0) || !isfinite(voxel_size) || !total) return ADFP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        hipError_t e = hipMemsetAsync(total, 0, sizeof(long long), st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    if (!points || !min_bound || !max_bound || !workspace || !out || !counts) return ADFP_E_ARG;
+    VdsArgs a;
+    unsigned long long ncell = 1;
+    for (int c = 0; c < 3; ++c) {
+        if (!isfinite(min_bound[c]) || !isfinite(max_bound[c]) || !(min_bound[c] <= max_bound[c])) return ADFP_E_ARG;
+        a.vmin[c] = min_bound[c] - voxel_size * 0.5;
+        const double f = floor((max_bound[c] - a.vmin[c]) / voxel_size);
+        if (!(f < (double)VDS_MAX_CELLS_PER_AXIS)) return ADFP_E_UNSUPPORTED;
+        a.dim[c] = (long long)f + 1;
+        ncell *= (unsigned long long)a.dim[c];
+    }
+    if (n > RECON_MAX_N) return ADFP_E_UNSUPPORTED;
+    if (workspace_bytes < adfp_voxel_down_sample_workspace_bytes(n)) return ADFP_E_WORKSPACE;
+    Arena A(workspace);
+    const VdsWork w = vds_layout(A, n, a);
+    const size_t sort_wsb = adfp_sort_workspace_bytes(n);
+    a.p = points; a.n = (int)n; a.vs = voxel_size; a.total = total; a.out = out; a.counts = counts;
+    int bits = 0;
+    while (bits < 64 && ((ncell - 1) >> bits) != 0ull) ++bits;
+    if (bits == 0) bits = 1;
+    const unsigned nb = (unsigned)ceil_div(n, ADFP_VDS_THREADS);
+    hipLaunchKernelGGL(k_vds_keys, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    for (int shift = 0; shift < bits; shift += 31) {                     // LSD: low segment first, every pass stable
+        hipLaunchKernelGGL(k_vds_segment, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a, shift);
+        ADFP_CHECK_LAUNCH();
+        const int kb = bits - shift < 31 ? bits - shift : 31;
+        int rc = adfp_sort_pairs(a.key, a.perm, w.key_tmp, w.perm_tmp, n, kb, w.sort_ws, sort_wsb, stream);
+        if (rc) return rc;
+    }
+    const VdsHead head = {a.key64, a.perm};
+    int rc = scan_items<ADFP_VDS_PER_THREAD, ADFP_VDS_SCAN_THREADS, ADFP_VDS_SCAN_PER_THREAD, true>(head, n, w.tile_counts, w.tile_offsets,
+                                                                                                      a.start, total, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_vds_mean, dim3(nb), dim3(ADFP_VDS_THREADS), 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
 }

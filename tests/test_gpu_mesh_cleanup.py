@@ -242,6 +242,36 @@ def test_merge_coincident_equals_host():
     assert check_merge(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), None) == 0
 
 
+def test_compaction_scans_more_tiles_than_one_round():
+    """k_tile_scan's one workgroup takes 256 x 8 = 2048 tile counts a round and carries the sum into the next round; a tile is 2048
+    flags, so 2048 * 2048 + 1 vertices are the smallest mesh whose vertex scan has a second round (2049 tiles: the carry, and a last
+    round of one tile).  adfp_mesh_compact_plan / _emit raw, against numpy: integers and copies, so equality."""
+    rng = np.random.default_rng(11)
+    nv, nf = 2048 * 2048 + 1, 1_400_000
+    faces = rng.integers(0, nv, size=(nf, 3), dtype=np.int32)
+    keep = rng.random(nf) < 0.5
+    faces[-1] = (nv - 1, 0, nv - 2)
+    keep[-1] = True                                                        # the vertex of the last tile is used
+    verts = rng.standard_normal((nv, 3)).astype(np.float32)
+    used = np.zeros(nv, bool)
+    used[faces[keep]] = True
+    L = M.lib()
+    v, f, k = (torch.from_numpy(a).to(DEV) for a in (verts, faces, keep.astype(np.uint8)))
+    with M._lib.device_guard(v.device):
+        st = M._lib.current_stream(v.device)
+        nbytes = L.adfp_mesh_compact_workspace_bytes(nv, nf)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+        totals = torch.empty(2, dtype=torch.int64, device=DEV)
+        M.check(L.adfp_mesh_compact_plan(M.ptr(f), nf, nv, M.ptr(k), M.ptr(ws), nbytes, M.ptr(totals), st), 'adfp_mesh_compact_plan')
+        assert tuple(totals.tolist()) == (int(used.sum()), int(keep.sum()))
+        vo = torch.empty((int(used.sum()), 3), dtype=torch.float32, device=DEV)
+        fo = torch.empty((int(keep.sum()), 3), dtype=torch.int32, device=DEV)
+        M.check(L.adfp_mesh_compact_emit(M.ptr(v), nv, M.ptr(f), nf, M.ptr(ws), nbytes, M.ptr(vo), vo.shape[0], M.ptr(fo), fo.shape[0], st),
+                'adfp_mesh_compact_emit')
+    assert np.array_equal(vo.cpu().numpy().view(np.int32), verts[used].view(np.int32))
+    assert np.array_equal(fo.cpu().numpy(), (np.cumsum(used) - used)[faces[keep]])
+
+
 def test_color_bytes_equals_numpy():
     rng = np.random.default_rng(4)
     raw = (rng.standard_normal((70001, 4)) * 0.7 + 0.5).astype(np.float32)

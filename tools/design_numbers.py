@@ -75,6 +75,7 @@ def main(template, d):
         v['mb_gmh' + res] = '%.0f' % g['get_bound_planes_host']['median_ms']
         v['mb_share' + res] = '%.1f' % (100 * g['bound_share_of_get_mesh'])
     ks = stats(P('mesh_bound_kernels.csv'))
+    # (the recorded trace is of the build that introduced the bound: its tile scan ran as k_mcl_tile_scan, today's k_tile_scan)
     for name in ('k_bnd_support(', 'k_bnd_support_fold', 'k_bnd_flag', 'k_bnd_emit', 'k_bnd_far<0>', 'k_bnd_far<1>', 'k_mcl_tile_scan'):
         r = next((r for k, r in ks.items() if name in k), None)
         if r:
