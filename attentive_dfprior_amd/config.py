@@ -1,0 +1,38 @@
+"""Drop-in for the reference's ``src/config.py``: ``load_config(path, default_path=None)`` with its ``inherit_from`` chain and
+recursive update, ``update_recursive`` and ``get_model(cfg)``.  yaml alone is needed: the reference's module imports ``conv_onet``.
+
+The run and every tool of this package take the default config as ``configs/df_prior.yaml`` relative to the working directory
+(``--default_config`` replaces it), as the reference's ``run.py`` does."""
+import yaml
+
+from . import get_model  # noqa: F401  (src/config.py:63-78 forwards to the same factory)
+
+DEFAULT_CONFIG = 'configs/df_prior.yaml'
+
+
+def load_config(path, default_path=None):
+    """The config of `path` merged over what it inherits: its ``inherit_from`` file (recursively), else `default_path`, else
+    nothing (src/config.py:10-42)."""
+    with open(path, 'r') as f:
+        cfg_special = yaml.full_load(f)
+    inherit_from = cfg_special.get('inherit_from')
+    if inherit_from is not None:
+        cfg = load_config(inherit_from, default_path)
+    elif default_path is not None:
+        with open(default_path, 'r') as f:
+            cfg = yaml.full_load(f)
+    else:
+        cfg = dict()
+    update_recursive(cfg, cfg_special)
+    return cfg
+
+
+def update_recursive(dict1, dict2):
+    """`dict2`'s entries written into `dict1`, dictionaries merged key by key (src/config.py:45-59)."""
+    for k, v in dict2.items():
+        if k not in dict1:
+            dict1[k] = dict()
+        if isinstance(v, dict):
+            update_recursive(dict1[k], v)
+        else:
+            dict1[k] = v

@@ -19,6 +19,7 @@ def stats(path):
 def main(template, d):
     v = {}
     P = lambda n: os.path.join(d, n)
+    rb_path = P('run_bench.json')
     # the Mesher's tail: host methods against the device path (tools/mesh_bench.py)
     mt = json.load(open(P('mesh_tail_bench.json')))['by_resolution']
 
@@ -328,6 +329,36 @@ def main(template, d):
         v['tc_volumes'] = 'No run of `tools/tsdfcast_bench.py` is in `profiles/`: none of these times has been measured.'
         v['tc_bitmaps'] = 'It is 49 KB for room0 and 93 KB for office0 (one bit per 8³ voxels of 758 × 574 × 451 and 738 × 779 × 656)'
         v['tc_reps'] = '5'; v['tc_samples'] = 'about 1 300'; v['tc_parity'] = 'not measured'
+    # the whole run: where a frame's time goes (tools/run_bench.py)
+    if os.path.exists(rb_path):
+        rb = json.load(open(rb_path))
+        a, n, o = rb['decode_ahead'], rb['no_decode_ahead'], rb['online_prior']
+        rows = ['| | decode-ahead | no decode-ahead | `--prior online` |', '|---|---|---|---|']
+        for label, key, fmt in (('tracked frame: fetch + tracking, ms', 'track_frame_ms', '%.2f'), ('… of which tracking (10 replays, the pose download)', 'track_only_ms', '%.2f'),
+                                ('… of which fetch (wait for the decode, upload, ingest)', 'fetch_ms', '%.2f'),
+                                ('tracked frame right after a mapped one (graphs re-captured), ms', 'track_frame_after_map_ms', '%.2f'),
+                                ('mapped frame, ordinary (60 iterations, selection, masks), ms', 'map_frame_ms', '%.2f'),
+                                ('mapped frame 0 (1500 iterations, captures), ms', 'map_first_frame_ms', '%.0f'),
+                                ('last frame (colour refinement, checkpoint, 128³ mesh), ms', 'map_last_frame_ms', '%.0f'),
+                                ('host decode of one frame (JPEG + PNG), ms', 'decode_ms', '%.2f'), ('… the loop waited for it, ms', 'decode_wait_ms', '%.2f'),
+                                ('GPU-idle share of a tracked frame (lower bound)', 'gpu_idle_share', '%.2f'), ('whole run of %d frames, s' % a['frames'], 'wall_s', '%.2f')):
+            rows.append('| %s | %s |' % (label, ' | '.join((fmt % r[key]) if r.get(key) is not None else '' for r in (a, n, o))))
+        relay = ('%.2f ms' % o['relay_corner_blocks_ms']) if o.get('relay_corner_blocks_ms') is not None else 'not taken (no corner-block copy)'
+        v['rb_numbers'] = ('Measured on one MI355X (`profiles/run_bench.json`; volume %s voxels, medians over the frames of one run each):\n\n' % ' × '.join(str(x) for x in rb['volume'])
+                           + '\n'.join(rows) + '\n\n'
+                           + 'The tracked frame\'s %d iterations replayed back to back take %.2f ms between two events (%.2f ms each; `README.md` quotes 0.15 ms), '
+                             'so the GPU is idle for at least %.0f %% of a tracked frame with decode-ahead and %.0f %% without.  '
+                             'The decode (%.1f ms) is the largest single item of a tracked frame, as expected, but it is not several times the rest: decode-ahead hides %.1f of '
+                             'its %.1f ms and takes the tracked frame from %.2f to %.2f ms.  '
+                             'Online prior, per mapped frame: one integrate %.2f ms and one full re-lay of the %.1f GB corner-block copy %s, each timed alone with synchronises; '
+                             'the mapped frame is %.2f ms longer than with the fused prior (%.2f against %.2f ms), %.0f %% of it -- not material beside 60 iterations, '
+                             'so the incremental re-lay is not the next thing to build.'
+                           % (rb['iterations']['tracking'][0], a['track_gpu_ms'], a['track_gpu_ms'] / rb['iterations']['tracking'][0], 100 * a['gpu_idle_share'], 100 * n['gpu_idle_share'],
+                              a['decode_ms'], n['decode_wait_ms'] - a['decode_wait_ms'], n['decode_wait_ms'], n['track_frame_ms'], a['track_frame_ms'],
+                              o['integrate_ms'], o['corner_block_bytes'] / 1e9, relay, o['map_frame_minus_fused_prior_ms'], o['map_frame_ms'], a['map_frame_ms'],
+                              100 * o['map_frame_minus_fused_prior_ms'] / o['map_frame_ms']))
+    else:
+        v['rb_numbers'] = 'No run of `tools/run_bench.py` is in `profiles/`: not measured.'
     s = open(template).read()
     out = re.sub(r'@@(\w+)@@', lambda m: v.get(m.group(1), m.group(0)), s)
     sys.stdout.write(out)
