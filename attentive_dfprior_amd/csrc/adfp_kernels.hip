@@ -470,6 +470,144 @@ struct RaySampler {
     }
 };
 
+// One LANE per ray: a wave takes 64 consecutive rays, lane r merges the two lists of ray ray0 + r with two pointers.
+// Both lists are monotone (uniform samples run near -> far, surface samples 0.95 d -> 1.05 d), so the sorted union (only the values
+// matter: torch.sort, Renderer.py:220) is their merge; ties go to the uniform element like a stable sort of the concatenation.
+// The heads zu(i), zs(j) are computed on demand, nothing else is kept per lane.
+// Rounds 4-6: a wave took four rays in turn, lane e computed element e, staged it in LDS and found its rank with a six-step binary
+// search through LDS -- ~150 wave instructions and a chain of dependent LDS round trips PER RAY over 76 800 waves a frame; here a
+// wave spends ~40 instructions per output slot on 64 rays at once and the chain holds no LDS read.
+// A lane's row is S * 8 bytes, so the rows leave through LDS: 8 slots of the wave's 64 rows are staged (64 x 8 doubles per wave,
+// column (c + (r >> 2)) & 7 of row r: conflict-free for the lane-per-row writes and for the row-major reads, no padding) and
+// written out with consecutive lanes on consecutive doubles of a row (64-byte pieces).  The block's 16 KB also serve the
+// relayout blocks' tile.
+// Degenerate rays (descending lists: far < near when the ray leaves the bound at once; NaN samples: NaN far plane, lindisp with a
+// zero sensor depth gives inf * 0 in the last uniform sample -- torch.sort orders NaN after every number) cannot be merged.  The
+// merge itself finds them: its output is the stable sort exactly when it comes out non-decreasing and free of NaN (one compare per
+// slot).  Such rays are redone after the wave's merge pass, one at a time and wave-wide, with the O(S^2) count.
+#define ADFP_SAMPLE_RAYS_PER_BLOCK 256
+// below this many rays the launch is k_sample_small (where the two forms cross)
+#ifndef ADFP_SAMPLE_MERGE_MIN_RAYS
+#define ADFP_SAMPLE_MERGE_MIN_RAYS 40000
+#endif
+__global__ __launch_bounds__(256) void k_sample(SampleArgs a) {
+    __shared__ __attribute__((aligned(16))) double stage[4][64 * 8];
+    static_assert(sizeof(stage) >= sizeof(float) * 32 * 65, "the relayout tile lives in the staging rows");
+    static_assert(64 * 8 >= ADFP_MAX_SAMPLES, "a degenerate ray's row is recounted in the wave's staging rows");
+    if ((int)blockIdx.x >= a.nb_sample) {              // block-uniform: the launch's grid-conversion blocks
+        relayout_multi_block<false>(a.rl, blockIdx.x - (unsigned)a.nb_sample, reinterpret_cast<float (*)[65]>(&stage[0][0]));
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int ray0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+    if (ray0 >= a.n_rays) return;                      // wave-uniform; no block-wide barrier below
+    double* v = stage[threadIdx.x >> 6];
+    const bool has_depth = a.depth != nullptr;
+    const bool live = ray0 + lane < a.n_rays;
+    const int ray = live ? ray0 + lane : a.n_rays - 1;   // clamped: every lane does valid loads, its stores are masked
+    RaySampler rs;
+    rs.ns = a.n_samples; rs.lindisp = a.lindisp != 0; rs.perturb = a.perturb > 0.f;
+    rs.has_depth = has_depth;
+    rs.nf = has_depth ? a.n_surface : 0;
+    rs.trand = a.t_rand ? a.t_rand + (long long)ray * a.n_samples : nullptr;
+    const int S = rs.ns + rs.nf;
+    float dmaxf = 0.f;
+    rs.dep = 0.f;
+    if (has_depth) {
+        rs.dep = a.depth[ray];
+        const int sg = a.dmax_seg > 0 ? (a.dmax_first + ray) / a.dmax_seg : 0;
+        if (a.dmax_parts) {                             // fold the segment's partial maxima (max is exact: any order)
+            unsigned pm = 0u;
+#pragma unroll
+            for (int p = 0; p < SEGMAX_PARTS; ++p) { const unsigned q = a.dmax_parts[sg * SEGMAX_PARTS + p]; pm = q > pm ? q : pm; }
+            dmaxf = ord2f(pm);
+        } else dmaxf = a.dmax_f ? a.dmax_f[sg] : ord2f(a.dmax_ord[sg]);
+    }
+    rs.dmax = (double)dmaxf;
+    rs.nearf = __fmul_rn(rs.dep, 0.01f);
+    {
+        // far_bb = min_axis max_side (bound - o)/d + 0.01   (Renderer.py:151-156), f64.  torch.max / torch.min propagate NaN (0/0: a
+        // zero direction component with the origin on that bound plane; inf/inf), and so does torch.clamp below -- the whole ray
+        // then samples NaN like the reference's
+        double far_bb = INFINITY;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double o = (double)a.ro[3 * ray + k], d = (double)a.rd[3 * ray + k];
+            const double t0 = (a.b[2 * k] - o) / d, t1 = (a.b[2 * k + 1] - o) / d;
+            const double tm = (t0 != t0 || t1 != t1) ? (double)NAN : (t0 > t1 ? t0 : t1);
+            far_bb = (tm != tm || far_bb != far_bb) ? (double)NAN : (tm < far_bb ? tm : far_bb);
+        }
+        far_bb += 0.01;
+        if (has_depth) {
+            const double hi = (double)__fmul_rn(dmaxf, 1.2f);
+            double f = far_bb < 0.0 ? 0.0 : far_bb;       // clamp(far_bb, 0, max(gt_depth*1.2))
+            rs.far = f > hi ? hi : f;
+        } else rs.far = far_bb;
+    }
+    // ---- the merge: slot k takes the uniform head if the surface list is used up or the uniform head is not the larger
+    int i = 0, j = 0;
+    double hu = rs.zu(0), hs = rs.nf > 0 ? rs.zs(0) : 0.0;
+    double prev = -INFINITY;
+    bool bad = false;
+    const int sw = lane >> 2;                          // the row's column rotation in the staging rows
+    for (int k0 = 0; k0 < S; k0 += 8) {
+        // the rows are the wave's own: LDS executes a wave's accesses in order, the fences keep the compiler from moving them
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            if (k0 + c >= S) break;                    // wave-uniform
+            const bool tu = j == rs.nf || (i < rs.ns && hu <= hs);
+            const double val = tu ? hu : hs;
+            bad |= !(val >= prev);                     // a descending step or a NaN: not a merge of two ascending lists
+            prev = val;
+            if (tu) { if (++i < rs.ns) hu = rs.zu(i); }
+            else    { if (++j < rs.nf) hs = rs.zs(j); }
+            v[lane * 8 + ((c + sw) & 7)] = val;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const int row = 8 * t + (lane >> 3), c = lane & 7;
+            if (ray0 + row < a.n_rays && k0 + c < S)
+                a.z[(long long)(ray0 + row) * S + k0 + c] = v[row * 8 + ((c + (row >> 2)) & 7)];
+        }
+    }
+    unsigned long long redo = __ballot(bad && live && rs.nf > 0);     // nf == 0: no sort in the reference either, the row stays as it is
+    if (redo == 0ull) return;
+    // ---- degenerate rays.  Their merged rows are in flight to the same addresses: the recount's stores go after them
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    const double far_l = rs.far; const float dep_l = rs.dep;
+    while (redo) {
+        const int r = __builtin_ctzll(redo);
+        redo &= redo - 1ull;
+        const int rray = ray0 + r;
+        rs.far = readlane_f64(far_l, r);
+        rs.dep = readlane_f32(dep_l, r);
+        rs.dmax = (double)readlane_f32(dmaxf, r);
+        rs.nearf = __fmul_rn(rs.dep, 0.01f);
+        rs.trand = a.t_rand ? a.t_rand + (long long)rray * a.n_samples : nullptr;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int e = lane; e < S; e += 64) v[e] = e < rs.ns ? rs.zu(e) : rs.zs(e - rs.ns);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        double* zrow = a.z + (long long)rray * S;
+        for (int e = lane; e < S; e += 64) {
+            const double val = v[e];
+            const bool vn = val != val;
+            int rank = 0;
+            for (int k = 0; k < S; ++k) {
+                const double o = v[k];
+                const bool on = o != o;
+                const bool less = vn ? !on : (o < val);                  // every number sorts before a NaN
+                const bool same = vn ? on : (o == val);
+                rank += less || (same && k < e);
+            }
+            zrow[rank] = val;
+        }
+    }
+}
+
+// SMALL batches (fewer than ADFP_SAMPLE_MERGE_MIN_RAYS rays: a Tracker or Mapper batch).  k_sample's merge is a serial chain of S steps
+// per lane whatever the batch -- ~20 us where this form takes 8 (200 rays) -- and pays only once the chip is full of rays.
 // One wave per ADFP_SAMPLE_RPW consecutive rays.  Lane e computes merged-list element e of the current ray (uniform e < ns, surface
 // otherwise), stages it in the wave's LDS row, and finds its rank in the sorted union by counting (only the values matter:
 // torch.sort, Renderer.py:220).
@@ -481,7 +619,7 @@ struct RaySampler {
 #ifndef ADFP_SAMPLE_RPW
 #define ADFP_SAMPLE_RPW 4
 #endif
-__global__ __launch_bounds__(256) void k_sample(SampleArgs a) {
+__global__ __launch_bounds__(256) void k_sample_small(SampleArgs a) {
     constexpr int RPW = ADFP_SAMPLE_RPW;
     static_assert(RPW == 1 || RPW == 2 || RPW == 4, "16 lanes per ray");
     if ((int)blockIdx.x >= a.nb_sample) {              // block-uniform: the launch's grid-conversion blocks
@@ -1574,11 +1712,13 @@ static int sample_rays_impl(const float* rays_o, const float* rays_d, const floa
         ADFP_CHECK_LAUNCH();
         a.dmax_ord = (const unsigned*)scratch;
     }
-    a.nb_sample = (n_rays + 4 * ADFP_SAMPLE_RPW - 1) / (4 * ADFP_SAMPLE_RPW);
+    const bool merge = n_rays >= ADFP_SAMPLE_MERGE_MIN_RAYS;
+    a.nb_sample = merge ? (n_rays + ADFP_SAMPLE_RAYS_PER_BLOCK - 1) / ADFP_SAMPLE_RAYS_PER_BLOCK : (n_rays + 4 * ADFP_SAMPLE_RPW - 1) / (4 * ADFP_SAMPLE_RPW);
     a.rl.n = 0;
     unsigned nb_rl = 0;
     if (relayout && relayout->n > 0) { a.rl = *relayout; nb_rl = relayout->first[relayout->n]; }
-    hipLaunchKernelGGL(k_sample, dim3((unsigned)a.nb_sample + nb_rl), dim3(256), 0, st, a);
+    if (merge) hipLaunchKernelGGL(k_sample, dim3((unsigned)a.nb_sample + nb_rl), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_sample_small, dim3((unsigned)a.nb_sample + nb_rl), dim3(256), 0, st, a);
     ADFP_CHECK_LAUNCH();
     return 0;
 }
