@@ -162,9 +162,13 @@ ADFP_DEV void mfma_chain_g(f32x4g acc[2][2], const unsigned* __restrict__ w, con
 ADFP_DEV void row_store(float* p, const f32x4 v) {
     *(f32x4*)p = v;
 }
-template <int CDIM, int NOUT, int TRAIN = 0>
+// after_gather(): called once the grid features are in registers and before the Fourier features and the layers -- where a tile loop
+// that fetches its NEXT tile's front one tile ahead issues those loads (k_decode_high_g): the network then runs over their latency.
+struct NoHook { ADFP_DEV void operator()() const {} };
+template <int CDIM, int NOUT, int TRAIN = 0, typename HOOK = NoHook>
 ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& grid, const GridDev& grid1, const float pn[3], const float (*pf)[3],
-                           int lane, float& amax, float (*out)[NOUT], unsigned* __restrict__ mw, float* srow0, unsigned rowbits) {
+                           int lane, float& amax, float (*out)[NOUT], unsigned* __restrict__ mw, float* srow0, unsigned rowbits,
+                           const HOOK& after_gather = HOOK()) {
     using L = DecLayoutG<CDIM, NOUT>;
     using ST = DecStage<CDIM>;
     const int g = lane >> 4;
@@ -198,6 +202,7 @@ ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& gri
         split8(x, ch[kc][0], cl[kc][0], amax);      // block 0: channels unit16(8 g + j)
         split8(y, ch[kc][1], cl[kc][1], amax);      // block 1
     }
+    after_gather();
     f16x8 eh[L::KG_E][2], el[L::KG_E][2];
 #pragma unroll
     for (int kg = 0; kg < L::KG_E; ++kg) {
@@ -306,7 +311,11 @@ ADFP_DEV void decode_net_g(const unsigned* __restrict__ ldsu, const GridDev& gri
 // VGPRs); with the image's word offset an opaque per-tile register value (off_low / off_col below) every access is
 // (offset + lane term) + small immediate again, and nothing that derives from it is loop invariant.
 // =============================================================================================
-template <int NT>
+//
+// RAYS (the launch's points are rays_o + rays_d * z_vals, P.mode == ADFP_PTS_RAYS -- the host picks the instantiation): the tile's z,
+// ro, rd and flags loads are issued back to back and waited for ONCE; with the mode and the flags pointer tested inside the loop
+// they were three dependent round trips (z + ro | rd | flags) at the head of every tile.
+template <int NT, bool RAYS>
 __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16(DecodeLCArgs a) {
     using LL = DecLayoutG<32, 1>;
     using LC = DecLayoutG<32, 4>;
@@ -335,11 +344,23 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16(DecodeLCArgs a) {
         bool pnan, keep_occ;                            // of the FRONT point: its lane with g & 1 == 0 stores the row
         {
             double pt[3];
-            load_point(a.P, q, pt);
+            unsigned f;
+            if constexpr (RAYS) {
+                // no branch between the loads: without flags the byte is read from the point's own z (any valid address) and dropped
+                RayFront fr;
+                ray_point_issue(a.P, q, fr);
+                const unsigned char* fp = a.flags ? a.flags + q : (const unsigned char*)(a.P.z + q);
+                const unsigned fb = *fp;
+                __builtin_amdgcn_sched_barrier(0);      // every load of the tile's head is issued above this line
+                ray_point_finish(fr, pt);
+                f = a.flags ? fb : 0u;
+            } else {
+                load_point(a.P, q, pt);
+                f = a.flags ? a.flags[q] : 0u;
+            }
             normalize3(a.nb, pt, pn);
             const float f0 = (float)pt[0], f1 = (float)pt[1], f2 = (float)pt[2];   // p.float() decoder.py:189
             pnan = (pt[0] != pt[0]) | (pt[1] != pt[1]) | (pt[2] != pt[2]);
-            const unsigned f = a.flags ? a.flags[q] : 0u;
             // in-band points keep the true low value for the HIGH pass; the attention pass overwrites them afterwards
             keep_occ = (f & ADFP_F_BAND) || in_bound(pt, a.b) || !a.apply_bound;           // Renderer.py:64
             pf[0][0] = f0; pf[0][1] = f1; pf[0][2] = f2; pf[1][0] = f0; pf[1][1] = f1; pf[1][2] = f2;
@@ -473,7 +494,14 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_lc16_train(DecodeLCTrai
 // The HIGH decoder on the in-band list (inference) in the G layout: DecodeArgs is k_decode_h's, a.packed points at the G image.
 // A tile is 32 consecutive LIST entries; the front point of a lane is entry 16 (g >> 1) + n of its tile.
 // =============================================================================================
-template <int NT>
+//
+// RAYS (P.mode == ADFP_PTS_RAYS, the host picks the instantiation): the front of a tile is a chain of dependent loads -- list[idx],
+// then z[q], ro / rd[q / S] and raw[4 q + 3] -- and the kernel runs two waves per SIMD, so one other wave is all that covers it.
+// The loop therefore fetches the NEXT tile's front while the current tile computes: the next tile is claimed at the top of the
+// current one and its list entry requested; once the current tile's grid features are gathered (the entry has arrived by then)
+// the next tile's z, ro, rd and low-decoder value are requested, and the network's layers run over their latency.  A tile starts
+// with ONE wait, for loads that have been in flight since the previous tile's gather.  Carried across the network: 10 registers.
+template <int NT, bool RAYS>
 __global__ __launch_bounds__(NT, NT / 256) void k_decode_high_g(DecodeArgs a) {
     using L = DecLayoutG<64, 1>;
     __shared__ __attribute__((aligned(16))) unsigned ldsu[L::P_TOTAL];
@@ -488,31 +516,77 @@ __global__ __launch_bounds__(NT, NT / 256) void k_decode_high_g(DecodeArgs a) {
     const int ntiles = (count + 31) >> 5;
     const TilePlan plan = tile_plan(ntiles, (int)gridDim.x, NT / 64, a.pool != nullptr);
     float amax = image_out_of_range<L::P_FLAG, L::NFLAG>(ldsu) ? INFINITY : 0.f;
-    for (int j = threadIdx.x >> 6, tile; (tile = claim_tile_pool<NT / 64>(j, &s_next, s_ring, plan, ntiles, a.pool, a.status)) >= 0;) {
-        const int idx = tile * 32 + 16 * (g >> 1) + n;
-        const bool valid = idx < count;
-        const int q = a.list[valid ? idx : 0];
-        float pn[3], pf[2][3];
-        bool pnan;
-        // the point's low-decoder value (added to the output at the end of the tile): requested NOW -- waited for after the network
-        // it was a full memory latency per tile with nothing in flight (13 % of the wave's tile time)
-        const float low_occ = (a.single || !valid) ? 0.f : a.raw[4ll * q + 3];
-        {
-            double pt[3];
-            load_point(a.P, q, pt);
-            normalize3(a.nb, pt, pn);
-            const float f0 = (float)pt[0], f1 = (float)pt[1], f2 = (float)pt[2];
-            pnan = (pt[0] != pt[0]) | (pt[1] != pt[1]) | (pt[2] != pt[2]);
-            pf[0][0] = f0; pf[0][1] = f1; pf[0][2] = f2; pf[1][0] = f0; pf[1][1] = f1; pf[1][2] = f2;
+    if constexpr (RAYS) {
+        const int lp = 16 * (g >> 1) + n;               // the lane's front point inside its tile
+        int j = threadIdx.x >> 6;
+        int tile = claim_tile_pool<NT / 64>(j, &s_next, s_ring, plan, ntiles, a.pool, a.status);
+        RayFront fr;
+        float low_next = 0.f;
+        // the low-decoder value of entry q, or (one sub-network alone: there is none) a word that is read and dropped
+        auto issue_front = [&](int q) {
+            ray_point_issue(a.P, q, fr);
+            const float* lo = a.single ? (const float*)(a.P.z + q) : a.raw + (4ll * q + 3);
+            low_next = *lo;
+        };
+        if (tile >= 0) {                                // the first tile's front: nothing to hide it behind
+            const int idx = tile * 32 + lp;
+            issue_front(a.list[idx < count ? idx : 0]);
         }
+        while (tile >= 0) {
+            const int idx = tile * 32 + lp;
+            const bool valid = idx < count;
+            // the next tile (none: entry 0 is fetched and dropped -- inside this loop count >= 1 and entry 0 is a point of the batch)
+            const int tile_n = claim_tile_pool<NT / 64>(j, &s_next, s_ring, plan, ntiles, a.pool, a.status);
+            const int idx_n = tile_n * 32 + lp;
+            const int q_n = a.list[(tile_n >= 0 && idx_n < count) ? idx_n : 0];
+            float pn[3], pf[2][3];
+            bool pnan;
+            const float low_occ = a.single ? 0.f : low_next;      // high + low: added at the end of the tile
+            {
+                double pt[3];
+                ray_point_finish(fr, pt);
+                normalize3(a.nb, pt, pn);
+                const float f0 = (float)pt[0], f1 = (float)pt[1], f2 = (float)pt[2];
+                pnan = (pt[0] != pt[0]) | (pt[1] != pt[1]) | (pt[2] != pt[2]);
+                pf[0][0] = f0; pf[0][1] = f1; pf[0][2] = f2; pf[1][0] = f0; pf[1][1] = f1; pf[1][2] = f2;
+            }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) swap_halves(pf[0][k], pf[1][k]);
-        float out[2][1];
-        decode_net_g<64, 1>(ldsu, a.g0, a.g1, pn, pf, lane, amax, out, nullptr, nullptr, 0u);
-        if (valid && (g & 1) == 0) {
-            const float o = g >> 1 ? out[1][0] : out[0][0];
-            const float v = pnan ? __builtin_nanf("") : o;
-            a.att_occ[idx] = a.single ? v : v + low_occ;    // high + low, decoder.py:342
+            for (int k = 0; k < 3; ++k) swap_halves(pf[0][k], pf[1][k]);
+            float out[2][1];
+            decode_net_g<64, 1, 0>(ldsu, a.g0, a.g1, pn, pf, lane, amax, out, nullptr, nullptr, 0u, [&]() { issue_front(q_n); });
+            if (valid && (g & 1) == 0) {
+                const float o = g >> 1 ? out[1][0] : out[0][0];
+                const float v = pnan ? __builtin_nanf("") : o;
+                a.att_occ[idx] = a.single ? v : v + low_occ;    // high + low, decoder.py:342
+            }
+            tile = tile_n;
+        }
+    } else {
+        for (int j = threadIdx.x >> 6, tile; (tile = claim_tile_pool<NT / 64>(j, &s_next, s_ring, plan, ntiles, a.pool, a.status)) >= 0;) {
+            const int idx = tile * 32 + 16 * (g >> 1) + n;
+            const bool valid = idx < count;
+            const int q = a.list[valid ? idx : 0];
+            float pn[3], pf[2][3];
+            bool pnan;
+            // the point's low-decoder value (added to the output at the end of the tile)
+            const float low_occ = (a.single || !valid) ? 0.f : a.raw[4ll * q + 3];
+            {
+                double pt[3];
+                load_point(a.P, q, pt);
+                normalize3(a.nb, pt, pn);
+                const float f0 = (float)pt[0], f1 = (float)pt[1], f2 = (float)pt[2];
+                pnan = (pt[0] != pt[0]) | (pt[1] != pt[1]) | (pt[2] != pt[2]);
+                pf[0][0] = f0; pf[0][1] = f1; pf[0][2] = f2; pf[1][0] = f0; pf[1][1] = f1; pf[1][2] = f2;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) swap_halves(pf[0][k], pf[1][k]);
+            float out[2][1];
+            decode_net_g<64, 1>(ldsu, a.g0, a.g1, pn, pf, lane, amax, out, nullptr, nullptr, 0u);
+            if (valid && (g & 1) == 0) {
+                const float o = g >> 1 ? out[1][0] : out[0][0];
+                const float v = pnan ? __builtin_nanf("") : o;
+                a.att_occ[idx] = a.single ? v : v + low_occ;    // high + low, decoder.py:342
+            }
         }
     }
     report_range(a.status, amax, ADFP_STATUS_F16_RANGE_HIGH, a.call_flag);

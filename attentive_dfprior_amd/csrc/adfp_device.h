@@ -40,13 +40,28 @@ struct PtsDev {
 // ------------------------------------------------------------------------------------
 // pts = rays_o + rays_d * z_vals, f32*f64 -> f64 product then f64 add (Renderer.py:223);
 // written with explicit _rn ops so the compiler cannot contract it into an fma.
+//
+// Ray mode in two halves, so that a tile loop can put the seven loads of a point in flight back to back (with whatever else the tile
+// reads at its head) and pay ONE memory round trip for them: issue = address arithmetic and loads only, finish = the f64 arithmetic.
+// load_point() below is the two halves in a row.  The caller must know that P.mode == ADFP_PTS_RAYS (the persistent inference
+// kernels take it as a template parameter: a branch on P.mode inside the tile loop puts the loads into basic blocks of their own,
+// and the loads of each block are waited for before the next block's are issued).
+struct RayFront { double z; float ro[3], rd[3]; };
+ADFP_DEV void ray_point_issue(const PtsDev& P, int q, RayFront& f) {
+    const int r = (int)((unsigned)q / (unsigned)P.S);
+    f.z = P.z[q];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { f.ro[k] = P.ro[3 * r + k]; f.rd[k] = P.rd[3 * r + k]; }
+}
+ADFP_DEV void ray_point_finish(const RayFront& f, double p[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = __dadd_rn((double)f.ro[k], __dmul_rn((double)f.rd[k], f.z));
+}
 ADFP_DEV void load_point(const PtsDev& P, int q, double p[3]) {
     if (P.mode == ADFP_PTS_RAYS) {
-        const int r = (int)((unsigned)q / (unsigned)P.S);
-        const double z = P.z[q];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            p[k] = __dadd_rn((double)P.ro[3 * r + k], __dmul_rn((double)P.rd[3 * r + k], z));
+        RayFront f;
+        ray_point_issue(P, q, f);
+        ray_point_finish(f, p);
     } else if (P.mode == ADFP_PTS_F64) {
         const double* s = (const double*)P.pts + 3ll * q;
         p[0] = s[0]; p[1] = s[1]; p[2] = s[2];

@@ -1841,7 +1841,8 @@ static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, in
         f.flags = a.flags; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = apply_bound; f.status = sc->status; f.call_flag = call_flag;
         f.pool = ws.counter ? ws.counter + 10 : nullptr;            // zero: this call's 64-byte counter block was cleared above (or by the caller)
         f.packed_low += DecLayoutH<32, 1>::P_TOTAL; f.packed_color += DecLayoutH<32, 4>::P_TOTAL;       // the G images
-        hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
+        if (P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, true>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
+        else hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, false>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
         ADFP_CHECK_LAUNCH();
     }
     // stage color, TRAINING, both networks f16-split with mask room: the same ONE launch, leaving masks (+ layer inputs)
@@ -1903,7 +1904,8 @@ static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, in
         } else if (sc->h_high) {
             a.packed = (const float*)((const unsigned*)sc->h_high + DecLayoutH<64, 1>::P_TOTAL);          // the G image
             a.pool = ws.counter ? ws.counter + 11 : nullptr;
-            hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
+            if (P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT, true>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
+            else hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT, false>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
         } else {
             a.packed = sc->w_high;
             hipLaunchKernelGGL((k_decode<64, 1, ROLE_HIGH, 512>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
@@ -1959,7 +1961,8 @@ extern "C" int adfp_decode_stage(const adfp_scene* sc, const adfp_points* pts, i
         f.flags = nullptr; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = 1; f.status = sc->status; f.call_flag = nullptr; f.pool = tile_counter;
         if (tile_counter) { hipError_t e = zero_async(tile_counter, 4, (hipStream_t)stream); if (e != hipSuccess) return (int)e; }
         f.packed_low += DecLayoutH<32, 1>::P_TOTAL; f.packed_color += DecLayoutH<32, 4>::P_TOTAL;       // the G images
-        hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT>), dim3(decode_grid((P.n + 31) / 32, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, (hipStream_t)stream, f);
+        if (P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, true>), dim3(decode_grid((P.n + 31) / 32, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, (hipStream_t)stream, f);
+        else hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, false>), dim3(decode_grid((P.n + 31) / 32, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, (hipStream_t)stream, f);
         ADFP_CHECK_LAUNCH();
         return 0;
     }

@@ -18,6 +18,7 @@ import bench                                                         # noqa: E40
 import isa_mix                                                       # noqa: E402
 
 OUT = os.path.join(ROOT, 'profiles', 'r06_isa_mix_lc16.txt')
+KERNEL = 'ILi768ELb1E'        # k_decode_lc16<768, true>: the ray-mode instantiation, the one a frame runs
 FLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize']
 
 
@@ -30,10 +31,10 @@ def main():
         buf = io.StringIO()
         with redirect_stdout(buf):
             for loop in (True, False):
-                sys.argv = ['isa_mix.py'] + (['--loop'] if loop else []) + [asm, 'k_decode_lc16', 'ILi768E']
+                sys.argv = ['isa_mix.py'] + (['--loop'] if loop else []) + [asm, 'k_decode_lc16', KERNEL]
                 isa_mix.main()
     with open(OUT, 'w') as f:
-        f.write(f'# source_hash={bench.source_hash()}  tools/gen_isa_mix.py: hipcc {" ".join(FLAGS)} -S --cuda-device-only; tools/isa_mix.py [--loop] k_decode_lc16 ILi768E\n')
+        f.write(f'# source_hash={bench.source_hash()}  tools/gen_isa_mix.py: hipcc {" ".join(FLAGS)} -S --cuda-device-only; tools/isa_mix.py [--loop] k_decode_lc16 {KERNEL}\n')
         f.write('# first entry: the TILE LOOP only (the smallest loop holding every MFMA: one 32-point tile, both networks); second: the whole kernel\n')
         f.write(buf.getvalue())
     print(open(OUT).read()[:1500])
