@@ -73,6 +73,25 @@ class AdfpKeyframe(C.Structure):
 KEYFRAMES_MAX = 16
 
 
+class AdfpBaFrame(C.Structure):
+    _fields_ = [('idx', C.c_void_p), ('c2w', C.c_void_p), ('depth_img', C.c_void_p), ('color_img', C.c_void_p), ('free_pose', C.c_int)]
+
+
+class AdfpBaHeadArgs(C.Structure):
+    _fields_ = [('n_frames', C.c_int), ('n', C.c_int), ('H0', C.c_int), ('H1', C.c_int), ('W0', C.c_int), ('W1', C.c_int),
+                ('H', C.c_int), ('W', C.c_int), ('fx', C.c_float), ('fy', C.c_float), ('cx', C.c_float), ('cy', C.c_float),
+                ('cam', C.c_void_p), ('c2w', C.c_void_p), ('pix_i', C.c_void_p), ('pix_j', C.c_void_p), ('rays_o', C.c_void_p),
+                ('rays_d', C.c_void_p), ('gt_depth', C.c_void_p), ('gt_color', C.c_void_p), ('frames', AdfpBaFrame * KEYFRAMES_MAX)]
+
+
+class AdfpBaTailArgs(C.Structure):
+    _fields_ = [('n_frames', C.c_int), ('n', C.c_int), ('fx', C.c_float), ('fy', C.c_float), ('cx', C.c_float), ('cy', C.c_float),
+                ('pix_i', C.c_void_p), ('pix_j', C.c_void_p), ('g_rays_o', C.c_void_p), ('g_rays_d', C.c_void_p),
+                ('cam', C.c_void_p), ('g_c2w', C.c_void_p), ('g_cam', C.c_void_p), ('free_flags', C.c_void_p), ('step', C.c_int),
+                ('exp_avg', C.c_void_p), ('exp_avg_sq', C.c_void_p), ('derived', C.c_void_p),
+                ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('skip_flag', C.c_void_p)]
+
+
 class AdfpIngestGeom(C.Structure):
     _fields_ = [('color_h', C.c_int), ('color_w', C.c_int), ('depth_h', C.c_int), ('depth_w', C.c_int), ('crop_h', C.c_int), ('crop_w', C.c_int),
                 ('crop_edge', C.c_int), ('color_order', C.c_int), ('depth_kind', C.c_int), ('color_out', C.c_int),
@@ -266,6 +285,9 @@ SYMBOLS = [
                                         C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('adfp_tracker_head', C.c_int, [C.POINTER(AdfpTrackerHeadArgs), C.c_void_p]),
     ('adfp_tracker_tail', C.c_int, [C.POINTER(AdfpTrackerTailArgs), C.c_void_p]),
+    ('adfp_ba_head', C.c_int, [C.POINTER(AdfpBaHeadArgs), C.c_void_p]),
+    ('adfp_ba_tail', C.c_int, [C.POINTER(AdfpBaTailArgs), C.c_void_p]),
+    ('adfp_cameras_from_tensors', C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     ('adfp_tracker_loss', C.c_int, [C.POINTER(AdfpTrackLossArgs), C.c_void_p]),
     ('adfp_track_keep_best', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('adfp_sort_workspace_bytes', C.c_size_t, [C.c_longlong]),

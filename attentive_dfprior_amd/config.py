@@ -9,6 +9,16 @@ from . import get_model  # noqa: F401  (src/config.py:63-78 forwards to the same
 
 DEFAULT_CONFIG = 'configs/df_prior.yaml'
 
+# Settings the reference's config files do not carry (it dropped its parent project's bundle adjustment); a config that names
+# them wins.  ``load_config`` returns the files' content unchanged: readers ask ``mapping_setting``.
+MAPPING_DEFAULTS = {'BA': False, 'BA_cam_lr': 0.0002}
+
+
+def mapping_setting(cfg, key):
+    """``cfg['mapping'][key]``, or this package's default for a key the reference's configs do not have."""
+    m = cfg.get('mapping') or {}
+    return m[key] if key in m else MAPPING_DEFAULTS[key]
+
 
 def load_config(path, default_path=None):
     """The config of `path` merged over what it inherits: its ``inherit_from`` file (recursively), else `default_path`, else

@@ -147,6 +147,13 @@ class MapperIteration(object):
     stage_lr    {'low': {'low': lr, 'high': lr, 'color': lr, 'decoders': lr, 'mlp': lr}, 'high': {...}, 'color': {...}}
                 (configs/df_prior.yaml:65-83 times lr_factor)
     train       which networks Adam updates: ('color', 'att') = fix_high: True, fix_color: False (src/Mapper.py:364-371)
+
+    Bundle adjustment (mapping.BA; the reference dropped it, its parent project has it): after ``new_frame``,
+        it.set_ba(camera_tensors, free, BA_cam_lr, frames, H, W, fx, fy, cx, cy)
+        loss = it.step(*it.sample_ba(pixs_per_image), stage, warmup)
+    makes the window's poses one more Adam group: the rays come from the camera tensors (adfp_ba_head), the backward also returns ray
+    cotangents and adfp_ba_tail -- in the sequence right after it -- turns them into ``g_cam`` and steps the poses.  Without ``set_ba``
+    the sequence of launches is the one it has always been.
     """
 
     def __init__(self, renderer, decoders, c, masks, tsdf_volume, tsdf_bnds, stage_lr, w_color_loss=0.2,
@@ -182,8 +189,21 @@ class MapperIteration(object):
         # torch.optim.Adam keeps one step counter PER PARAMETER and advances it only when the parameter has a gradient (the high
         # and colour grids join in later stages): one device counter + derived scalars per group
         self.groups = list(c.keys()) + list(self.nets)
-        self.step_count = torch.zeros(len(self.groups), dtype=torch.int32, device=dev)
-        self.derived = torch.empty((len(self.groups), 2), dtype=torch.float32, device=dev)
+        # ... and behind them the slot of bundle adjustment's pose group (set_ba), which only a BA iteration hands to the kernels
+        ng = len(self.groups)
+        self._steps_all = torch.zeros(ng + 1, dtype=torch.int32, device=dev)
+        self._derived_all = torch.empty((ng + 1, 2), dtype=torch.float32, device=dev)
+        self.step_count, self.derived = self._steps_all[:ng], self._derived_all[:ng]
+        # Bundle adjustment (set_ba): the window's camera tensors, their moments and gradient, the poses made of them and the gauge
+        # flags, in static buffers of ADFP_KEYFRAMES_MAX rows so that captured graphs stay valid from frame to frame
+        KM = _lib.KEYFRAMES_MAX
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.ba_cam, self.ba_g_cam = torch.zeros((KM, 7), **f32), torch.zeros((KM, 7), **f32)
+        self.ba_exp_avg, self.ba_exp_avg_sq = torch.zeros((KM, 7), **f32), torch.zeros((KM, 7), **f32)
+        self.ba_c2w, self.ba_g_c2w = torch.zeros((KM, 16), **f32), torch.zeros((KM, 16), **f32)
+        self.ba_free = torch.zeros((KM,), dtype=torch.uint8, device=dev)
+        self._ba = None                                                  # set_ba's settings of this frame, or None: BA is off
+        self._ba_pix = {}                                                # ray count -> (pix_i, pix_j) static buffers
         self._pool = None
         self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
         self._loss_scratch = {}                                          # ray count -> scratch of adfp_mapper_loss_step (its ticket word starts at zero)
@@ -230,7 +250,8 @@ class MapperIteration(object):
         for m, v in list(self.gstate.values()) + list(self.fstate.values()):
             m.zero_()
             v.zero_()
-        self.step_count.zero_()
+        self._steps_all.zero_()
+        self._ba = None                                       # bundle adjustment is off until set_ba (which zeroes the pose group's moments)
         if masks is not None:
             for k in self.c:
                 if (self.masks[k] is None) != (masks.get(k) is None):
@@ -244,6 +265,143 @@ class MapperIteration(object):
         """Distributed mode with frustum masks: the selected voxels' flat indices, once per frame (one host sync, like the
         reference's own boolean indexing at src/Mapper.py:345-361); identical on every rank, so the compact buckets line up."""
         self._index = {k: (None if m is None else torch.nonzero(m.reshape(-1), as_tuple=False).reshape(-1)) for k, m in self.masks.items()}
+
+    # ---- bundle adjustment ----------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def set_ba(self, cams, free, lr, frames, H, W, fx, fy, cx, cy, window=None):
+        """Turn bundle adjustment on for this frame (call it after ``new_frame``): the poses of the window's frames become one
+        more Adam group behind the existing ones.
+
+        cams    [F,7] camera tensors (``common.get_tensor_from_camera``: quaternion first, then translation), copied
+        free    F bools; a frame that is not free is the gauge: its stored matrix is used verbatim and never stepped
+        lr      ``mapping.BA_cam_lr``: the group's learning rate in stage 'color' (0 in 'low' and 'high', where the group still
+                advances its moments and step counter, like a ``torch.optim.Adam`` group with lr 0 that receives gradients)
+        frames  F tuples (c2w [4,4], depth [H,W], color [H,W,3]) of float32 device tensors: the window's image views and stored
+                poses (``KeyframeStore.frame``); a free frame's c2w is not read
+        window  (H0, H1, W0, W1) the pixels are drawn from, default the whole image
+
+        The rays of an iteration then come from ``sample_ba``; ``step`` also turns the ray cotangents into ``g_cam`` and steps the
+        pose group (adfp_ba_tail); ``camera_tensors`` / ``poses`` read the result."""
+        if self.distributed:
+            raise ValueError('bundle adjustment is not available with distributed=True')
+        F = len(frames)
+        if not 1 <= F <= _lib.KEYFRAMES_MAX:
+            raise ValueError(f'bundle adjustment: a window of {F} frames, 1 .. {_lib.KEYFRAMES_MAX} (ADFP_KEYFRAMES_MAX) are supported')
+        cams = torch.as_tensor(cams).detach().to(self.dev, torch.float32).reshape(-1, 7)
+        free = [bool(v) for v in free]
+        if cams.shape[0] != F or len(free) != F:
+            raise ValueError(f'bundle adjustment: {F} frames, {cams.shape[0]} camera tensors, {len(free)} free flags')
+        H, W = int(H), int(W)
+        window = (0, H, 0, W) if window is None else tuple(int(v) for v in window)
+        views = []
+        for frame in frames:
+            view = []
+            for t, shape, name in zip(frame, ((4, 4), (H, W), (H, W, 3)), ('c2w', 'depth', 'color')):
+                _lib.require_cuda(t, name)
+                if tuple(t.shape) != shape:
+                    raise ValueError(f'bundle adjustment: {name} of shape {tuple(t.shape)}, expected {shape}')
+                view.append(t.detach().float().contiguous())              # the keyframe store's views pass through as they are
+            views.append(tuple(view))
+        with torch.cuda.device(self.dev):
+            self.ba_cam.zero_()
+            self.ba_cam[:F].copy_(cams)
+            self.ba_free.copy_(torch.tensor(free + [False] * (_lib.KEYFRAMES_MAX - F), dtype=torch.uint8), non_blocking=False)
+            self.ba_exp_avg.zero_()
+            self.ba_exp_avg_sq.zero_()
+            self.ba_g_cam.zero_()
+            self._steps_all[len(self.groups):].zero_()
+        self._ba = dict(F=F, free=free, lr=float(lr), frames=views, H=H, W=W, intr=(float(fx), float(fy), float(cx), float(cy)), window=window)
+
+    @staticmethod
+    def ba_stage_lr(stage, lr):
+        """The pose group's learning rate in a stage: ``mapping.BA_cam_lr`` in 'color', 0 in 'low' and 'high'."""
+        return float(lr) if stage == 'color' else 0.0
+
+    @property
+    def ba_active(self):
+        return self._ba is not None
+
+    @property
+    def camera_tensors(self):
+        """[F,7] the window's camera tensors as they stand (a view of the static buffer; the gauge frame's row is never stepped)."""
+        return self.ba_cam[:self._ba['F']]
+
+    @torch.no_grad()
+    def poses(self, dst=None):
+        """The window's poses [F,4,4] made of the camera tensors as they stand (adfp_cameras_from_tensors; the gauge frame's row is
+        its stored matrix).  ``dst``: F tensors [4,4] float32 on the device, or None per frame, written INSTEAD (the keyframe
+        store's rows); then nothing is returned."""
+        ba = self._ba
+        F = ba['F']
+        with torch.cuda.device(self.dev):
+            out = None
+            if dst is None:
+                out = torch.empty((F, 4, 4), dtype=torch.float32, device=self.dev)
+                dst = [out[f] if ba['free'][f] else None for f in range(F)]
+            arr = (C.c_void_p * F)()
+            for f, t in enumerate(dst):
+                if t is not None:
+                    _lib.require_cuda(t, 'dst')
+                    if t.numel() != 16 or t.dtype != torch.float32 or not t.is_contiguous():
+                        raise ValueError('poses: a destination must be a contiguous float32 [4,4]')
+                    arr[f] = t.data_ptr()
+            check(lib().adfp_cameras_from_tensors(F, ptr(self.ba_cam), arr, _lib.current_stream(self.dev)), 'adfp_cameras_from_tensors')
+            if out is not None:
+                for f in range(F):
+                    if not ba['free'][f]:
+                        out[f].copy_(ba['frames'][f][0])
+        return out
+
+    @torch.no_grad()
+    def sample_ba(self, n, pick=None):
+        """The iteration's ray batch with bundle adjustment on: ``n`` random pixels of every window frame through the pose its
+        camera tensor gives NOW (the gauge frame: its stored pose), written by one launch (adfp_ba_head) into ``input_buffers(F n)``,
+        which are returned.  The draws are ``common.get_samples_multi``'s: one ``torch.randint`` per frame, in order.  ``pick``: F
+        int64 index tensors [n] over the window to use instead (tests)."""
+        with torch.cuda.device(self.dev):
+            a, out, keep = self._ba_head_args(n, pick)
+            check(lib().adfp_ba_head(C.byref(a), _lib.current_stream(self.dev)), 'adfp_ba_head')
+        self._ba['N'] = out[2].shape[0]
+        return out
+
+    def _ba_head_args(self, n, pick=None):
+        """adfp_ba_head's arguments for ``n`` pixels per frame (drawn here unless ``pick`` gives them), the four output buffers and the
+        tensors the arguments point into."""
+        ba = self._ba
+        F, n = ba['F'], int(n)
+        N = F * n
+        out = self.input_buffers(N)
+        H0, H1, W0, W1 = ba['window']
+        pix = self._ba_pix.get(N)
+        if pix is None:
+            pix = self._ba_pix[N] = (torch.empty((N,), device=self.dev), torch.empty((N,), device=self.dev))
+        a = _lib.AdfpBaHeadArgs()
+        a.n_frames, a.n, a.H0, a.H1, a.W0, a.W1, a.H, a.W = F, n, H0, H1, W0, W1, ba['H'], ba['W']
+        a.fx, a.fy, a.cx, a.cy = ba['intr']
+        a.cam, a.c2w, a.pix_i, a.pix_j = self.ba_cam.data_ptr(), self.ba_c2w.data_ptr(), pix[0].data_ptr(), pix[1].data_ptr()
+        a.rays_o, a.rays_d, a.gt_depth, a.gt_color = (t.data_ptr() for t in out)
+        keep = []
+        for f, (c2w, depth, color) in enumerate(ba['frames']):
+            if pick is None:
+                idx = torch.randint((H1 - H0) * (W1 - W0), (n,), device=self.dev)          # src/common.py:101
+            else:
+                idx = pick[f].to(self.dev, torch.int64).contiguous()
+                if tuple(idx.shape) != (n,):
+                    raise ValueError(f'sample_ba: pick[{f}] must hold {n} indices')
+            keep.append(idx)
+            j = a.frames[f]
+            j.idx, j.c2w, j.depth_img, j.color_img, j.free_pose = idx.data_ptr(), c2w.data_ptr(), depth.data_ptr(), color.data_ptr(), int(ba['free'][f])
+        return a, out, keep
+
+    @torch.no_grad()
+    def gradient_ba(self, stage, warmup=False):
+        """Loss and d loss / d camera tensors [F,7] of the batch ``sample_ba`` left in the input buffers, without stepping anything
+        (tests, diagnostics): ``(loss, g_cam, grid gradients, flat parameter gradients)``, device tensors."""
+        ba = self._ba
+        with torch.cuda.device(self.dev):
+            self._sync_tsdf_blocks()
+            grids, flats = self._sequence(*self.input_buffers(ba['N']), stage, warmup, adam=False)
+        return self.loss.clone(), self.ba_g_cam[:ba['F']].clone(), grids, {k: v.clone() for k, v in flats.items()}
 
     def _allreduce_gradients(self, grids, flats, end):
         """SUM over the ranks of what this stage's backward produced.  Without masks: the stage's prefix of the contiguous
@@ -321,9 +479,16 @@ class MapperIteration(object):
         # ONE launch for the loss, its cotangents, the loss word (written, not accumulated: no zero fill) and -- when an optimiser step
         # follows -- the step counters / bias corrections of torch.optim.Adam for this stage's groups (adfp_mapper_loss_step)
         used_groups = self._stage_groups(stage, need_grid, need_flat) if adam else []
-        lrs = (C.c_float * len(self.groups))(*([-1.0] * len(self.groups)))
+        ba = self._ba
+        n_groups = len(self.groups) + (1 if ba is not None else 0)          # bundle adjustment: the pose group behind the others
+        lrs = (C.c_float * n_groups)(*([-1.0] * n_groups))
         for gname, lrv in used_groups:
             lrs[self.groups.index(gname)] = float(lrv)
+        if ba is not None:
+            if ba.get('N') != N or ro.data_ptr() != self.input_buffers(N)[0].data_ptr():
+                raise ValueError('bundle adjustment is on: the ray batch must be the one sample_ba wrote')
+            if adam:
+                lrs[n_groups - 1] = self.ba_stage_lr(stage, ba['lr'])
         scratch = self._loss_scratch.get(N)
         if scratch is None:
             scratch = self._loss_scratch[N] = torch.zeros(int(L.adfp_mapper_loss_scratch_bytes(N)) // 8 + 1, dtype=torch.float64, device=dev)
@@ -332,12 +497,12 @@ class MapperIteration(object):
         skip = C.c_void_p(aux['counter_ptr'] + 32)
         b1, b2 = self.betas
         if N > 0:
-            check(L.adfp_mapper_loss_step(C.byref(la), ptr(scratch), scratch.numel() * 8, ptr(self.step_count), ptr(self.derived),
-                                          len(self.groups) if adam else 0, lrs, b1, b2, skip, st), 'adfp_mapper_loss_step')
+            check(L.adfp_mapper_loss_step(C.byref(la), ptr(scratch), scratch.numel() * 8, ptr(self._steps_all), ptr(self._derived_all),
+                                          n_groups if adam else 0, lrs, b1, b2, skip, st), 'adfp_mapper_loss_step')
         else:                                   # an empty ray shard: nothing to launch for the loss
             self.loss.zero_()
             if adam:
-                check(L.adfp_adam_prep(ptr(self.step_count), ptr(self.derived), len(self.groups), lrs, b1, b2, skip, st), 'adfp_adam_prep')
+                check(L.adfp_adam_prep(ptr(self._steps_all), ptr(self._derived_all), n_groups, lrs, b1, b2, skip, st), 'adfp_adam_prep')
         out_grids, out_flats, end = {}, {}, 0
         for kind, name, key, off, n in self._bucket_layout:
             view = self.bucket[off:off + n]
@@ -348,9 +513,23 @@ class MapperIteration(object):
             elif kind == 'flat' and need_flat[name]:
                 out_flats[name] = view
                 end = off + n
-        grids, flats, _ = eng.render_backward(dec, self.c, self.tsdf, self.tsdf_bnds, rend.bound, stage, aux, g_depth, None,
-                                              g_color if stage == 'color' else None, g_weight, need_grid, need_flat, ray_keep=keep,
-                                              out_grids_cl=out_grids, out_flats=out_flats, grids_prezeroed=True, side_lane=eng.lane_for(stage))
+        grids, flats, g_rays = eng.render_backward(dec, self.c, self.tsdf, self.tsdf_bnds, rend.bound, stage, aux, g_depth, None,
+                                                   g_color if stage == 'color' else None, g_weight, need_grid, need_flat,
+                                                   need_rays=ba is not None, ray_keep=keep, out_grids_cl=out_grids, out_flats=out_flats,
+                                                   grids_prezeroed=True, side_lane=eng.lane_for(stage))
+        if ba is not None:
+            # ray cotangents -> g_c2w -> g_cam per window frame and (adam) the pose group's Adam step: ONE launch, one workgroup per frame
+            pix = self._ba_pix[N]
+            ta = _lib.AdfpBaTailArgs()
+            ta.n_frames, ta.n = ba['F'], N // ba['F']
+            ta.fx, ta.fy, ta.cx, ta.cy = ba['intr']
+            ta.pix_i, ta.pix_j, ta.g_rays_o, ta.g_rays_d = pix[0].data_ptr(), pix[1].data_ptr(), g_rays[0].data_ptr(), g_rays[1].data_ptr()
+            ta.cam, ta.g_c2w, ta.g_cam, ta.free_flags = self.ba_cam.data_ptr(), self.ba_g_c2w.data_ptr(), self.ba_g_cam.data_ptr(), self.ba_free.data_ptr()
+            ta.step = 1 if adam else 0
+            ta.exp_avg, ta.exp_avg_sq = self.ba_exp_avg.data_ptr(), self.ba_exp_avg_sq.data_ptr()
+            ta.derived = self._derived_all[len(self.groups)].data_ptr()
+            ta.beta1, ta.beta2, ta.eps, ta.skip_flag = b1, b2, self.eps, skip.value
+            check(L.adfp_ba_tail(C.byref(ta), st), 'adfp_ba_tail')
         self.bucket_bytes = end * 4
         if self.distributed:
             import torch.distributed as tdist
@@ -456,11 +635,17 @@ class MapperIteration(object):
             self.dec.absorb_status()
             self._sync_shadows()             # a grid somebody else wrote since our last step is re-laid out here, outside the graph
 
+            ba = self._ba
+            # bundle adjustment adds launches and bakes the group's lr and the intrinsics in; which frame is the gauge is device data
+            ba_key = (False, 0) if ba is None else (True, ba['F'], ba['lr'], ba['intr'])
+
             def graph_key():
-                return (N, stage, bool(warmup), frozenset(self.dec._exact_latch))
+                return (N, stage, bool(warmup), frozenset(self.dec._exact_latch)) + ba_key
             key = graph_key()
             st = self.input_buffers(N)
             srcs = (rays_o, rays_d, gt_depth, gt_color)
+            if ba is not None and (ba.get('N') != N or not all(s_ is d_ for d_, s_ in zip(st, srcs))):
+                raise ValueError('bundle adjustment is on: the ray batch must be the one sample_ba wrote')
             if all(s_ is d_ for d_, s_ in zip(st, srcs)):
                 pass                                            # the caller filled the static buffers itself (common.get_samples_multi(out=...))
             elif all(s_.dtype == torch.float32 and s_.device == d_.device and s_.shape == d_.shape for d_, s_ in zip(st, srcs)):

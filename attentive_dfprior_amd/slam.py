@@ -17,6 +17,8 @@ Deliberate differences from the reference:
   * ``pretrained_decoders.low_high: null`` leaves the decoders as the seed initialised them.
   * ``--prior online``: the TSDF prior is fused during the run from the ESTIMATED poses of the mapped frames.
   * ``--last_frame N`` ends the run at frame N (the reference hard-codes frame 4640 of ScanNet scene 50).
+  * ``mapping.BA: True`` (default False): bundle adjustment as the reference's parent project runs it -- with more than four
+    keyframes the window's poses, all but the oldest keyframe's, are optimised with the map (``mapping.BA_cam_lr``, stage color).
 """
 import logging
 import os
@@ -30,6 +32,7 @@ import torch
 
 from . import get_model
 from .common import get_camera_from_tensor, get_tensor_from_camera, random_select
+from .config import mapping_setting
 
 log = logging.getLogger('attentive_dfprior_amd')
 STAGES = ('low', 'high', 'color')
@@ -175,6 +178,9 @@ class Mapper(object):
         self.save_selected_keyframes_info = m['save_selected_keyframes_info']
         if self.save_selected_keyframes_info:
             self.selected_keyframes = {}
+        # bundle adjustment (the reference's parent project; the reference dropped it): off unless the config asks for it
+        self.BA = bool(mapping_setting(cfg, 'BA'))
+        self.BA_cam_lr = float(mapping_setting(cfg, 'BA_cam_lr'))       # a user setting: not scaled by lr_factor
 
         self.keyframe_dict = []
         self.keyframe_list = []
@@ -220,6 +226,31 @@ class Mapper(object):
         return get_samples_multi(0, self.H, 0, self.W, pixs_per_image, self.H, self.W, self.fx, self.fy, self.cx, self.cy, frames,
                                  self.device, out=it.input_buffers(n))
 
+    def _ba_begin(self, it, optimize_frame, frames):
+        """Bundle adjustment for this mapped frame: the window's poses join the iteration's Adam.  The oldest keyframe of the window
+        stays fixed (the gauge); every other frame, the current one (-1) included, gets the camera tensor of its pose.  Returns the
+        free flags, one per window frame."""
+        from . import _lib
+        if len(optimize_frame) > _lib.KEYFRAMES_MAX:
+            raise ValueError(f'mapping.BA: a window of {len(optimize_frame)} frames, at most {_lib.KEYFRAMES_MAX} are supported')
+        oldest_frame = min(f for f in optimize_frame if f != -1)
+        free = [f != oldest_frame for f in optimize_frame]
+        poses = torch.stack([torch.as_tensor(c2w).detach().float().reshape(4, 4) for c2w, _, _ in frames]).cpu()      # one download
+        cams = torch.stack([get_tensor_from_camera(m) for m in poses])
+        it.set_ba(cams, free, self.BA_cam_lr, frames, self.H, self.W, self.fx, self.fy, self.cx, self.cy)
+        return free
+
+    def _ba_end(self, it, optimize_frame, free, keyframe_dict, cur_c2w):
+        """After the iterations: every free keyframe's new pose into its row of the store and into keyframe_dict; returns the current
+        frame's new pose.  One launch writes them all."""
+        cur = torch.empty_like(cur_c2w, dtype=torch.float32).contiguous()
+        dst = [None if not fr else (cur if f == -1 else self.keyframe_store.frame(f)[0]) for f, fr in zip(optimize_frame, free)]
+        it.poses(dst=dst)
+        for f, fr in zip(optimize_frame, free):
+            if fr and f != -1:
+                keyframe_dict[f]['est_c2w'] = self.keyframe_store.frame(f)[0].clone()
+        return cur
+
     def _integrate_prior(self, idx, gt_color, gt_depth):
         """--prior online: frame idx into the prior volume with its ESTIMATED pose, as get_tsdf.init_tsdf_volume integrates a frame
         with its ground-truth one (columns 1 and 2 flipped back to the camera the volume integrates in, colours floor(255 c))."""
@@ -252,7 +283,9 @@ class Mapper(object):
     def optimize_map(self, num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w, keyframe_dict, keyframe_list,
                      tsdf_volume, cur_c2w):
         """Mapping iterations of one frame (src/Mapper.py:262-484): the keyframe window, then num_joint_iters iterations, each a ray
-        batch over the window and one MapperIteration.step in the stage its index selects.  Returns None."""
+        batch over the window and one MapperIteration.step in the stage its index selects.  With ``mapping.BA`` and more than four
+        keyframes the window's poses are optimised too (all but the oldest keyframe's) and the current frame's new pose is returned;
+        else None."""
         if len(keyframe_dict) == 0:
             optimize_frame = []
         else:
@@ -286,6 +319,9 @@ class Mapper(object):
         it = self._iteration(lr_factor, masks)
         it.new_frame(masks)                                   # a fresh Adam (:374) and this frame's frustum masks
         frames = [self.keyframe_store.frame(f) if f != -1 else (cur_c2w, cur_gt_depth, cur_gt_color) for f in optimize_frame]
+        ba = self.BA and len(self.keyframe_list) > 4
+        if ba:
+            free = self._ba_begin(it, optimize_frame, frames)
         self.last_window = (list(optimize_frame), pixs_per_image)
         low_end = int(num_joint_iters * self.low_iter_ratio)
         high_end = int(num_joint_iters * self.high_iter_ratio)
@@ -301,9 +337,12 @@ class Mapper(object):
             if (not (idx == 0 and self.no_vis_on_first_frame)) and ('Demo' not in self.output):
                 self.visualizer.vis(idx, joint_iter, cur_gt_depth, cur_gt_color, cur_c2w, self.c, self.decoders, tsdf_volume, self.tsdf_bnds)
 
-            batch = self._sample_batch(it, frames, pixs_per_image)
+            # with bundle adjustment the rays come from the poses the camera tensors give in THIS iteration
+            batch = it.sample_ba(pixs_per_image) if ba else self._sample_batch(it, frames, pixs_per_image)
             warmup = low_end < joint_iter <= low_end + 5 and idx <= 1
             it.step(*batch, self.stage, warmup=warmup)
+        if ba:
+            return self._ba_end(it, optimize_frame, free, keyframe_dict, cur_c2w)
         return None
 
     def run(self):
@@ -354,8 +393,11 @@ class Mapper(object):
             self._integrate_prior(idx, gt_color, gt_depth)
 
         for outer_joint_iter in range(outer_joint_iters):
-            self.optimize_map(num_joint_iters, lr_factor, idx, gt_color, gt_depth, gt_c2w, self.keyframe_dict, self.keyframe_list,
-                              tsdf_volume, cur_c2w=cur_c2w)
+            new_c2w = self.optimize_map(num_joint_iters, lr_factor, idx, gt_color, gt_depth, gt_c2w, self.keyframe_dict, self.keyframe_list,
+                                        tsdf_volume, cur_c2w=cur_c2w)
+            if new_c2w is not None:                           # bundle adjustment moved the frame's pose
+                cur_c2w = new_c2w
+                self.estimate_c2w_list[idx] = cur_c2w.detach().cpu()
 
             # add new frame to keyframe set
             if outer_joint_iter == outer_joint_iters - 1:

@@ -585,7 +585,7 @@ int adfp_select_pixels(const long long* idx /*[n] int64 device*/, int n, int H0,
  * torch.cat) in ONE launch: frame f contributes n rays -- pixel idx[t] of the window like adfp_select_pixels, its ray like
  * adfp_rays_from_uv (bit for bit), sensor depth and colour -- at rows [f n, f n + n) of the outputs.  The draws stay the caller's (one
  * torch.randint per frame: the reference's index stream).  c2w: device [4,4] row-major fp32, or NULL and the pose in c2w_host (rows
- * 0-2 of the matrix, row-major).  No gradient towards the poses (bundle adjustment takes the per-frame entries). */
+ * 0-2 of the matrix, row-major).  No gradient towards the poses (bundle adjustment takes adfp_ba_head / adfp_ba_tail). */
 #define ADFP_KEYFRAMES_MAX 16
 typedef struct adfp_keyframe {
     const long long* idx;      /* [n] int64, device */
@@ -628,6 +628,50 @@ typedef struct adfp_tracker_tail_args {
     const double* loss; double* best_loss; float* best_cam;
 } adfp_tracker_tail_args;
 int adfp_tracker_tail(const adfp_tracker_tail_args* args /*host*/, void* stream);
+/* ---- The Mapper's bundle adjustment: the window's poses as parameters of the Mapper's Adam ------------------------------------ */
+/* The reference dropped this code (a `camera_tensor_id = 0` is left at src/Mapper.py:413); its parent project runs it under
+ * mapping.BA.  Three launches around the fused Mapper iteration, for 1 <= n_frames <= ADFP_KEYFRAMES_MAX window frames with n >= 1
+ * rays each; frame f owns rows [f n, f n + n) of every per-ray array and row f of cam [F,7] / c2w [F,16] / g_c2w [F,16] / g_cam [F,7].
+ * A frame is FREE (its pose is the camera tensor cam[f], quaternion first, then translation) or FIXED (the gauge: its stored
+ * matrix is used verbatim).
+ * adfp_ba_head = adfp_camera_from_tensor per free frame + adfp_sample_keyframes over the window, bit for bit: c2w[f] (a fixed frame's
+ *   is a copy of its stored [4,4]), and per ray pix_i / pix_j (what the tail takes), rays_o / rays_d, gt_depth, gt_color.
+ * adfp_ba_tail = per frame adfp_rays_from_uv_backward on its rows + adfp_camera_from_tensor_backward, bit for bit (one workgroup per
+ *   frame with adfp_tracker_tail's partition and summation order: reproducible), then with step != 0 the Adam update of the frame's
+ *   7 parameters with the pose group's `derived` = {step size, sqrt(bias correction 2)} as adfp_adam_prep / adfp_mapper_loss_step
+ *   leave them ({0, 0} = that iteration is skipped; skip_flag, optional, as there).  A fixed frame gets g_c2w = g_cam = 0; its
+ *   tensor and moments are not touched.
+ * adfp_cameras_from_tensors: cam[f] -> the 16 floats at dst[f] for every f with dst[f] != NULL (dst: HOST array of n_frames device
+ *   pointers) -- the write-back of the optimised poses into their keyframe rows.
+ * Errors, before any launch: ADFP_E_ARG for a NULL pointer (a fixed frame's c2w included; a free frame's may be NULL), n_frames
+ * outside [1, ADFP_KEYFRAMES_MAX], n < 1, a pixel window outside the image; ADFP_E_UNSUPPORTED beyond 2^29 rays. */
+typedef struct adfp_ba_frame {
+    const long long* idx;      /* [n] int64 device: the frame's draw over the window [H0,H1) x [W0,W1), row-major */
+    const float* c2w;          /* device [4,4]: the stored pose, read when free_pose == 0 */
+    const float* depth_img;    /* [H,W] fp32 */
+    const float* color_img;    /* [H,W,3] fp32 */
+    int free_pose;
+} adfp_ba_frame;
+typedef struct adfp_ba_head_args {
+    int n_frames, n; int H0, H1, W0, W1, H, W;
+    float fx, fy, cx, cy;
+    const float* cam; float* c2w;
+    float* pix_i; float* pix_j; float* rays_o; float* rays_d; float* gt_depth; float* gt_color;
+    adfp_ba_frame frames[ADFP_KEYFRAMES_MAX];
+} adfp_ba_head_args;
+int adfp_ba_head(const adfp_ba_head_args* args /*host*/, void* stream);
+typedef struct adfp_ba_tail_args {
+    int n_frames, n; float fx, fy, cx, cy;
+    const float* pix_i; const float* pix_j; const float* g_rays_o; const float* g_rays_d;
+    float* cam; float* g_c2w; float* g_cam;
+    const unsigned char* free_flags;         /* device [F]: nonzero = frame f is free (device memory: a captured graph serves any gauge) */
+    int step;                                /* 0: gradients only */
+    float* exp_avg; float* exp_avg_sq;       /* [F,7] each */
+    const float* derived;                    /* device [2], the pose group's */
+    float beta1, beta2, eps; const int* skip_flag;
+} adfp_ba_tail_args;
+int adfp_ba_tail(const adfp_ba_tail_args* args /*host*/, void* stream);
+int adfp_cameras_from_tensors(int n_frames, const float* cam /*[F,7] device*/, float* const* dst /*host [F]*/, void* stream);
 /* The tracking loss (src/Tracker.py:115-129) and its cotangents:
  *   tmp = |gt_depth - depth| / sqrt(uncertainty + 1e-10)        (float64, uncertainty detached)
  *   mask = keep & (gt_depth > 0) [& tmp < 10 median(tmp over the kept rays) when handle_dynamic]

@@ -20,6 +20,9 @@ def main(template, d):
     v = {}
     P = lambda n: os.path.join(d, n)
     rb_path = P('run_bench.json')
+    ba_path = P('ba_bench.json')
+    bench_train_5000x64 = [r for r in (json.loads(l) for l in open(P('r06_bench_train.json')) if l.strip())
+                           if r.get('rays') == 5000 and r.get('samples_per_ray') == 64][0]['ms_per_iter_fused_graph']
     # the Mesher's tail: host methods against the device path (tools/mesh_bench.py)
     mt = json.load(open(P('mesh_tail_bench.json')))['by_resolution']
 
@@ -359,6 +362,30 @@ def main(template, d):
                               100 * o['map_frame_minus_fused_prior_ms'] / o['map_frame_ms']))
     else:
         v['rb_numbers'] = 'No run of `tools/run_bench.py` is in `profiles/`: not measured.'
+    # bundle adjustment beside the plain Mapper iteration (tools/ba_bench.py)
+    if os.path.exists(ba_path):
+        ba = json.load(open(ba_path))
+        rows = ['| stage | BA off, ms per iteration | BA on, ms per iteration | on / off |', '|---|---|---|---|']
+        for st in ('low', 'high', 'color'):
+            r = ba['stages'][st]
+            rows.append('| %s | %.3f (blocks %.3f – %.3f) | %.3f (blocks %.3f – %.3f) | %.2f× |' % (
+                st, r['ms_per_iter_ba_off'], min(r['ba_off_blocks_ms']), max(r['ba_off_blocks_ms']),
+                r['ms_per_iter_ba_on'], min(r['ba_on_blocks_ms']), max(r['ba_on_blocks_ms']), r['ratio_on_over_off']))
+        v['ba_numbers'] = ('Measured on one MI355X (`profiles/ba_bench.json`): the %s iteration of %d rays × %d samples over a %d-frame window, sampling '
+                           'included, graph replay, the two modes alternating in blocks of %d iterations (%d blocks each, medians; host clock around a '
+                           'device synchronise):\n\n' % (ba['scene'], ba['rays'], ba['samples_per_ray'], ba['frames'], ba['iters_per_block'], ba['rounds'])
+                           + '\n'.join(rows) + '\n\n'
+                           + 'The head alone takes %.1f µs and the tail alone %.1f µs per launch, launched back to back between two events, so nearly all of the '
+                             'difference is the backward itself: asked for ray cotangents together with grid and weight gradients it runs the exact f32 '
+                             'kernels for every network (`Engine.ht_nets`); it has not been traced kernel by kernel for this case.  '
+                             'No threshold is set: what the ray-gradient path costs beside the grid gradients is the ratio above.  '
+                             'Beside the BA-off figure of stage color (%.3f ms: ten poses, a fresh draw and one sampling launch per iteration) stands '
+                             '`bench_train.py`\'s fused graph-replayed iteration of the collection before this feature (`profiles/r06_bench_train.json`: '
+                             'one pose, a fixed batch of 5 000 rays × 64 samples, stage color): %.3f ms.'
+                           % (ba['head_us_per_call_back_to_back'], ba['tail_us_per_call_back_to_back'], ba['stages']['color']['ms_per_iter_ba_off'],
+                              bench_train_5000x64))
+    else:
+        v['ba_numbers'] = 'No run of `tools/ba_bench.py` is in `profiles/`: not measured.'
     s = open(template).read()
     out = re.sub(r'@@(\w+)@@', lambda m: v.get(m.group(1), m.group(0)), s)
     sys.stdout.write(out)
