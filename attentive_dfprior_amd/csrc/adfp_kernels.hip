@@ -1685,7 +1685,7 @@ static int sample_rays_impl(const float* rays_o, const float* rays_d, const floa
     if (!rays_o || !rays_d || !z_vals || !bound || n_rays < 0 || n_samples <= 0 || n_surface < 0) return ADFP_E_ARG;
     if (first_ray < 0 || (first_ray > 0 && ((!depth_max && !seg_parts) || segment <= 0))) return ADFP_E_ARG;
     if (perturb > 0.f && !t_rand) return ADFP_E_ARG;
-    if (n_samples + n_surface > ADFP_MAX_SAMPLES) return ADFP_E_UNSUPPORTED;
+    if (n_samples + (gt_depth ? n_surface : 0) > ADFP_MAX_SAMPLES) return ADFP_E_UNSUPPORTED;      // without sensor depth the surface list is not made
     if (n_rays == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     SampleArgs a;

@@ -979,12 +979,15 @@ class Engine(object):
             ws = self.bwd_workspace(N * S, dev)
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
             a.options = self.bwd_options | (_lib.BWD_GRIDS_PREZEROED if (grids_prezeroed and not grids_cl) else 0)
+            stream = _lib.current_stream(dev)
             lane = self.side_lane(dev) if side_lane else None
-            if lane is not None:
+            # torch hands its streams out of a pool of 32, round-robin: the stream this call runs on (a graph capture's, a holder's
+            # warm-up stream) can BE the lane's stream.  That is no second lane -- adfp_render_backward refuses it -- and the call
+            # then runs on one stream, in order (the same gradients: tests/test_gpu_grad.py)
+            if lane is not None and lane[0].cuda_stream != (stream.value or 0):
                 a.side_stream = lane[0].cuda_stream
                 for k in range(2):
                     a.side_events[k] = lane[1][k].cuda_event
-            stream = _lib.current_stream(dev)
             check(L.adfp_render_backward(C.byref(sc), C.byref(a), stream), 'adfp_render_backward')
             grids = dict(direct)
             if grids_cl:                                  # the kernels' channels-last gradients -> the reference's layout: ONE launch

@@ -30,6 +30,31 @@ def test_too_many_samples_is_rejected_not_truncated():
         rend.render_batch_ray(sc.c, dec, rd, ro, DEV, sc.tsdf_volume, sc.tsdf_bnds.to(DEV), 'color', gt_depth=gd)
 
 
+def test_the_sample_limit_is_256_exactly():
+    """The boundary pair: 241 + 16 = 257 is refused, 240 + 16 = 256 renders the same 50 rays to finite values.  Without sensor depth
+    the surface list is not made and does not count: 256 + 16 renders, 257 + 0 is refused."""
+    sc, dec, rend, ro, rd, gd = _setup(ns=241, nf=16)
+    tb = sc.tsdf_bnds.to(DEV)
+    with torch.no_grad(), pytest.raises(RuntimeError, match='UNSUPPORTED|unsupported'):
+        rend.render_batch_ray(sc.c, dec, rd, ro, DEV, sc.tsdf_volume, tb, 'color', gt_depth=gd)
+    rend = A.Renderer(make_cfg(240, 16), None, sc)
+    with torch.no_grad():
+        d, u, c, w = rend.render_batch_ray(sc.c, dec, rd, ro, DEV, sc.tsdf_volume, tb, 'color', gt_depth=gd)
+    assert tuple(w.shape) == (50, 256, 1)
+    for t in (d, u, c, w):
+        assert bool(torch.isfinite(t).all())
+    assert float(d.abs().max()) > 0
+    rend = A.Renderer(make_cfg(256, 16), None, sc)
+    with torch.no_grad():
+        d, u, c, w = rend.render_batch_ray(sc.c, dec, rd, ro, DEV, sc.tsdf_volume, tb, 'color')
+    assert tuple(w.shape) == (50, 256, 1)
+    for t in (d, u, c, w):
+        assert bool(torch.isfinite(t).all())
+    rend = A.Renderer(make_cfg(257, 0), None, sc)
+    with torch.no_grad(), pytest.raises(RuntimeError, match='UNSUPPORTED|unsupported'):
+        rend.render_batch_ray(sc.c, dec, rd, ro, DEV, sc.tsdf_volume, tb, 'color')
+
+
 def test_workspace_too_small_and_null_pointers():
     sc, dec, rend, ro, rd, gd = _setup()
     L = _lib.lib()

@@ -40,8 +40,10 @@ def grad_close(got, ref, what, tol=GTOL, mode=None):
         assert_close_scale(got.detach(), ref, tol, what, flip_frac=2e-3 if last.startswith('grid') else 0.0)
 
 
-def run(mini, stage, warm, sd=None, n_samples=None, n_surface=None, rays=None, bwd_options=None, capture=None, side_lane=None):
-    """capture: a dict; the backward then exports its ReLU decisions and capture['relu_masks'] = Engine.relu_masks(...)."""
+def run(mini, stage, warm, sd=None, n_samples=None, n_surface=None, rays=None, bwd_options=None, capture=None, side_lane=None, with_depth=True):
+    """capture: a dict; the backward then exports its ReLU decisions and capture['relu_masks'] = Engine.relu_masks(...).
+    with_depth=False: the render call gets no sensor depth (N_surface is ignored, far = the slab test's); the loss still masks on
+    the batch's gt_depth."""
     sd = mini.sd if sd is None else sd
     dec = A.DF()
     dec.load_state_dict(sd)
@@ -63,7 +65,7 @@ def run(mini, stage, warm, sd=None, n_samples=None, n_surface=None, rays=None, b
     ro, rd, gd, gc = rays if rays is not None else (mini.rays_o, mini.rays_d, mini.gt_depth, mini.gt_color)
     ro, rd, gd, gc = ro.to(DEV), rd.to(DEV), gd.to(DEV), gc.to(DEV)
     d, u, col, w = rend.render_batch_ray(c, dec, rd, ro, DEV, mini.tsdf_volume.to(DEV), mini.tsdf_bnds.to(DEV), stage,
-                                         gt_depth=gd)
+                                         gt_depth=gd if with_depth else None)
     loss = mapper_loss(d, col, w, gd, gc, stage, warm)
     loss.backward()
     if capture is not None:
@@ -71,32 +73,33 @@ def run(mini, stage, warm, sd=None, n_samples=None, n_surface=None, rays=None, b
     return loss, c, dec
 
 
-def oracle_grads(mini, sd, rays, stage, warm, n_samples, n_surface, relu_masks=None):
+def oracle_grads(mini, sd, rays, stage, warm, n_samples, n_surface, relu_masks=None, with_depth=True):
     """The oracle's autograd under the Mapper loss -> (loss, {grid: grad}, {parameter: grad}); relu_masks: the kernels' ReLU
     decisions, forced (oracle.adfp_oracle._relu)."""
     c_or = {k: v.clone().requires_grad_(True) for k, v in mini.c.items()}
     sd_or = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     ro, rd, gd, gc = rays
-    d2, u2, col2, w2 = O.render_batch_ray(sd_or, c_or, rd, ro, mini.tsdf_volume, mini.tsdf_bnds, mini.bound, stage, gd, n_samples,
-                                          n_surface, relu_masks=relu_masks)
+    d2, u2, col2, w2 = O.render_batch_ray(sd_or, c_or, rd, ro, mini.tsdf_volume, mini.tsdf_bnds, mini.bound, stage, gd if with_depth else None,
+                                          n_samples, n_surface, relu_masks=relu_masks)
     loss2 = O.mapper_loss(d2, col2, w2, gd, gc, stage, warm)
     loss2.backward()
     zero = lambda t: t.grad if t.grad is not None else torch.zeros_like(t)           # noqa: E731
     return loss2, {k: zero(v) for k, v in c_or.items()}, {k: zero(v) for k, v in sd_or.items()}
 
 
-def check_tight(mini, stage, warm, mode, sd=None, n_samples=None, n_surface=None, rays=None, what=''):
+def check_tight(mini, stage, warm, mode, sd=None, n_samples=None, n_surface=None, rays=None, what='', with_depth=True, out=None):
     """THE gradient criterion: kernels vs the oracle's autograd along the kernels' own ReLU decisions, every element of every
     grid and parameter gradient within conftest.TIGHT_GRAD_TOL x the tensor's scale; and the forced decisions are legitimate --
-    they differ from relu's own only on units whose pre-activation is within rounding of zero."""
+    they differ from relu's own only on units whose pre-activation is within rounding of zero.
+    out: a dict that receives the kernels' side (`c`, `dec`) and the oracle's grid gradients (`oracle_grids`)."""
     sd = mini.sd if sd is None else sd
     ns = n_samples or mini.n_samples
     nf = n_surface if n_surface is not None else mini.n_surface
     rays = rays if rays is not None else (mini.rays_o, mini.rays_d, mini.gt_depth, mini.gt_color)
     cap = {}
-    loss, c, dec = run(mini, stage, warm, sd=sd, n_samples=ns, n_surface=nf, rays=rays, capture=cap)
+    loss, c, dec = run(mini, stage, warm, sd=sd, n_samples=ns, n_surface=nf, rays=rays, capture=cap, with_depth=with_depth)
     O.reset_relu_flips()
-    loss2, gc_or, gsd_or = oracle_grads(mini, sd, rays, stage, warm, ns, nf, relu_masks=cap['relu_masks'])
+    loss2, gc_or, gsd_or = oracle_grads(mini, sd, rays, stage, warm, ns, nf, relu_masks=cap['relu_masks'], with_depth=with_depth)
     flips = dict(O.RELU_FLIPS)
     assert_forced_decisions_are_boundary_units(flips)
     assert abs(loss.item() - loss2.item()) <= 1e-5 * abs(loss2.item())
@@ -106,6 +109,8 @@ def check_tight(mini, stage, warm, mode, sd=None, n_samples=None, n_surface=None
     for name, p in dec.named_parameters():
         got = p.grad if p.grad is not None else torch.zeros_like(p)
         assert_grad_tight(got, gsd_or[name], f'{what}{stage} d/d {name}', mode)
+    if out is not None:
+        out.update(c=c, dec=dec, oracle_grids=gc_or)
     return flips
 
 
@@ -475,6 +480,38 @@ def test_side_lane_changes_nothing_but_the_schedule(mini, n_rays):
         for k in got['side']:
             assert torch.isfinite(got['side'][k]).all(), k
             assert_close_scale(got['side'][k], got['one_stream'][k], 3e-6, f'{stage}, {n_rays} rays: {k}: side lane vs one stream')
+
+
+def test_a_side_lane_that_is_the_callers_own_stream_is_no_second_lane(mini, monkeypatch):
+    """torch hands streams out of a pool of 32, round-robin, so in a long process the engine's lane stream and the stream a call
+    runs on (torch.cuda.graph's capture stream, MapperIteration's warm-up stream) are sooner or later the same one --
+    adfp_render_backward refuses such a lane (ADFP_E_ARG), and which test of the suite met it depended on how many streams the
+    tests before it had taken.  Forced here: the call runs on the lane's own stream.  It must run, on one stream, and give the
+    one-stream gradients."""
+    from attentive_dfprior_amd import engine
+    rays = synthetic.make_ray_batch(synthetic.mini_scene(), 67, seed=8, poses=3)
+    kw = dict(sd=O.random_state_dict(seed=17), n_samples=48, n_surface=16, rays=rays)
+
+    def grads(c, dec):
+        out = {k: v.grad.clone() for k, v in c.items() if v.grad is not None}
+        out.update({n: p.grad.detach().clone() for n, p in dec.named_parameters() if p.grad is not None})
+        return out
+    loss, c, dec = run(mini, 'color', True, side_lane=False, **kw)
+    want = grads(c, dec)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    evs = [torch.cuda.Event() for _ in range(2)]
+    for ev in evs:
+        ev.record(torch.cuda.current_stream())
+    monkeypatch.setattr(engine.Engine, 'side_lane', lambda self, device: (s, evs))
+    with torch.cuda.stream(s):
+        loss2, c, dec = run(mini, 'color', True, side_lane=True, **kw)
+        got = grads(c, dec)
+    s.synchronize()
+    assert abs(loss2.item() - loss.item()) <= 1e-6 * abs(loss.item())
+    assert set(got) == set(want) and len(got) > 3
+    for k in got:
+        assert_close_scale(got[k], want[k], 3e-6, f'{k}: the lane is the caller\'s stream vs one stream')
 
 
 @pytest.mark.parametrize('stage', ['low', 'color'])

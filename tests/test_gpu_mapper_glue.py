@@ -22,7 +22,9 @@ with ADFP_LIB_PATH, this file and tests/test_gpu_mapper_iteration.py run once pe
       bit for bit: the dropped rays' rows are +-w_color or NaN instead of +0.0.  test_gpu_mapper_iteration.py: 6 passed -- the
       backward masks the dropped rays once more with ray_keep, so the fused path (and test_fused_gradient_against_the_oracle
       here) is not affected by a leak in this one cotangent; the raw entry is.
-With the unmodified kernels all 54 pass, in both ADFP_MATH modes: no test here exposed a defect."""
+With the unmodified kernels all 54 pass, in both ADFP_MATH modes: no test here exposed a defect.
+(Since then: three LOSS_CASES with rows of 129 and 256 samples, and a 129-sample case of test_fused_gradient_against_the_oracle,
+which now runs on an engine whose backward scratch holds an earlier iteration's cotangents -- HISTORY.md, sample-count range log.)"""
 import ctypes as C
 import math
 import os
@@ -172,6 +174,9 @@ LOSS_CASES = [  # N, S, stage, warm-up, keep: every N and S of interest, every s
     (16385, 1, 'high', False, 'zero'),
     (16385, 48, 'color', False, 'null'),
     (16385, 65, 'color', True, 'mixed'),
+    (64, 129, 'color', True, 'mixed'),           # rows of three and four 64-sample passes, the last one ragged (129) or full (256 = the maximum)
+    (65, 256, 'color', True, 'mixed'),
+    (5000, 256, 'high', False, 'zero'),
 ]
 PREP_STEPS = [0, 1, 9, 999, 99999]
 PREP_LRS = [0.1, 0.005, 0.0, -1.0]
@@ -498,25 +503,37 @@ def rows_of_the_kept_rays(masks, keep, N, S):
     return out
 
 
+FUSED_CASES = [('low', True, (32, 16)), ('high', True, (32, 16)), ('color', False, (32, 16)), ('color', True, (32, 16)),
+               ('color', True, (100, 29))]      # S = 129: three chunks in composite_bwd_block, the dropped rays' zero fill in steps of 64
+
+
 @pytest.mark.parametrize('mode', MODES)
-@pytest.mark.parametrize('stage,warm', [('low', True), ('high', True), ('color', False), ('color', True)])
-def test_fused_gradient_against_the_oracle(stage, warm, mode, monkeypatch):
+@pytest.mark.parametrize('stage,warm,samples', FUSED_CASES,
+                         ids=[f'{st}-{w}' + ('' if smp == (32, 16) else f'-{smp[0]}+{smp[1]}') for st, w, smp in FUSED_CASES])
+def test_fused_gradient_against_the_oracle(stage, warm, samples, mode, monkeypatch):
     """The Mapper's counterpart of the Tracker's test of this name: MapperIteration._sequence(adam=False) on
     test_gpu_mapper_iteration.setup()'s batch (700 rays, some dropped, some at zero depth) -- pre-filter job, forward, loss +
     cotangents, backward with ray_keep -- against the oracle's autograd of oracle.mapper_loss over the kept rays, rendered with
     depth_max = the max of the kept depths.  Criterion: conftest.assert_grad_tight (TIGHT_GRAD_TOL of each tensor's scale on
     every element, both math modes) with the kernels' ReLU decisions of the kept rays' points forced on the oracle; the loss
     within 1e-5 relative.  A cotangent off by a constant factor, or a dropped ray that leaks, moves these gradients; Adam's
-    normalisation hides both from a parameter trajectory."""
+    normalisation hides both from a parameter trajectory.
+    samples: (N_samples, N_surface).  (100, 29): rows of 129 samples -- the dropped rays (ray_keep) are zero-filled in several
+    steps of 64, the kept ones carry the transmittance and the suffix sum across three chunks."""
     import test_gpu_mapper_iteration as MI
     monkeypatch.setenv('ADFP_MATH', mode)
-    sc, dec, rend, rays, masks = MI.setup()
+    sc, dec, rend, rays, masks = MI.setup(samples)
     for p in dec.high_decoder.parameters():
         p.requires_grad_(True)
     tsdf, tb = sc.tsdf_volume.to(DEV), sc.tsdf_bnds.to(DEV)
     grids = {k: v.clone().to(DEV) for k, v in sc.c.items()}
     it = mapping.MapperIteration(rend, dec, grids, None, tsdf, tb, MI.STAGE_LR, train=('high', 'color', 'att'), use_graph=False, distributed=False)
     sd = {k: v.detach().cpu().clone() for k, v in dec.state_dict().items()}
+    # The backward's scratch is kept across calls.  An iteration on the same rays with shortened depths (nothing beyond the box:
+    # every ray kept) leaves a cotangent in every sample's slot; the dropped rays of the measured call must not inherit them.
+    near = [t.float().contiguous() for t in (rays[0], rays[1], rays[2] * 0.3, rays[3])]
+    assert R.prefilter(*[t.cpu() for t in near[:3]], sc.bound)[0].sum() > 0.95 * rays[0].shape[0]
+    it._sequence(*near, stage, warm, adam=False)               # (adam=False leaves the bucket's grid slots zero for the next call)
     cap = ReluCapture(rend)
     g_grids, g_flats = it._sequence(*[t.float().contiguous() for t in rays], stage, warm, adam=False)
     torch.cuda.synchronize()
@@ -540,10 +557,11 @@ def test_fused_gradient_against_the_oracle(stage, warm, mode, monkeypatch):
     assert_forced_decisions_are_boundary_units(dict(O.RELU_FLIPS))
     assert abs(loss - ref.item()) <= 1e-5 * abs(ref.item()), (loss, ref.item())
 
+    tag = f'fused {stage} warm={warm}' + ('' if samples == (32, 16) else f' {samples[0]}+{samples[1]}')
     used = {'low': ('low',), 'high': ('low', 'high'), 'color': ('low', 'high', 'color')}[stage]
     assert sorted(g_grids) == sorted(used)
     for name in used:                                          # grids: returned in the reference layout
-        assert_grad_tight(g_grids[name], c_or['grid_' + name].grad, f'fused {stage} warm={warm} d/d grid_{name}', mode)
+        assert_grad_tight(g_grids[name], c_or['grid_' + name].grad, f'{tag} d/d grid_{name}', mode)
     nets = {'high': ('high_decoder', 'high'), 'color': ('color_decoder', 'color'), 'att': ('mlp', 'att')}
     want = {'low': (), 'high': ('high', 'att'), 'color': ('high', 'color', 'att')}[stage]
     assert sorted(g_flats) == sorted(want)
@@ -554,6 +572,6 @@ def test_fused_gradient_against_the_oracle(stage, warm, mode, monkeypatch):
             cnt = prm.numel()
             got = g_flats[key][off:off + cnt].view(prm.shape)
             r = sd_or[f'{attr}.{pname}'].grad
-            assert_grad_tight(got, r if r is not None else torch.zeros_like(got), f'fused {stage} warm={warm} d/d {attr}.{pname}', mode)
+            assert_grad_tight(got, r if r is not None else torch.zeros_like(got), f'{tag} d/d {attr}.{pname}', mode)
             off += cnt
         assert off == g_flats[key].numel()

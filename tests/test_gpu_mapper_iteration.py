@@ -21,7 +21,8 @@ STAGE_LR = {'low': dict(low=0.1, high=0.0, color=0.0, decoders=0.0, mlp=0.0),
 SCHEDULE = [('low', False), ('low', False), ('high', True), ('high', False), ('color', False), ('color', False)]
 
 
-def setup():
+def setup(samples=(32, 16)):
+    """samples: (N_samples, N_surface) of the renderer."""
     sc = synthetic.mini_scene()
     sd = O.random_state_dict(seed=3)
     dec = A.DF()
@@ -30,7 +31,7 @@ def setup():
     dec = dec.to(DEV)
     for p in list(dec.low_decoder.parameters()) + list(dec.high_decoder.parameters()):
         p.requires_grad_(False)
-    rend = A.Renderer(make_cfg(32, 16), None, sc)
+    rend = A.Renderer(make_cfg(*samples), None, sc)
     ro, rd, gd, gc = synthetic.make_ray_batch(sc, 700, seed=9, zero_frac=0.1)
     gd = gd * (0.6 + 1.2 * torch.rand(gd.shape, generator=torch.Generator().manual_seed(1)))     # some beyond the box: dropped
     rd[5, 0] = 0.0

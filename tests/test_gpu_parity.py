@@ -134,16 +134,19 @@ def test_rays_tsdf_image_vs_golden(mini, gm):
 
 
 # --------------------------------------------------------------------------- oracle, seeded
-@pytest.mark.parametrize('n_samples,n_surface', [(48, 16), (96, 32), (17, 5), (64, 0), (1, 1)])
+@pytest.mark.parametrize('n_samples,n_surface', [(48, 16), (96, 32), (17, 5), (64, 0), (1, 1), (200, 55), (224, 32), (256, 0), (255, 1)])
 @pytest.mark.parametrize('stage', ['low', 'color'])
 def test_sample_counts_vs_oracle(mini, gm, stage, n_samples, n_surface):
-    """S = 64 (benchmark), 128 (config 5), ragged, no surface samples, degenerate."""
+    """S = 64 (benchmark), 128 (config 5), ragged, no surface samples, degenerate; S = 255 and the maximum, 256 (k_tsdf's ray mode
+    fills its chunk exactly with 8 rays, k_composite runs its fourth chunk) with many, no and one surface sample: the first 64 rays of
+    the batch suffice there (the oracle is the cost)."""
+    n = 64 if n_samples + n_surface > 128 else mini.rays_o.shape[0]
     dec, rend = build(mini, mini.sd, n_samples, n_surface)
     with torch.no_grad():
-        d, u, c, w = rend.render_batch_ray(gm.c, dec, gm.rays_d, gm.rays_o, DEV, gm.tsdf, gm.tsdf_bnds, stage,
-                                           gt_depth=gm.gt_depth)
-    od, ou, oc, ow = O.render_batch_ray(mini.sd, mini.c, mini.rays_d, mini.rays_o, mini.tsdf_volume, mini.tsdf_bnds,
-                                        mini.bound, stage, mini.gt_depth, n_samples, n_surface)
+        d, u, c, w = rend.render_batch_ray(gm.c, dec, gm.rays_d[:n], gm.rays_o[:n], DEV, gm.tsdf, gm.tsdf_bnds, stage,
+                                           gt_depth=gm.gt_depth[:n])
+    od, ou, oc, ow = O.render_batch_ray(mini.sd, mini.c, mini.rays_d[:n], mini.rays_o[:n], mini.tsdf_volume, mini.tsdf_bnds,
+                                        mini.bound, stage, mini.gt_depth[:n], n_samples, n_surface)
     assert tuple(w.shape) == tuple(ow.shape)
     assert_close(d, od, TOL, 'depth')
     assert_close(c, oc, TOL, 'color')
@@ -203,6 +206,62 @@ def test_composite_entry_vs_oracle(mini):
     assert_close_scale(v, ov, 2e-6, 'var')
     for got, ref, what in ((d, od, 'depth'), (rgb, orgb, 'rgb'), (wts, ow, 'weights'), (v, ov, 'var')):
         assert_close(got, ref, 1e-4, what)
+
+
+def composite_rows(S, n=333):
+    """raw [n, S, 4] and z [n, S] of the compositing sweep: random rows, the all-opaque row 5 and the all-empty row 6 of
+    test_composite_entry_vs_oracle, and rows that exist because k_composite carries the transmittance across chunks of 64 samples."""
+    g = torch.Generator().manual_seed(S)
+    raw = torch.randn(n, S, 4, generator=g) * 0.3
+    raw[5, :, 3] = 100.0
+    raw[6, :, 3] = -100.0
+    raw[9, S - 1, 3] = 100.0                                  # opaque only in the last sample: it takes whatever the carry left
+    if S > 64:
+        raw[7, :64, 3] = -100.0                               # the first chunk empty (carry = 1, up to 64 factors of 1 + 1e-10), opaque from the
+        raw[7, 64:, 3] = 100.0                                # second chunk's first lane on: weight 1 at index 64
+        raw[8, :63, 3] = -1.0                                 # 63 equal factors, then opaque in the first chunk's LAST lane: the next
+        raw[8, 63:, 3] = 100.0                                # chunks start from a carry of ~1e-10
+    if S > 128:
+        raw[10, :128, 3] = -100.0                             # two empty chunks, ordinary samples behind them
+    z = torch.sort(torch.rand(n, S, generator=g, dtype=torch.float64) * 5, dim=1)[0]
+    return raw, z
+
+
+def raw2outputs_f64(raw, z):
+    """oracle.adfp_oracle.raw2outputs (src/common.py:234-251, occupancy branch) evaluated in float64 on the same float32 inputs."""
+    raw = raw.double()
+    alpha = torch.sigmoid(10 * raw[..., 3])
+    ones = torch.ones((alpha.shape[0], 1), dtype=torch.float64)
+    weights = alpha * torch.cumprod(torch.cat([ones, 1. - alpha + 1e-10], -1), -1)[:, :-1]
+    rgb = torch.sum(weights[..., None] * raw[..., :3], -2)
+    depth = torch.sum(weights * z, -1)
+    tmp = z - depth.unsqueeze(-1)
+    return depth, torch.sum(weights * tmp * tmp, dim=1), rgb, weights
+
+
+@pytest.mark.parametrize('S', [1, 63, 64, 65, 128, 129, 255, 256])
+def test_composite_entry_over_the_sample_range(S):
+    """adfp_composite alone, one to four chunks of 64 lanes with the running carry of the transmittance, against a float64
+    evaluation of raw2outputs.  The float32 oracle is itself up to 1.3e-6 x scale away from that evaluation on the designed rows
+    (the rounding of 1 - alpha compounds over 63 factors), so each output's error, relative to the tensor's scale, may be the
+    larger of test_composite_entry_vs_oracle's bar (2e-7 depth, 2e-6 the others) and twice the float32 oracle's own error on the
+    same inputs; and every element is within the north-star bar of the float32 oracle."""
+    raw, z = composite_rows(S)
+    d, v, rgb, wts = common.raw2outputs_nerf_color(raw.to(DEV), z.to(DEV), None, occupancy=True, device=DEV)
+    oracle = O.raw2outputs(raw.clone(), z)
+    exact = raw2outputs_f64(raw, z)
+    assert tuple(wts.shape[:2]) == (333, S)
+    if S > 64:                                                # the designed rows are what they are meant to be
+        assert float(exact[3][7, 64]) > 0.999999 and float(exact[3][7, :64].max()) == 0.0
+        assert 0.99 < float(exact[3][8, 63]) < 0.9999 and float(exact[3][8, 64:].max()) < 2e-10
+    for got, ref32, ref64, what, bar in zip((d, v, rgb, wts.reshape(333, S)), oracle, exact, ('depth', 'var', 'rgb', 'weights'), (2e-7, 2e-6, 2e-6, 2e-6)):
+        got, ref32 = got.double().cpu().reshape(ref64.shape), ref32.double().reshape(ref64.shape)
+        scale = ref64.abs().max().clamp_min(1e-30)
+        e_kernel = float((got - ref64).abs().max() / scale)
+        e_oracle = float((ref32 - ref64).abs().max() / scale)
+        print(f'S {S} {what}: kernel {e_kernel:.2e} x scale, float32 oracle {e_oracle:.2e} x scale')
+        assert e_kernel <= max(bar, 2.0 * e_oracle), f'S {S} {what}: {e_kernel:.2e} x scale; the float32 oracle is {e_oracle:.2e} away'
+        assert_close(got, ref32, 1e-4, f'S {S} {what}')
 
 
 def test_relayout_round_trip(gm):

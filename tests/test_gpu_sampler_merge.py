@@ -11,6 +11,10 @@ case runs on both sides of the threshold itself.  The rows hold what the merge a
   which a uniform and a surface sample are EXACTLY equal (the tie goes to the uniform element, like torch.sort's stable order -- only
   the values matter, and they are equal, but the merge must still emit both); N_surface = 0 (no sort); perturb = 1 with a fixed t_rand.
 
+Every case also runs with rows above 64 samples (LONG_ROWS: S = 65, 129, 255, 256 = the ABI's maximum; 250 uniform samples alone):
+k_sample's staging rounds of 8 slots end ragged at 65 and 255, its wave-wide recount of a degenerate row and k_sample_small's
+lane-per-element loops take two to four passes, and k_sample_small's LDS row is full at 256.
+
 The comparison is on the int64 view of the f64 rows.  Both sides' NaNs are first replaced by ONE quiet NaN: which sign and payload
 an invalid operation returns is the processor's choice (x86 gives the negative default NaN, the GPU the positive one), not the
 sampler's."""
@@ -38,6 +42,11 @@ I_DESC = (3, 70)            # far < near
 I_NAN = (71, 128)           # NaN far plane
 I_ZERO = (5, 64, 128, 129)  # zero depth
 I_TIE = 66
+# rows above 64 samples: S = 65 (a ragged last staging round of k_sample: 65 = 8 x 8 + 1; one element in the second pass of the lane-per-
+# element loops), 129, 255 (ragged again) and 256 = ADFP_MAX_SAMPLES (k_sample_small's whole LDS row, four passes per lane in the
+# recount of a degenerate row)
+LONG_ROWS = [(48, 17), (100, 29), (200, 55), (224, 32)]
+MAX_NS = 250            # test_no_surface_samples' longest row; t_rand has that many columns
 
 
 class ExactScene(object):
@@ -80,7 +89,7 @@ def setup():
     dec.bound = sc.bound
     dec = dec.to(DEV)
     ro, rd, gd = make_rays()
-    t_rand = torch.rand(MERGE_MIN_RAYS + N, 48, generator=torch.Generator().manual_seed(12))
+    t_rand = torch.rand(MERGE_MIN_RAYS + N, MAX_NS, generator=torch.Generator().manual_seed(12))
     return dict(sc=sc, dec=dec, c=to_dev(sc.c, DEV), vol=sc.tsdf_volume.to(DEV), bnds=sc.tsdf_bnds.to(DEV),
                 ro=ro, rd=rd, gd=gd, t_rand=t_rand)
 
@@ -113,7 +122,7 @@ def run(s, n, ns, nf, lindisp=False, perturb=0.0):
 
 
 @pytest.mark.parametrize('n', SIZES)
-@pytest.mark.parametrize('ns,nf', [(48, 16), (5, 3)])
+@pytest.mark.parametrize('ns,nf', [(48, 16), (5, 3)] + LONG_ROWS)
 @pytest.mark.parametrize('lindisp', [False, True])
 def test_merge_bit_exact(setup, n, ns, nf, lindisp):
     ref = run(setup, n, ns, nf, lindisp=lindisp)
@@ -140,7 +149,7 @@ def test_merge_bit_exact(setup, n, ns, nf, lindisp):
 
 
 @pytest.mark.parametrize('n', SIZES)
-@pytest.mark.parametrize('ns', [48, 5])
+@pytest.mark.parametrize('ns', [48, 5, 250])
 def test_no_surface_samples(setup, n, ns):
     """N_surface = 0: the uniform list as it is, no sort (the descending rows stay descending)."""
     ref = run(setup, n, ns, 0)
@@ -148,7 +157,7 @@ def test_no_surface_samples(setup, n, ns):
 
 
 @pytest.mark.parametrize('n', SIZES)
-@pytest.mark.parametrize('ns,nf', [(48, 16), (5, 3)])
+@pytest.mark.parametrize('ns,nf', [(48, 16), (5, 3)] + LONG_ROWS)
 def test_perturbed(setup, n, ns, nf):
     run(setup, n, ns, nf, perturb=1.0)
 

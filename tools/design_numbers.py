@@ -208,6 +208,9 @@ def main(template, d):
     tight = re.findall(r'tight, \S+: (\d+) tensors, worst element (\S+) x scale', t)
     v['grad_tight_n'] = str(sum(int(a) for a, _ in tight)); v['grad_tight_worst'] = '%.1e' % max(float(b) for _, b in tight)
     v['grad_loose_worst'] = '%.1e' % max(float(b) for b in re.findall(r'loose, \S+: \d+ parameter tensors, worst element (\S+) x scale', t))
+    t = open(P('r09_grad_stats_sample_range.txt')).read()                    # the sample-count sweep (S = 1..256), rays leaving the bound, the fused path at S = 129
+    tight = re.findall(r'tight, \S+: (\d+) tensors, worst element (\S+) x scale', t)
+    v['grad_range_n'] = str(sum(int(a) for a, _ in tight)); v['grad_range_worst'] = '%.1e' % max(float(b) for _, b in tight)
     # ---- forward kernels of the frame
     h = stats(P('r06_kernel_stats_headline.csv'))
     for name in ('k_forward_head', 'k_sample', 'k_tsdf', 'k_decode_lc16', 'k_decode_high_g', 'k_attention_g', 'k_fallback_points', 'k_composite'):

@@ -2,13 +2,14 @@
 (tests/conftest.py: assert_grad_tight, assert_param_grad_close, assert_close) into the summaries kept under profiles/.
 
     python tools/stats_summary.py grad   <raw log> > profiles/r05_grad_stats.txt
-    python tools/stats_summary.py parity <raw log> > profiles/r05_parity_stats.txt"""
+    python tools/stats_summary.py parity <raw log> > profiles/r05_parity_stats.txt
+    python tools/stats_summary.py grad-cases <raw log> > profiles/r09_grad_stats_sample_range.txt      (the summary, then the worst per case)"""
 import re
 import statistics
 import sys
 
 
-def grad(path):
+def grad(path, scope='every gradient comparison of the GPU suite'):
     tight, loose = {}, {}
     for line in open(path):
         t = line.split()
@@ -22,7 +23,7 @@ def grad(path):
             m = re.search(r'max (\S+) fro (\S+) rows_bad (\d+)/(\d+)', line)
             if m:
                 loose.setdefault(t[0], []).append((float(m.group(1)), float(m.group(2)), int(m.group(3)), line.strip()))
-    print('# tests/ on the MI355X with ADFP_GRAD_STATS=<file>: every gradient comparison of the GPU suite, summarised by tools/stats_summary.py')
+    print(f'# tests/ on the MI355X with ADFP_GRAD_STATS=<file>: {scope}, summarised by tools/stats_summary.py')
     print('# "tight" = conftest.assert_grad_tight: kernels vs the oracle\'s autograd along the ReLU decisions the kernels\' backward took (forced in the oracle);')
     print('# "loose" = conftest.assert_param_grad_close: kernels vs the reference\'s own (unforced) autograd gradients (tests/golden/mini_<stage>.npz / the unforced oracle)')
     for mode, v in sorted(tight.items()):
@@ -37,6 +38,22 @@ def grad(path):
     print('\nten worst loose comparisons:')
     for x in sorted((x for v in loose.values() for x in v), reverse=True)[:10]:
         print('  ' + x[3])
+
+
+def grad_cases(path):
+    """grad(), then the worst tight element of every case (the label in front of ' d/d '): a jump between two neighbouring cases --
+    S = 64 and 65, 128 and 129 of tests/test_gpu_grad_sample_range.py -- would show here."""
+    grad(path, 'the gradient comparisons of tests/test_gpu_grad_sample_range.py and of test_gpu_mapper_glue.py::test_fused_gradient_against_the_oracle')
+    cases = {}
+    for line in open(path):
+        t = line.split()
+        if t and t[0] == 'tight' and ' d/d ' in line:
+            key = (line.split(' d/d ')[0].split(' ', 2)[2], t[1])
+            worst, n = cases.get(key, (0.0, 0))
+            cases[key] = (max(worst, float(t[-1])), n + 1)
+    print('\nworst tight element per case (x scale), in the order the tests ran:')
+    for (what, mode), (worst, n) in cases.items():
+        print(f'  {mode:5s} {what}: {worst:.2e} over {n} tensors')
 
 
 def parity(path):
@@ -59,4 +76,4 @@ def parity(path):
 
 
 if __name__ == '__main__':
-    (grad if sys.argv[1] == 'grad' else parity)(sys.argv[2])
+    {'grad': grad, 'grad-cases': grad_cases, 'parity': parity}[sys.argv[1]](sys.argv[2])
