@@ -20,6 +20,19 @@ def mapping_setting(cfg, key):
     return m[key] if key in m else MAPPING_DEFAULTS[key]
 
 
+# meshing.simplify_voxel_size: None or 0 = the marching-cubes mesh as it is; a positive number = the voxel (in the config's units,
+# multiplied by `scale` like the bounds) of mesh.simplify_vertex_clustering, run by Mesher.mesh_arrays after the component clean-up
+# and before the colour query.  meshing.simplify_contraction: 'quadric' or 'average'.  (Vertex clustering by this package's own
+# rules, include/adfp.h "mesh simplification": open3d's simplify_vertex_clustering was never run against it.)
+MESHING_DEFAULTS = {'simplify_voxel_size': None, 'simplify_contraction': 'quadric'}
+
+
+def meshing_setting(cfg, key):
+    """``cfg['meshing'][key]``, or this package's default for a key the reference's configs do not have."""
+    m = cfg.get('meshing') or {}
+    return m[key] if key in m else MESHING_DEFAULTS[key]
+
+
 def load_config(path, default_path=None):
     """The config of `path` merged over what it inherits: its ``inherit_from`` file (recursively), else `default_path`, else
     nothing (src/config.py:10-42)."""

@@ -223,6 +223,68 @@ def merge_coincident(verts, faces, colors=None):
     return _merge_coincident(v, f, c)
 
 
+# ---- mesh simplification (csrc/adfp_meshsimplify.h; contract: include/adfp.h, "mesh simplification") ---------------------------
+SIMPLIFY_CONTRACTIONS = _lib.SIMPLIFY
+
+
+def _simplify_vertex_clustering(v, f, voxel_size, contraction, c):
+    dev = v.device
+    V, F = int(v.shape[0]), int(f.shape[0])
+    empty = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev),
+             torch.empty((0, 3), dtype=torch.uint8, device=dev) if c is not None else None)
+    if V == 0 or F == 0:
+        return empty
+    L = lib()
+    with _lib.device_guard(dev):
+        st = _lib.current_stream(dev)
+        lo, hi = (x.tolist() for x in torch.aminmax(v, dim=0))           # the bounds: one read-back
+        if not np.isfinite(lo + hi).all():
+            raise ValueError('simplify_vertex_clustering: the vertices are not all finite')
+        nbytes = L.adfp_mesh_simplify_workspace_bytes(V, F)
+        if nbytes == 0:
+            raise RuntimeError(f'simplify_vertex_clustering: {V} vertices, {F} faces are more than the int32 sort carries')
+        ws = _ws(nbytes, dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        lo_c, hi_c = (C.c_double * 3)(*lo), (C.c_double * 3)(*hi)
+        check(L.adfp_mesh_simplify_plan(ptr(v), V, ptr(f), F, ptr(c), float(voxel_size), SIMPLIFY_CONTRACTIONS[contraction],
+                                        C.byref(lo_c), C.byref(hi_c), ptr(ws), nbytes, ptr(totals), st), 'adfp_mesh_simplify_plan')
+        nv, nf = (int(t) for t in totals.tolist())                       # the counts: one read-back
+        if nf == 0:
+            return empty
+        vo = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        fo = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        co = torch.empty((nv, 3), dtype=torch.uint8, device=dev) if c is not None else None
+        check(L.adfp_mesh_simplify_emit(V, F, ptr(ws), nbytes, ptr(vo), ptr(co), nv, ptr(fo), nf, st), 'adfp_mesh_simplify_emit')
+    return vo, fo, co
+
+
+def simplify_vertex_clustering(verts, faces, voxel_size, contraction='quadric', colors=None):
+    """Vertex clustering on the device (what open3d users call simplify_vertex_clustering): one vertex per occupied cell of a
+    voxel_size lattice (adfp_voxel_down_sample's cells), at the cell's average (contraction='average') or where the quadric of
+    the cell's faces puts it, moving from the average only along well-conditioned directions and by at most a voxel
+    ('quadric'); faces follow, collapsed and duplicate faces and the clusters no face uses are dropped.  colors (uint8 [V,3])
+    are averaged per cell, rounding half up.  Returns (verts f32 [V',3], faces int32 [F',3], colors uint8 [V',3] or None) as
+    device tensors: vertices in ascending cell key, faces in input order, smallest index first; the same bits every run.
+    A voxel larger than the model gives an empty mesh.  The rules are include/adfp.h's ("mesh simplification"), this package's
+    own statement of vertex clustering: open3d is not installed here and its function was never run against this one."""
+    v, f = _mesh_tensors(verts, faces, 'simplify_vertex_clustering')
+    if v is None:
+        raise ValueError('simplify_vertex_clustering: verts is None')
+    vs = float(voxel_size)
+    if not (vs > 0.0 and np.isfinite(vs)):
+        raise ValueError(f'simplify_vertex_clustering: voxel_size must be positive and finite, got {voxel_size!r}')
+    if contraction not in SIMPLIFY_CONTRACTIONS:
+        raise ValueError(f'simplify_vertex_clustering: contraction must be one of {sorted(SIMPLIFY_CONTRACTIONS)}, got {contraction!r}')
+    c = None
+    if colors is not None:
+        require_cuda(colors, 'simplify_vertex_clustering colors')
+        c = colors.detach().reshape(-1, 3).to(v.device, torch.uint8).contiguous()
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f'simplify_vertex_clustering: {c.shape[0]} colours for {v.shape[0]} vertices')
+    _check_indices(f, int(v.shape[0]), 'simplify_vertex_clustering')
+    return _simplify_vertex_clustering(v, f, vs, contraction, c)
+
+
 def color_bytes(rgb):
     """(clip(rgb[:, :3], 0, 1) * 255) truncated to uint8 [n,3] on the device; rgb: float32 rows of at least three channels."""
     require_cuda(rgb, 'color_bytes rgb')

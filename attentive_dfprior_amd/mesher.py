@@ -14,6 +14,11 @@ csrc/adfp_bound.h, while Qhull keeps the facets of the few hundred hull vertices
 ``get_bound_planes`` (numpy and Qhull over every point) and the module's ``merge_coincident`` remain as the host statements of the
 same steps: the tests compare the device path against them.
 
+Two cfg keys the reference does not have (``config.MESHING_DEFAULTS``): ``meshing.simplify_voxel_size`` (default None = off; a
+positive number, in the config's units, clusters the cleaned mesh's vertices per voxel cell before the colour query,
+``mesh.simplify_vertex_clustering``) and ``meshing.simplify_contraction`` ('quadric' or 'average').  Vertex clustering by this
+package's own rules (include/adfp.h, "mesh simplification"): open3d's function was never run against it.
+
 Deviations, both documented in INTEGRATION.md:
   * the mesh bound (``get_bound_from_frames``) is the convex hull of the keyframes' camera centres and back-projected valid
     depth pixels (scipy.spatial.ConvexHull, per frame, then over the union of the frames' hull vertices), scaled by
@@ -29,6 +34,7 @@ import torch
 import torch.nn.functional as F
 
 from . import mesh as M
+from .config import meshing_setting
 
 
 class Mesher(object):
@@ -47,6 +53,12 @@ class Mesher(object):
         self.color_mesh_extraction_method = cfg['meshing']['color_mesh_extraction_method']
         self.get_largest_components = cfg['meshing']['get_largest_components']
         self.depth_test = cfg['meshing']['depth_test']
+        # this package's own keys (config.MESHING_DEFAULTS; the reference's configs have neither): a positive simplify_voxel_size
+        # (in the config's units, like the bounds) clusters the cleaned mesh's vertices before the colour query
+        self.simplify_voxel_size = meshing_setting(cfg, 'simplify_voxel_size')
+        self.simplify_contraction = meshing_setting(cfg, 'simplify_contraction')
+        if self.simplify_contraction not in M.SIMPLIFY_CONTRACTIONS:
+            raise ValueError(f'meshing.simplify_contraction={self.simplify_contraction!r}: one of {sorted(M.SIMPLIFY_CONTRACTIONS)}')
 
         self.bound = slam.bound
         self.verbose = slam.verbose
@@ -320,6 +332,9 @@ class Mesher(object):
                 verts, faces = M._clean_components(verts, faces, seen.to(torch.uint8),
                                                    self.remove_small_geometry_threshold * self.scale * self.scale,
                                                    bool(self.get_largest_components))
+            if self.simplify_voxel_size is not None and self.simplify_voxel_size > 0:
+                verts, faces, _ = M._simplify_vertex_clustering(verts, faces, float(self.simplify_voxel_size) * self.scale,
+                                                                self.simplify_contraction, None)
             vertex_colors = None
             if color:
                 vc = [M.color_bytes(self.eval_points(pnts, decoders, tsdf_volume, self.tsdf_bnds, c, 'color', device))

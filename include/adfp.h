@@ -1141,6 +1141,52 @@ int adfp_mesh_merge_emit(const float* verts, const unsigned char* colors, long l
  * first three are used); NaN gives 0. */
 int adfp_mesh_color_bytes(const float* rgb, long long n, int stride, unsigned char* out, void* stream);
 
+/* ---- mesh simplification (vertex clustering: what open3d users call TriangleMesh::simplify_vertex_clustering) ----------------
+ * One vertex per occupied voxel cell.  open3d is not installed where this was written and its function was never run against
+ * this one: the rules below are this package's own statement of vertex clustering.  They follow open3d's cell rule and its
+ * quadric accumulation as we read it; three choices are ours: the truncated placement, the dropped unreferenced clusters and
+ * the output order.  Deterministic: no atomics decide anything, the same input gives the same bits.
+ * Inputs: verts [V][3] f32, faces [F][3] int32, colors [V][3] uint8 or NULL (all device); voxel_size (f64, > 0, finite);
+ * contraction ADFP_SIMPLIFY_AVERAGE or ADFP_SIMPLIFY_QUADRIC; min_bound, max_bound: HOST f64 [3], the exact per-axis minimum and
+ * maximum of the vertices.
+ * Cells: adfp_voxel_down_sample's rule on (double)verts -- vmin = min_bound - voxel_size * 0.5, N_c = floor((max_bound_c - vmin_c)
+ * / voxel_size) + 1 (more than 2^21 is ADFP_E_UNSUPPORTED), i_c = floor((p_c - vmin_c) / voxel_size), key (i_0 N_1 + i_1) N_2 +
+ * i_2, the vertices sorted stably by key in passes of 31 key bits from the lowest.  Cluster k = the k-th occupied cell in
+ * ascending key order.
+ * Average: m_k = the f64 sum of the cell's vertices in input order over their count n (each component divided).  Colour per
+ * channel: (2 S + n) / (2 n) in integers (round half up), S the cell's integer sum.  Colours are these in both modes.
+ * Quadric placement: for a face with vertices p0, p1, p2 in f64, g = (p1 - p0) x (p2 - p0), l = sqrt((g0 g0 + g1 g1) + g2 g2); a
+ * face with l == 0 or non-finite l contributes nothing; else n = g / l, w = l / 2.  The face contributes once per corner to that
+ * corner's cluster (twice to a cluster that holds two of its vertices, as open3d does): with d = -n . (p0 - m_k), A += w n n^T,
+ * b += w d n, summed per cluster in ascending face index, then corner index (the 3 F contributions are generated face-major and
+ * sorted stably by cluster).  With A = sum lambda_i e_i e_i^T (eight cyclic Jacobi sweeps in f64), lambda_max the largest:
+ * x = sum over {i : lambda_i > 1e-3 lambda_max} of e_i (e_i . (-b)) / lambda_i -- a flat patch moves along its normal only, an
+ * edge along two directions, a corner freely.  If lambda_max is not positive, or max_c |x_c| > voxel_size, the cluster keeps m_k;
+ * else its position is m_k + x.  Positions are rounded to f32 once, at the end.  (Sums and products of the quadric are not
+ * promised bit for bit against another evaluation order; a cluster whose lambda_i / lambda_max or max |x_c| sits at its threshold
+ * can fall either way.)
+ * Faces: each face maps through vertex -> cluster; a face with two equal indices is dropped; a survivor is rotated so that its
+ * smallest index is first (orientation kept); among faces with the same rotated triple the earliest input face survives
+ * (oppositely oriented copies are different triples: both stay); survivors keep input order.  A face with an index outside
+ * [0, V) is never dereferenced: it contributes nothing and is dropped.
+ * Vertices: clusters that no surviving face references are dropped, the rest keep ascending key order, faces are renumbered
+ * (adfp_mesh_compact_plan on the triples, inside the workspace).
+ * _plan writes totals[2] (device long long) = (vertices, faces) that remain; the caller reads them, allocates, and calls _emit with
+ * the same counts, workspace and totals; colors_out may be given only when _plan had colors.  V = 0 or F = 0 writes totals (0, 0)
+ * and launches nothing.  adfp_mesh_simplify_workspace_bytes(V, F): 0 for V <= 0, F <= 0 or beyond the limits.  One lane per cell
+ * walks the cell's run: a voxel as large as the model is served, slowly.
+ * Errors, before any launch: ADFP_E_ARG for a null pointer, a negative count, voxel_size <= 0 or non-finite, non-finite bounds or
+ * min_bound > max_bound, contraction outside {0, 1}, more out than in; ADFP_E_UNSUPPORTED for V or 3 F above 2^31 - 1025 or more
+ * than 2^21 cells on an axis; ADFP_E_WORKSPACE. */
+#define ADFP_SIMPLIFY_AVERAGE 0
+#define ADFP_SIMPLIFY_QUADRIC 1
+size_t adfp_mesh_simplify_workspace_bytes(long long n_verts, long long n_faces);
+int adfp_mesh_simplify_plan(const float* verts, long long n_verts, const int* faces, long long n_faces, const unsigned char* colors /*or NULL*/,
+                            double voxel_size, int contraction, const double min_bound[3], const double max_bound[3], void* workspace,
+                            size_t workspace_bytes, long long* totals, void* stream);
+int adfp_mesh_simplify_emit(long long n_verts, long long n_faces, const void* workspace, size_t workspace_bytes, float* verts_out,
+                            unsigned char* colors_out /*or NULL*/, long long n_verts_out, int* faces_out, long long n_faces_out, void* stream);
+
 /* ---- mesh bound (mesher.Mesher.get_bound_planes: the hull of the keyframes' camera centres and back-projected depth pixels) ----
  * The point work of a quickhull in rounds (mesh.depth_hull keeps the facets of the few hundred hull vertices with Qhull on the
  * host).  The scene: depth [K][H][W] (f32, device), poses [K][16] (f32, device; row-major [4,4] est_c2w), fx, fy, cx, cy (f64, host).
