@@ -40,10 +40,14 @@ def grad_close(got, ref, what, tol=GTOL, mode=None):
         assert_close_scale(got.detach(), ref, tol, what, flip_frac=2e-3 if last.startswith('grid') else 0.0)
 
 
-def run(mini, stage, warm, sd=None, n_samples=None, n_surface=None, rays=None, bwd_options=None, capture=None, side_lane=None, with_depth=True):
-    """capture: a dict; the backward then exports its ReLU decisions and capture['relu_masks'] = Engine.relu_masks(...).
+def run(mini, stage, warm, sd=None, n_samples=None, n_surface=None, rays=None, bwd_options=None, capture=None, side_lane=None, with_depth=True,
+        rend=None):
+    """capture: a dict; the backward then exports its ReLU decisions and capture['relu_masks'] = Engine.relu_masks(...),
+    capture['saved'] = the training state the backward ran on.
     with_depth=False: the render call gets no sensor depth (N_surface is ignored, far = the slab test's); the loss still masks on
-    the batch's gt_depth."""
+    the batch's gt_depth.
+    rend: an existing Renderer (of the same sample counts) to make the call on -- its engine's grow-only scratch then holds what
+    the calls before left there -- or a callable, run on the call's fresh Renderer first."""
     sd = mini.sd if sd is None else sd
     dec = A.DF()
     dec.load_state_dict(sd)
@@ -51,8 +55,12 @@ def run(mini, stage, warm, sd=None, n_samples=None, n_surface=None, rays=None, b
     dec = dec.to(DEV)
     for p in dec.parameters():
         p.requires_grad_(True)
-    rend = A.Renderer(make_cfg(n_samples or mini.n_samples, n_surface if n_surface is not None else mini.n_surface),
-                      None, mini)
+    if not isinstance(rend, A.Renderer):
+        prime = rend
+        rend = A.Renderer(make_cfg(n_samples or mini.n_samples, n_surface if n_surface is not None else mini.n_surface),
+                          None, mini)
+        if prime is not None:
+            prime(rend)
     if bwd_options is not None:
         rend._engine.bwd_options = bwd_options
     if side_lane is not None:                                # the autograd path takes the lane only when told to (default: MapperIteration alone)
@@ -70,6 +78,7 @@ def run(mini, stage, warm, sd=None, n_samples=None, n_surface=None, rays=None, b
     loss.backward()
     if capture is not None:
         capture['relu_masks'] = cap.masks(stage)
+        capture['saved'] = cap.saved
     return loss, c, dec
 
 
@@ -87,17 +96,18 @@ def oracle_grads(mini, sd, rays, stage, warm, n_samples, n_surface, relu_masks=N
     return loss2, {k: zero(v) for k, v in c_or.items()}, {k: zero(v) for k, v in sd_or.items()}
 
 
-def check_tight(mini, stage, warm, mode, sd=None, n_samples=None, n_surface=None, rays=None, what='', with_depth=True, out=None):
+def check_tight(mini, stage, warm, mode, sd=None, n_samples=None, n_surface=None, rays=None, what='', with_depth=True, out=None, rend=None):
     """THE gradient criterion: kernels vs the oracle's autograd along the kernels' own ReLU decisions, every element of every
     grid and parameter gradient within conftest.TIGHT_GRAD_TOL x the tensor's scale; and the forced decisions are legitimate --
     they differ from relu's own only on units whose pre-activation is within rounding of zero.
-    out: a dict that receives the kernels' side (`c`, `dec`) and the oracle's grid gradients (`oracle_grids`)."""
+    out: a dict that receives the kernels' side (`c`, `dec`, `capture`: run's) and the oracle's gradients (`oracle_grids`, `oracle_params`).
+    rend: as run's."""
     sd = mini.sd if sd is None else sd
     ns = n_samples or mini.n_samples
     nf = n_surface if n_surface is not None else mini.n_surface
     rays = rays if rays is not None else (mini.rays_o, mini.rays_d, mini.gt_depth, mini.gt_color)
     cap = {}
-    loss, c, dec = run(mini, stage, warm, sd=sd, n_samples=ns, n_surface=nf, rays=rays, capture=cap, with_depth=with_depth)
+    loss, c, dec = run(mini, stage, warm, sd=sd, n_samples=ns, n_surface=nf, rays=rays, capture=cap, with_depth=with_depth, rend=rend)
     O.reset_relu_flips()
     loss2, gc_or, gsd_or = oracle_grads(mini, sd, rays, stage, warm, ns, nf, relu_masks=cap['relu_masks'], with_depth=with_depth)
     flips = dict(O.RELU_FLIPS)
@@ -110,7 +120,7 @@ def check_tight(mini, stage, warm, mode, sd=None, n_samples=None, n_surface=None
         got = p.grad if p.grad is not None else torch.zeros_like(p)
         assert_grad_tight(got, gsd_or[name], f'{what}{stage} d/d {name}', mode)
     if out is not None:
-        out.update(c=c, dec=dec, oracle_grids=gc_or)
+        out.update(c=c, dec=dec, oracle_grids=gc_or, oracle_params=gsd_or, capture=cap)
     return flips
 
 

@@ -3,7 +3,8 @@
 
     python tools/stats_summary.py grad   <raw log> > profiles/r05_grad_stats.txt
     python tools/stats_summary.py parity <raw log> > profiles/r05_parity_stats.txt
-    python tools/stats_summary.py grad-cases <raw log> > profiles/r09_grad_stats_sample_range.txt      (the summary, then the worst per case)"""
+    python tools/stats_summary.py grad-cases <raw log> > profiles/r09_grad_stats_sample_range.txt      (the summary, then the worst per case)
+    python tools/stats_summary.py grad-cases <raw log> "<which comparisons>" > profiles/r10_grad_stats_inband_range.txt"""
 import re
 import statistics
 import sys
@@ -40,10 +41,11 @@ def grad(path, scope='every gradient comparison of the GPU suite'):
         print('  ' + x[3])
 
 
-def grad_cases(path):
+def grad_cases(path, scope='the gradient comparisons of tests/test_gpu_grad_sample_range.py and of test_gpu_mapper_glue.py::test_fused_gradient_against_the_oracle'):
     """grad(), then the worst tight element of every case (the label in front of ' d/d '): a jump between two neighbouring cases --
-    S = 64 and 65, 128 and 129 of tests/test_gpu_grad_sample_range.py -- would show here."""
-    grad(path, 'the gradient comparisons of tests/test_gpu_grad_sample_range.py and of test_gpu_mapper_glue.py::test_fused_gradient_against_the_oracle')
+    S = 64 and 65, 128 and 129 of tests/test_gpu_grad_sample_range.py, an in-band count of 4 096 and 4 097 of
+    tests/test_gpu_grad_inband_range.py -- would show here."""
+    grad(path, scope)
     cases = {}
     for line in open(path):
         t = line.split()
@@ -76,4 +78,4 @@ def parity(path):
 
 
 if __name__ == '__main__':
-    {'grad': grad, 'grad-cases': grad_cases, 'parity': parity}[sys.argv[1]](sys.argv[2])
+    {'grad': grad, 'grad-cases': grad_cases, 'parity': parity}[sys.argv[1]](*sys.argv[2:4])
