@@ -393,6 +393,10 @@ SYMBOLS = [
                                           C.c_void_p]),
     ('adfp_mesh_simplify_emit', C.c_int, [C.c_longlong, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_longlong,
                                           C.c_void_p, C.c_longlong, C.c_void_p]),
+    # mesh colours from the keyframes
+    ('adfp_mesh_project_colors', C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int,
+                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # mesh bound: the scene is (depth, poses, K, H, W, fx, fy, cx, cy)
     ('adfp_bound_support_workspace_bytes', C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
     ('adfp_bound_support', C.c_int, _BOUND_SCENE + [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -433,6 +437,7 @@ SHADE_MODE = {'color': 0, 'shaded': 1, 'normal': 2}     # ADFP_SHADE_COLOR / _SH
 UNIT_VOXELS = 16                        # ADFP_UNIT_VOXELS
 SEEN_RULE = {'frustum': 0, 'max_depth': 1, 'depth_test': 2}     # ADFP_SEEN_FRUSTUM / _MAX_DEPTH / _DEPTH_TEST
 SIMPLIFY = {'average': 0, 'quadric': 1}     # ADFP_SIMPLIFY_AVERAGE / _QUADRIC
+BLEND = {'weighted': 0, 'best': 1}          # ADFP_BLEND_WEIGHTED / _BEST
 BOUND_MAX_DIRECTIONS = 1024             # ADFP_BOUND_MAX_DIRECTIONS
 CAST_NO_SKIP = 1                       # ADFP_CAST_NO_SKIP
 LABEL_ROUNDS_MAX = 128                # above the worst case of adfp_mesh_face_labels_rounds (2 log2(F) + 2 < 66)

@@ -27,10 +27,19 @@ def mapping_setting(cfg, key):
 MESHING_DEFAULTS = {'simplify_voxel_size': None, 'simplify_contraction': 'quadric'}
 
 
+# color_mesh_extraction_method: keyframe_projection (mesher.Mesher, mesh.project_colors): projection_depth_tol = how far, in the
+# config's units (multiplied by `scale`), a keyframe's depth may lie from the vertex's for the keyframe to count as seeing it --
+# 0.05 is the 5 cm the completion ratio and the F-score call "the same surface"; projection_blend 'weighted' (cos / depth^2 over all
+# views) or 'best' (the view of largest weight alone); projection_border = pixels kept clear of the image's edge.
+PROJECTION_DEFAULTS = {'projection_depth_tol': 0.05, 'projection_blend': 'weighted', 'projection_border': 0}
+
+
 def meshing_setting(cfg, key):
     """``cfg['meshing'][key]``, or this package's default for a key the reference's configs do not have."""
     m = cfg.get('meshing') or {}
-    return m[key] if key in m else MESHING_DEFAULTS[key]
+    if key in m:
+        return m[key]
+    return MESHING_DEFAULTS[key] if key in MESHING_DEFAULTS else PROJECTION_DEFAULTS[key]
 
 
 def load_config(path, default_path=None):

@@ -3356,6 +3356,7 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
 #include "adfp_keyframes.h"     // the Mapper's keyframe selection
 #include "adfp_ba.h"            // the Mapper's bundle adjustment
 #include "adfp_meshclean.h"     // mesh clean-up (the seen mask is adfp_recon.h's k_cull_seen)
+#include "adfp_meshcolor.h"     // mesh colours from the keyframes' images
 #include "adfp_meshshade.h"     // mesh views: vertex normals and the shading pass
 #include "adfp_meshsimplify.h"  // mesh simplification: vertex clustering
 #include "adfp_bound.h"         // mesh bound

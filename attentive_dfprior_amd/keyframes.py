@@ -238,6 +238,10 @@ class KeyframeStore(object):
         """The first n (default: all) keyframe depth images, a contiguous [n,H,W] f32 view (what Mesher.seen_mask reads)."""
         return self._depth[:self._n if n is None else int(n)]
 
+    def colors(self, n=None):
+        """The first n (default: all) keyframe colour images, a contiguous [n,H,W,3] f32 view (what mesh.project_colors reads)."""
+        return self._color[:self._n if n is None else int(n)]
+
     def frame(self, i):
         """(c2w [4,4], depth [H,W], color [H,W,3]) of keyframe i: device views."""
         if not 0 <= i < self._n:

@@ -326,6 +326,70 @@ def vertex_normals(verts, faces, device=None):
     return out
 
 
+# ---- mesh colours from the keyframes (csrc/adfp_meshcolor.h; the rule: include/adfp.h, "mesh colours from the keyframes") ------
+BLENDS = _lib.BLEND
+
+
+def _project_colors(v, n, depth, color, c2w, fx, fy, cx, cy, depth_tol, border, blend):
+    """project_colors on prepared tensors: v f32 [V,3], n f32 [V,3] or None, depth f32 [K,H,W], color f32 [K,H,W,3], all contiguous
+    on one device; c2w [K,4,4] on any device (read back once and inverted on the host, as Mesher.seen_mask does)."""
+    dev = v.device
+    V, K, H, W = int(v.shape[0]), int(depth.shape[0]), int(depth.shape[1]), int(depth.shape[2])
+    rgb = torch.zeros((V, 3), dtype=torch.float32, device=dev)
+    wsum = torch.zeros(V, dtype=torch.float32, device=dev)
+    count = torch.zeros(V, dtype=torch.int32, device=dev)
+    best = torch.full((V,), -1, dtype=torch.int32, device=dev)
+    w2c = center = None
+    if K:
+        m = c2w.detach().cpu().numpy()
+        w2c = torch.from_numpy(np.ascontiguousarray(np.linalg.inv(m)[:, :3, :])).to(dev).float().reshape(K, 12).contiguous()
+        center = torch.from_numpy(np.ascontiguousarray(m[:, :3, 3])).to(dev).float().contiguous()
+    with _lib.device_guard(dev):
+        check(lib().adfp_mesh_project_colors(ptr(v) if V else None, ptr(n) if V else None, V, ptr(w2c), ptr(center),
+                                             ptr(depth) if K else None, ptr(color) if K else None, K, float(fx), float(fy), float(cx),
+                                             float(cy), W, H, float(depth_tol), int(border), BLENDS[blend], ptr(rgb), ptr(wsum), ptr(count),
+                                             ptr(best), _lib.current_stream(dev)), 'adfp_mesh_project_colors')
+    return rgb, wsum, count, best
+
+
+def project_colors(verts, normals, depth, color, c2w, fx, fy, cx, cy, depth_tol, border=0, blend='weighted'):
+    """Vertex colours from the keyframes' images on the device (adfp_mesh_project_colors): every vertex is projected into every
+    keyframe, a view counts only where the four depth pixels around the projection all lie within depth_tol of the vertex's
+    depth (no hole, no depth edge in the footprint), and the bilinear colours of the views that count are blended: 'weighted'
+    by cos(view, normal) / depth^2, or 'best' = the view of largest weight alone.  verts [V,3] (the keyframes' world); normals
+    [V,3] (mesh.vertex_normals' output: its f32 rounding is used) or None (every weight's cosine is 1); depth [K,H,W], color
+    [K,H,W,3], c2w [K,4,4] (est_c2w, inverted on the host as Mesher.seen_mask inverts them); border: pixels kept clear of the
+    image's edge.  Returns device tensors (rgb f32 [V,3], wsum f32 [V], count int32 [V], best int32 [V]): zeros and best = -1
+    where no keyframe sees the vertex.  The same bits every run.  The rule, operation for operation: include/adfp.h."""
+    if blend not in BLENDS:
+        raise ValueError(f'project_colors: blend must be one of {sorted(BLENDS)}, got {blend!r}')
+    tol = float(depth_tol)
+    if not (tol >= 0.0 and np.isfinite(tol)):
+        raise ValueError(f'project_colors: depth_tol must be finite and not negative, got {depth_tol!r}')
+    require_cuda(verts, 'project_colors verts')
+    v = verts.detach().reshape(-1, 3).to(torch.float32).contiguous()
+    dev = v.device
+    n = None
+    if normals is not None:
+        n = (normals if torch.is_tensor(normals) else torch.from_numpy(np.asarray(normals)))
+        n = n.detach().reshape(-1, 3).to(dev, torch.float32).contiguous()
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f'project_colors: {n.shape[0]} normals for {v.shape[0]} vertices')
+    d = depth.detach().to(dev, torch.float32)
+    if d.dim() != 3:
+        raise ValueError(f'project_colors: depth must be [K,H,W], got {tuple(d.shape)}')
+    K, H, W = (int(s) for s in d.shape)
+    col = color.detach().to(dev, torch.float32)
+    if tuple(col.shape) != (K, H, W, 3):
+        raise ValueError(f'project_colors: color must be [{K},{H},{W},3], got {tuple(col.shape)}')
+    m = c2w if torch.is_tensor(c2w) else torch.from_numpy(np.asarray(c2w))
+    if tuple(m.shape) != (K, 4, 4):
+        raise ValueError(f'project_colors: c2w must be [{K},4,4], got {tuple(m.shape)}')
+    if int(border) < 0 or 2 * int(border) > min(W, H) - 2:
+        raise ValueError(f'project_colors: border {border} leaves no pixel of a {W} x {H} image')
+    return _project_colors(v, n, d.contiguous(), col.contiguous(), m, fx, fy, cx, cy, tol, int(border), blend)
+
+
 def _np(x):
     if x is None:
         return None

@@ -19,6 +19,11 @@ positive number, in the config's units, clusters the cleaned mesh's vertices per
 ``mesh.simplify_vertex_clustering``) and ``meshing.simplify_contraction`` ('quadric' or 'average').  Vertex clustering by this
 package's own rules (include/adfp.h, "mesh simplification"): open3d's function was never run against it.
 
+``color_mesh_extraction_method: keyframe_projection`` (this package's own value of the reference's key) colours the vertices that a
+keyframe sees from the keyframes' images (``mesh.project_colors``, csrc/adfp_meshcolor.h) and the rest by the direct point query;
+``meshing.projection_depth_tol`` (default 0.05, in the config's units), ``projection_blend`` ('weighted' or 'best') and
+``projection_border`` (pixels) steer it.
+
 Deviations, both documented in INTEGRATION.md:
   * the mesh bound (``get_bound_from_frames``) is the convex hull of the keyframes' camera centres and back-projected valid
     depth pixels (scipy.spatial.ConvexHull, per frame, then over the union of the frames' hull vertices), scaled by
@@ -35,6 +40,11 @@ import torch.nn.functional as F
 
 from . import mesh as M
 from .config import meshing_setting
+
+
+# direct_point_query: the colour decoder at every vertex (the reference's default).  keyframe_projection: the keyframes' own
+# images where a keyframe sees the vertex (mesh.project_colors), the decoder elsewhere.  The reference's render_ray is not offered.
+COLOR_METHODS = ('direct_point_query', 'keyframe_projection')
 
 
 class Mesher(object):
@@ -59,6 +69,16 @@ class Mesher(object):
         self.simplify_contraction = meshing_setting(cfg, 'simplify_contraction')
         if self.simplify_contraction not in M.SIMPLIFY_CONTRACTIONS:
             raise ValueError(f'meshing.simplify_contraction={self.simplify_contraction!r}: one of {sorted(M.SIMPLIFY_CONTRACTIONS)}')
+        # color_mesh_extraction_method: keyframe_projection (this package's own; the rule is include/adfp.h's "mesh colours from the
+        # keyframes"): depth_tol in the config's units (times `scale`, like the bounds), the blend and the border in pixels
+        self.projection_depth_tol = float(meshing_setting(cfg, 'projection_depth_tol')) * self.scale
+        self.projection_blend = meshing_setting(cfg, 'projection_blend')
+        self.projection_border = int(meshing_setting(cfg, 'projection_border'))
+        if self.projection_blend not in M.BLENDS:
+            raise ValueError(f'meshing.projection_blend={self.projection_blend!r}: one of {sorted(M.BLENDS)}')
+        if not (self.projection_depth_tol >= 0 and np.isfinite(self.projection_depth_tol)) or self.projection_border < 0:
+            raise ValueError(f'meshing.projection_depth_tol={self.projection_depth_tol!r}, projection_border={self.projection_border!r}: '
+                             'a finite tolerance and a border, neither negative')
 
         self.bound = slam.bound
         self.verbose = slam.verbose
@@ -320,6 +340,31 @@ class Mesher(object):
         remap[used] = np.arange(len(used))
         return vertices[used], remap[faces].astype(np.int32)
 
+    def projected_colors(self, verts, faces, keyframe_dict, device='cuda:0', keyframe_store=None):
+        """(rgb f32 [V,3], count int32 [V]) of the mesh's vertices from the keyframes' images (mesh.project_colors with the
+        mesh's own vertex normals and this Mesher's projection_* settings): count = 0 where no keyframe sees the vertex.  Depth,
+        colour and poses come from ``keyframe_store`` (a keyframes.KeyframeStore of the same keyframes in the same order: its
+        resident blocks are read in place) or are stacked from ``keyframe_dict`` once, as seen_mask stacks the depths."""
+        dev = torch.device(device)
+        K = len(keyframe_dict)
+        if keyframe_store is not None:
+            if len(keyframe_store) < K:
+                raise ValueError(f'projected_colors: the store holds {len(keyframe_store)} keyframes, keyframe_dict {K}')
+            depth, image, poses = keyframe_store.depths(K), keyframe_store.colors(K), keyframe_store.poses(K)
+        elif K:
+            depth = torch.stack([keyframe['depth'] for keyframe in keyframe_dict]).to(dev, torch.float32)
+            image = torch.stack([keyframe['color'] for keyframe in keyframe_dict]).to(dev, torch.float32)
+            poses = torch.stack([keyframe['est_c2w'].detach() for keyframe in keyframe_dict]).to(torch.float32)
+        else:
+            depth = torch.zeros((0, self.H, self.W), dtype=torch.float32, device=dev)
+            image = torch.zeros((0, self.H, self.W, 3), dtype=torch.float32, device=dev)
+            poses = torch.zeros((0, 4, 4), dtype=torch.float32)
+        normals = M.vertex_normals(verts, faces)
+        rgb, _, count, _ = M.project_colors(verts, normals, depth.reshape(K, self.H, self.W), image.reshape(K, self.H, self.W, 3),
+                                            poses.reshape(K, 4, 4), self.fx, self.fy, self.cx, self.cy, self.projection_depth_tol,
+                                            self.projection_border, self.projection_blend)
+        return rgb, count
+
     def mesh_arrays(self, verts, faces, c, decoders, keyframe_dict, estimate_c2w_list, idx, tsdf_volume, device='cuda:0',
                     color=True, clean_mesh=True, get_mask_use_all_frames=False, keyframe_store=None):
         """get_mesh from the marching-cubes output (device verts f32 [V,3], faces int32 [F,3]) to the arrays write_ply takes
@@ -340,6 +385,10 @@ class Mesher(object):
                 vc = [M.color_bytes(self.eval_points(pnts, decoders, tsdf_volume, self.tsdf_bnds, c, 'color', device))
                       for pnts in torch.split(verts, self.points_batch_size, dim=0)]
                 vertex_colors = torch.cat(vc, 0) if vc else torch.zeros((0, 3), dtype=torch.uint8, device=verts.device)
+                if self.color_mesh_extraction_method == 'keyframe_projection' and verts.shape[0]:
+                    # the keyframes' colour where a keyframe sees the vertex, the decoder's elsewhere
+                    rgb, count = self.projected_colors(verts, faces, keyframe_dict, device, keyframe_store)
+                    vertex_colors = torch.where((count > 0)[:, None], M.color_bytes(rgb), vertex_colors)
             verts, faces, vertex_colors = M._merge_coincident(verts, faces, vertex_colors)
             vertices = verts.cpu().numpy() / np.float32(self.scale)
             return vertices, faces.cpu().numpy(), (vertex_colors.cpu().numpy() if vertex_colors is not None else None)
@@ -353,8 +402,8 @@ class Mesher(object):
         then read."""
         if not str(mesh_out_file).lower().endswith('.ply'):
             raise NotImplementedError(f'{mesh_out_file}: only .ply output is supported')
-        if color and self.color_mesh_extraction_method != 'direct_point_query':
-            raise NotImplementedError(f'color_mesh_extraction_method={self.color_mesh_extraction_method!r}: only direct_point_query')
+        if color and self.color_mesh_extraction_method not in COLOR_METHODS:
+            raise NotImplementedError(f'color_mesh_extraction_method={self.color_mesh_extraction_method!r}: one of {COLOR_METHODS}')
         with torch.no_grad():
             xyz = self.get_grid_uniform(self.resolution)['xyz']
             z, ax = self.lattice(c, decoders, tsdf_volume, xyz, device)

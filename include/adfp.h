@@ -1187,6 +1187,40 @@ int adfp_mesh_simplify_plan(const float* verts, long long n_verts, const int* fa
 int adfp_mesh_simplify_emit(long long n_verts, long long n_faces, const void* workspace, size_t workspace_bytes, float* verts_out,
                             unsigned char* colors_out /*or NULL*/, long long n_verts_out, int* faces_out, long long n_faces_out, void* stream);
 
+/* ---- mesh colours from the keyframes (Mesher's color_mesh_extraction_method: keyframe_projection) ---------------------------
+ * Every vertex is projected into every keyframe; the keyframe's own depth image rejects the views in which the vertex is occluded
+ * or falls on a hole; the surviving views are blended.  The rule below is this package's own statement: nothing of it is in the
+ * reference.  One launch, no workspace.  Nothing is decided by an atomic: the same input gives the same bits every run.
+ * Inputs (device unless said): verts [V][3] f32 (the Mesher's scaled world); normals [V][3] f32 or NULL; per keyframe k < K:
+ * w2c [K][12] f32, formed as adfp_mesh_seen_mask's (the top three rows of np.linalg.inv of the f32 pose), center [K][3] f32 =
+ * c2w[:3, 3], depth [K][H][W] f32, color [K][H][W][3] f32; fx, fy, cx, cy, depth_tol (f32, host); W, H, border >= 0, blend.
+ * For vertex p = verts[i] and keyframe k, all in f32, every product and sum rounded on its own (no FMA):
+ *   1. cam, X, Z, zz, u, v: adfp_mesh_seen_mask's projection, operation for operation (cam = ((w0 x + w1 y) + w2 z) + w3 per row,
+ *      X = -cam.x, Z = cam.z, zz = Z + 1e-8, u = (fx X + cx Z) / zz, v = (fy cam.y + cy Z) / zz).
+ *   2. in frame iff zz < 0 && border <= u <= W - 1 - border && border <= v <= H - 1 - border.  A NaN fails.
+ *   3. x0 = min((int)floorf(u), W - 2), y0 = min((int)floorf(v), H - 2), ax = u - x0, ay = v - y0, z = -Z.
+ *   4. visible iff each of the four depths d at (y0 + dy, x0 + dx), dx, dy in {0, 1}, has d > 0 && fabsf(d - z) <= depth_tol.  All
+ *      four must agree: a footprint that straddles a depth edge is where colours bleed; one hole or one far corner drops the view.
+ *   5. per channel c = ((w00 c00 + w01 c01) + w10 c10) + w11 c11, c_yx the colour at (y0 + y, x0 + x), w00 = (1 - ax)(1 - ay),
+ *      w01 = ax (1 - ay), w10 = (1 - ax) ay, w11 = ax ay.
+ *   6. to = center - p, dist = sqrtf((to.x to.x + to.y to.y) + to.z to.z), cosv = fabsf((to.x n.x + to.y n.y) + to.z n.z) /
+ *      fmaxf(dist, 1e-12f), or 1 without normals; w = cosv / fmaxf(z z, 1e-12f).  The view contributes iff it is visible and
+ *      w > 0: a zero or NaN normal contributes nothing.
+ *   7. ADFP_BLEND_WEIGHTED: contributing views in ascending k: acc += w c, wsum += w; rgb = acc / wsum.
+ *   8. ADFP_BLEND_BEST: the contributing view of largest w wins, a later view only if its w is strictly greater; rgb = its c,
+ *      wsum = its w.
+ * Outputs: rgb [V][3] f32 (zeros where no view contributes), wsum [V] f32, count [V] int32 (the contributing views, in both
+ * modes), best [V] int32 (the view of largest w, the smallest index among equals; -1 if none).  V = 0 returns 0 and touches
+ * nothing; K = 0 writes zeros and best = -1.
+ * Errors, before any launch: ADFP_E_ARG for a null pointer (normals may be NULL; the keyframe arrays may be NULL when K = 0), a
+ * negative count, H or W < 1, an unknown blend, depth_tol negative or not finite, border < 0 or 2 border > min(W, H) - 2;
+ * ADFP_E_UNSUPPORTED for H or W < 2 (the footprint is 2 x 2), H or W > 32768, K > 32768, V > 2^31 - 1025. */
+#define ADFP_BLEND_WEIGHTED 0
+#define ADFP_BLEND_BEST     1
+int adfp_mesh_project_colors(const float* verts, const float* normals /*or NULL*/, long long n_verts, const float* w2c, const float* center,
+                             const float* depth, const float* color, long long n_keyframes, float fx, float fy, float cx, float cy, int W,
+                             int H, float depth_tol, int border, int blend, float* rgb, float* wsum, int* count, int* best, void* stream);
+
 /* ---- mesh bound (mesher.Mesher.get_bound_planes: the hull of the keyframes' camera centres and back-projected depth pixels) ----
  * The point work of a quickhull in rounds (mesh.depth_hull keeps the facets of the few hundred hull vertices with Qhull on the
  * host).  The scene: depth [K][H][W] (f32, device), poses [K][16] (f32, device; row-major [4,4] est_c2w), fx, fy, cx, cy (f64, host).

@@ -426,6 +426,53 @@ def main(template, d):
                                  thousands(3 * sb['faces'])))
     else:
         v['sb_numbers'] = 'No run of `tools/simplify_bench.py` is in `profiles/`: not measured.'
+    # mesh colours from the keyframes: the device call beside the numpy statement (tools/color_mesh_bench.py)
+    cm_path = Q('color_mesh_bench.json')
+    if os.path.exists(cm_path):
+        cm = json.load(open(cm_path))
+        cases = cm['cases']
+        first = next(iter(cases.values()))
+        rows = ['| keyframes | blend | device call, ms | numpy statement on %s vertices, s | covered vertices | pairs in frame / all pairs | contributing pairs '
+                '| colour difference, byte steps |' % thousands(cm['host_vertices']), '|---|---|---|---|---|---|---|---|']
+        for name, r in cases.items():
+            K, blend = name.split('_')
+            rows.append('| %s | %s | %.3f (%.3f) | %.3f | %.1f %% | %s / %s | %s | %.2f |' % (
+                K, blend, r['device']['median_ms'], r['device']['min_ms'], r['host_s'], 100 * r['covered_share'], thousands(r['pairs_in_frame']),
+                thousands(r['pairs']), thousands(r['pairs_contributing']), r['image_difference_keyframe_projection']))
+        agree = all(r['count_equal_share'] == 1.0 and r['best_equal_share'] == 1.0 for r in cases.values())
+        worst = max(r['max_colour_difference_where_counts_agree'] for r in cases.values())
+        last = list(cases.values())[-2]
+        frame = [r['pairs_in_frame'] / r['pairs'] for r in cases.values()]
+        contrib = [r['pairs_contributing'] / r['pairs_in_frame'] for r in cases.values()]
+        blends = max(abs(cases[a]['image_difference_keyframe_projection'] - cases[b]['image_difference_keyframe_projection'])
+                     for a, b in zip(list(cases)[0::2], list(cases)[1::2]))
+        v['cm_numbers'] = (
+            'Measured on one MI355X on %s (`profiles/color_mesh_bench.json`, one run of `tools/color_mesh_bench.py`): the cleaned %s mesh at 512³ '
+            '(%s vertices, %s faces) against synthetic keyframes at Replica\'s frame (680 × 1200, f = 600) on `tools/mesh_bench.py`\'s many-pose path, '
+            'analytic depth with its band of zero depth, a smooth analytic texture, `depth_tol` %g, `border` %d.  The device call is `mesh.project_colors` '
+            '(the poses\' read-back and inversion on the host, the launch): %d calls back to back between two device synchronisations, %d such repetitions, '
+            'milliseconds per call, median (min).  The host side is the tests\' numpy statement on every %dth vertex (%s), run once: not a tuned '
+            'implementation, so its time says what the statement costs.  The colour difference is the mean absolute difference, in byte steps, between '
+            'the mesh rendered through `render_mesh`\'s colour view (`MeshViews.render`, mode `color`) at the first %d keyframes\' poses and those '
+            'keyframes\' images, over the %s pixels where the mesh is hit and the keyframe has depth; the direct point query\'s colours (the seed-initialised '
+            'colour decoder\'s, which no one trained) measure %.2f there.\n\n' % (
+                cm['date'], cm['workload'].split(',')[0], thousands(cm['verts']), thousands(cm['faces']), cm['depth_tol'], cm['border'], cm['calls_per_rep'],
+                cm['reps'], round(cm['verts'] / cm['host_vertices']), thousands(cm['host_vertices']), first['image_difference_views'],
+                thousands(first['image_difference_pixels']), first['image_difference_direct_point_query'])
+            + '\n'.join(rows) +
+            '\n\nOn the %s vertices that both sides computed, `count` and `best` are %s and the colours differ by at most %.1e (0 = the same f32 values) '
+            'over the %d cases.  Between %.0f %% and %.0f %% of the pairs pass the frame test, and of those between %.0f %% and %.0f %% contribute: the '
+            'others fall on the zero-depth band, face a keyframe whose depth at their pixel lies further away than the tolerance, or straddle a depth '
+            'edge.  Which of the three dominates was not measured.  %.0f %% of the vertices stay uncovered at %s keyframes and keep the decoder\'s '
+            'colour -- the level set of a seed-initialised decoder is not the room\'s walls everywhere -- so the colour difference falls with the covered '
+            'share instead of reaching zero.  The two blends differ by at most %.2f byte steps here: the texture is smooth and the poses exact, so every '
+            'view of a vertex shows the same colour.  No kernel trace was collected; per vertex-keyframe pair the largest weighted call costs %.1f ps, '
+            'which includes the host\'s share of the call.' % (
+                thousands(cm['host_vertices']), 'equal everywhere' if agree else 'NOT equal everywhere', worst, len(cases), 100 * min(frame), 100 * max(frame),
+                100 * min(contrib), 100 * max(contrib), 100 * (1 - last['covered_share']), list(cases)[-2].split('_')[0], blends,
+                last['device']['median_ms'] * 1e9 / last['pairs']))
+    else:
+        v['cm_numbers'] = 'No run of `tools/color_mesh_bench.py` is in `profiles/`: not measured.'
     s = open(template).read()
     out = re.sub(r'@@(\w+)@@', lambda m: v.get(m.group(1), m.group(0)), s)
     sys.stdout.write(out)
