@@ -356,6 +356,11 @@ SYMBOLS = [
                                   C.c_longlong, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_float * 3), C.c_double, C.POINTER(C.c_ubyte * 3), C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    ('adfp_draw_segments_workspace_bytes', C.c_size_t, [C.c_longlong, C.c_longlong]),
+    ('adfp_draw_segments', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                     C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int,
+                                     C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     ('adfp_refuse_touch', C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int, C.c_float, C.c_double, C.c_double, C.POINTER(C.c_int * 3),
                                     C.POINTER(C.c_int * 3), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -434,6 +439,7 @@ TRI_LEAF_DEFAULT = 4                   # ADFP_TRI_LEAF_DEFAULT
 TRI_LEAVES = (4, 8, 16)                # the leaf sizes adfp_tri_bvh_build takes
 CULL = {'none': 0, 'back': 1, 'front': 2}     # ADFP_CULL_NONE / ADFP_CULL_BACK / ADFP_CULL_FRONT
 SHADE_MODE = {'color': 0, 'shaded': 1, 'normal': 2}     # ADFP_SHADE_COLOR / _SHADED / _NORMAL
+SEG_MAX_RANGES = 8                      # adfp_draw_segments' n_ranges
 UNIT_VOXELS = 16                        # ADFP_UNIT_VOXELS
 SEEN_RULE = {'frustum': 0, 'max_depth': 1, 'depth_test': 2}     # ADFP_SEEN_FRUSTUM / _MAX_DEPTH / _DEPTH_TEST
 SIMPLIFY = {'average': 0, 'quadric': 1}     # ADFP_SIMPLIFY_AVERAGE / _QUADRIC

@@ -3358,6 +3358,7 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
 #include "adfp_meshclean.h"     // mesh clean-up (the seen mask is adfp_recon.h's k_cull_seen)
 #include "adfp_meshcolor.h"     // mesh colours from the keyframes' images
 #include "adfp_meshshade.h"     // mesh views: vertex normals and the shading pass
+#include "adfp_segments.h"      // mesh views: depth-tested line segments over a view
 #include "adfp_meshsimplify.h"  // mesh simplification: vertex clustering
 #include "adfp_bound.h"         // mesh bound
 #include "adfp_ingest.h"        // frame ingestion

@@ -113,6 +113,65 @@ class MeshViews(object):
         return {k: v[0] if len(v) == 1 else torch.cat(v) for k, v in parts.items()}
 
 
+def draw_segments(rgb, depth, c2w, fx, fy, cx, cy, segments, colors, ranges=None, width=2.0, near_clip=1e-3, bias=(0.0, 0.0),
+                  hidden_alpha=0.0, want_seg=False, chunk=CHUNK):
+    """3D line segments painted over views IN PLACE (adfp_draw_segments; the arithmetic is include/adfp.h's): rgb uint8 [P,H,W,3]
+    and depth f32 [P,H,W] (MeshViews.render's, device tensors; depth None = nothing occludes), c2w [P,4,4] OpenCV axes; segments
+    [N,2,3] world endpoints and colors uint8 [N,3], one list for all views; ranges int64 [P,R,2] (R <= 8) or [R,2] for all views:
+    view p draws the segments k with b <= k < e for one of its ranges [b, e); None draws all.  width: the line's width in pixels
+    (round caps); a segment's pixel is drawn where the line lies no deeper than depth (1 + bias[0]) + bias[1] or nothing was hit, and
+    is otherwise blended with weight hidden_alpha (0: hidden lines vanish).  The views go through the kernels `chunk` at a time.
+    Returns None, or with want_seg the int32 [P,H,W] image of segment indices (-1: none)."""
+    _lib.require_cuda(rgb, 'rgb')
+    dev = rgb.device
+    if rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[3] != 3 or not rgb.is_contiguous():
+        raise ValueError(f'draw_segments: rgb must be a contiguous uint8 [P,H,W,3] tensor, got {rgb.dtype} {tuple(rgb.shape)}')
+    P, H, W = (int(s) for s in rgb.shape[:3])
+    m = _c2w_rows(c2w, dev)
+    if int(m.shape[0]) != P:
+        raise ValueError(f'draw_segments: {int(m.shape[0])} poses for {P} views')
+    if depth is not None:
+        if tuple(depth.shape) != (P, H, W):
+            raise ValueError(f'draw_segments: depth {tuple(depth.shape)} for views {(P, H, W)}')
+        depth = depth.to(dev, torch.float32).contiguous()
+    s = segments if torch.is_tensor(segments) else torch.from_numpy(np.asarray(segments, dtype=np.float64))
+    s = s.detach().to(dev, torch.float64).reshape(-1, 2, 3).contiguous()
+    c = colors if torch.is_tensor(colors) else torch.from_numpy(np.ascontiguousarray(colors))
+    if c.dtype != torch.uint8:
+        raise ValueError(f'draw_segments: colours must be uint8, got {c.dtype}')
+    c = c.to(dev).reshape(-1, 3).contiguous()
+    N = int(s.shape[0])
+    if int(c.shape[0]) != N:
+        raise ValueError(f'draw_segments: {int(c.shape[0])} colours for {N} segments')
+    r, R, n_listed = None, 0, N
+    if ranges is not None:
+        r = ranges if torch.is_tensor(ranges) else torch.from_numpy(np.asarray(ranges, dtype=np.int64))
+        r = r.detach().to(torch.int64)
+        if r.dim() == 2:
+            r = r[None].expand(P, -1, -1)
+        if r.dim() != 3 or int(r.shape[0]) != P or r.shape[2] != 2 or not 1 <= int(r.shape[1]) <= _lib.SEG_MAX_RANGES:
+            raise ValueError(f'draw_segments: ranges must be [P,R,2] or [R,2] with R in [1, {_lib.SEG_MAX_RANGES}], got {tuple(r.shape)}')
+        R = int(r.shape[1])
+        lens = (r[..., 1].clamp(max=N) - r[..., 0].clamp(min=0)).clamp(min=0).sum(1)
+        n_listed = int(lens.max()) if P else 0                                  # the one read of the ranges on the host
+        r = r.to(dev).contiguous()
+    seg = torch.empty((P, H, W), dtype=torch.int32, device=dev) if want_seg else None
+    ws = None
+    for p0 in range(0, P, chunk):
+        n = min(chunk, P - p0)
+        need = lib().adfp_draw_segments_workspace_bytes(n, n_listed)
+        if need and (ws is None or ws.numel() < need):
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        with _lib.device_guard(dev):
+            check(lib().adfp_draw_segments(ptr(rgb[p0:p0 + n]), ptr(depth[p0:p0 + n]) if depth is not None else None,
+                                           ptr(seg[p0:p0 + n]) if want_seg else None, n, H, W, ptr(m[p0:p0 + n]), float(fx), float(fy),
+                                           float(cx), float(cy), ptr(s) if N else None, ptr(c) if N else None, N,
+                                           ptr(r[p0:p0 + n]) if r is not None else None, R, n_listed, 0.5 * float(width), float(near_clip),
+                                           float(bias[0]), float(bias[1]), float(hidden_alpha), ptr(ws), need,
+                                           _lib.current_stream(dev)), 'adfp_draw_segments')
+    return seg
+
+
 def render_mesh(input_mesh, poses, cam, out, mode='shaded', smooth=True, cull='none', depth=False, near=None, far=20.0,
                 ambient=0.3, albedo=(0.8, 0.8, 0.8), background=(255, 255, 255), chunk=CHUNK, device='cuda:0'):
     """Render the PLY `input_mesh` (its vertex colours when it has them) from `poses` ([P,4,4] camera-to-world, OpenCV axes) with

@@ -961,6 +961,50 @@ int adfp_shade_hits(const int* face, const float* bary, long long n_views, int H
                     const int* faces, long long n_faces, const double* c2w, double fx, double fy, double cx, double cy,
                     const double* vertex_normals, const unsigned char* vertex_colors, const float albedo[3] /*host*/, double ambient,
                     const unsigned char background[3] /*host*/, int mode, float* normal, unsigned char* rgb, void* stream);
+/* 3D line segments drawn over such views with the mesh in the way (a trajectory, a camera frustum): rgb [n_views][H][W][3] u8
+ * (device) is painted in place, depth [n_views][H][W] f32 (device: adfp_render_hits's, or NULL = nothing occludes), seg
+ * [n_views][H][W] int32 (device, or NULL) receives per pixel the index of the segment drawn there.  c2w [n_views][12] and fx, fy, cx,
+ * cy are the render's; segments [n_seg][2][3] f64 world endpoints and colors [n_seg][3] u8 (device) are ONE list shared by all
+ * views; ranges [n_views][n_ranges][2] int64 (device; NULL = every view draws [0, n_seg)) says which part of it each view draws.
+ * Everything below is f64, one operation at a time in the order written, no contraction; the camera, axes and pixel centres are
+ * adfp_render_depth's: pixel (row i, col j) has its centre at the screen point (j, i).  rgb and seg are a function of the arguments
+ * alone: the same bytes every run, equal to a brute force over all pixels and listed segments (tests/segments_ref.py).
+ *   View: a view whose 12 pose entries are not all finite is left untouched; its seg is -1.
+ *   Listed segments: view v draws segment k iff one of its ranges [b, e) holds k, b <= k < e.  Ranges are clamped to [0, n_seg); an
+ *     empty or inverted range holds nothing; a segment held by two ranges counts once.  n_listed (host) must be at least the largest
+ *     sum over a view's ranges of their clamped lengths (a segment held twice counted twice): the listed segments are laid out
+ *     range after range and what lies beyond n_listed is not drawn.  Without ranges n_listed is not read (it is n_seg).
+ *   Camera space per endpoint P, as the depth render's vertices: e = P - o, cam_c = ((R0c e0 + R1c e1) + R2c e2).  A segment with a
+ *     non-finite endpoint coordinate draws nothing.
+ *   Near clip, endpoints A and B: both Az < near_clip and Bz < near_clip: nothing.  Else if Az < near_clip: t = (near_clip - Az) /
+ *     (Bz - Az) and A becomes (Ax + t (Bx - Ax), Ay + t (By - Ay), near_clip); else if Bz < near_clip the same with A and B
+ *     exchanged.
+ *   Screen per endpoint: u = fx (x / z) + cx, v = fy (y / z) + cy, w = 1 / z.  A non-finite u, v or w: nothing.
+ *   Coverage of pixel (i, j): a = (u1 - u0, v1 - v0), dw = w1 - w0, L = ax ax + ay ay; p = (j - u0, i - v0); s = 0 when L is 0, else
+ *     (px ax + py ay) / L; s = s when s > 0 else 0 (NaN goes to 0), then s = 1 when s > 1; q = (px - s ax, py - s ay).  The pixel is
+ *     covered iff qx qx + qy qy <= half_width half_width: round caps, no antialiasing, no square root.
+ *   Depth of the line at the pixel, perspective-correct: z = 1 / (w0 + s dw).
+ *   Winner: among the listed segments that cover the pixel the one of least z; among equal z the smallest index k.  The winner is
+ *     the minimum over a set: it does not depend on tiles, on the order of the ranges or on the run.  seg = its k, or -1.
+ *   Visibility of the winner, D the pixel's depth value widened: visible when depth is NULL, or D is 0 (nothing hit), or
+ *     z <= D (1 + bias_rel) + bias_abs.  Visibility is monotone in z: if any covering segment is visible, the winner is.
+ *   Paint: visible: the three bytes become colors[k].  Hidden with hidden_alpha > 0: per channel byte = floor((hidden_alpha c +
+ *     (1 - hidden_alpha) p) + 0.5), c the segment's byte and p the old one, widened.  Hidden with hidden_alpha 0: unchanged.
+ * Two launches per 32768 views: one lane per (view, listed slot) projects it into a 64-byte record of the workspace
+ * (adfp_draw_segments_workspace_bytes(n_views, n_listed) = 64 n_views n_listed rounded up to 256; 0 for a count that is not positive
+ * or beyond the limits); one workgroup per 16 x 16 pixel tile and view then reads the view's records 256 at a time, drops those
+ * whose box misses the tile grown by half_width + 1 pixels and tests the rest per pixel.  No atomics; one write per pixel.
+ * ADFP_E_ARG, before any launch: NULL rgb or c2w; NULL segments or colors with n_seg > 0; a negative count; H or W < 1; fx or fy
+ * zero or an intrinsic not finite; half_width outside (0, 64]; near_clip not positive and finite; a negative or non-finite bias;
+ * hidden_alpha outside [0, 1] or NaN; n_ranges outside [1, 8] with ranges; a NULL or too small workspace when something is listed.
+ * ADFP_E_UNSUPPORTED: H or W above 32768, a count above 2^31 - 1025, n_views n_listed above 2^34.  n_views = 0 does nothing; n_seg = 0
+ * or n_listed = 0 leaves rgb as it is and writes -1 to seg (the workspace may be NULL). */
+size_t adfp_draw_segments_workspace_bytes(long long n_views, long long n_listed);
+int adfp_draw_segments(unsigned char* rgb, const float* depth, int* seg, long long n_views, int H, int W, const double* c2w,
+                       double fx, double fy, double cx, double cy, const double* segments, const unsigned char* colors,
+                       long long n_seg, const long long* ranges, int n_ranges, long long n_listed, double half_width,
+                       double near_clip, double bias_rel, double bias_abs, double hidden_alpha, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* check_proj (eval_recon.py:70-96) for a batch of poses: any[p] (int32, device) = 1 iff pose p projects some point into the
  * image, else 0.  w2c [n_poses][12] (f32, device) = the top three rows of inv(c2w'), c2w' = c2w with columns 1 and 2 negated,
  * inverted in f64 and rounded to f32 by the caller; the per-point test is adfp_cull_vertices's.  n_poses = 0 does nothing;
