@@ -12,6 +12,8 @@ static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 static long long ceil_div(long long n, long long d) { return (n + d - 1) / d; }
 
 static const long long RECON_MAX_N = 0x7fffffffll - ADFP_RS_TILE;       // the sort's tile arithmetic is int
+// the radix sort's table for n pairs: [digits][tiles] counts + [digits] totals
+static size_t sort_table_bytes(long long n) { return ((size_t)ceil_div(n, ADFP_RS_TILE) + 1) * ADFP_RS_DIGITS * 4; }
 
 // (addresses are formed as integers: a size query carves a null base, and pointer arithmetic on NULL is undefined)
 struct Arena {

@@ -1299,26 +1299,22 @@ static int make_pts(const adfp_points* p, PtsDev* d) {
     return 0;
 }
 
-// workspace carve-up (all offsets 256-B aligned)
+// the forward's workspace (adfp_workspace_bytes measures this layout, the entry points carve the caller's buffer with it)
 struct Workspace {
-    double* z; float* raw; unsigned char* flags; int* list; float* att_occ; float* att_u; int* counter;
+    int* counter;                // 256 bytes of device words: in-band count [0], range flag [8], tile pools [10..12], the sampler's at byte 64
     unsigned* segparts;          // [SEGMAX_SEGS][SEGMAX_PARTS] ordered-uint partial maxima of gt_depth (k_forward_head -> k_sample)
-    size_t bytes;
+    double* z; float* raw; int* list; float* att_occ; float* att_u; unsigned char* flags;
 };
-static size_t align256(size_t x) { return al256(x); }
-// (offsets are formed as integers: the size queries carve a NULL base, and pointer arithmetic on NULL is undefined)
-template <typename T> static T* at(void* base, size_t o) { return (T*)((uintptr_t)base + o); }
-static Workspace carve(void* base, long long P) {
-    Workspace w; size_t o = 0;
-    w.counter = at<int>(base, o); o += 256;
-    w.segparts = at<unsigned>(base, o); o += align256((size_t)SEGMAX_SEGS * SEGMAX_PARTS * 4);
-    w.z = at<double>(base, o); o += align256((size_t)P * 8);
-    w.raw = at<float>(base, o); o += align256((size_t)P * 16);
-    w.list = at<int>(base, o); o += align256((size_t)P * 4);
-    w.att_occ = at<float>(base, o); o += align256((size_t)P * 4);
-    w.att_u = at<float>(base, o); o += align256((size_t)P * 4);
-    w.flags = at<unsigned char>(base, o); o += align256((size_t)P);
-    w.bytes = o;
+static Workspace layout_forward(Arena& A, long long P) {
+    Workspace w;
+    w.counter = A.take<int>(64);
+    w.segparts = A.take<unsigned>((size_t)SEGMAX_SEGS * SEGMAX_PARTS);
+    w.z = A.take<double>((size_t)P);
+    w.raw = A.take<float>((size_t)P * 4);
+    w.list = A.take<int>((size_t)P);
+    w.att_occ = A.take<float>((size_t)P);
+    w.att_u = A.take<float>((size_t)P);
+    w.flags = A.take<unsigned char>((size_t)P);
     return w;
 }
 
@@ -1450,6 +1446,105 @@ static int pack_jobs_table(int n_jobs, const adfp_pack_job* jobs, int* status, P
     }
     return 0;
 }
+static int decode_grid(int ntiles, int waves_per_wg, int wg_per_cu) {
+    int g = (ntiles + waves_per_wg - 1) / waves_per_wg;
+    const int cap = num_cu() * wg_per_cu;
+    if (g > cap) g = cap;
+    return g < 1 ? 1 : g;
+}
+
+// ---- the forward's network launchers: which kernel runs a network in a call is decided HERE and nowhere else.  A call site builds
+// the argument struct (decode_args / attention_args: value-initialised, then the fields that differ) and keeps its own checks and
+// sequence; the launcher picks the instantiation from the images that are there and the training buffers, points `packed` at the
+// image that kernel reads, sizes the grid and launches.
+struct NetImages { const adfp_grid* grid; const adfp_grid* grid1; const float* w; const void* h; unsigned* masks; float* act; };      // own grid, second grid (HIGH: low), exact f32 image, f16-split images (H, then G), training buffers
+static NetImages net_images(const adfp_scene* sc, const adfp_train_state* s, int role) {
+    if (role == ROLE_LOW) return {&sc->low, &sc->low, sc->w_low, sc->h_low, s ? s->masks_low : nullptr, s ? s->act_low : nullptr};
+    if (role == ROLE_HIGH) return {&sc->high, &sc->low, sc->w_high, sc->h_high, s ? s->masks_high : nullptr, s ? s->act_high : nullptr};
+    return {&sc->color, &sc->color, sc->w_color, sc->h_color, s ? s->masks_color : nullptr, s ? s->act_color : nullptr};
+}
+static DecodeArgs decode_args(const adfp_scene* sc, const PtsDev& P) {
+    DecodeArgs a{};
+    a.P = P; a.nb = make_norm(sc->bound); fill_bound(a.b, sc->bound); a.status = sc->status;
+    return a;
+}
+// One decoder over a.P.  Training forward (f16-split image + mask room): k_decode_h<..., 512, 1 | 2>, leaving masks (| layer inputs).
+// Inference, f16-split: LOW / COLOR and a HIGH alone (a.single) read the H image; HIGH on the in-band list reads the G image
+// (k_decode_high_g, with a.pool).  No f16-split image: the exact f32 kernel.
+template <int CDIM, int NOUT, int ROLE>
+static int launch_decoder(DecodeArgs a, const NetImages& n, hipStream_t st) {
+    const int ntiles = (a.P.n + 31) / 32;
+    int* const pool = a.pool;
+    a.g0 = make_grid(*n.grid); a.g1 = make_grid(*n.grid1); a.packed = n.h ? (const float*)n.h : n.w; a.masks = nullptr; a.act = nullptr; a.pool = nullptr;
+    if (n.h && n.masks) {
+        a.masks = n.masks; a.act = n.act;
+        if (a.act) hipLaunchKernelGGL((k_decode_h<CDIM, NOUT, ROLE, 512, 2>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((k_decode_h<CDIM, NOUT, ROLE, 512, 1>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
+    } else if constexpr (ROLE == ROLE_HIGH) {
+        if (n.h && !a.single) {
+            a.packed = (const float*)((const unsigned*)n.h + DecLayoutH<64, 1>::P_TOTAL);          // the G image
+            a.pool = pool;
+            if (a.P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT, true>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
+            else hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT, false>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
+        } else if (n.h) hipLaunchKernelGGL((k_decode_h<64, 1, ROLE_HIGH, 512>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((k_decode<64, 1, ROLE_HIGH, 512>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
+    } else {
+        if (n.h) hipLaunchKernelGGL((k_decode_h<CDIM, NOUT, ROLE, ADFP_DECH_NT>), dim3(decode_grid(ntiles, ADFP_DECH_NT / 64, ADFP_DECH_WG)), dim3(ADFP_DECH_NT), 0, st, a);
+        else hipLaunchKernelGGL((k_decode<CDIM, NOUT, ROLE, 256>), dim3(decode_grid(ntiles, 4, 2)), dim3(256), 0, st, a);
+    }
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+// LOW and COLOR on every point in ONE launch (both f16-split images; reads their G images).  Inference: k_decode_lc16 with the tile
+// pool.  Training (state: mask room for both networks): k_decode_lc16_train, one network per wave when every (tile, network) pair
+// can have a wave of its own.
+static int launch_low_color(const adfp_scene* sc, const PtsDev& P, const unsigned char* flags, float* raw, float* w, int apply_bound, int* call_flag,
+                            int* pool, const adfp_train_state* state, hipStream_t st) {
+    DecodeLCTrainArgs t{};
+    DecodeLCArgs& f = t.f;
+    f.P = P; f.nb = make_norm(sc->bound); fill_bound(f.b, sc->bound);
+    f.g_low = make_grid(sc->low); f.g_color = make_grid(sc->color);
+    f.packed_low = (const unsigned*)sc->h_low + DecLayoutH<32, 1>::P_TOTAL; f.packed_color = (const unsigned*)sc->h_color + DecLayoutH<32, 4>::P_TOTAL;   // the G images
+    f.flags = flags; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = apply_bound; f.status = sc->status; f.call_flag = call_flag;
+    const int ntiles = (P.n + 31) / 32;
+    if (!state) {
+        f.pool = pool;
+        if (P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, true>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
+        else hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, false>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
+    } else {
+        t.masks_low = state->masks_low; t.masks_color = state->masks_color; t.act_low = state->act_low; t.act_color = state->act_color;
+        t.split_networks = 2 * ntiles <= num_cu() * (ADFP_LCT_NT / 64) ? 1 : 0;
+        if (t.split_networks) hipLaunchKernelGGL((k_decode_lc16_train<ADFP_LCT_NT, true>), dim3(decode_grid(2 * ntiles, ADFP_LCT_NT / 64, 1)), dim3(ADFP_LCT_NT), 0, st, t);
+        else hipLaunchKernelGGL((k_decode_lc16_train<ADFP_LCT_NT, false>), dim3(decode_grid(ntiles, ADFP_LCT_NT / 64, 1)), dim3(ADFP_LCT_NT), 0, st, t);
+    }
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+static AttArgs attention_args(const adfp_scene* sc, float* raw, float* w) {
+    AttArgs t{};
+    t.raw = raw; t.w = w; t.status = sc->status;
+    return t;
+}
+// The attention network over ntiles tiles of the in-band list (t.count_ptr) or of t.n_rows rows.  Training forward (f16-split image +
+// mask room): k_attention_h<1> at 256 threads.  Inference, f16-split: the list reads the G image (k_attention_g, with t.pool), rows
+// read the H image (k_attention_h<0>).  No f16-split image: the exact f32 kernel.
+static int launch_attention(AttArgs t, const adfp_scene* sc, int ntiles, hipStream_t st) {
+    int* const pool = t.pool;
+    t.packed = sc->h_att ? (const float*)sc->h_att : sc->w_att; t.pool = nullptr;
+    if (sc->h_att && t.masks) hipLaunchKernelGGL((k_attention_h<1, 256>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, t);
+    else {
+        t.masks = nullptr; t.act = nullptr;
+        if (sc->h_att && t.count_ptr) {
+            t.packed = (const float*)((const unsigned*)sc->h_att + AttLayoutH::P_TOTAL);                 // the G image
+            t.pool = pool;
+            hipLaunchKernelGGL(k_attention_g<512>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
+        } else if (sc->h_att) hipLaunchKernelGGL(k_attention_h<0>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
+        else hipLaunchKernelGGL(k_attention, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
+    }
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" {
 
 int adfp_version(void) { return ADFP_VERSION; }
@@ -1475,7 +1570,7 @@ long long adfp_attention_packed_floats(void) { return AttLayout::P_TOTAL; }
 
 size_t adfp_workspace_bytes(long long n_points) {
     if (n_points < 0) return 0;
-    return carve(nullptr, n_points).bytes;
+    return layout_bytes(layout_forward, n_points);
 }
 
 int adfp_relayout_grid(const float* src, float* dst, int C, int Z, int Y, int X, void* stream) {
@@ -1792,14 +1887,7 @@ int adfp_sample_tsdf(const adfp_tsdf* tsdf, const double tsdf_bnds[3][2], const 
     return launch_tsdf(&sc, P, nullptr, nullptr, nullptr, nullptr, nullptr, out, (hipStream_t)stream);
 }
 
-static int decode_grid(int ntiles, int waves_per_wg, int wg_per_cu) {
-    int g = (ntiles + waves_per_wg - 1) / waves_per_wg;
-    const int cap = num_cu() * wg_per_cu;
-    if (g > cap) g = cap;
-    return g < 1 ? 1 : g;
-}
-
-static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, int apply_bound, float* raw, float* w, Workspace& ws_in, hipStream_t st,
+static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, int apply_bound, float* raw, float* w, const Workspace& ws_in, hipStream_t st,
                             const adfp_train_state* state = nullptr, bool ws_counter_is_zero = false) {
     if (P.n == 0) return 0;
     Workspace ws = ws_in;
@@ -1825,108 +1913,25 @@ static int eval_points_impl(const adfp_scene* sc, const PtsDev& P, int stage, in
         int rc = launch_tsdf(sc, P, ws.flags, ws.list, ws.att_u, nullptr, ws.counter, nullptr, st);   // w = 1 comes from the LOW decoder
         if (rc) return rc;
     }
-    DecodeArgs a;
-    a.P = P; a.nb = make_norm(sc->bound); fill_bound(a.b, sc->bound);
-    a.list = nullptr; a.count_ptr = nullptr; a.flags = fuse ? ws.flags : nullptr;
-    a.raw = raw; a.w = w; a.att_occ = nullptr; a.write_w = 1; a.apply_bound = apply_bound;   // attention overwrites w on the band
-    a.status = sc->status; a.masks = nullptr; a.act = nullptr; a.single = 0; a.call_flag = call_flag;
-    const int ntiles = (P.n + 31) / 32;
-    // stage color, inference, both networks f16-split: LOW and COLOR on every point in ONE launch (k_decode_lc16)
-    const bool fused_lc = stage == ADFP_STAGE_COLOR && !state && sc->h_low && sc->h_color;
-    if (fused_lc) {
-        DecodeLCArgs f;
-        f.P = P; f.nb = a.nb; fill_bound(f.b, sc->bound);
-        f.g_low = make_grid(sc->low); f.g_color = make_grid(sc->color);
-        f.packed_low = (const unsigned*)sc->h_low; f.packed_color = (const unsigned*)sc->h_color;
-        f.flags = a.flags; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = apply_bound; f.status = sc->status; f.call_flag = call_flag;
-        f.pool = ws.counter ? ws.counter + 10 : nullptr;            // zero: this call's 64-byte counter block was cleared above (or by the caller)
-        f.packed_low += DecLayoutH<32, 1>::P_TOTAL; f.packed_color += DecLayoutH<32, 4>::P_TOTAL;       // the G images
-        if (P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, true>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
-        else hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, false>), dim3(decode_grid(ntiles, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, st, f);
-        ADFP_CHECK_LAUNCH();
-    }
-    // stage color, TRAINING, both networks f16-split with mask room: the same ONE launch, leaving masks (+ layer inputs)
-    const bool fused_lc_train = stage == ADFP_STAGE_COLOR && state && sc->h_low && sc->h_color && state->masks_low && state->masks_color;
-    if (fused_lc_train) {
-        DecodeLCTrainArgs t;
-        DecodeLCArgs& f = t.f;
-        f.P = P; f.nb = a.nb; fill_bound(f.b, sc->bound);
-        f.g_low = make_grid(sc->low); f.g_color = make_grid(sc->color);
-        f.packed_low = (const unsigned*)sc->h_low + DecLayoutH<32, 1>::P_TOTAL; f.packed_color = (const unsigned*)sc->h_color + DecLayoutH<32, 4>::P_TOTAL;   // the G images
-        f.flags = a.flags; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = apply_bound; f.status = sc->status; f.call_flag = call_flag; f.pool = nullptr;
-        t.masks_low = state->masks_low; t.masks_color = state->masks_color; t.act_low = state->act_low; t.act_color = state->act_color;
-        // few tiles (every (tile, network) pair can have a wave of its own): one network per wave
-        t.split_networks = 2 * ntiles <= num_cu() * (ADFP_LCT_NT / 64) ? 1 : 0;
-        if (t.split_networks) hipLaunchKernelGGL((k_decode_lc16_train<ADFP_LCT_NT, true>), dim3(decode_grid(2 * ntiles, ADFP_LCT_NT / 64, 1)), dim3(ADFP_LCT_NT), 0, st, t);
-        else hipLaunchKernelGGL((k_decode_lc16_train<ADFP_LCT_NT, false>), dim3(decode_grid(ntiles, ADFP_LCT_NT / 64, 1)), dim3(ADFP_LCT_NT), 0, st, t);
-        ADFP_CHECK_LAUNCH();
-    }
-    // LOW on every point
-    a.g0 = make_grid(sc->low); a.g1 = a.g0;
-    if (fused_lc || fused_lc_train) {
-    } else if (sc->h_low && state && state->masks_low) {              // training forward: leaves the ReLU masks (+ layer inputs)
-        a.packed = (const float*)sc->h_low; a.masks = state->masks_low; a.act = state->act_low;
-        if (a.act) hipLaunchKernelGGL((k_decode_h<32, 1, ROLE_LOW, 512, 2>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((k_decode_h<32, 1, ROLE_LOW, 512, 1>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
-        a.masks = nullptr; a.act = nullptr;
-    } else if (sc->h_low) {
-        a.packed = (const float*)sc->h_low;
-            hipLaunchKernelGGL((k_decode_h<32, 1, ROLE_LOW, ADFP_DECH_NT>), dim3(decode_grid(ntiles, ADFP_DECH_NT / 64, ADFP_DECH_WG)), dim3(ADFP_DECH_NT), 0, st, a);
+    int* const pool = ws.counter ? ws.counter + 10 : nullptr;      // tile pools [10..12]: zero, this call's counter block was cleared above (or by the caller)
+    DecodeArgs a = decode_args(sc, P);
+    a.flags = fuse ? ws.flags : nullptr; a.raw = raw; a.w = w; a.write_w = 1; a.apply_bound = apply_bound; a.call_flag = call_flag;      // attention overwrites w on the band
+    int rc;
+    // stage color, both networks f16-split (training: with mask room): LOW and COLOR on every point in ONE launch
+    if (stage == ADFP_STAGE_COLOR && sc->h_low && sc->h_color && (!state || (state->masks_low && state->masks_color))) {
+        rc = launch_low_color(sc, P, a.flags, raw, w, apply_bound, call_flag, pool, state, st); if (rc) return rc;
     } else {
-        a.packed = sc->w_low;
-        hipLaunchKernelGGL((k_decode<32, 1, ROLE_LOW, 256>), dim3(decode_grid(ntiles, 4, 2)), dim3(256), 0, st, a);
-    }
-    ADFP_CHECK_LAUNCH();
-    if (stage == ADFP_STAGE_COLOR && !fused_lc && !fused_lc_train) {
-        a.g0 = make_grid(sc->color); a.g1 = a.g0;
-        if (sc->h_color && state && state->masks_color) {
-            a.packed = (const float*)sc->h_color; a.masks = state->masks_color; a.act = state->act_color;
-            if (a.act) hipLaunchKernelGGL((k_decode_h<32, 4, ROLE_COLOR, 512, 2>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((k_decode_h<32, 4, ROLE_COLOR, 512, 1>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
-            a.masks = nullptr; a.act = nullptr;
-        } else if (sc->h_color) {
-            a.packed = (const float*)sc->h_color;
-            hipLaunchKernelGGL((k_decode_h<32, 4, ROLE_COLOR, ADFP_DECH_NT>), dim3(decode_grid(ntiles, ADFP_DECH_NT / 64, ADFP_DECH_WG)), dim3(ADFP_DECH_NT), 0, st, a);
-        } else {
-            a.packed = sc->w_color;
-            hipLaunchKernelGGL((k_decode<32, 4, ROLE_COLOR, 256>), dim3(decode_grid(ntiles, 4, 2)), dim3(256), 0, st, a);
-        }
-        ADFP_CHECK_LAUNCH();
+        rc = launch_decoder<32, 1, ROLE_LOW>(a, net_images(sc, state, ROLE_LOW), st); if (rc) return rc;
+        if (stage == ADFP_STAGE_COLOR) { rc = launch_decoder<32, 4, ROLE_COLOR>(a, net_images(sc, state, ROLE_COLOR), st); if (rc) return rc; }
     }
     if (fuse) {
-        a.g0 = make_grid(sc->high); a.g1 = make_grid(sc->low);
-        a.list = ws.list; a.count_ptr = ws.counter; a.att_occ = ws.att_occ;
-        if (sc->h_high && state && state->masks_high) {
-            a.packed = (const float*)sc->h_high; a.masks = state->masks_high; a.act = state->act_high;
-            if (a.act) hipLaunchKernelGGL((k_decode_h<64, 1, ROLE_HIGH, 512, 2>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((k_decode_h<64, 1, ROLE_HIGH, 512, 1>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
-            a.masks = nullptr; a.act = nullptr;
-        } else if (sc->h_high) {
-            a.packed = (const float*)((const unsigned*)sc->h_high + DecLayoutH<64, 1>::P_TOTAL);          // the G image
-            a.pool = ws.counter ? ws.counter + 11 : nullptr;
-            if (P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT, true>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
-            else hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT, false>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
-        } else {
-            a.packed = sc->w_high;
-            hipLaunchKernelGGL((k_decode<64, 1, ROLE_HIGH, 512>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
-        }
-        ADFP_CHECK_LAUNCH();
-        AttArgs t;
-        t.list = ws.list; t.count_ptr = ws.counter; t.att_occ = ws.att_occ; t.att_u = ws.att_u;
-        t.flags = ws.flags; t.raw = raw; t.w = w; t.apply_bound = apply_bound; t.status = sc->status; t.n_rows = 0; t.call_flag = call_flag;
-        t.masks = nullptr; t.act = nullptr;
-        if (sc->h_att && state && state->masks_att) {
-            t.packed = (const float*)sc->h_att; t.masks = state->masks_att; t.act = state->act_att;
-            hipLaunchKernelGGL((k_attention_h<1, 256>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, t);
-        } else if (sc->h_att) {
-            t.packed = (const float*)((const unsigned*)sc->h_att + AttLayoutH::P_TOTAL);                 // the G image
-            t.pool = ws.counter ? ws.counter + 12 : nullptr;
-            hipLaunchKernelGGL(k_attention_g<512>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
-        } else {
-            t.packed = sc->w_att;
-            hipLaunchKernelGGL(k_attention, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
-        }
-        ADFP_CHECK_LAUNCH();
+        a.list = ws.list; a.count_ptr = ws.counter; a.att_occ = ws.att_occ; a.pool = pool ? pool + 1 : nullptr;
+        rc = launch_decoder<64, 1, ROLE_HIGH>(a, net_images(sc, state, ROLE_HIGH), st); if (rc) return rc;
+        AttArgs t = attention_args(sc, raw, w);
+        t.list = ws.list; t.count_ptr = ws.counter; t.att_occ = ws.att_occ; t.att_u = ws.att_u; t.flags = ws.flags;
+        t.apply_bound = apply_bound; t.call_flag = call_flag; t.pool = pool ? pool + 2 : nullptr;
+        if (state) { t.masks = state->masks_att; t.act = state->act_att; }
+        rc = launch_attention(t, sc, (P.n + 31) / 32, st); if (rc) return rc;
     }
     // the f32 repair of a call whose f16-split kernels left the f16 range (adfp_fallback.h): returns at once when the flag is clear
     if (call_flag && sc->flat_low && (!fuse || (sc->flat_high && sc->flat_att)) && (stage != ADFP_STAGE_COLOR || sc->flat_color)) {
@@ -1952,50 +1957,20 @@ extern "C" int adfp_decode_stage(const adfp_scene* sc, const adfp_points* pts, i
     if (grid_too_big(sc->low) || grid_too_big(sc->color)) return ADFP_E_UNSUPPORTED;
     PtsDev P; int rc = make_pts(pts, &P); if (rc) return rc;
     if (P.n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
     if (kind == ADFP_DEC_LOW_COLOR) {                  // the fused launch of stage color (f16-split images only)
         if (!sc->low.data || !sc->color.data || !sc->h_low || !sc->h_color) return ADFP_E_ARG;
-        DecodeLCArgs f;
-        f.P = P; f.nb = make_norm(sc->bound); fill_bound(f.b, sc->bound);
-        f.g_low = make_grid(sc->low); f.g_color = make_grid(sc->color);
-        f.packed_low = (const unsigned*)sc->h_low; f.packed_color = (const unsigned*)sc->h_color;
-        f.flags = nullptr; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = 1; f.status = sc->status; f.call_flag = nullptr; f.pool = tile_counter;
-        if (tile_counter) { hipError_t e = zero_async(tile_counter, 4, (hipStream_t)stream); if (e != hipSuccess) return (int)e; }
-        f.packed_low += DecLayoutH<32, 1>::P_TOTAL; f.packed_color += DecLayoutH<32, 4>::P_TOTAL;       // the G images
-        if (P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, true>), dim3(decode_grid((P.n + 31) / 32, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, (hipStream_t)stream, f);
-        else hipLaunchKernelGGL((k_decode_lc16<ADFP_LC_NT, false>), dim3(decode_grid((P.n + 31) / 32, ADFP_LC_NT / 64, 1)), dim3(ADFP_LC_NT), 0, (hipStream_t)stream, f);
-        ADFP_CHECK_LAUNCH();
-        return 0;
+        if (tile_counter) { hipError_t e = zero_async(tile_counter, 4, st); if (e != hipSuccess) return (int)e; }
+        return launch_low_color(sc, P, nullptr, raw, w, 1, nullptr, tile_counter, nullptr, st);
     }
-    DecodeArgs a;
-    a.P = P; a.nb = make_norm(sc->bound); fill_bound(a.b, sc->bound);
-    a.list = nullptr; a.count_ptr = nullptr; a.flags = nullptr;
-    a.raw = raw; a.w = w; a.att_occ = nullptr; a.write_w = 1; a.apply_bound = 1; a.status = sc->status;
-    a.masks = nullptr; a.act = nullptr; a.single = 0; a.call_flag = nullptr;
-    const int ntiles = (P.n + 31) / 32;
-    hipStream_t st = (hipStream_t)stream;
+    DecodeArgs a = decode_args(sc, P);
+    a.raw = raw; a.w = w; a.write_w = 1; a.apply_bound = 1;
     if (kind == ADFP_DEC_LOW) {
         if (!sc->low.data || !(sc->w_low || sc->h_low)) return ADFP_E_ARG;
-        a.g0 = make_grid(sc->low); a.g1 = a.g0;
-        if (sc->h_low) {
-            a.packed = (const float*)sc->h_low;
-            hipLaunchKernelGGL((k_decode_h<32, 1, ROLE_LOW, ADFP_DECH_NT>), dim3(decode_grid(ntiles, ADFP_DECH_NT / 64, ADFP_DECH_WG)), dim3(ADFP_DECH_NT), 0, st, a);
-        } else {
-            a.packed = sc->w_low;
-            hipLaunchKernelGGL((k_decode<32, 1, ROLE_LOW, 256>), dim3(decode_grid(ntiles, 4, 2)), dim3(256), 0, st, a);
-        }
-    } else {
-        if (!sc->color.data || !(sc->w_color || sc->h_color)) return ADFP_E_ARG;
-        a.g0 = make_grid(sc->color); a.g1 = a.g0;
-        if (sc->h_color) {
-            a.packed = (const float*)sc->h_color;
-            hipLaunchKernelGGL((k_decode_h<32, 4, ROLE_COLOR, ADFP_DECH_NT>), dim3(decode_grid(ntiles, ADFP_DECH_NT / 64, ADFP_DECH_WG)), dim3(ADFP_DECH_NT), 0, st, a);
-        } else {
-            a.packed = sc->w_color;
-            hipLaunchKernelGGL((k_decode<32, 4, ROLE_COLOR, 256>), dim3(decode_grid(ntiles, 4, 2)), dim3(256), 0, st, a);
-        }
+        return launch_decoder<32, 1, ROLE_LOW>(a, net_images(sc, nullptr, ROLE_LOW), st);
     }
-    ADFP_CHECK_LAUNCH();
-    return 0;
+    if (!sc->color.data || !(sc->w_color || sc->h_color)) return ADFP_E_ARG;
+    return launch_decoder<32, 4, ROLE_COLOR>(a, net_images(sc, nullptr, ROLE_COLOR), st);
 }
 
 // ---- one sub-network alone: what `decoders.low_decoder(p, c_grid)` / `decoders.mlp(p, occ, tsdf_volume, tsdf_bnds)` compute in
@@ -2009,33 +1984,20 @@ extern "C" int adfp_decode_single(const adfp_scene* sc, const adfp_points* pts, 
     if (grid_too_big(sc->low) || grid_too_big(sc->high) || grid_too_big(sc->color)) return ADFP_E_UNSUPPORTED;
     PtsDev P; int rc = make_pts(pts, &P); if (rc) return rc;
     if (P.n == 0) return 0;
-    DecodeArgs a;
-    a.P = P; a.nb = make_norm(sc->bound); fill_bound(a.b, sc->bound);
-    a.list = nullptr; a.count_ptr = nullptr; a.flags = nullptr;
-    a.raw = out4; a.w = nullptr; a.att_occ = nullptr; a.write_w = 0; a.apply_bound = 0; a.status = sc->status;
-    a.masks = nullptr; a.act = nullptr; a.single = 1; a.call_flag = nullptr;
-    const int ntiles = (P.n + 31) / 32;
+    DecodeArgs a = decode_args(sc, P);
+    a.raw = out4; a.single = 1;
     hipStream_t st = (hipStream_t)stream;
     if (kind == ADFP_DEC_LOW) {
         if (!sc->low.data || !(sc->w_low || sc->h_low)) return ADFP_E_ARG;
-        a.g0 = make_grid(sc->low); a.g1 = a.g0;
-        if (sc->h_low) { a.packed = (const float*)sc->h_low; hipLaunchKernelGGL((k_decode_h<32, 1, ROLE_LOW, ADFP_DECH_NT>), dim3(decode_grid(ntiles, ADFP_DECH_NT / 64, ADFP_DECH_WG)), dim3(ADFP_DECH_NT), 0, st, a); }
-        else { a.packed = sc->w_low; hipLaunchKernelGGL((k_decode<32, 1, ROLE_LOW, 256>), dim3(decode_grid(ntiles, 4, 2)), dim3(256), 0, st, a); }
-    } else if (kind == ADFP_DEC_COLOR) {
+        return launch_decoder<32, 1, ROLE_LOW>(a, net_images(sc, nullptr, ROLE_LOW), st);
+    }
+    if (kind == ADFP_DEC_COLOR) {
         if (!sc->color.data || !(sc->w_color || sc->h_color)) return ADFP_E_ARG;
-        a.g0 = make_grid(sc->color); a.g1 = a.g0;
-        if (sc->h_color) { a.packed = (const float*)sc->h_color; hipLaunchKernelGGL((k_decode_h<32, 4, ROLE_COLOR, ADFP_DECH_NT>), dim3(decode_grid(ntiles, ADFP_DECH_NT / 64, ADFP_DECH_WG)), dim3(ADFP_DECH_NT), 0, st, a); }
-        else { a.packed = sc->w_color; hipLaunchKernelGGL((k_decode<32, 4, ROLE_COLOR, 256>), dim3(decode_grid(ntiles, 4, 2)), dim3(256), 0, st, a); }
-    } else if (kind == ADFP_DEC_HIGH) {
-        if (!sc->high.data || !sc->low.data || !(sc->w_high || sc->h_high)) return ADFP_E_ARG;
-        a.g0 = make_grid(sc->high); a.g1 = make_grid(sc->low);
-        a.att_occ = out4;                                   // HIGH writes one float per point: out4 is [P] here
-        a.raw = nullptr;
-        if (sc->h_high) { a.packed = (const float*)sc->h_high; hipLaunchKernelGGL((k_decode_h<64, 1, ROLE_HIGH, 512>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a); }
-        else { a.packed = sc->w_high; hipLaunchKernelGGL((k_decode<64, 1, ROLE_HIGH, 512>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a); }
-    } else return ADFP_E_ARG;
-    ADFP_CHECK_LAUNCH();
-    return 0;
+        return launch_decoder<32, 4, ROLE_COLOR>(a, net_images(sc, nullptr, ROLE_COLOR), st);
+    }
+    if (kind != ADFP_DEC_HIGH || !sc->high.data || !sc->low.data || !(sc->w_high || sc->h_high)) return ADFP_E_ARG;
+    a.att_occ = out4; a.raw = nullptr;                      // HIGH writes one float per point: out4 is [P] here
+    return launch_decoder<64, 1, ROLE_HIGH>(a, net_images(sc, nullptr, ROLE_HIGH), st);
 }
 extern "C" int adfp_attention_rows(const adfp_scene* sc, const float* occ, const float* tsdf_val, long long n, float* out4, float* w,
                                    float* scratch_u, void* stream) {
@@ -2045,14 +2007,9 @@ extern "C" int adfp_attention_rows(const adfp_scene* sc, const float* occ, const
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_inv_tsdf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tsdf_val, scratch_u, n);
     ADFP_CHECK_LAUNCH();
-    AttArgs t;
-    t.list = nullptr; t.count_ptr = nullptr; t.att_occ = occ; t.att_u = scratch_u; t.flags = nullptr;
-    t.raw = out4; t.w = w; t.apply_bound = 0; t.n_rows = (int)n; t.status = sc->status; t.masks = nullptr; t.act = nullptr; t.call_flag = nullptr;
-    const int ntiles = (int)((n + 31) / 32);
-    if (sc->h_att) { t.packed = (const float*)sc->h_att; hipLaunchKernelGGL(k_attention_h<0>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t); }
-    else { t.packed = sc->w_att; hipLaunchKernelGGL(k_attention, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t); }
-    ADFP_CHECK_LAUNCH();
-    return 0;
+    AttArgs t = attention_args(sc, out4, w);
+    t.att_occ = occ; t.att_u = scratch_u; t.n_rows = (int)n;
+    return launch_attention(t, sc, (int)((n + 31) / 32), st);
 }
 
 static int check_scene(const adfp_scene* sc, int stage) {
@@ -2071,8 +2028,9 @@ int adfp_eval_points_train(const adfp_scene* scene, const adfp_points* pts, int 
     if (!raw || !w || !workspace) return ADFP_E_ARG;
     if (state && stage != ADFP_STAGE_LOW && (!state->flags || !state->list || !state->counter || !state->att_occ || !state->att_u)) return ADFP_E_ARG;
     PtsDev P; rc = make_pts(pts, &P); if (rc) return rc;
-    Workspace ws = carve(workspace, P.n);
-    if (workspace_bytes < ws.bytes) return ADFP_E_WORKSPACE;
+    Arena A(workspace);
+    const Workspace ws = layout_forward(A, P.n);
+    if (workspace_bytes < A.bytes()) return ADFP_E_WORKSPACE;
     return eval_points_impl(scene, P, stage, (flags & ADFP_EVAL_APPLY_BOUND) ? 1 : 0, raw, w, ws, (hipStream_t)stream, state);
 }
 int adfp_eval_points(const adfp_scene* scene, const adfp_points* pts, int stage, int flags, float* raw, float* w,
@@ -2544,8 +2502,9 @@ int adfp_render_forward(const adfp_scene* scene, const adfp_render_args* r, void
     if (gt_depth && !r->depth_max && r->depth_max_segment > 0 &&
         ((fr ? (long long)fr->H * fr->W : (long long)r->n_rays) + r->depth_max_segment - 1) / r->depth_max_segment > SEGMAX_SEGS)
         return ADFP_E_UNSUPPORTED;
-    Workspace ws = carve(r->workspace, Pn);
-    if (r->workspace_bytes < ws.bytes) return ADFP_E_WORKSPACE;
+    Arena A(r->workspace);
+    const Workspace ws = layout_forward(A, Pn);
+    if (r->workspace_bytes < A.bytes()) return ADFP_E_WORKSPACE;
     if (r->n_rays == 0) {                                // the images and the grid conversions are still owed
         rc = r->n_pack_jobs ? adfp_pack_images(r->n_pack_jobs, r->pack_jobs, scene->status, stream) : 0;
         return rc ? rc : adfp_relayout_grids(r->n_relayout_jobs, r->relayout_jobs, 0, stream);
@@ -2622,54 +2581,62 @@ int adfp_render_forward(const adfp_scene* scene, const adfp_render_args* r, void
 #define STG_ROWS_MAX 163840
 
 #define OUTER_NSLOT 256         // workgroups per weight-gradient launch = private gradient copies (one per CU); outer_slots() = the launch's cap
-struct BwdWorkspace { float* g_raw; float* att_g; float* g_pts; float* stage; int stage_rows; float* partial; int part_stride; float* gmax; float* gmax_parts;
-                      int gmax_pending;              // > 0: gmax_parts[0 .. gmax_pending) still wait to be folded into gmax (backward_points)
-                      // adfp_render_backward's first two launches (zero fill of the gradient outputs, k_composite_bwd), held back so that
-                      // backward_points can send them off in ONE launch with k_bin_keys (k_backward_head)
-                      bool head_zeroes_g_pts;        // ... and g_pts with them
-                      float* g_pts_dec; size_t g_pts_stride;   // [ADFP_PGRAD_MAX_JOBS][P,3]: the decoders' own d/d position buffers (k_decode_bwd_h_pgrad3)
-                      bool pgrad_separate;           // adfp_render_backward: the decoders write those and k_rays_grad adds them up
-                      int pgrad_used;                // how many of them the call's launch wrote
-                      bool head_pending; ZeroJobs head_zero; unsigned head_zero_blocks; CompositeBwdArgs head_comp;
-                      // adfp_backward_args.side_stream / side_events (host objects of the caller): the sort's own lane; join_pending =
-                      // the main stream has not waited for the sort's end yet (flush_scatter does)
-                      hipStream_t side; hipEvent_t side_ev[2]; bool side_join_pending;
-                      float* gc; size_t gc_stride; int* bin_key; int* bin_val; int* bin_key_sorted; int* bin_perm; int* sort_table;
-                      size_t bytes; };
-static BwdWorkspace carve_bwd(void* base, long long P) {
-    BwdWorkspace w; size_t o = 0;
-    w.gmax_pending = 0; w.head_pending = false; w.head_zeroes_g_pts = false; w.pgrad_separate = false; w.pgrad_used = 0;
-    w.side = nullptr; w.side_ev[0] = w.side_ev[1] = nullptr; w.side_join_pending = false;
-    w.g_raw = at<float>(base, o); o += align256((size_t)P * 16);
-    w.att_g = at<float>(base, o); o += align256((size_t)P * 4);
-    w.g_pts = at<float>(base, o); o += align256((size_t)P * 12);
-    w.g_pts_stride = align256((size_t)P * 12) / 4;
-    w.g_pts_dec = at<float>(base, o); o += ADFP_PGRAD_MAX_JOBS * w.g_pts_stride * 4;
+// the backward's workspace: pointers and strides, nothing a call changes (adfp_backward_workspace_bytes measures this layout, the
+// two backward entries carve the caller's buffer with it)
+struct BwdWorkspace {
+    float* g_raw; float* att_g;
+    float* g_pts;                                // [P,3] d/d position
+    float* g_pts_dec; size_t g_pts_stride;       // directly behind it, [ADFP_PGRAD_MAX_JOBS][P,3]: the decoders' own d/d position buffers (k_decode_bwd_h_pgrad3)
+    float* stage; int stage_rows; float* partial; int part_stride;
+    float* gmax;                                 // largest |cotangent of raw| of the call (grad_scale)
+    float* gmax_parts;                           // ... per ray / per workgroup, before k_max_reduce
+    // spatially ordered grid-gradient scatter of the f16-split backward (k_scatter_sorted): d/d c rows, sort keys, sorted order
+    float* gc; size_t gc_stride;                 // one [P][32] block of rows per grid (ADFP_SCATTER_MAX_JOBS of them)
+    int* bin_key; int* bin_val; int* bin_key_sorted; int* bin_perm; int* sort_table;
+};
+static BwdWorkspace layout_backward(Arena& A, long long P) {
+    BwdWorkspace w;
+    w.g_raw = A.take<float>((size_t)P * 4);
+    w.att_g = A.take<float>((size_t)P);
+    w.g_pts = A.take<float>((size_t)P * 3);
+    w.g_pts_stride = al256((size_t)P * 12) / 4;
+    w.g_pts_dec = A.take<float>(ADFP_PGRAD_MAX_JOBS * w.g_pts_stride);
     w.stage_rows = (int)(P < STG_ROWS_MAX ? P : STG_ROWS_MAX);
     if (w.stage_rows < 32) w.stage_rows = 32;
-    w.stage = at<float>(base, o); o += align256((size_t)w.stage_rows * AttStage::NCOLS * 4);
+    w.stage = A.take<float>((size_t)w.stage_rows * AttStage::NCOLS);
     int fmax = DecLayout<32, 1>::F_TOTAL;
     if (DecLayout<64, 1>::F_TOTAL > fmax) fmax = DecLayout<64, 1>::F_TOTAL;
     if (DecLayout<32, 4>::F_TOTAL > fmax) fmax = DecLayout<32, 4>::F_TOTAL;
     if (AttLayout::F_TOTAL > fmax) fmax = AttLayout::F_TOTAL;
     w.part_stride = (fmax + 63) / 64 * 64;
-    w.partial = at<float>(base, o); o += align256((size_t)OUTER_NSLOT * w.part_stride * 4);
-    w.gmax = at<float>(base, o); o += 256;            // largest |cotangent of raw| of the call (grad_scale)
-    w.gmax_parts = at<float>(base, o); o += align256((size_t)P * 4);     // ... per ray / per workgroup, before k_max_reduce
-    // spatially ordered grid-gradient scatter of the f16-split backward (k_scatter_sorted): d/d c rows, sort keys, sorted order
-    w.gc_stride = align256((size_t)P * 128) / 4;                          // one [P][32] block of rows per grid (ADFP_SCATTER_MAX_JOBS of them)
-    w.gc = at<float>(base, o); o += ADFP_SCATTER_MAX_JOBS * w.gc_stride * 4;
-    w.bin_key = at<int>(base, o); o += align256((size_t)P * 4);
-    w.bin_val = at<int>(base, o); o += align256((size_t)P * 4);
-    w.bin_key_sorted = at<int>(base, o); o += align256((size_t)P * 4);
-    w.bin_perm = at<int>(base, o); o += align256((size_t)P * 4);
-    w.sort_table = at<int>(base, o); o += align256(((((size_t)P + ADFP_RS_TILE - 1) / ADFP_RS_TILE) + 1) * ADFP_RS_DIGITS * 4);     // [digits][tiles] + [digits] totals
-    w.bytes = o;
+    w.partial = A.take<float>((size_t)OUTER_NSLOT * w.part_stride);
+    w.gmax = A.take<float>(64);
+    w.gmax_parts = A.take<float>((size_t)P);
+    w.gc_stride = al256((size_t)P * 128) / 4;
+    w.gc = A.take<float>(ADFP_SCATTER_MAX_JOBS * w.gc_stride);
+    w.bin_key = A.take<int>((size_t)P);
+    w.bin_val = A.take<int>((size_t)P);
+    w.bin_key_sorted = A.take<int>((size_t)P);
+    w.bin_perm = A.take<int>((size_t)P);
+    w.sort_table = A.take<int>(sort_table_bytes(P) / 4);
     return w;
 }
+// what ONE backward call carries beside its workspace
+struct BackwardCall {
+    int gmax_pending = 0;                  // > 0: gmax_parts[0 .. gmax_pending) still wait to be folded into gmax (backward_points)
+    // adfp_render_backward's first two launches (zero fill of the gradient outputs, k_composite_bwd), held back so that
+    // backward_points can send them off in ONE launch with k_bin_keys (k_backward_head)
+    bool head_pending = false; ZeroJobs head_zero; unsigned head_zero_blocks = 0; CompositeBwdArgs head_comp;
+    bool head_zeroes_g_pts = false;        // ... and g_pts with them
+    bool pgrad_separate = false;           // adfp_render_backward: the decoders write g_pts_dec and k_rays_grad adds them up
+    int pgrad_used = 0;                    // how many of them the call's launch wrote
+    // adfp_backward_args.side_stream / side_events (host objects of the caller): the sort's own lane; join_pending =
+    // the main stream has not waited for the sort's end yet (flush_scatter does)
+    hipStream_t side = nullptr; hipEvent_t side_ev[2] = {nullptr, nullptr}; bool side_join_pending = false;
+};
 extern "C" size_t adfp_backward_workspace_bytes(long long n_points) {
     if (n_points < 0) return 0;
-    return carve_bwd(nullptr, n_points).bytes;
+    return layout_bytes(layout_backward, n_points);
 }
 
 static void add_job(OuterArgs& a, int colA, int colB, int dst, int rs, int cs, int nr, int j0, int nc) {
@@ -2749,7 +2716,7 @@ static int launch_outer(OuterArgs& oa, const BwdWorkspace& bw, const int* count_
 }
 
 template <int CDIM, int NOUT, int ROLE, bool PGRAD>
-static int run_decode_bwd_p(DecodeBwdArgs a, int total, const int* count_ptr, float* flat, BwdWorkspace& bw, hipStream_t st) {
+static int run_decode_bwd_p(DecodeBwdArgs a, int total, const int* count_ptr, float* flat, const BwdWorkspace& bw, hipStream_t st) {
     if (total == 0) return 0;
     // the scatter cache keeps its slot number in the top 5 bits of the voxel index
     if (ROLE != ROLE_HIGH && a.g_grid && (long long)a.g0.X * a.g0.Y * a.g0.Z >= (1ll << 27)) return ADFP_E_UNSUPPORTED;
@@ -2809,7 +2776,7 @@ static int radix_sort_pairs(int* key_a, int* val_a, int* key_b, int* val_b, int 
     if (val_fin) *val_fin = vin;
     return 0;
 }
-extern "C" size_t adfp_sort_workspace_bytes(long long n) { return n < 0 ? 0 : ((size_t)((n + ADFP_RS_TILE - 1) / ADFP_RS_TILE) + 1) * ADFP_RS_DIGITS * 4; }
+extern "C" size_t adfp_sort_workspace_bytes(long long n) { return n < 0 ? 0 : sort_table_bytes(n); }
 extern "C" int adfp_sort_pairs(int* key, int* val, int* key_tmp, int* val_tmp, long long n, int key_bits, void* workspace, size_t workspace_bytes,
                                void* stream) {
     if (!key || !val || !key_tmp || !val_tmp || !workspace || n < 0 || key_bits < 1 || key_bits > 31) return ADFP_E_ARG;
@@ -2838,16 +2805,16 @@ __global__ __launch_bounds__(256) void k_backward_head(BwdHeadArgs h) {
     if (blk < h.nb_bin) { bin_keys_block(h.b, blk); return; }
     zero_multi_block(h.z, (unsigned)(blk - h.nb_bin));
 }
-static int launch_backward_head(BwdWorkspace& bw, const BinArgs* bins, int P, hipStream_t st) {
+static int launch_backward_head(BackwardCall& call, const BinArgs* bins, int P, hipStream_t st) {
     BwdHeadArgs h;
-    h.c = bw.head_comp; h.z = bw.head_zero;
-    h.nb_comp = (bw.head_comp.n_rays + 3) / 4;
+    h.c = call.head_comp; h.z = call.head_zero;
+    h.nb_comp = (call.head_comp.n_rays + 3) / 4;
     h.nb_bin = bins ? (P + 255) / 256 : 0;
     if (bins) h.b = *bins; else memset(&h.b, 0, sizeof(h.b));
     h.b.max_parts = nullptr;
-    hipLaunchKernelGGL(k_backward_head, dim3(h.nb_comp + h.nb_bin + bw.head_zero_blocks), dim3(256), 0, st, h);
+    hipLaunchKernelGGL(k_backward_head, dim3(h.nb_comp + h.nb_bin + call.head_zero_blocks), dim3(256), 0, st, h);
     ADFP_CHECK_LAUNCH();
-    bw.head_pending = false;
+    call.head_pending = false;
     return 0;
 }
 
@@ -2866,14 +2833,14 @@ static void launch_pgrad_single(const DecodeBwdHArgs& a, int role, int blocks, h
     else if (role == ROLE_LOW) hipLaunchKernelGGL((k_decode_bwd_h<32, 1, ROLE_LOW, false, false, 512, true>), dim3(blocks), dim3(512), 0, st, a);
     else hipLaunchKernelGGL((k_decode_bwd_h<32, 4, ROLE_COLOR, false, false, 512, true>), dim3(blocks), dim3(512), 0, st, a);
 }
-static int flush_pgrad(BinPlan& bp, BwdWorkspace& bw, hipStream_t st) {
+static int flush_pgrad(BinPlan& bp, const BwdWorkspace& bw, BackwardCall& call, hipStream_t st) {
     DecodeBwdH3Args& m = bp.pgrad;
     if (m.n == 0) return 0;
-    if (m.n >= 2 && bw.pgrad_separate) {               // side by side, each into its own buffer (k_rays_grad adds them up)
+    if (m.n >= 2 && call.pgrad_separate) {               // side by side, each into its own buffer (k_rays_grad adds them up)
         for (int k = 0; k < m.n; ++k) m.j[k].g_pts = bw.g_pts_dec + (size_t)k * bw.g_pts_stride;
         hipLaunchKernelGGL(k_decode_bwd_h_pgrad3, dim3(m.first[m.n]), dim3(512), 0, st, m);
         ADFP_CHECK_LAUNCH();
-        bw.pgrad_used = m.n;
+        call.pgrad_used = m.n;
     } else {                                           // one after the other, accumulating into g_pts
         for (int k = 0; k < m.n; ++k) { launch_pgrad_single(m.j[k], m.role[k], m.first[k + 1] - m.first[k], st); ADFP_CHECK_LAUNCH(); }
     }
@@ -2893,7 +2860,7 @@ static int flush_scatter(BinPlan& bp, hipStream_t st) {
 
 template <int CDIM, int NOUT, int ROLE>
 static int run_decode_bwd_h(const DecodeBwdArgs& o, const void* t, const unsigned* masks, const float* act, int* status, const int* skip, int total,
-                            const int* count_ptr, float* flat, BwdWorkspace& bw, BinPlan& bp, const unsigned char* flags, int options, hipStream_t st) {
+                            const int* count_ptr, float* flat, const BwdWorkspace& bw, BinPlan& bp, const unsigned char* flags, int options, hipStream_t st) {
     if (total == 0) return 0;
     // d/d c rows + k_scatter_sorted instead of the in-kernel scatter: for a grid on one of the two lattices the points were
     // sorted by (k_bin_keys); a third lattice keeps the in-kernel scatter
@@ -2998,7 +2965,7 @@ static int run_decode_bwd_h(const DecodeBwdArgs& o, const void* t, const unsigne
 }
 
 template <int CDIM, int NOUT, int ROLE>
-static int run_decode_bwd(DecodeBwdArgs a, int total, const int* count_ptr, float* flat, BwdWorkspace& bw, hipStream_t st) {
+static int run_decode_bwd(DecodeBwdArgs a, int total, const int* count_ptr, float* flat, const BwdWorkspace& bw, hipStream_t st) {
     return a.g_pts ? run_decode_bwd_p<CDIM, NOUT, ROLE, true>(a, total, count_ptr, flat, bw, st)
                    : run_decode_bwd_p<CDIM, NOUT, ROLE, false>(a, total, count_ptr, flat, bw, st);
 }
@@ -3025,28 +2992,50 @@ static int zero_grad_jobs(const adfp_scene* sc, const GradOut& g, int options, Z
     return 0;
 }
 
+// What backward_points needs to know about one decoder: its grids, its exact and T images, what the training forward left, where
+// its gradients go -- and, for HIGH alone, the in-band list it runs over, the list's cotangents and the band flags.
+struct NetBwd {
+    const adfp_grid* grid; const adfp_grid* grid1; const float* w; const void* ht; const unsigned* masks; const float* act; unsigned* dbg_masks;
+    float* flat; float* g_grid;
+    const int* list; const int* count_ptr; const float* att_g; const unsigned char* flags;
+};
+static NetBwd net_bwd(const adfp_scene* sc, const adfp_train_state& s, const GradOut& go, const BwdWorkspace& bw, int role) {
+    if (role == ROLE_LOW) return {&sc->low, &sc->low, sc->w_low, sc->ht_low, s.masks_low, s.act_low, s.dbg_masks_low, go.flat_low, go.grid_low, nullptr, nullptr, nullptr, nullptr};
+    if (role == ROLE_HIGH) return {&sc->high, &sc->low, sc->w_high, sc->ht_high, s.masks_high, s.act_high, s.dbg_masks_high, go.flat_high, go.grid_high, s.list, s.counter, bw.att_g, s.flags};
+    return {&sc->color, &sc->color, sc->w_color, sc->ht_color, s.masks_color, s.act_color, s.dbg_masks_color, go.flat_color, go.grid_color, nullptr, nullptr, nullptr, nullptr};
+}
+// one decoder's backward over P points (HIGH: list entries): the f16-split kernels (h: backward_points' use_h rule) or the exact ones
+template <int CDIM, int NOUT, int ROLE>
+static int run_decoder_bwd(DecodeBwdArgs a, const NetBwd& n, bool h, const adfp_scene* sc, const adfp_train_state& state, int P, const BwdWorkspace& bw,
+                           BinPlan& bp, int options, hipStream_t st) {
+    a.g0 = make_grid(*n.grid); a.g1 = make_grid(*n.grid1); a.packed = n.w; a.g_grid = n.g_grid; a.dbg_masks = n.dbg_masks;
+    a.list = n.list; a.count_ptr = n.count_ptr; a.att_g = n.att_g;
+    if (h) return run_decode_bwd_h<CDIM, NOUT, ROLE>(a, n.ht, n.masks, n.act, sc->status, state.counter ? state.counter + 8 : nullptr, P, n.count_ptr, n.flat, bw, bp, n.flags, options, st);
+    return n.w ? run_decode_bwd<CDIM, NOUT, ROLE>(a, P, n.count_ptr, n.flat, bw, st) : ADFP_E_ARG;
+}
+
 // DF.forward backward over P points: bw.g_raw holds the cotangent of raw [P,4] (the attention pass reads .w and rewrites it
 // with d/d(high+low)); g_pts (bw.g_pts, zeroed here) receives d/d position when pgrad.
 static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, int P, const adfp_train_state& state, const float* g_weight,
-                           const GradOut& go, bool pgrad, int options, BwdWorkspace& bw, hipStream_t st) {
+                           const GradOut& go, bool pgrad, int options, const BwdWorkspace& bw, BackwardCall& call, hipStream_t st) {
     int rc;
     hipError_t e;
     // whatever path leaves this function: the main stream has waited for the side lane (a capture must see it joined)
-    struct SideJoin { BwdWorkspace& bw; hipStream_t st;
+    struct SideJoin { BackwardCall& call; hipStream_t st;
                       hipError_t join() {
-                          if (!bw.side_join_pending) return hipSuccess;
-                          bw.side_join_pending = false;
-                          hipError_t e_ = hipEventRecord(bw.side_ev[1], bw.side);            // after the lane's last launch
-                          return e_ == hipSuccess ? hipStreamWaitEvent(st, bw.side_ev[1], 0) : e_;
+                          if (!call.side_join_pending) return hipSuccess;
+                          call.side_join_pending = false;
+                          hipError_t e_ = hipEventRecord(call.side_ev[1], call.side);        // after the lane's last launch
+                          return e_ == hipSuccess ? hipStreamWaitEvent(st, call.side_ev[1], 0) : e_;
                       }
-                      ~SideJoin() { (void)join(); } } side_join{bw, st};
+                      ~SideJoin() { (void)join(); } } side_join{call, st};
     struct CuReserve { int saved; CuReserve() : saved(t_cu_reserve) {} ~CuReserve() { t_cu_reserve = saved; } } cu_reserve;     // see num_cu()
     const bool fuse = stage != ADFP_STAGE_LOW;
     DecodeBwdArgs a;
     a.P = Pd; a.nb = make_norm(sc->bound); fill_bound(a.b, sc->bound);
     a.list = nullptr; a.count_ptr = nullptr; a.g_raw = bw.g_raw; a.att_g = nullptr; a.stage = nullptr; a.dbg_masks = nullptr;
     a.g_pts = pgrad ? bw.g_pts : nullptr;
-    if (pgrad && !(bw.head_pending && bw.head_zeroes_g_pts)) { e = zero_async(bw.g_pts, (size_t)P * 12, st); if (e != hipSuccess) return (int)e; }
+    if (pgrad && !(call.head_pending && call.head_zeroes_g_pts)) { e = zero_async(bw.g_pts, (size_t)P * 12, st); if (e != hipSuccess) return (int)e; }
     // a decoder takes the f16-split backward when its T image and the forward's masks are there and -- if its weight gradients
     // are wanted -- the forward also left the layer inputs.  A position gradient comes from the f16-split kernels only on its own
     // (the Tracker: networks and grids frozen); together with weight or grid gradients (bundle adjustment) the exact kernels run.
@@ -3055,11 +3044,13 @@ static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, in
     };
     // The grid gradients of the decoders that take the f16-split backward are scattered in spatial order (k_scatter_sorted): one
     // radix sort of the points by (coarsest such grid's cell, finest grid's cell inside it), shared by all of them.
+    const NetBwd low = net_bwd(sc, state, go, bw, ROLE_LOW), high = net_bwd(sc, state, go, bw, ROLE_HIGH), color = net_bwd(sc, state, go, bw, ROLE_COLOR);
+    auto net_h = [&](const NetBwd& n) { return use_h(n.ht, n.masks, n.act, n.flat, n.g_grid); };
     BinPlan bp; bp.ok = false; bp.pend.n_jobs = 0; bp.pgrad.n = 0;
     {
-        const bool h_low = go.grid_low && use_h(sc->ht_low, state.masks_low, state.act_low, go.flat_low, go.grid_low);
-        const bool h_high = fuse && go.grid_high && use_h(sc->ht_high, state.masks_high, state.act_high, go.flat_high, go.grid_high);
-        const bool h_color = stage == ADFP_STAGE_COLOR && go.grid_color && use_h(sc->ht_color, state.masks_color, state.act_color, go.flat_color, go.grid_color);
+        const bool h_low = go.grid_low && net_h(low);
+        const bool h_high = fuse && go.grid_high && net_h(high);
+        const bool h_color = stage == ADFP_STAGE_COLOR && go.grid_color && net_h(color);
         const adfp_grid* fine = nullptr; const adfp_grid* coarse = nullptr;
         auto vox = [](const adfp_grid& g) { return (long long)g.X * g.Y * g.Z; };
         const adfp_grid* cand[3] = {h_low ? &sc->low : nullptr, h_high ? &sc->high : nullptr, h_color ? &sc->color : nullptr};
@@ -3080,20 +3071,20 @@ static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, in
                 b.key = bw.bin_key; b.val = bw.bin_val;
                 const float* fold_parts = nullptr;            // the per-ray maxima still to be folded: by the sort's first launch when the
                 int fold_n = 0;                               // head carries k_composite_bwd (they are not written yet), else by k_bin_keys
-                if (bw.head_pending) {
-                    rc = launch_backward_head(bw, &b, P, st); if (rc) return rc;
-                    if (bw.gmax_pending > 0) { fold_parts = bw.gmax_parts; fold_n = bw.gmax_pending; }
+                if (call.head_pending) {
+                    rc = launch_backward_head(call, &b, P, st); if (rc) return rc;
+                    if (call.gmax_pending > 0) { fold_parts = bw.gmax_parts; fold_n = call.gmax_pending; }
                 } else {
-                    b.max_parts = bw.gmax_pending > 0 ? bw.gmax_parts : nullptr; b.max_n = bw.gmax_pending; b.max_out = bw.gmax;
+                    b.max_parts = call.gmax_pending > 0 ? bw.gmax_parts : nullptr; b.max_n = call.gmax_pending; b.max_out = bw.gmax;
                     hipLaunchKernelGGL(k_bin_keys, dim3((P + 255) / 256 + (b.max_parts ? 1 : 0)), dim3(256), 0, st, b);
                     ADFP_CHECK_LAUNCH();
                 }
-                bw.gmax_pending = 0;
+                call.gmax_pending = 0;
                 // stable LSD radix sort (adfp_sort.h), ping-pong between the two buffer pairs -- on the caller's side lane when there is
                 // one: nine short launches nobody but k_scatter_sorted waits for, beside the backward kernels instead of in front of them
                 const int* vfin = nullptr;
                 hipStream_t sort_st = st;
-                if (bw.side) {
+                if (call.side) {
                     // The gradient scale is folded HERE, on the main stream (one small launch): riding on the sort's first launch it would
                     // make the first backward kernel wait for the side lane -- two cross-stream hops of ~15 us each (measured: 36 us
                     // between k_backward_head's end and k_attention_bwd_h's start).
@@ -3102,11 +3093,11 @@ static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, in
                         ADFP_CHECK_LAUNCH();
                         fold_parts = nullptr; fold_n = 0;
                     }
-                    e = hipEventRecord(bw.side_ev[0], st);                       // the keys exist
-                    if (e == hipSuccess) e = hipStreamWaitEvent(bw.side, bw.side_ev[0], 0);
+                    e = hipEventRecord(call.side_ev[0], st);                       // the keys exist
+                    if (e == hipSuccess) e = hipStreamWaitEvent(call.side, call.side_ev[0], 0);
                     if (e != hipSuccess) return (int)e;
-                    sort_st = bw.side;
-                    bw.side_join_pending = true;
+                    sort_st = call.side;
+                    call.side_join_pending = true;
                     t_cu_reserve = ADFP_SIDE_CU_RESERVE;          // the whole-CU kernels below leave the lane room (restored on return)
                 }
                 rc = radix_sort_pairs(bw.bin_key, bw.bin_val, bw.bin_key_sorted, bw.bin_perm, P, bin_key_bits(coarse->X, coarse->Y, coarse->Z), bw.sort_table, nullptr, &vfin, sort_st,
@@ -3119,11 +3110,11 @@ static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, in
         }
     }
 
-    if (bw.head_pending) { rc = launch_backward_head(bw, nullptr, P, st); if (rc) return rc; }      // no sorted scatter: zero fill + compositing backward
-    if (bw.gmax_pending > 0) {                       // no sorted scatter in this call: the fold is a launch of its own
-        hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, st, bw.gmax_parts, bw.gmax_pending, bw.gmax);
+    if (call.head_pending) { rc = launch_backward_head(call, nullptr, P, st); if (rc) return rc; }      // no sorted scatter: zero fill + compositing backward
+    if (call.gmax_pending > 0) {                       // no sorted scatter in this call: the fold is a launch of its own
+        hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, st, bw.gmax_parts, call.gmax_pending, bw.gmax);
         ADFP_CHECK_LAUNCH();
-        bw.gmax_pending = 0;
+        call.gmax_pending = 0;
     }
     if (fuse) {
         const bool att_full_h = use_h(sc->ht_att, state.masks_att, state.act_att, go.flat_att);
@@ -3199,33 +3190,13 @@ static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, in
         }
         if (go.flat_att) { rc = outer_end(bw, AttLayout::F_TOTAL, go.flat_att, st); if (rc) return rc; }
         }
-        if (go.grid_high || go.flat_high || pgrad) {
-            DecodeBwdArgs hgh = a;
-            hgh.g0 = make_grid(sc->high); hgh.g1 = make_grid(sc->low); hgh.packed = sc->w_high;
-            hgh.list = state.list; hgh.count_ptr = state.counter; hgh.att_g = bw.att_g; hgh.g_grid = go.grid_high; hgh.dbg_masks = state.dbg_masks_high;
-            if (use_h(sc->ht_high, state.masks_high, state.act_high, go.flat_high, go.grid_high))
-                rc = run_decode_bwd_h<64, 1, ROLE_HIGH>(hgh, sc->ht_high, state.masks_high, state.act_high, sc->status, state.counter ? state.counter + 8 : nullptr, P, state.counter, go.flat_high, bw, bp, state.flags, options, st);
-            else rc = sc->w_high ? run_decode_bwd<64, 1, ROLE_HIGH>(hgh, P, state.counter, go.flat_high, bw, st) : ADFP_E_ARG;
-            if (rc) return rc;
-        }
+        if (go.grid_high || go.flat_high || pgrad) { rc = run_decoder_bwd<64, 1, ROLE_HIGH>(a, high, net_h(high), sc, state, P, bw, bp, options, st); if (rc) return rc; }
     }
-    if (go.grid_low || go.flat_low || pgrad) {
-        DecodeBwdArgs lw = a;
-        lw.g0 = make_grid(sc->low); lw.g1 = lw.g0; lw.packed = sc->w_low; lw.g_grid = go.grid_low; lw.dbg_masks = state.dbg_masks_low;
-        if (use_h(sc->ht_low, state.masks_low, state.act_low, go.flat_low, go.grid_low))
-            rc = run_decode_bwd_h<32, 1, ROLE_LOW>(lw, sc->ht_low, state.masks_low, state.act_low, sc->status, state.counter ? state.counter + 8 : nullptr, P, nullptr, go.flat_low, bw, bp, nullptr, options, st);
-        else rc = sc->w_low ? run_decode_bwd<32, 1, ROLE_LOW>(lw, P, nullptr, go.flat_low, bw, st) : ADFP_E_ARG;
-        if (rc) return rc;
-    }
+    if (go.grid_low || go.flat_low || pgrad) { rc = run_decoder_bwd<32, 1, ROLE_LOW>(a, low, net_h(low), sc, state, P, bw, bp, options, st); if (rc) return rc; }
     if (stage == ADFP_STAGE_COLOR && (go.grid_color || go.flat_color || pgrad)) {
-        DecodeBwdArgs cl = a;
-        cl.g0 = make_grid(sc->color); cl.g1 = cl.g0; cl.packed = sc->w_color; cl.g_grid = go.grid_color; cl.dbg_masks = state.dbg_masks_color;
-        if (use_h(sc->ht_color, state.masks_color, state.act_color, go.flat_color, go.grid_color))
-            rc = run_decode_bwd_h<32, 4, ROLE_COLOR>(cl, sc->ht_color, state.masks_color, state.act_color, sc->status, state.counter ? state.counter + 8 : nullptr, P, nullptr, go.flat_color, bw, bp, nullptr, options, st);
-        else rc = sc->w_color ? run_decode_bwd<32, 4, ROLE_COLOR>(cl, P, nullptr, go.flat_color, bw, st) : ADFP_E_ARG;
-        if (rc) return rc;
+        rc = run_decoder_bwd<32, 4, ROLE_COLOR>(a, color, net_h(color), sc, state, P, bw, bp, options, st); if (rc) return rc;
     }
-    rc = flush_pgrad(bp, bw, st); if (rc) return rc;
+    rc = flush_pgrad(bp, bw, call, st); if (rc) return rc;
     e = side_join.join();                            // the sorted order is what k_scatter_sorted reads
     if (e != hipSuccess) return (int)e;
     return flush_scatter(bp, st);
@@ -3249,8 +3220,9 @@ extern "C" int adfp_render_backward(const adfp_scene* sc, const adfp_backward_ar
     if (r->S > 64 * CB_MAXC) return ADFP_E_UNSUPPORTED;
     const long long Pn = (long long)r->n_rays * r->S;
     if (Pn > 0x7fffffffll) return ADFP_E_UNSUPPORTED;
-    BwdWorkspace bw = carve_bwd(r->workspace, Pn);
-    if (r->workspace_bytes < bw.bytes) return ADFP_E_WORKSPACE;
+    Arena A(r->workspace);
+    const BwdWorkspace bw = layout_backward(A, Pn);
+    if (r->workspace_bytes < A.bytes()) return ADFP_E_WORKSPACE;
     const bool fuse = r->stage != ADFP_STAGE_LOW;
     if (fuse && (!r->state.flags || !r->state.list || !r->state.counter || !r->state.att_occ || !r->state.att_u)) return ADFP_E_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -3258,38 +3230,38 @@ extern "C" int adfp_render_backward(const adfp_scene* sc, const adfp_backward_ar
     if (r->n_rays == 0) return zero_grad_outputs(sc, go, r->options, st);    // every non-NULL output is zeroed, then accumulated into
     const int P = (int)Pn;
     // the zero fill and the compositing backward leave with backward_points' first launch (k_backward_head)
+    BackwardCall call;
     {
         ZeroBatch zb;
         rc = zero_grad_jobs(sc, go, r->options, zb, st); if (rc) return rc;
-        bw.head_zeroes_g_pts = false;
         if ((r->g_rays_o || r->g_rays_d) && zb.z.n + 1 < ZERO_MULTI) {  // the position gradients' accumulator and the decoders' own buffers
             hipError_t ze = zb.add(bw.g_pts, (size_t)P * 12, st);       // ride along (the Tracker); contiguous: g_pts, then g_pts_dec
             if (ze == hipSuccess) ze = zb.add(bw.g_pts_dec, ADFP_PGRAD_MAX_JOBS * bw.g_pts_stride * 4, st);
             if (ze != hipSuccess) return (int)ze;
-            bw.head_zeroes_g_pts = true; bw.pgrad_separate = true;
+            call.head_zeroes_g_pts = true; call.pgrad_separate = true;
         }
-        bw.head_zero = zb.z; bw.head_zero_blocks = zb.blocks;
-        bw.head_zero.n = zb.z.n;
-        CompositeBwdArgs& c = bw.head_comp;
+        call.head_zero = zb.z; call.head_zero_blocks = zb.blocks;
+        call.head_zero.n = zb.z.n;
+        CompositeBwdArgs& c = call.head_comp;
         c.raw = r->raw; c.z = r->z_vals; c.n_rays = r->n_rays; c.S = r->S; c.g_depth = r->g_depth; c.g_var = r->g_uncertainty; c.g_color = r->g_color;
         c.g_raw = bw.g_raw; c.keep = r->ray_keep; c.gmax = bw.gmax_parts; c.g_weight = r->g_weight; c.skip = r->state.counter ? r->state.counter + 8 : nullptr;
-        bw.head_pending = true;
+        call.head_pending = true;
     }
-    bw.gmax_pending = r->n_rays;                     // folded into bw.gmax by the sort's first launch (or k_max_reduce)
+    call.gmax_pending = r->n_rays;                     // folded into bw.gmax by the sort's first launch (or k_max_reduce)
     if (r->side_stream) {                            // the sort's own lane (adfp_backward_args.side_stream)
         if (!r->side_events[0] || !r->side_events[1] || r->side_stream == stream) return ADFP_E_ARG;
-        bw.side = (hipStream_t)r->side_stream;
-        for (int k = 0; k < 2; ++k) bw.side_ev[k] = (hipEvent_t)r->side_events[k];
+        call.side = (hipStream_t)r->side_stream;
+        for (int k = 0; k < 2; ++k) call.side_ev[k] = (hipEvent_t)r->side_events[k];
     }
 
     PtsDev Pd;
     Pd.mode = ADFP_PTS_RAYS; Pd.S = r->S; Pd.n = P; Pd.pts = nullptr; Pd.ro = r->rays_o; Pd.rd = r->rays_d; Pd.z = r->z_vals;
     const bool pgrad = r->g_rays_o || r->g_rays_d;
-    rc = backward_points(sc, r->stage, Pd, P, r->state, r->g_weight, go, pgrad, r->options, bw, st);
+    rc = backward_points(sc, r->stage, Pd, P, r->state, r->g_weight, go, pgrad, r->options, bw, call, st);
     if (rc) return rc;
     if (pgrad) {
-        RaysGradExtra ex; ex.n = bw.pgrad_used;
-        for (int k = 0; k < 3; ++k) ex.p[k] = k < bw.pgrad_used ? bw.g_pts_dec + (size_t)k * bw.g_pts_stride : nullptr;
+        RaysGradExtra ex; ex.n = call.pgrad_used;
+        for (int k = 0; k < 3; ++k) ex.p[k] = k < call.pgrad_used ? bw.g_pts_dec + (size_t)k * bw.g_pts_stride : nullptr;
         hipLaunchKernelGGL(k_rays_grad, dim3((r->n_rays + 3) / 4), dim3(256), 0, st, bw.g_pts, r->z_vals, r->n_rays, r->S,
                            r->g_rays_o, r->g_rays_d, ex);
         ADFP_CHECK_LAUNCH();
@@ -3326,8 +3298,9 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
     int rc = check_backward_scene(sc, r->stage); if (rc) return rc;
     if (!r->workspace) return ADFP_E_ARG;
     PtsDev Pd; rc = make_pts(pts, &Pd); if (rc) return rc;
-    BwdWorkspace bw = carve_bwd(r->workspace, Pd.n);
-    if (r->workspace_bytes < bw.bytes) return ADFP_E_WORKSPACE;
+    Arena A(r->workspace);
+    const BwdWorkspace bw = layout_backward(A, Pd.n);
+    if (r->workspace_bytes < A.bytes()) return ADFP_E_WORKSPACE;
     const bool fuse = r->stage != ADFP_STAGE_LOW;
     if (fuse && (!r->state.flags || !r->state.list || !r->state.counter || !r->state.att_occ || !r->state.att_u)) return ADFP_E_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -3339,7 +3312,8 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
     ADFP_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, st, bw.gmax_parts, ((Pd.n + 255) / 256) * 4, bw.gmax);
     ADFP_CHECK_LAUNCH();
-    rc = backward_points(sc, r->stage, Pd, Pd.n, r->state, r->g_w, go, r->g_pts != nullptr, r->options, bw, st);
+    BackwardCall call;
+    rc = backward_points(sc, r->stage, Pd, Pd.n, r->state, r->g_w, go, r->g_pts != nullptr, r->options, bw, call, st);
     if (rc) return rc;
     if (r->g_pts) {
         hipError_t e = hipMemcpyAsync(r->g_pts, bw.g_pts, (size_t)Pd.n * 12, hipMemcpyDeviceToDevice, st);

@@ -255,6 +255,26 @@ int main() {
     { adfp_points_backward_args p2 = pb; p2.workspace_bytes -= 1; EXPECT_CODE(adfp_eval_points_backward(&sc, &pts, &p2, st), ADFP_E_WORKSPACE);
       p2 = pb; p2.workspace = nullptr; EXPECT_NEG(adfp_eval_points_backward(&sc, &pts, &p2, st)); }
     EXPECT_REACHES_LAUNCH(adfp_eval_points_backward(&sc, &pts, &pb, st));
+    {   // what the render layouts promise to the outside: every entry refuses its size query's answer less one byte and accepts the
+        // answer itself -- without points, with one, with few, and beyond the staging rows' cap (163 840 points)
+        const int shapes[5][2] = {{0, 48}, {1, 1}, {33, 13}, {500, 48}, {2600, 64}};
+        for (int k = 0; k < 5; ++k) {
+            const long long Pn = (long long)shapes[k][0] * shapes[k][1];
+            const size_t fwd = adfp_workspace_bytes(Pn), bwd = adfp_backward_workspace_bytes(Pn);
+            adfp_render_args r2 = ra; r2.n_rays = shapes[k][0]; r2.n_samples = shapes[k][1]; r2.n_surface = 0;
+            r2.workspace_bytes = fwd - 1; EXPECT_CODE(adfp_render_forward(&sc, &r2, st), ADFP_E_WORKSPACE);
+            r2.workspace_bytes = fwd; EXPECT_REACHES_LAUNCH(adfp_render_forward(&sc, &r2, st));
+            adfp_points p2 = pts; p2.n_points = Pn;
+            EXPECT_CODE(adfp_eval_points(&sc, &p2, ADFP_STAGE_COLOR, 0, dev<float>(10), dev<float>(11), dev<void>(12), fwd - 1, st), ADFP_E_WORKSPACE);
+            EXPECT_REACHES_LAUNCH(adfp_eval_points(&sc, &p2, ADFP_STAGE_COLOR, 0, dev<float>(10), dev<float>(11), dev<void>(12), fwd, st));
+            adfp_backward_args b2 = ba; b2.n_rays = shapes[k][0]; b2.S = shapes[k][1];
+            b2.workspace_bytes = bwd - 1; EXPECT_CODE(adfp_render_backward(&sc, &b2, st), ADFP_E_WORKSPACE);
+            b2.workspace_bytes = bwd; EXPECT_REACHES_LAUNCH(adfp_render_backward(&sc, &b2, st));
+            adfp_points_backward_args q2 = pb;
+            q2.workspace_bytes = bwd - 1; EXPECT_CODE(adfp_eval_points_backward(&sc, &p2, &q2, st), ADFP_E_WORKSPACE);
+            q2.workspace_bytes = bwd; EXPECT_REACHES_LAUNCH(adfp_eval_points_backward(&sc, &p2, &q2, st));
+        }
+    }
 
     // ---- mapping / tracking helpers
     const float c2w[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};

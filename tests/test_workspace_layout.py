@@ -1,4 +1,5 @@
-"""CPU: every workspace / index size query of the mesh tools returns what tests/golden/workspace_bytes.json recorded.  The launchers
+"""CPU: every workspace / index size query of the mesh tools and of the render path (adfp_workspace_bytes,
+adfp_backward_workspace_bytes) returns what tests/golden/workspace_bytes.json recorded.  The launchers
 carve their workspaces with the same layout functions that answer these queries (csrc/adfp_host.h's Arena), so a fixed table of
 sizes pins the layouts: a buffer added, dropped, reordered or rounded differently moves a number here.  The table was recorded from
 the build before the layouts moved to the arena; `python tests/test_workspace_layout.py` rewrites it from the current build, which
@@ -22,7 +23,8 @@ FEW = [-1, 0, 1, 256, 257, 2048, 2049, 4097, 10 ** 6, RECON_MAX_N // 3, RECON_MA
 ONE_ARG = ['adfp_sort_workspace_bytes', 'adfp_nn_index_bytes', 'adfp_nn_build_workspace_bytes', 'adfp_recon_reduce_workspace_bytes',
            'adfp_sample_surface_workspace_bytes', 'adfp_tri_bvh_build_workspace_bytes', 'adfp_vertex_normals_workspace_bytes',
            'adfp_voxel_down_sample_workspace_bytes', 'adfp_mesh_face_labels_workspace_bytes',
-           'adfp_mesh_component_keep_workspace_bytes', 'adfp_mesh_merge_workspace_bytes', 'adfp_bound_classify_workspace_bytes']
+           'adfp_mesh_component_keep_workspace_bytes', 'adfp_mesh_merge_workspace_bytes', 'adfp_bound_classify_workspace_bytes',
+           'adfp_workspace_bytes', 'adfp_backward_workspace_bytes']
 MC_SHAPES = [(0, 4, 4), (4, -1, 4), (4, 4, 0), (1, 1, 1), (2, 2, 2), (1, 1, 1023), (1, 1024, 1), (1025, 1, 1), (16, 16, 8), (8, 16, 16),
              (3, 5, 7), (17, 31, 65), (100, 100, 100), (257, 129, 33), (512, 512, 512), (2048, 2048, 2048), (1290, 1290, 1290)]
 BOUND_SHAPES = [(0, 4, 4, 8), (-1, 4, 4, 8), (1, 0, 4, 8), (1, 4, 0, 8), (1, 4, 4, 0), (1, 1, 1, 1), (1, 4, 4, 8), (3, 17, 31, 26),

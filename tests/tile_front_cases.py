@@ -110,7 +110,7 @@ def digest(*arrays):
 
 
 def ws_offsets(lib, P):
-    """Byte offsets of the in-band list and of att_occ in the forward workspace of a P-point call (csrc/adfp_kernels.hip carve():
+    """Byte offsets of the in-band list and of att_occ in the forward workspace of a P-point call (csrc/adfp_kernels.hip layout_forward():
     counter block, per-segment maxima, z, raw, list, att_occ, att_u, flags, each rounded up to 256 bytes)."""
     al = lambda n: (n + 255) // 256 * 256
     seg = lib.adfp_workspace_bytes(256) - 256 - 37 * 256
