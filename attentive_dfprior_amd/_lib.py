@@ -413,6 +413,9 @@ SYMBOLS = [
     # frame ingestion
     ('adfp_ingest_frames', C.c_int, [C.POINTER(AdfpIngestGeom), C.c_int, C.POINTER(AdfpIngestJob), C.c_void_p]),
     ('adfp_ingest_out_shape', C.c_int, [C.POINTER(AdfpIngestGeom), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ('adfp_undistort_map', C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p]),
+    ('adfp_ingest_frames_undistort', C.c_int, [C.POINTER(AdfpIngestGeom), C.c_void_p, C.c_int, C.POINTER(AdfpIngestJob), C.c_void_p]),
+    ('adfp_undistort_image', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # visualisation
     ('adfp_vis_canvas_shape', C.c_int, [C.POINTER(AdfpVisGeom), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ('adfp_vis_workspace_bytes', C.c_size_t, [C.POINTER(AdfpVisGeom)]),

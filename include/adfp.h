@@ -1347,6 +1347,38 @@ typedef struct adfp_ingest_job { const unsigned char* color; const void* depth; 
 int adfp_ingest_frames(const adfp_ingest_geom* geom, int n_jobs, const adfp_ingest_job* jobs /*host*/, void* stream);
 int adfp_ingest_out_shape(const adfp_ingest_geom* geom, int* H, int* W);    /* host only */
 
+/* ---- lens undistortion (cfg cam.distortion), stage U in front of stage A of frame ingestion ----
+ * This package's own statement of the scheme of cv2.undistort(img, K, dist) with newCameraMatrix = K: a 1/32-pixel fixed-point
+ * map, bilinear taps, constant border 0.  It has NOT been compared with cv2 (not a dependency, not installed where this was
+ * written): no byte parity with cv2 is claimed.  tests/undistort_ref.py states the rule in numpy.
+ *
+ * Map: one int32 pair (iu, iv) per pixel (u, v) of the decoded colour image [color_h][color_w], all in f64, in this operation
+ * order, no FMA; dist = k1 k2 p1 p2 [k3 [k4 k5 k6]] (4, 5 or 8 coefficients, the missing ones 0):
+ *   x = (u - cx) / fx;  y = (v - cy) / fy;  r2 = x*x + y*y
+ *   kr = (1 + ((k3*r2 + k2)*r2 + k1)*r2) / (1 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *   xd = x*kr + p1*(2*x*y) + p2*(r2 + 2*(x*x));   yd = y*kr + p1*(r2 + 2*(y*y)) + p2*(2*x*y)
+ *   U = fx*xd + cx;  V = fy*yd + cy
+ *   iu = rint(clamp(32*U, -2^30, 2^30)), iv likewise (nearest-even; clamped BEFORE the conversion to int)
+ *   a non-finite U or V gives (INT32_MIN, INT32_MIN)
+ * Remap, all integer: sx = iu >> 5, sy = iv >> 5 (arithmetic), a = iu & 31, b = iv & 31; taps p00 = S[sy][sx], p01 = S[sy][sx+1],
+ * p10 = S[sy+1][sx], p11 = S[sy+1][sx+1] per channel, a tap outside [0, color_h) x [0, color_w) contributing 0;
+ *   byte = ((32-a)(32-b) p00 + a(32-b) p01 + (32-a)b p10 + ab p11 + 512) >> 10
+ * (the weights sum to 1024).  The sentinel entry gives 0, as every entry whose taps all lie outside.
+ *
+ * adfp_undistort_map: host only, once per dataset and colour size; map is a HOST array [color_h][color_w][2].  ADFP_E_ARG for a
+ * null pointer, a size < 1, fx or fy 0 or non-finite, cx or cy non-finite; ADFP_E_UNSUPPORTED for n_dist outside {4, 5, 8} or a
+ * size above 32768.
+ * adfp_ingest_frames_undistort: adfp_ingest_frames with the byte above standing where stage A reads a source byte; stages A-D and
+ * the depth path are untouched, no intermediate image exists.  map is a DEVICE array [color_h][color_w][2], 8-byte aligned
+ * (otherwise ADFP_E_ARG); a NULL map is adfp_ingest_frames exactly.  Errors as adfp_ingest_frames.
+ * adfp_undistort_image: dst [h][w][3] uint8 = the remap of src [h][w][3] through map [h][w][2] (all device; dst must not overlap
+ * src); the channel order is kept.  ADFP_E_ARG for a null pointer, a misaligned map, h or w < 1; ADFP_E_UNSUPPORTED above 32768. */
+int adfp_undistort_map(int color_h, int color_w, double fx, double fy, double cx, double cy, const double* dist, int n_dist,
+                       int* map /*host [color_h][color_w][2]*/);
+int adfp_ingest_frames_undistort(const adfp_ingest_geom* geom, const int* map /*device [color_h][color_w][2]*/, int n_jobs,
+                                 const adfp_ingest_job* jobs /*host*/, void* stream);
+int adfp_undistort_image(const unsigned char* src, const int* map, int h, int w, unsigned char* dst, void* stream);
+
 /* ---- visualisation (visualizer.Visualizer: the reference's src/utils/Visualizer.py:71-114, everything after render_img) ----
  * The frame's input images -- gt_depth [H][W] f32, gt_color [H][W][3] f32 or f64 (gt_color_f64) -- and the rendered ones -- depth
  * [H][W] f64, color [H][W][3] f32 -- go in as they lie in device memory, and two launches write the uint8 canvas [rows][cols][3]

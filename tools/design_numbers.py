@@ -112,6 +112,18 @@ def main(template, d):
             shape, thousands(la['bytes_per_frame']), la['ms_1_frame'] * 1e3, la['ms_per_frame_of_8'] * 1e3, float(k1['avg_us']), float(k8['avg_us']),
             ib['frames_per_batch'] * la['bytes_per_frame'] / (float(k8['avg_us']) * 1e-6) / 1e12))
     v['ing_table'], v['ing_launch_table'] = '\n'.join(rows), '\n'.join(lrows)
+    tum = ib['tum']                                             # lens undistortion at TUM RGB-D's frame (--tum-only)
+    v['ing_tum_out'] = '%d × %d' % tuple(tum['out'])
+    v['ing_tum_reps'], v['ing_tum_iters'] = str(tum['reps']), str(tum['iters'])
+    v['ing_tum_host'] = cell(tum['host_statement'], '%.2f')
+    for key, field in (('dev1', 'device_1_frame'), ('dev8', 'device_8_frames_per_frame'), ('plain1', 'plain_device_1_frame'),
+                       ('plain8', 'plain_device_8_frames_per_frame')):
+        v['ing_tum_' + key] = cell(tum[field], '%.3f')
+    for key, kind in (('l', 'undistort'), ('pl', 'plain')):
+        v['ing_tum_%s1' % key] = '%.1f' % (tum['launch'][kind]['ms_1_frame'] * 1e3)
+        v['ing_tum_%s8' % key] = '%.1f' % (tum['launch'][kind]['ms_8_frames'] * 1e3)
+    v['ing_tum_ratio8'] = '%.2f' % tum['launch_undistort_over_plain_8_frames']
+    v['ing_tum_map_ms'], v['ing_tum_map_numpy_ms'] = '%.1f' % tum['map_library_ms'], '%.0f' % tum['map_numpy_ms']
     # the Visualizer after render_img: host chain against device route (tools/vis_bench.py) and the per-configuration kernel trace
     vb = json.load(open(P('vis_bench.json')))
     v['vis_cpus'], v['vis_threads'] = str(vb['host']['cpus']), str(vb['host']['torch_threads'])
