@@ -20,6 +20,21 @@ def mapping_setting(cfg, key):
     return m[key] if key in m else MAPPING_DEFAULTS[key]
 
 
+# tracking.init: what a tracked frame starts from.  'guess' = the constant-speed guess as it is (the reference's path, and what an
+# absent key means); 'icp' = the guess refined by icp.DepthICP, point-to-plane ICP of the whole depth image against the raycast of
+# the TSDF prior -- with tracking.iters: 0 that result is the frame's pose.  tracking.icp: keywords of DepthICP's constructor
+# (strides, iters, dist_tol, cos_tol, min_pivot, min_pairs, max_jump, max_shift, max_angle, near); lengths are metres and are NOT
+# multiplied by `scale`.
+TRACKING_DEFAULTS = {'init': 'guess', 'icp': {}}
+TRACKING_INITS = ('guess', 'icp')
+
+
+def tracking_setting(cfg, key):
+    """``cfg['tracking'][key]``, or this package's default for a key the reference's configs do not have."""
+    t = cfg.get('tracking') or {}
+    return t[key] if key in t else TRACKING_DEFAULTS[key]
+
+
 # meshing.simplify_voxel_size: None or 0 = the marching-cubes mesh as it is; a positive number = the voxel (in the config's units,
 # multiplied by `scale` like the bounds) of mesh.simplify_vertex_clustering, run by Mesher.mesh_arrays after the component clean-up
 # and before the colour query.  meshing.simplify_contraction: 'quadric' or 'average'.  (Vertex clustering by this package's own

@@ -3339,3 +3339,4 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
 #include "adfp_vis.h"           // visualisation
 #include "adfp_metrics.h"       // rendering metrics
 #include "adfp_tsdfcast.h"      // TSDF raycast
+#include "adfp_icp.h"           // depth ICP against the TSDF raycast

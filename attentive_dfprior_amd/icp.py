@@ -1,0 +1,169 @@
+"""Frame-to-model point-to-plane ICP over the whole depth image on the MI355X (adfp_depth_normals, adfp_icp_*, csrc/adfp_icp.h):
+KinectFusion's tracker against the TSDF prior that is resident for the whole run.
+
+The Tracker starts a frame from the constant-speed guess and looks at 200 pixels per iteration; the prior volume, its raycast
+(tsdf_raycast.TsdfRaycaster) and the frame's full sensor depth image are on the device all along.  DepthICP aligns the whole sensor
+depth image with the raycast of the prior from the guess and hands the Tracker a better start -- or, with ``tracking.iters: 0``, is
+the tracker (``tracking.init: icp``, slam.Tracker).
+
+    icp = DepthICP(tsdf_volume, tsdf_bnds, H, W, fx, fy, cx, cy, engine=renderer._engine)
+    cam = icp.refine(guess_c2w, gt_depth)          # [7] float32 on the device: quaternion r, i, j, k, then the translation
+    icp.last_stats()                               # [steps + 1, 6] float64 on the host, on demand
+
+The rule (normal map, association, normal equations, solve, gate) is stated in include/adfp.h ("Depth ICP") and restated in numpy in
+tests/icp_ref.py.  Everything is decided on the device: a refinement is a fixed sequence of launches with no read-back, and a
+refinement that fails (too few pairs, a direction the pairs do not constrain, a result too far from the guess) returns the guess."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr
+from .tsdf_raycast import TsdfRaycaster
+
+OK, FEW_PAIRS, DEGENERATE, REJECTED = 0, 1, 2, 3
+STATUS_NAMES = {v: k for k, v in _lib.ICP_STATUS.items()}
+STATS_COLUMNS = ('pairs', 'rmse', 'pivot_ratio', 'omega', 'shift', 'status')
+
+
+class DepthICP(object):
+    """ICP of H x W sensor depth images against one TSDF volume ([1,1,Z,Y,X] float32 on the device) inside `tsdf_bnds`.
+
+    strides / iters: the levels, coarse to fine: iters[k] steps over every strides[k]-th pixel of every strides[k]-th row.  dist_tol
+    (metres) and cos_tol gate a pair; min_pivot is the smallest LDL^T pivot over the largest diagonal entry a step accepts; min_pairs
+    is the SHARE of a level's strided pixels a step needs as pairs; max_jump (metres, 0: off) invalidates normals across depth
+    edges; max_shift (metres) and max_angle (radians) bound how far the result may move from the guess; near (metres of sensor
+    depth, 0: from the camera) is where the model's raycast starts marching -- a ray whose first sample lies in unobserved space
+    (-1 in a fused volume, which the camera's own voxel is unless another frame saw it) reports no surface.  `engine`: share a
+    Renderer's Engine, so that one invalidate_tsdf serves both.  All buffers are allocated here, once; refine() allocates only the
+    raycaster's scratch and synchronises nothing."""
+
+    def __init__(self, tsdf_volume, tsdf_bnds, H, W, fx, fy, cx, cy, engine=None, strides=(4, 2, 1), iters=(4, 3, 3), dist_tol=0.1,
+                 cos_tol=0.8, min_pivot=1e-6, min_pairs=0.05, max_jump=0.0, max_shift=0.5, max_angle=0.5, near=0.0):
+        self.raycaster = TsdfRaycaster(tsdf_volume, tsdf_bnds, engine=engine)
+        self.H, self.W, self.fx, self.fy, self.cx, self.cy = int(H), int(W), float(fx), float(fy), float(cx), float(cy)
+        self.strides, self.iters = tuple(int(s) for s in strides), tuple(int(n) for n in iters)
+        if len(self.strides) != len(self.iters) or not self.strides or min(self.strides) < 1 or min(self.iters) < 0:
+            raise ValueError(f'strides {strides!r} and iters {iters!r}: one step count >= 0 per stride >= 1')
+        self.dist_tol, self.cos_tol, self.min_pivot, self.min_pairs = float(dist_tol), float(cos_tol), float(min_pivot), float(min_pairs)
+        self.max_jump, self.max_shift, self.max_angle = float(max_jump), float(max_shift), float(max_angle)
+        self.near = float(near)
+        self.n_steps = sum(self.iters)
+        dev = self.dev = tsdf_volume.device
+        nbytes = int(lib().adfp_icp_workspace_bytes(self.H, self.W))
+        if nbytes == 0:
+            raise RuntimeError(f'adfp_icp_workspace_bytes refuses a {self.H} x {self.W} image')
+        self.depth = torch.zeros((2, self.H, self.W), dtype=torch.float32, device=dev)             # sensor, model
+        self.normals = torch.zeros((2, self.H, self.W, 3), dtype=torch.float32, device=dev)
+        self.p_ref = torch.zeros((4, 4), dtype=torch.float32, device=dev)
+        self.state = torch.zeros((_lib.ICP_STATE_BYTES // 8,), dtype=torch.float64, device=dev)
+        self.stats = torch.zeros((self.n_steps + 1, _lib.ICP_STATS), dtype=torch.float64, device=dev)
+        self.workspace = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+        self.c2w_out = torch.zeros((4, 4), dtype=torch.float32, device=dev)
+        self.cam_out = torch.zeros((7,), dtype=torch.float32, device=dev)
+
+    def invalidate_tsdf(self):
+        self.raycaster.invalidate_tsdf()
+
+    def strided_pixels(self, stride):
+        return ((self.H + stride - 1) // stride) * ((self.W + stride - 1) // stride)
+
+    def pairs_needed(self, stride):
+        """min_pairs as a count at this level"""
+        return float(math.ceil(self.min_pairs * self.strided_pixels(stride)))
+
+    # ---- the launches ----------------------------------------------------------------------------------------------------------
+    def compute_normals(self, depth, out=None):
+        """depth [V,H,W] float32 on the device -> normals [V,H,W,3] (adfp_depth_normals, one launch)."""
+        _lib.require_cuda(depth, 'depth')
+        if depth.dtype != torch.float32 or depth.dim() != 3 or tuple(depth.shape[1:]) != (self.H, self.W) or not depth.is_contiguous():
+            raise ValueError(f'depth: expected contiguous float32 [V,{self.H},{self.W}], got {depth.dtype} {tuple(depth.shape)}')
+        V = depth.shape[0]
+        with _lib.device_guard(depth.device):
+            if out is None:
+                out = torch.empty((V, self.H, self.W, 3), dtype=torch.float32, device=depth.device)
+            check(lib().adfp_depth_normals(ptr(depth), V, self.H, self.W, self.fx, self.fy, self.cx, self.cy, self.max_jump, ptr(out),
+                                           _lib.current_stream(depth.device)), 'adfp_depth_normals')
+        return out
+
+    def _begin(self, guess, st):
+        check(lib().adfp_icp_begin(ptr(guess), ptr(self.state), st), 'adfp_icp_begin')
+
+    def _step(self, maps, p_ref, stride, row, st, sums=None):
+        depth, normals = maps
+        check(lib().adfp_icp_step(ptr(depth[0]), ptr(normals[0]), ptr(depth[1]), ptr(normals[1]), ptr(p_ref), self.H, self.W, self.fx, self.fy,
+                                  self.cx, self.cy, int(stride), self.dist_tol, self.cos_tol, self.min_pivot, self.pairs_needed(stride),
+                                  ptr(self.state), ptr(self.stats), self.stats.shape[0], int(row), ptr(sums), ptr(self.workspace),
+                                  self.workspace.numel() * 8, st), 'adfp_icp_step')
+
+    def _end(self, row, st):
+        check(lib().adfp_icp_end(ptr(self.state), self.max_shift, self.max_angle, ptr(self.c2w_out), ptr(self.cam_out), ptr(self.stats),
+                                 self.stats.shape[0], int(row), st), 'adfp_icp_end')
+
+    def run_steps(self):
+        """begin, the steps level by level, end, on the maps and the reference pose this object holds (refine's tail: a fixed sequence
+        of launches that a HIP graph can capture).  Returns cam_out [7]."""
+        with _lib.device_guard(self.dev):
+            st = _lib.current_stream(self.dev)
+            self._begin(self.p_ref, st)
+            row = 0
+            for stride, n in zip(self.strides, self.iters):
+                for _ in range(n):
+                    self._step((self.depth, self.normals), self.p_ref, stride, row, st)
+                    row += 1
+            self._end(row, st)
+        return self.cam_out
+
+    def set_frame(self, guess_c2w, gt_depth):
+        """The refinement's inputs: the sensor depth, the raycast of the prior from the guess, both normal maps (one launch)."""
+        if isinstance(guess_c2w, np.ndarray):
+            guess_c2w = torch.from_numpy(guess_c2w)
+        g = guess_c2w.detach().to(self.dev, torch.float32)
+        if tuple(g.shape) == (3, 4):
+            g = torch.cat([g, g.new_tensor([[0., 0., 0., 1.]])], 0)
+        if tuple(g.shape) != (4, 4):
+            raise ValueError(f'guess_c2w: expected [4,4] or [3,4], got {tuple(guess_c2w.shape)}')
+        if tuple(gt_depth.shape) != (self.H, self.W):
+            raise ValueError(f'gt_depth: expected [{self.H},{self.W}], got {tuple(gt_depth.shape)}')
+        _lib.require_cuda(gt_depth, 'gt_depth')
+        self.p_ref.copy_(g)
+        self.depth[0].copy_(gt_depth)
+        self.raycaster.render_depth(self.p_ref, self.H, self.W, self.fx, self.fy, self.cx, self.cy, near=self.near, out=self.depth[1:2])
+        self.compute_normals(self.depth, out=self.normals)
+
+    def refine(self, guess_c2w, gt_depth):
+        """guess_c2w [4,4] (or [3,4]) camera-to-world, gt_depth [H,W] on the device -> the camera tensor [7] float32 on the device
+        (this object's own buffer: the next refine overwrites it).  The guess itself comes back when the refinement fails."""
+        self.set_frame(guess_c2w, gt_depth)
+        return self.run_steps()
+
+    def last_stats(self):
+        """The stats rows of the last refinement on the host (one download): a row per step -- pairs, rmse before the update,
+        smallest pivot ratio, |omega|, |t|, status -- and the gate's row: 0, 0, 0, angle and shift from the guess, final status."""
+        return self.stats.cpu()
+
+    def last_status(self):
+        return int(self.last_stats()[-1, 5].item())
+
+    def step_system(self, c2w, depth_s, normals_s, depth_m, normals_m, p_ref, stride=1):
+        """One step from the estimate `c2w` (float32 [4,4]) on the caller's maps: -> (sums [29] float64, stats row [6], estimate
+        after the step [4,4] float32, its camera tensor [7]), all on the device.  For tests: the sums are the step's normal
+        equations as adfp_icp_step's order lists them."""
+        dev = self.dev
+        c2w = c2w.detach().to(dev, torch.float32).contiguous()
+        p_ref = p_ref.detach().to(dev, torch.float32).contiguous()
+        depth = torch.stack([depth_s.to(dev, torch.float32), depth_m.to(dev, torch.float32)]).contiguous()
+        normals = torch.stack([normals_s.to(dev, torch.float32), normals_m.to(dev, torch.float32)]).contiguous()
+        if tuple(depth.shape) != (2, self.H, self.W) or tuple(normals.shape) != (2, self.H, self.W, 3):
+            raise ValueError(f'maps: expected [{self.H},{self.W}] depths and [{self.H},{self.W},3] normals')
+        sums = torch.zeros((_lib.ICP_SUMS,), dtype=torch.float64, device=dev)
+        with _lib.device_guard(dev):
+            st = _lib.current_stream(dev)
+            self._begin(c2w, st)
+            self._step((depth, normals), p_ref, stride, 0, st, sums=sums)
+            # no gate: the step's own result comes out
+            check(lib().adfp_icp_end(ptr(self.state), float('inf'), float('inf'), ptr(self.c2w_out), ptr(self.cam_out), None, 0, 0, st),
+                  'adfp_icp_end')
+        return sums, self.stats[0].clone(), self.c2w_out.clone(), self.cam_out.clone()

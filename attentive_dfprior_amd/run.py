@@ -2,7 +2,7 @@
 
     python -m attentive_dfprior_amd.run CONFIG [--input_folder ..] [--output ..] [--tsdf_volume PATH --tsdf_bounds PATH]
                                                [--prior file|online] [--prior_voxel_size M] [--seed N] [--last_frame N]
-                                               [--no_prefetch] [--default_config PATH]
+                                               [--no_prefetch] [--default_config PATH] [--tracking_init guess|icp]
 
 The prior TSDF volume comes from the files ``python -m attentive_dfprior_amd.get_tsdf CONFIG`` writes
 (``<dataset>_tsdf_volume/<scene>_tsdf_volume.pt`` and ``_bounds.pt``, or the two paths given), or with ``--prior online`` is fused
@@ -29,12 +29,17 @@ def parse_args(argv=None):
     parser.add_argument('--last_frame', type=int, help='end the run at this frame index')
     parser.add_argument('--no_prefetch', action='store_true', help='decode every frame when it is needed instead of one frame ahead')
     parser.add_argument('--default_config', type=str, default=DEFAULT_CONFIG, help='the config every other one inherits from')
+    parser.add_argument('--tracking_init', choices=('guess', 'icp'),
+                        help="replaces the config's tracking.init: guess = the constant-speed guess as it is; icp = the guess refined by "
+                             'point-to-plane ICP of the depth image against the TSDF prior (icp.DepthICP)')
     return parser.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
     cfg = load_config(args.config, args.default_config if os.path.exists(args.default_config) else None)
+    if args.tracking_init is not None:
+        cfg.setdefault('tracking', {})['init'] = args.tracking_init
     if args.seed is not None:
         setup_seed(args.seed)
     slam = DF_Prior(cfg, args)

@@ -19,6 +19,9 @@ Deliberate differences from the reference:
   * ``--last_frame N`` ends the run at frame N (the reference hard-codes frame 4640 of ScanNet scene 50).
   * ``mapping.BA: True`` (default False): bundle adjustment as the reference's parent project runs it -- with more than four
     keyframes the window's poses, all but the oldest keyframe's, are optimised with the map (``mapping.BA_cam_lr``, stage color).
+  * ``tracking.init: icp`` (default ``guess``): the constant-speed guess is refined by point-to-plane ICP of the frame's whole depth
+    image against the raycast of the TSDF prior (``icp.DepthICP``) before the iterations start from it; with ``tracking.iters: 0``
+    the refined pose is the frame's pose.  ``Tracker.icp_status`` holds one status per tracked frame.
 """
 import logging
 import os
@@ -32,7 +35,7 @@ import torch
 
 from . import get_model
 from .common import get_camera_from_tensor, get_tensor_from_camera, random_select
-from .config import mapping_setting
+from .config import TRACKING_INITS, mapping_setting, tracking_setting
 
 log = logging.getLogger('attentive_dfprior_amd')
 STAGES = ('low', 'high', 'color')
@@ -497,8 +500,22 @@ class Tracker(object):
         self.decoders = self.shared_decoders
         self.visualizer = self._new_visualizer()
         self._it = None
+        # tracking.init: icp -- the guess goes through icp.DepthICP first; one status per tracked frame (icp.OK ...)
+        self.init = tracking_setting(cfg, 'init')
+        if self.init not in TRACKING_INITS:
+            raise ValueError(f'tracking.init {self.init!r}: one of {TRACKING_INITS}')
+        self.icp_kwargs = dict(tracking_setting(cfg, 'icp') or {})
+        self._icp = None
+        self.icp_status = []
 
     # ---- the parts a test replaces with recording stand-ins ----------------------------------------------------------------
+    def _new_icp(self):
+        """The raycaster inside shares the Renderer's Engine: its empty-space bitmap is keyed on the prior volume's version counter
+        (--prior online integrates through PyTorch, which bumps it) and dropped by the Renderer's invalidate_tsdf."""
+        from .icp import DepthICP
+        return DepthICP(self.tsdf_volume_shared, self.tsdf_bnds, self.H, self.W, self.fx, self.fy, self.cx, self.cy,
+                        engine=self.renderer._engine, **self.icp_kwargs)
+
     def _new_visualizer(self):
         from .visualizer import Visualizer
         t = self.cfg['tracking']
@@ -520,6 +537,12 @@ class Tracker(object):
         if self._it is None:
             self._it = self._new_iteration()
         return self._it
+
+    @property
+    def icp(self):
+        if self._icp is None:
+            self._icp = self._new_icp()
+        return self._icp
 
     def optimize_cam_in_batch(self, camera_tensor, gt_color, gt_depth, batch_size, optimizer, tsdf_volume):
         """One iteration of camera optimisation (src/Tracker.py:75-134) on the frame and pose the iteration holds since its last
@@ -561,7 +584,12 @@ class Tracker(object):
             if not self.no_vis_on_first_frame:
                 self.visualizer.vis(idx, 0, gt_depth, gt_color, c2w.to(self.device), self.c, self.decoders, tsdf_volume, tsdf_bnds)
         else:
-            camera_tensor = get_tensor_from_camera(self.guess(idx).detach())
+            if self.init == 'icp':
+                # the guess aligned with the prior's surface over the whole depth image; the guess itself when that fails.  On the
+                # device, no read-back: the iterations below are queued behind it
+                camera_tensor = self.icp.refine(self.guess(idx).detach(), gt_depth)
+            else:
+                camera_tensor = get_tensor_from_camera(self.guess(idx).detach())
             if self.num_cam_iters > 0:
                 it = self.iteration
                 it.new_frame(camera_tensor.to(self.device), gt_depth, gt_color)          # a fresh Adam, like :219-229
@@ -569,9 +597,18 @@ class Tracker(object):
                     self.visualizer.vis(idx, cam_iter, gt_depth, gt_color, it.camera_tensor, self.c, self.decoders, tsdf_volume, tsdf_bnds)
                     it.step(self.tracking_pixels)
                 camera_tensor = it.best_camera_tensor                                    # the lowest-loss pose, kept on the device
-            # tracking.iters: 0 keeps the guess
+            # tracking.iters: 0 keeps the guess (tracking.init: icp: what the ICP made of it)
             top = get_camera_from_tensor(camera_tensor.detach().clone()).cpu()           # the frame's one download
             c2w = torch.cat([top.float(), torch.tensor([[0., 0., 0., 1.]])], dim=0)
+            if self.init == 'icp':
+                stats = self.icp.last_stats()                                            # behind the download: nothing is waited for
+                self.icp_status.append(int(stats[-1, 5].item()))
+                if self.verbose:
+                    from .icp import STATUS_NAMES
+                    last = stats[:-1][stats[:-1, 0] > 0]
+                    step = last[-1].tolist() if len(last) else [0.0] * 6
+                    print(f'ICP frame {idx}: {STATUS_NAMES[self.icp_status[-1]]}, last step {step[0]:.0f} pairs, rmse {step[1]:.5f} m, '
+                          f'pivot ratio {step[2]:.2e}; moved {stats[-1, 4].item():.4f} m {stats[-1, 3].item():.4f} rad from the guess')
 
         self.estimate_c2w_list[idx] = c2w.clone()
         self.gt_c2w_list[idx] = gt_c2w.clone().cpu()

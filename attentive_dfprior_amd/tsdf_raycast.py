@@ -45,13 +45,14 @@ class TsdfRaycaster(object):
         Z, Y, X = self.tsdf_volume.shape[2:]
         return min((ext[0][1] - ext[0][0]) / X, (ext[1][1] - ext[1][0]) / Y, (ext[2][1] - ext[2][0]) / Z)
 
-    def render_depth(self, c2w, H, W, fx, fy, cx, cy, near=0., far=0., step=None, skip=True, tsdf_blocks=None, count=False):
+    def render_depth(self, c2w, H, W, fx, fy, cx, cy, near=0., far=0., step=None, skip=True, tsdf_blocks=None, count=False, out=None):
         """c2w [V,4,4] or [4,4] -> depth [V,H,W] or [H,W] float32 on the volume's device.
 
         near, far: the ray interval in sensor depth (far = 0: to the volume's exit); step: metres between samples, default half a
         voxel; skip=False looks every sample up (the same image, byte for byte).  tsdf_blocks: None reads the corner-block copy if
         the engine holds a current one, False never, a tensor is the caller's own copy.  count=True also returns the number of
-        trilinear lookups the call made (one read-back)."""
+        trilinear lookups the call made (one read-back).  out: a contiguous float32 [V,H,W] on the volume's device to write into
+        instead of a new tensor (icp.DepthICP's model slot)."""
         t = self.tsdf_volume
         dev = t.device
         if isinstance(c2w, np.ndarray):
@@ -83,8 +84,13 @@ class TsdfRaycaster(object):
             if skip:
                 bricks = self._engine.tsdf_bricks(t)
                 nbytes = bricks.numel() * 4
-            depth = torch.empty((V, int(H), int(W)), dtype=torch.float32, device=dev)
-            n = torch.zeros((1,), dtype=torch.int64, device=dev) if count else None
+            if out is None:
+                depth = torch.empty((V, int(H), int(W)), dtype=torch.float32, device=dev)
+            else:
+                if out.dtype != torch.float32 or tuple(out.shape) != (V, int(H), int(W)) or out.device != dev or not out.is_contiguous():
+                    raise ValueError(f'out: expected contiguous float32 [{V},{int(H)},{int(W)}] on {dev}, got {out.dtype} {tuple(out.shape)}')
+                depth = out
+            n =torch.zeros((1,), dtype=torch.int64, device=dev) if count else None
             check(L.adfp_tsdf_raycast(C.byref(td), C.byref(b), ptr(bricks), nbytes, ptr(m), V, int(H), int(W), fx, fy, cx, cy,
                                       float(near), float(far), float(step), 0 if skip else _lib.CAST_NO_SKIP, ptr(depth), ptr(n), st),
                   'adfp_tsdf_raycast')

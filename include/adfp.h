@@ -1494,6 +1494,59 @@ int adfp_tsdf_raycast(const adfp_tsdf* tsdf /*host*/, const double tsdf_bnds[3][
                       const float* c2w /*[V][4][4]*/, int V, int H, int W, float fx, float fy, float cx, float cy, double near, double far,
                       double step, int options, float* depth /*[V][H][W]*/, unsigned long long* lookups, void* stream);
 
+/* ---- Depth ICP (icp.DepthICP, tracking.init: icp: KinectFusion's frame-to-model point-to-plane ICP over the whole depth image, the
+ * sensor depth against the raycast of the TSDF prior; no counterpart in the reference) ----  tests/icp_ref.py states the rule in numpy.
+ * Camera convention: adfp_get_rays'.  Pixel (u, v) with depth d is the camera point V = ((u - cx) / fx d, -(v - cy) / fy d, -d); d <= 0
+ * or non-finite is invalid.  Vertices are never stored, they are recomputed from the depth.  fx, fy, cx, cy are f32 values; all
+ * arithmetic below is f64 on f32 loads.
+ * Normal map (adfp_depth_normals, one launch for V images): a = V(v, u + 1) - V(v, u), b = V(v + 1, u) - V(v, u), n = normalize(b x a),
+ *   negated when n . V(v, u) > 0.  n = 0 (invalid) on the last row and column, when any of the three depths is invalid, when |b x a| = 0,
+ *   and, with max_jump > 0, when either neighbour's depth differs from the pixel's by more than max_jump.  normals [V][H][W][3] f32.
+ * One step (adfp_icp_step; T is the f64 camera-to-world estimate in the state block, p_ref the f32 pose the model maps were raycast
+ *   from).  For every sensor pixel with u % stride == 0, v % stride == 0 and a valid normal N_s:
+ *     x = T V_s, n_s = R_T N_s;  x_c = R_ref^T (x - t_ref), z = -x_c.z, required > 0;
+ *     u' = floor(fx x_c.x / z + cx + 0.5), v' = floor(-fy x_c.y / z + cy + 0.5), required inside the image with a valid model normal;
+ *     m = p_ref V_m(u', v'), n = R_ref N_m(u', v');  the pair is kept if |x - m| <= dist_tol and n_s . n >= cos_tol.
+ *   Per pair r = n . (m - x), J = [x x n, n] for the twist xi = (w, t) applied on the left (x <- x + w x x + t).  The ADFP_ICP_SUMS = 29
+ *   f64 sums, in this order: the 21 upper entries of sum J^T J row by row, the 6 of sum J^T r, sum r^2, the pair count.  They are
+ *   added in an order fixed by the launch geometry (no atomics): the same inputs give the same bytes.
+ *   Solve: pairs < min_pairs (a count) gives ADFP_ICP_FEW_PAIRS.  Otherwise LDL^T without pivoting, pivots d_0 .. d_5 in turn; the
+ *   first d_j that is not > min_pivot max diag(A) stops it with ADFP_ICP_DEGENERATE.  In either case T stays and every later step
+ *   of the bracket does nothing but write its stats row (zeros and the status).  Otherwise T <- Exp(xi) T with the closed-form SE(3)
+ *   exponential (R = I + A K + B K^2, translation (I + B K + C K^2) t, A = sin th / th, B = (1 - cos th) / th^2, C = (1 - A) / th^2;
+ *   below th = |w| = 1e-12 the series R = I + K, I + K / 2).
+ *   stats row (ADFP_ICP_STATS = 6 doubles): pairs, rmse before the update (sqrt(sum r^2 / pairs), 0 without pairs), the smallest pivot
+ *   ratio d_j / max diag(A) over the pivots computed, |w|, |t|, status.  sums (device [29], or NULL) receives the step's sums.
+ * Bracket: adfp_icp_begin sets T = guess (device [16] f32) and status OK.  adfp_icp_end: with status OK, shift = |t_T - t_guess| and
+ *   angle = atan2(|vee(D - D^T)| / 2, (tr D - 1) / 2) of D = R_T R_guess^T; shift > max_shift or angle > max_angle (or NaN) gives
+ *   ADFP_ICP_REJECTED.  c2w_out [16] f32 is T rounded (last row 0 0 0 1) when the status is OK, else the guess's own bits; cam_out [7]
+ *   f32 is common.get_tensor_from_camera of c2w_out in f64 (columns normalised, negated for a negative determinant, the trace branch
+ *   or the largest-diagonal branch, unit length, r >= 0): quaternion r, i, j, k, then the translation.  Its stats row, when stats is
+ *   given: 0, 0, 0, angle, shift, the final status.
+ * state: ADFP_ICP_STATE_BYTES of device memory, 8-byte aligned, the caller's; nothing else persists between the calls.  workspace:
+ * adfp_icp_workspace_bytes(H, W) (0 for H or W outside [1, 32768]), 8-byte aligned.  Asynchronous on `stream`, no allocation, no
+ * pointer kept, no read-back, graph-capturable; adfp_icp_step is two launches, the others one.  Errors, all before any launch:
+ * ADFP_E_ARG for a null pointer (sums, and adfp_icp_end's stats, may be NULL), V, H, W or stride < 1, a NaN tolerance or intrinsic,
+ * fx or fy 0, a misaligned block, a workspace below adfp_icp_workspace_bytes, a stats row outside [0, stats_rows);
+ * ADFP_E_UNSUPPORTED for H or W above 32768 or V above 65535. */
+#define ADFP_ICP_SUMS 29
+#define ADFP_ICP_STATS 6
+#define ADFP_ICP_STATE_BYTES 272
+#define ADFP_ICP_OK 0
+#define ADFP_ICP_FEW_PAIRS 1
+#define ADFP_ICP_DEGENERATE 2
+#define ADFP_ICP_REJECTED 3
+size_t adfp_icp_workspace_bytes(int H, int W);
+int adfp_depth_normals(const float* depth /*[V][H][W]*/, int V, int H, int W, float fx, float fy, float cx, float cy, float max_jump,
+                       float* normals /*[V][H][W][3]*/, void* stream);
+int adfp_icp_begin(const float* guess /*[16]*/, void* state, void* stream);
+int adfp_icp_step(const float* depth_s, const float* normals_s, const float* depth_m, const float* normals_m, const float* p_ref /*[16]*/,
+                  int H, int W, float fx, float fy, float cx, float cy, int stride, double dist_tol, double cos_tol, double min_pivot,
+                  double min_pairs, void* state, double* stats /*[stats_rows][6]*/, int stats_rows, int row, double* sums /*[29] or NULL*/,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int adfp_icp_end(void* state, double max_shift, double max_angle, float* c2w_out /*[16]*/, float* cam_out /*[7]*/,
+                 double* stats /*or NULL*/, int stats_rows, int row, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

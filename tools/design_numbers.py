@@ -485,6 +485,32 @@ def main(template, d):
                 last['device']['median_ms'] * 1e9 / last['pairs']))
     else:
         v['cm_numbers'] = 'No run of `tools/color_mesh_bench.py` is in `profiles/`: not measured.'
+    # depth ICP beside the tracking it precedes (tools/icp_bench.py)
+    ic_path = Q('icp_bench.json')
+    if os.path.exists(ic_path):
+        ic = json.load(open(ic_path))
+        cell3 = lambda s, f='%.3f': (f + ' (' + f + ', ' + f + ')') % (s['median_ms'], s['min_ms'], s['max_ms'])
+        rows = ['| leg | ms, median (min, max) |', '|---|---|']
+        for label, key in (('raycast of the model from the guess', 'raycast'), ('normal maps of both images, one launch', 'normals'),
+                           ('one step at stride 4 (with `adfp_icp_begin`)', 'step_s4'), ('one step at stride 2', 'step_s2'),
+                           ('one step at stride 1', 'step_s1'), ('begin, the ten steps, end', 'steps'),
+                           ('`refine` as a whole', 'refine'), ('`new_frame` and ten `TrackerIteration.step` replays of 200 pixels', 'track10')):
+            rows.append('| %s | %s |' % (label, cell3(ic[key])))
+        v['icp_numbers'] = ('Measured on one MI355X (`profiles/icp_bench.json`, one run of `tools/icp_bench.py --reps %d`): Replica\'s frame, %d × %d, in '
+                            'the room0 box-room volume (%s voxels), a corner-facing pose inside the room, the sensor depth the raycast at the true pose, the '
+                            'guess %.1f mm and %.2f° off; strides %s with %s steps.  Device events around each leg, the legs alternating within a repetition:\n\n'
+                            % (ic['reps'], ic['frame'][0], ic['frame'][1], ' × '.join(str(x) for x in ic['volume']), ic['error_before_m_rad'][0] * 1e3,
+                               ic['error_before_m_rad'][1] * 57.29577951308232, ', '.join(str(x) for x in ic['levels']['strides']),
+                               ', '.join(str(x) for x in ic['levels']['iters']))
+                            + '\n'.join(rows) + '\n\n'
+                            + 'The refinement ended with status %d (0 = OK) %.2f mm and %.3f° from the true pose, on %s to %s pairs per step (%s and %s valid normals '
+                              'in the sensor and the model image), smallest pivot ratio %.1e.  `refine` takes %.2f × the time of the ten tracking iterations it precedes.  '
+                              'No threshold is set and no speed target: these are the first times of this path.'
+                            % (ic['status'], ic['error_after_m_rad'][0] * 1e3, ic['error_after_m_rad'][1] * 57.29577951308232,
+                               thousands(int(min(ic['pairs_per_step']))), thousands(int(max(ic['pairs_per_step']))), thousands(ic['valid_sensor_normals']),
+                               thousands(ic['valid_model_normals']), ic['pivot_ratio_min'], ic['refine_over_track10']))
+    else:
+        v['icp_numbers'] = 'No run of `tools/icp_bench.py` is in `profiles/`: not measured.'
     s = open(template).read()
     out = re.sub(r'@@(\w+)@@', lambda m: v.get(m.group(1), m.group(0)), s)
     sys.stdout.write(out)

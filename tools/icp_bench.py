@@ -1,0 +1,126 @@
+"""The depth ICP (icp.DepthICP, csrc/adfp_icp.h) at Replica's frame, 680 x 1200, in the room0 box-room volume (4/256 m voxels), from
+a corner-facing pose inside the room with the guess 35 mm / 1.5 degrees off.  The sensor depth is the raycast at the true pose.
+
+  raycast    the model's depth image from the guess (adfp_tsdf_raycast), what refine starts with
+  normals    adfp_depth_normals for both images in one launch
+  step_sN    one adfp_icp_step (the sums' launch and the solve's) over every N-th pixel of every N-th row, N = 4, 2, 1
+  steps      begin, the ten steps of the default levels (4, 3, 3 at strides 4, 2, 1), end
+  refine     DepthICP.refine as a whole: upload of the guess, copy of the sensor depth, raycast, normals, steps
+  track10    ten TrackerIteration.step replays of 200 pixels after a new_frame: the tracking the refinement precedes
+
+Device events around each leg, median (min, max) of `--reps` repetitions after a warm-up; the legs alternate within a repetition.  No
+thresholds: the numbers go into DESIGN.md section 5.13.
+
+    python tools/icp_bench.py [--reps 7] [--json profiles/icp_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import icp_ref                                                 # noqa: E402
+import attentive_dfprior_amd as A                              # noqa: E402
+from attentive_dfprior_amd import _lib, common, synthetic      # noqa: E402
+from attentive_dfprior_amd.icp import DepthICP                 # noqa: E402
+from attentive_dfprior_amd.tracking import TrackerIteration    # noqa: E402
+
+DEV = 'cuda:0'
+GEO = (680, 1200, 600.0, 600.0, 599.5, 339.5)                  # configs/Replica/replica.yaml
+CFG = {'rendering': {'lindisp': False, 'perturb': 0.0, 'N_samples': 48, 'N_surface': 16, 'N_importance': 0},
+       'scale': 1, 'occupancy': True, 'meshing': {'resolution': 256}}
+
+
+def stats(ms):
+    ms = sorted(ms)
+    return {'median_ms': ms[len(ms) // 2], 'min_ms': ms[0], 'max_ms': ms[-1], 'all_ms': ms}
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=7)
+    ap.add_argument('--json', default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'icp_bench needs a GPU'
+    assert a.reps >= 5, 'at least 5 repetitions'
+    sc = synthetic.Scene('room0', device=DEV, grid_std_scale=20.0)
+    sc.c['grid_high'] = sc.c['grid_high'] * 100
+    sc.H, sc.W, sc.fx, sc.fy, sc.cx, sc.cy = GEO
+    dec = A.DF()
+    dec.load_state_dict(synthetic.seeded_state_dict(0))
+    dec.bound = sc.bound
+    dec = dec.to(DEV)
+    for p in dec.parameters():
+        p.requires_grad_(False)
+    rend = A.Renderer(CFG, None, sc)
+    tb = sc.tsdf_bnds.to(DEV)
+    icp = DepthICP(sc.tsdf_volume, tb, *GEO, engine=rend._engine)
+    P = sc.default_c2w(offset=(0.3, 0.2, 0.1), yaw=0.75, pitch=-0.6)
+    G = torch.from_numpy((icp_ref.exp_se3(np.asarray(icp_ref.TWIST)) @ P.cpu().numpy().astype(np.float64)).astype(np.float32))
+    sensor = icp.raycaster.render_depth(P, *GEO)
+    color = torch.rand((GEO[0], GEO[1], 3), generator=torch.Generator().manual_seed(0)).to(DEV)
+    cam = icp.refine(G, sensor).clone()
+    rows = icp.last_stats().numpy()
+    got = icp.c2w_out.cpu().numpy()
+    e0, e1 = icp_ref.pose_error(G.numpy(), P.cpu().numpy()), icp_ref.pose_error(got, P.cpu().numpy())
+    fused = TrackerIteration(rend, dec, sc.c, sc.tsdf_volume, tb, GEO[0], GEO[1], *GEO[2:], 20, 20)
+    st = _lib.current_stream(torch.device(DEV))
+
+    def one_step(stride):
+        def fn():
+            icp._begin(icp.p_ref, st)
+            icp._step((icp.depth, icp.normals), icp.p_ref, stride, 0, st)
+        return fn
+
+    def track10():
+        fused.new_frame(cam, sensor, color)
+        for _ in range(10):
+            fused.step(200)
+
+    legs = {'raycast': lambda: icp.raycaster.render_depth(icp.p_ref, *GEO, out=icp.depth[1:2]),
+            'normals': lambda: icp.compute_normals(icp.depth, out=icp.normals),
+            'step_s4': one_step(4), 'step_s2': one_step(2), 'step_s1': one_step(1),
+            'steps': icp.run_steps, 'refine': lambda: icp.refine(G, sensor), 'track10': track10}
+    for fn in legs.values():
+        fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in legs}
+    for _ in range(a.reps):
+        for k, fn in legs.items():
+            t[k].append(timed(fn))
+    res = {'device': torch.cuda.get_device_name(0), 'reps': a.reps, 'frame': list(GEO[:2]), 'volume': list(sc.tsdf_volume.shape[2:][::-1]),
+           'levels': {'strides': list(icp.strides), 'iters': list(icp.iters)},
+           'begin_is_timed_with_each_step': True,
+           'status': int(rows[-1, 5]), 'pairs_per_step': rows[:-1, 0].tolist(), 'pivot_ratio_min': float(rows[:-1, 2].min()),
+           'error_before_m_rad': list(e0), 'error_after_m_rad': list(e1),
+           'valid_sensor_normals': int((icp.normals[0] != 0).any(-1).sum()), 'valid_model_normals': int((icp.normals[1] != 0).any(-1).sum())}
+    res.update({k: stats(v) for k, v in t.items()})
+    res['refine_over_track10'] = res['refine']['median_ms'] / res['track10']['median_ms']
+    for k in legs:
+        print(f'{k:8s} {res[k]["median_ms"]:.3f} ({res[k]["min_ms"]:.3f}, {res[k]["max_ms"]:.3f}) ms', flush=True)
+    print(f'status {res["status"]}, pairs {rows[0, 0]:.0f} .. {rows[-2, 0]:.0f}, error {e0[0] * 1e3:.1f} mm {np.degrees(e0[1]):.2f} deg -> '
+          f'{e1[0] * 1e3:.2f} mm {np.degrees(e1[1]):.3f} deg; refine / ten tracking iterations = {res["refine_over_track10"]:.2f}')
+    assert common.get_camera_from_tensor(cam).shape == (3, 4)
+    if a.json:
+        with open(a.json, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
