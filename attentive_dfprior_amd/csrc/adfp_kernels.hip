@@ -1258,7 +1258,7 @@ __global__ __launch_bounds__(256) void k_gather_rows(GatherJobs j, unsigned* __r
 // t_cu_reserve: compute units the calling thread's CURRENT entry point leaves to its side lane (adfp_backward_args.side_stream): the
 // persistent kernels of the backward take a whole CU per workgroup (132-160 KB of LDS, the whole register file), so the sort's
 // short launches on the second stream would otherwise wait for a whole kernel to retire (measured: a 6-us histogram launch took
-// 130 us behind k_decode_bwd_roles).  Set and restored by backward_points (CuReserve); 0 everywhere else.
+// 130 us behind k_decode_bwd_roles).  Set by plan_sorted_scatter, restored by backward_points (CuReserve); 0 everywhere else.
 static thread_local int t_cu_reserve = 0;
 #ifndef ADFP_SIDE_CU_RESERVE
 #define ADFP_SIDE_CU_RESERVE 4
@@ -2684,10 +2684,9 @@ static void attention_jobs(OuterArgs& a) {
     add_job(a, ST::AGL, ST::AX, A::F_BO, 1, 0, 2, 2, 1);
 }
 
-// weight gradients of one network: outer_begin (zero the per-workgroup copies), launch_outer per staging chunk,
+// weight gradients of one network: outer_begin (zero the per-workgroup copies), launch_outer / launch_outer_h per staging chunk,
 // outer_end (sum the copies into the flat gradient)
-static int outer_begin(const BwdWorkspace& bw, int n_floats, hipStream_t st) {
-    (void)n_floats;
+static int outer_begin(const BwdWorkspace& bw, hipStream_t st) {
     return (int)zero_async(bw.partial, (size_t)OUTER_NSLOT * bw.part_stride * 4, st);
 }
 static int outer_end(const BwdWorkspace& bw, int n_floats, float* flat, hipStream_t st) {
@@ -2700,53 +2699,72 @@ static int outer_end_scaled(const BwdWorkspace& bw, int n_floats, float* flat, h
     ADFP_CHECK_LAUNCH();
     return 0;
 }
+// rows per workgroup of a weight-gradient launch: at most OUTER_NSLOT workgroups (each owns one private gradient copy), at least 64 rows each
+static int outer_rows_per_wg(int rows) {
+    const int per = (rows + OUTER_NSLOT - 1) / OUTER_NSLOT;
+    return ((per < 64 ? 64 : per) + OUTER_RT - 1) / OUTER_RT * OUTER_RT;
+}
+// The staging loops: fn(lo, hi) for every chunk of at most rows_cap of `total` rows, in order; the first error ends the loop.  Nothing
+// is called for total == 0.
+template <class F>
+static int for_chunks(int total, int rows_cap, F fn) {
+    for (int lo = 0; lo < total; lo += rows_cap) {
+        const int rc = fn(lo, lo + rows_cap < total ? lo + rows_cap : total);
+        if (rc) return rc;
+    }
+    return 0;
+}
 static int launch_outer(OuterArgs& oa, const BwdWorkspace& bw, const int* count_ptr, int lo, int hi, float* flat, hipStream_t st) {
-    const float* stage = bw.stage;
-    oa.stage = stage; oa.count_ptr = count_ptr; oa.chunk_lo = lo; oa.chunk_hi = hi; oa.flat = flat;
+    oa.stage = bw.stage; oa.count_ptr = count_ptr; oa.chunk_lo = lo; oa.chunk_hi = hi; oa.flat = flat;
     oa.partial = bw.partial; oa.part_stride = bw.part_stride;
     const int rows = hi - lo;
     if (oa.ncols > OUTER_MAXCOLS || (oa.ncols & 3) || oa.njobs > OUTER_NW * OUTER_JW) return ADFP_E_UNSUPPORTED;
-    // rows per workgroup: at most OUTER_NSLOT workgroups (each owns one private gradient copy), at least 64 rows each
-    int per = (rows + OUTER_NSLOT - 1) / OUTER_NSLOT;
-    per = ((per < 64 ? 64 : per) + OUTER_RT - 1) / OUTER_RT * OUTER_RT;
+    const int per = outer_rows_per_wg(rows);
     oa.rows_per_wave = per;
     hipLaunchKernelGGL(k_outer_lds, dim3((rows + per - 1) / per), dim3(512), 0, st, oa);
     ADFP_CHECK_LAUNCH();
     return 0;
 }
 
-template <int CDIM, int NOUT, int ROLE, bool PGRAD>
-static int run_decode_bwd_p(DecodeBwdArgs a, int total, const int* count_ptr, float* flat, const BwdWorkspace& bw, hipStream_t st) {
+// ---- the backward's kernel launchers: as in the forward, which instantiation runs is decided HERE and nowhere else; call sites pass
+// what they want as values.  What must not move on this path: a call's ordered list of (kernel, grid, block, stream) with the event
+// calls between them, the contents of every kernel argument, the precedence of the error returns, what zero points launch.
+// the exact backward of one decoder over ntiles tiles: with staging rows for the weight gradients (staged), with d/d position (pgrad)
+template <int CDIM, int NOUT, int ROLE>
+static int launch_decode_bwd(const DecodeBwdArgs& a, bool staged, bool pgrad, int ntiles, hipStream_t st) {
+    const dim3 grid(decode_grid(ntiles, 4, 1)), block(256);
+    if (staged && pgrad) hipLaunchKernelGGL((k_decode_bwd<CDIM, NOUT, ROLE, true, true, 256>), grid, block, 0, st, a);
+    else if (staged) hipLaunchKernelGGL((k_decode_bwd<CDIM, NOUT, ROLE, true, false, 256>), grid, block, 0, st, a);
+    else if (pgrad) hipLaunchKernelGGL((k_decode_bwd<CDIM, NOUT, ROLE, false, true, 256>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_decode_bwd<CDIM, NOUT, ROLE, false, false, 256>), grid, block, 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+// one decoder's exact backward over `total` points (HIGH: list entries); a.g_pts = d/d position wanted, flat = weight gradients wanted
+template <int CDIM, int NOUT, int ROLE>
+static int run_decode_bwd(DecodeBwdArgs a, int total, float* flat, const BwdWorkspace& bw, hipStream_t st) {
     if (total == 0) return 0;
     // the scatter cache keeps its slot number in the top 5 bits of the voxel index
     if (ROLE != ROLE_HIGH && a.g_grid && (long long)a.g0.X * a.g0.Y * a.g0.Z >= (1ll << 27)) return ADFP_E_UNSUPPORTED;
+    const bool pgrad = a.g_pts != nullptr;
     if (!flat) {
-        a.stage = nullptr; a.chunk_lo = 0; a.chunk_hi = total;
-        const int ntiles = (total + 31) / 32;
-        hipLaunchKernelGGL((k_decode_bwd<CDIM, NOUT, ROLE, false, PGRAD, 256>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, a);
-        ADFP_CHECK_LAUNCH();
-        return 0;
+        a.chunk_lo = 0; a.chunk_hi = total;
+        return launch_decode_bwd<CDIM, NOUT, ROLE>(a, false, pgrad, (total + 31) / 32, st);
     }
-    OuterArgs oa; decoder_jobs<CDIM, NOUT>(oa);
+    OuterArgs oa{}; decoder_jobs<CDIM, NOUT>(oa);
     a.stage = bw.stage;
     const int rows_cap = (int)((size_t)bw.stage_rows * AttStage::NCOLS / DecStage<CDIM>::NCOLS);
-    int rc = outer_begin(bw, DecLayout<CDIM, NOUT>::F_TOTAL, st);
+    int rc = outer_begin(bw, st);
     if (rc) return rc;
-    for (int lo = 0; lo < total; lo += rows_cap) {
-        const int hi = lo + rows_cap < total ? lo + rows_cap : total;
+    rc = for_chunks(total, rows_cap, [&](int lo, int hi) -> int {
         a.chunk_lo = lo; a.chunk_hi = hi;
-        const int ntiles = (hi - lo + 31) / 32;
-        hipLaunchKernelGGL((k_decode_bwd<CDIM, NOUT, ROLE, true, PGRAD, 256>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, a);
-        ADFP_CHECK_LAUNCH();
-        rc = launch_outer(oa, bw, count_ptr, lo, hi, flat, st);
-        if (rc) return rc;
-    }
+        const int rc_ = launch_decode_bwd<CDIM, NOUT, ROLE>(a, true, pgrad, (hi - lo + 31) / 32, st);
+        return rc_ ? rc_ : launch_outer(oa, bw, a.count_ptr, lo, hi, flat, st);
+    });
+    if (rc) return rc;
     return outer_end(bw, DecLayout<CDIM, NOUT>::F_TOTAL, flat, st);
 }
-// The f16-split backward of one decoder (adfp_backward_h.h): `t` = its T image, `masks` / `act` = what the training forward
-// left.  Weight gradients: the G part of the staging rows is chunked like the exact path's rows (so that a chunk is still in
-// the Infinity Cache when k_outer_h reads it back); the X part lies in `act` for all rows.
-#define ADFP_BWDH_NT 384
+#define ADFP_BWDH_NT 384         // threads of k_decode_bwd_h with the in-kernel scatter (launch_decode_bwd_h)
 // sort of the call's points for k_scatter_sorted (set up once per backward call by backward_points)
 // Sorts n (key, value) pairs by the low key_bits bits of the key, stable.  The two buffer pairs are used in turn; *key_fin / *val_fin
 // = the pair the last pass wrote (a / b).  table: ADFP_RS_DIGITS * (ceil(n / ADFP_RS_TILE) + 1) ints.
@@ -2806,12 +2824,12 @@ __global__ __launch_bounds__(256) void k_backward_head(BwdHeadArgs h) {
     zero_multi_block(h.z, (unsigned)(blk - h.nb_bin));
 }
 static int launch_backward_head(BackwardCall& call, const BinArgs* bins, int P, hipStream_t st) {
-    BwdHeadArgs h;
+    BwdHeadArgs h{};
     h.c = call.head_comp; h.z = call.head_zero;
     h.nb_comp = (call.head_comp.n_rays + 3) / 4;
     h.nb_bin = bins ? (P + 255) / 256 : 0;
-    if (bins) h.b = *bins; else memset(&h.b, 0, sizeof(h.b));
-    h.b.max_parts = nullptr;
+    if (bins) h.b = *bins;
+    h.b.max_parts = nullptr;                     // the per-ray maxima are not written yet: plan_sorted_scatter has them folded later
     hipLaunchKernelGGL(k_backward_head, dim3(h.nb_comp + h.nb_bin + call.head_zero_blocks), dim3(256), 0, st, h);
     ADFP_CHECK_LAUNCH();
     call.head_pending = false;
@@ -2858,127 +2876,161 @@ static int flush_scatter(BinPlan& bp, hipStream_t st) {
     return 0;
 }
 
+// What backward_points needs to know about one decoder: its grids, its exact and T images, what the training forward left, where
+// its gradients go -- and, for HIGH alone, the in-band list it runs over, the list's cotangents and the band flags.
+struct NetBwd {
+    const adfp_grid* grid; const adfp_grid* grid1; const float* w; const void* ht; const unsigned* masks; const float* act; unsigned* dbg_masks;
+    float* flat; float* g_grid;
+    const int* list; const int* count_ptr; const float* att_g; const unsigned char* flags;
+};
+
+// the f16-split backward of one decoder over ntiles tiles: with the G part of the staging rows for k_outer_h (staged); with the
+// in-kernel write-combining scatter (ADFP_BWDH_NT threads: its LDS structures) or without it (512 threads: d/d c rows, or no grid
+// gradient at all).  The position-gradient instantiations are launch_pgrad_single's.
 template <int CDIM, int NOUT, int ROLE>
-static int run_decode_bwd_h(const DecodeBwdArgs& o, const void* t, const unsigned* masks, const float* act, int* status, const int* skip, int total,
-                            const int* count_ptr, float* flat, const BwdWorkspace& bw, BinPlan& bp, const unsigned char* flags, int options, hipStream_t st) {
+static int launch_decode_bwd_h(const DecodeBwdHArgs& a, bool staged, bool in_kernel_scatter, int ntiles, hipStream_t st) {
+    const int nt = in_kernel_scatter ? ADFP_BWDH_NT : 512;
+    const dim3 grid(decode_grid(ntiles, nt / 64, 1)), block(nt);
+    if (staged && in_kernel_scatter) hipLaunchKernelGGL((k_decode_bwd_h<CDIM, NOUT, ROLE, true, true, ADFP_BWDH_NT>), grid, block, 0, st, a);
+    else if (staged) hipLaunchKernelGGL((k_decode_bwd_h<CDIM, NOUT, ROLE, true, false, 512>), grid, block, 0, st, a);
+    else if (in_kernel_scatter) hipLaunchKernelGGL((k_decode_bwd_h<CDIM, NOUT, ROLE, false, true, ADFP_BWDH_NT>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_decode_bwd_h<CDIM, NOUT, ROLE, false, false, 512>), grid, block, 0, st, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+// k_outer_h's arguments for a decoder (the X part of a row lies in the training forward's `act`, the G part in the staging rows) ...
+template <int CDIM, int NOUT>
+static OuterHArgs outer_h_decoder(const DecodeBwdHArgs& a, const float* act, float* flat, const BwdWorkspace& bw) {
+    using ST = DecStage<CDIM>;
+    OuterHArgs oh{};
+    decoder_jobs<CDIM, NOUT>(oh.o);
+    oh.o.stage = bw.stage; oh.o.flat = flat; oh.o.partial = bw.partial; oh.o.part_stride = bw.part_stride;
+    oh.act = act; oh.nxm4 = ST::NXM / 4; oh.ngm4 = ST::NGM / 4; oh.g_dst4 = ST::SGH(0) / 4; oh.x_gap_at4 = 8; oh.x_gap4 = 24; oh.x_skip4 = 8;
+    oh.P = a.P; oh.list = a.list; oh.masks = a.masks; oh.bm = (const float*)a.packed_t;   // P_BM = word 0 of the T image
+    oh.col_se = ST::SE; oh.col_sgp = ST::SGP(0); oh.status = a.status; oh.skip = a.skip;
+    return oh;
+}
+// ... and for the attention network (whole half rows, no points, no virtual columns); overwrite: see OuterHArgs
+static OuterHArgs outer_h_attention(const AttBwdHArgs& t, const float* act, float* flat, bool overwrite, const BwdWorkspace& bw) {
+    OuterHArgs oh{};
+    attention_jobs(oh.o);
+    oh.o.stage = bw.stage; oh.o.flat = flat; oh.o.partial = bw.partial; oh.o.part_stride = bw.part_stride;
+    oh.act = act; oh.nxm4 = 416 / 4; oh.ngm4 = 416 / 4; oh.g_dst4 = 416 / 4; oh.x_gap_at4 = 1 << 20;
+    oh.status = t.status; oh.skip = t.skip; oh.overwrite = overwrite ? 1 : 0;
+    return oh;
+}
+// k_outer_h over rows [lo, hi) of the staging chunk on at most `slots` workgroups.  block = a workgroup's whole share: computed here
+// when the row count is known, by the kernel for a list (count on the device: br = 0, the even split of even_block)
+static int launch_outer_h(OuterHArgs& oh, const int* count_ptr, int lo, int hi, int slots, hipStream_t st) {
+    const int rows = hi - lo;
+    const int br = count_ptr ? 0 : outer_rows_per_wg(rows);
+    const int nblk = br ? (rows + br - 1) / br : (rows + OUTER_RT - 1) / OUTER_RT;
+    oh.o.count_ptr = count_ptr; oh.o.chunk_lo = lo; oh.o.chunk_hi = hi; oh.o.rows_per_wave = br;
+    hipLaunchKernelGGL(k_outer_h, dim3(nblk < slots ? nblk : slots), dim3(512), 0, st, oh);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+// the role-split kernel's workgroups, dealt to the three roles in proportion to what a tile costs each (the third role takes the rest)
+static void deal_roles(int nslot, int* nP, int* nH) {
+    *nP = (nslot * ROLE_SHARE_P + 128) / 256; *nH = (nslot * ROLE_SHARE_H + 128) / 256;
+    if (*nP < 1) *nP = 1;
+    if (*nH < 1) *nH = 1;
+    while (*nP + *nH > nslot - 1) { if (*nP > *nH) --*nP; else --*nH; }
+}
+// Weight gradients inside the chain kernel (adfp_backward_fused.h): no staging rows, no k_outer_h; the one-wave or the role-split
+// kernel, each with its reduction into `flat`.  Every workgroup OVERWRITES its slot of bw.partial (no 20 MB zero fill per network),
+// and the reduction reads the slots in use.
+template <int NOUT, int ROLE>
+static int decode_bwd_h_fused(const DecodeBwdHArgs& a, const float* act, int total, float* flat, int options, const BwdWorkspace& bw, hipStream_t st) {
+    constexpr int F = DecLayout<32, NOUT>::F_TOTAL;
+    DecodeBwdFArgs f{};
+    f.P = a.P; f.nb = a.nb; f.packed_t = a.packed_t; f.g_raw = a.g_raw; f.masks = a.masks; f.act = act;
+    f.gc_out = a.gc_out; f.total = total; f.status = a.status; f.gmax = a.gmax; f.skip = a.skip;
+    f.partial = bw.partial; f.part_stride = bw.part_stride;
+    const int ntiles = (total + 31) / 32;
+    // (role P stages a tile's positions through LDS and allows a 32-point tile to span five rays: fewer than 8 samples per
+    // ray keep the one-wave kernel)
+    if ((options & ADFP_BWD_FUSED_ONE_WAVE) || (a.P.mode == ADFP_PTS_RAYS && a.P.S < 8)) {
+        const int nwg = (ntiles + 3) / 4, nslot = nwg < OUTER_NSLOT ? nwg : OUTER_NSLOT;
+        hipLaunchKernelGGL((k_decode_bwd_fused<NOUT, ROLE>), dim3(nslot), dim3(256), 0, st, f);
+        ADFP_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_reduce_partials_scaled, dim3((F + 31) / 32), dim3(256), 0, st, bw.partial, nslot, bw.part_stride, F, flat, bw.gmax);
+    } else {
+        // role-split kernel (adfp_backward_roles.h): one 512-thread workgroup per CU (num_cu(): fewer beside a side lane); every
+        // role walks all tiles, so a small call still wants all three
+        int cus = num_cu(); if (cus > OUTER_NSLOT) cus = OUTER_NSLOT;
+        const int g = 3 * ((ntiles + 7) / 8), nslot = g < 3 ? 3 : (g > cus ? cus : g);
+        int nP, nH; deal_roles(nslot, &nP, &nH);
+        hipLaunchKernelGGL((k_decode_bwd_roles<NOUT, ROLE>), dim3(nslot), dim3(512), 0, st, f, nP, nH);
+        ADFP_CHECK_LAUNCH();
+        // a slot holds only the elements of its workgroup's role: each element is added up over its owners
+        hipLaunchKernelGGL((k_reduce_partials_roles<32, NOUT>), dim3((F + 31) / 32), dim3(256), 0, st, bw.partial, nP, nH, nslot, bw.part_stride, flat, bw.gmax);
+    }
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+// Position gradient only (backward_points' use_h: frozen network and grid): deferred, the call's decoders run side by side in ONE
+// launch (flush_pgrad at the end of backward_points)
+static int defer_pgrad(BinPlan& bp, DecodeBwdHArgs a, int role, int total) {
+    DecodeBwdH3Args& m = bp.pgrad;
+    if (m.n >= ADFP_PGRAD_MAX_JOBS) return ADFP_E_UNSUPPORTED;
+    a.chunk_lo = 0; a.chunk_hi = total;
+    if (m.n == 0) m.first[0] = 0;
+    m.j[m.n] = a; m.role[m.n] = role;
+    m.first[m.n + 1] = m.first[m.n] + decode_grid((total + 31) / 32, 8, 1);
+    ++m.n;
+    return 0;
+}
+// Weight gradients through staging rows: the G part of the rows is chunked like the exact path's rows (so that a chunk is still in
+// the Infinity Cache when k_outer_h reads it back); the X part lies in `act` for all rows.
+template <int CDIM, int NOUT, int ROLE>
+static int decode_bwd_h_staged(DecodeBwdHArgs a, const float* act, bool in_kernel_scatter, int total, float* flat, const BwdWorkspace& bw, hipStream_t st) {
+    OuterHArgs oh = outer_h_decoder<CDIM, NOUT>(a, act, flat, bw);
+    a.stage = bw.stage;
+    const int rows_cap = (int)((size_t)bw.stage_rows * AttStage::NCOLS / DecStage<CDIM>::NGM);
+    int rc = outer_begin(bw, st);
+    if (rc) return rc;
+    rc = for_chunks(total, rows_cap, [&](int lo, int hi) -> int {
+        a.chunk_lo = lo; a.chunk_hi = hi;
+        const int rc_ = launch_decode_bwd_h<CDIM, NOUT, ROLE>(a, true, in_kernel_scatter, (hi - lo + 31) / 32, st);
+        return rc_ ? rc_ : launch_outer_h(oh, a.count_ptr, lo, hi, OUTER_NSLOT, st);
+    });
+    if (rc) return rc;
+    return outer_end_scaled(bw, DecLayout<CDIM, NOUT>::F_TOTAL, flat, st);
+}
+// The f16-split backward of one decoder (adfp_backward_h.h) over `total` points (HIGH: list entries): n.ht = its T image, n.masks /
+// n.act = what the training forward left.  Which of the three paths above it takes is decided here.
+template <int CDIM, int NOUT, int ROLE>
+static int run_decode_bwd_h(const DecodeBwdArgs& o, const NetBwd& n, int* status, const int* skip, int total, const BwdWorkspace& bw, BinPlan& bp,
+                            int options, hipStream_t st) {
     if (total == 0) return 0;
     // d/d c rows + k_scatter_sorted instead of the in-kernel scatter: for a grid on one of the two lattices the points were
     // sorted by (k_bin_keys); a third lattice keeps the in-kernel scatter
     const bool binned = bp.ok && o.g_grid && ((o.g0.X == bp.args.RX && o.g0.Y == bp.args.RY && o.g0.Z == bp.args.RZ) ||
                                               (o.g0.X == bp.args.CX && o.g0.Y == bp.args.CY && o.g0.Z == bp.args.CZ));
     if (!binned && o.g_grid && (long long)o.g0.X * o.g0.Y * o.g0.Z >= (1ll << 27)) return ADFP_E_UNSUPPORTED;     // scatter cache slot bits
-    DecodeBwdHArgs a;
-    a.P = o.P; a.nb = o.nb; a.g0 = o.g0; a.packed_t = (const unsigned*)t; a.list = o.list; a.count_ptr = o.count_ptr;
-    a.g_raw = o.g_raw; a.att_g = o.att_g; a.masks = masks; a.g_grid = o.g_grid; a.stage = nullptr; a.status = status; a.gmax = bw.gmax; a.skip = skip;
     float* const gc_rows = binned ? bw.gc + (size_t)bp.pend.n_jobs * bw.gc_stride : nullptr;       // this grid's d/d c rows
-    a.gc_out = gc_rows;
-    a.g_pts = o.g_pts;
-    constexpr int NW = ADFP_BWDH_NT / 64;
-    if (o.g_pts) {                                      // position gradient only (backward_points' use_h): frozen network and grid
-        if (flat || o.g_grid) return ADFP_E_ARG;
-        a.chunk_lo = 0; a.chunk_hi = total;
-        // deferred: the call's decoders run side by side in ONE launch (flush_pgrad at the end of backward_points)
-        DecodeBwdH3Args& m = bp.pgrad;
-        if (m.n >= ADFP_PGRAD_MAX_JOBS) return ADFP_E_UNSUPPORTED;
-        if (m.n == 0) m.first[0] = 0;
-        m.j[m.n] = a; m.role[m.n] = ROLE;
-        m.first[m.n + 1] = m.first[m.n] + decode_grid((total + 31) / 32, 8, 1);
-        ++m.n;
-        return 0;
-    }
+    DecodeBwdHArgs a{};
+    a.P = o.P; a.nb = o.nb; a.g0 = o.g0; a.packed_t = (const unsigned*)n.ht; a.list = o.list; a.count_ptr = o.count_ptr;
+    a.g_raw = o.g_raw; a.att_g = o.att_g; a.masks = n.masks; a.g_grid = o.g_grid; a.status = status; a.gmax = bw.gmax; a.skip = skip;
+    a.gc_out = gc_rows; a.g_pts = o.g_pts;
+    const bool in_kernel_scatter = o.g_grid && !binned;
+    auto then_bins = [&](int rc) { return rc ? rc : binned ? scatter_bins(bp, o, gc_rows, n.flags) : 0; };      // the grid joins the call's k_scatter_sorted
+    if (o.g_pts) return n.flat || o.g_grid ? ADFP_E_ARG : defer_pgrad(bp, a, ROLE, total);
     if constexpr (CDIM == 32) {
-        // weight gradients inside the chain kernel (adfp_backward_fused.h): no staging rows, no k_outer_h.  Needs the grid
-        // gradient on the sorted scatter (or not wanted): the in-kernel scatter's LDS structures do not fit beside the reduction copy.
-        if (flat && !count_ptr && (binned || !o.g_grid) && !(options & ADFP_BWD_STAGED_WGRAD)) {
-            DecodeBwdFArgs f;
-            f.P = o.P; f.nb = o.nb; f.packed_t = (const unsigned*)t; f.g_raw = o.g_raw; f.masks = masks; f.act = act;
-            f.gc_out = gc_rows; f.total = total; f.status = status; f.gmax = bw.gmax; f.skip = skip;
-            f.partial = bw.partial; f.part_stride = bw.part_stride;
-            // every workgroup OVERWRITES its slot of bw.partial (no 20 MB zero fill per network), and the reduction reads the slots in use
-            const int ntiles = (total + 31) / 32;
-            int nslot;
-            // (role P stages a tile's positions through LDS and allows a 32-point tile to span five rays: fewer than 8 samples per
-            // ray keep the one-wave kernel)
-            if ((options & ADFP_BWD_FUSED_ONE_WAVE) || (o.P.mode == ADFP_PTS_RAYS && o.P.S < 8)) {
-                const int nwg = (ntiles + 3) / 4;
-                nslot = nwg < OUTER_NSLOT ? nwg : OUTER_NSLOT;
-                hipLaunchKernelGGL((k_decode_bwd_fused<NOUT, ROLE>), dim3(nslot), dim3(256), 0, st, f);
-                ADFP_CHECK_LAUNCH();
-                hipLaunchKernelGGL(k_reduce_partials_scaled, dim3((DecLayout<CDIM, NOUT>::F_TOTAL + 31) / 32), dim3(256), 0, st, bw.partial, nslot, bw.part_stride,
-                                   DecLayout<CDIM, NOUT>::F_TOTAL, flat, bw.gmax);
-            } else {
-                // role-split kernel (adfp_backward_roles.h): one 512-thread workgroup per CU, dealt to the three roles in proportion to
-                // what a tile costs each; every role walks all tiles, so a small call still wants all three
-                int cus = num_cu(); if (cus > OUTER_NSLOT) cus = OUTER_NSLOT;
-                int g = 3 * ((ntiles + 7) / 8);
-                nslot = g < 3 ? 3 : (g > cus ? cus : g);
-                int nP = (nslot * ROLE_SHARE_P + 128) / 256, nH = (nslot * ROLE_SHARE_H + 128) / 256;
-                if (nP < 1) nP = 1;
-                if (nH < 1) nH = 1;
-                while (nP + nH > nslot - 1) { if (nP > nH) --nP; else --nH; }
-                hipLaunchKernelGGL((k_decode_bwd_roles<NOUT, ROLE>), dim3(nslot), dim3(512), 0, st, f, nP, nH);
-                ADFP_CHECK_LAUNCH();
-                // a slot holds only the elements of its workgroup's role: each element is added up over its owners
-                hipLaunchKernelGGL((k_reduce_partials_roles<CDIM, NOUT>), dim3((DecLayout<CDIM, NOUT>::F_TOTAL + 31) / 32), dim3(256), 0, st, bw.partial, nP, nH, nslot,
-                                   bw.part_stride, flat, bw.gmax);
-            }
-            ADFP_CHECK_LAUNCH();
-            return binned ? scatter_bins(bp, o, gc_rows, flags) : 0;
-        }
+        // the fused path needs the grid gradient on the sorted scatter (or not wanted): the in-kernel scatter's LDS structures do not
+        // fit beside the reduction copy
+        if (n.flat && !o.count_ptr && !in_kernel_scatter && !(options & ADFP_BWD_STAGED_WGRAD))
+            return then_bins(decode_bwd_h_fused<NOUT, ROLE>(a, n.act, total, n.flat, options, bw, st));
     }
-    if (!flat) {
-        a.chunk_lo = 0; a.chunk_hi = total;
-        if (o.g_grid && !binned) hipLaunchKernelGGL((k_decode_bwd_h<CDIM, NOUT, ROLE, false, true, ADFP_BWDH_NT>), dim3(decode_grid((total + 31) / 32, NW, 1)), dim3(ADFP_BWDH_NT), 0, st, a);
-        else hipLaunchKernelGGL((k_decode_bwd_h<CDIM, NOUT, ROLE, false, false, 512>), dim3(decode_grid((total + 31) / 32, 8, 1)), dim3(512), 0, st, a);
-        ADFP_CHECK_LAUNCH();
-        return binned ? scatter_bins(bp, o, gc_rows, flags) : 0;
-    }
-    using ST = DecStage<CDIM>;
-    OuterHArgs oa; decoder_jobs<CDIM, NOUT>(oa.o);
-    oa.act = act; oa.nxm4 = ST::NXM / 4; oa.ngm4 = ST::NGM / 4; oa.g_dst4 = ST::SGH(0) / 4; oa.x_gap_at4 = 8; oa.x_gap4 = 24; oa.x_skip4 = 8; oa.P = o.P; oa.list = o.list; oa.masks = masks; oa.bm = (const float*)t;   // P_BM = word 0 of the T image
-    oa.col_se = ST::SE; oa.col_sgp = ST::SGP(0); oa.status = status; oa.skip = skip; oa.overwrite = 0;
-    a.stage = bw.stage;
-    const int rows_cap = (int)((size_t)bw.stage_rows * AttStage::NCOLS / ST::NGM);
-    int rc = outer_begin(bw, DecLayout<CDIM, NOUT>::F_TOTAL, st);
-    if (rc) return rc;
-    for (int lo = 0; lo < total; lo += rows_cap) {
-        const int hi = lo + rows_cap < total ? lo + rows_cap : total;
-        a.chunk_lo = lo; a.chunk_hi = hi;
-        if (o.g_grid && !binned) hipLaunchKernelGGL((k_decode_bwd_h<CDIM, NOUT, ROLE, true, true, ADFP_BWDH_NT>), dim3(decode_grid((hi - lo + 31) / 32, NW, 1)), dim3(ADFP_BWDH_NT), 0, st, a);
-        else hipLaunchKernelGGL((k_decode_bwd_h<CDIM, NOUT, ROLE, true, false, 512>), dim3(decode_grid((hi - lo + 31) / 32, 8, 1)), dim3(512), 0, st, a);
-        ADFP_CHECK_LAUNCH();
-        oa.o.stage = bw.stage; oa.o.count_ptr = count_ptr; oa.o.chunk_lo = lo; oa.o.chunk_hi = hi; oa.o.flat = flat;
-        oa.o.partial = bw.partial; oa.o.part_stride = bw.part_stride;
-        {   // block = a workgroup's whole share: computed here when the row count is known, by the kernel for a list (count on the device: br = 0)
-            const int rows = hi - lo;
-            int br = 0;
-            if (!count_ptr) { br = (rows + OUTER_NSLOT - 1) / OUTER_NSLOT; br = ((br < 64 ? 64 : br) + OUTER_RT - 1) / OUTER_RT * OUTER_RT; }
-            const int nblk = br ? (rows + br - 1) / br : (rows + OUTER_RT - 1) / OUTER_RT;
-            oa.o.rows_per_wave = br;
-            hipLaunchKernelGGL(k_outer_h, dim3(nblk < OUTER_NSLOT ? nblk : OUTER_NSLOT), dim3(512), 0, st, oa);
-        }
-        ADFP_CHECK_LAUNCH();
-    }
-    rc = outer_end_scaled(bw, DecLayout<CDIM, NOUT>::F_TOTAL, flat, st);
-    if (rc) return rc;
-    return binned ? scatter_bins(bp, o, gc_rows, flags) : 0;
-}
-
-template <int CDIM, int NOUT, int ROLE>
-static int run_decode_bwd(DecodeBwdArgs a, int total, const int* count_ptr, float* flat, const BwdWorkspace& bw, hipStream_t st) {
-    return a.g_pts ? run_decode_bwd_p<CDIM, NOUT, ROLE, true>(a, total, count_ptr, flat, bw, st)
-                   : run_decode_bwd_p<CDIM, NOUT, ROLE, false>(a, total, count_ptr, flat, bw, st);
+    if (n.flat) return then_bins(decode_bwd_h_staged<CDIM, NOUT, ROLE>(a, n.act, in_kernel_scatter, total, n.flat, bw, st));
+    a.chunk_lo = 0; a.chunk_hi = total;                 // no weight gradients: one launch, no staging rows
+    return then_bins(launch_decode_bwd_h<CDIM, NOUT, ROLE>(a, false, in_kernel_scatter, (total + 31) / 32, st));
 }
 
 // gradient outputs shared by the two backward entries
 struct GradOut { float* grid_low; float* grid_high; float* grid_color; float* flat_low; float* flat_high; float* flat_color; float* flat_att; };
 
-static int zero_grad_jobs(const adfp_scene* sc, const GradOut& g, int options, ZeroBatch& zb, hipStream_t st);
-static int zero_grad_outputs(const adfp_scene* sc, const GradOut& g, int options, hipStream_t st) {
-    ZeroBatch zb;
-    int rc = zero_grad_jobs(sc, g, options, zb, st); if (rc) return rc;
-    return (int)zb.flush(st);
-}
 static int zero_grad_jobs(const adfp_scene* sc, const GradOut& g, int options, ZeroBatch& zb, hipStream_t st) {
     const bool zg = !(options & ADFP_BWD_GRIDS_PREZEROED);
     struct { float* p; size_t n; } zs[7] = {
@@ -2991,14 +3043,14 @@ static int zero_grad_jobs(const adfp_scene* sc, const GradOut& g, int options, Z
         if (zs[k].p) { hipError_t e = zb.add(zs[k].p, zs[k].n * 4, st); if (e != hipSuccess) return (int)e; }
     return 0;
 }
+static int zero_grad_outputs(const adfp_scene* sc, const GradOut& g, int options, hipStream_t st) {
+    ZeroBatch zb;
+    int rc = zero_grad_jobs(sc, g, options, zb, st); if (rc) return rc;
+    return (int)zb.flush(st);
+}
 
-// What backward_points needs to know about one decoder: its grids, its exact and T images, what the training forward left, where
-// its gradients go -- and, for HIGH alone, the in-band list it runs over, the list's cotangents and the band flags.
-struct NetBwd {
-    const adfp_grid* grid; const adfp_grid* grid1; const float* w; const void* ht; const unsigned* masks; const float* act; unsigned* dbg_masks;
-    float* flat; float* g_grid;
-    const int* list; const int* count_ptr; const float* att_g; const unsigned char* flags;
-};
+// adfp_train_state.counter + 8: the device flag "the forward call was repaired by the f32 fallback" (zero gradients, adfp.h)
+static const int* skip_flag(const adfp_train_state& s) { return s.counter ? s.counter + 8 : nullptr; }
 static NetBwd net_bwd(const adfp_scene* sc, const adfp_train_state& s, const GradOut& go, const BwdWorkspace& bw, int role) {
     if (role == ROLE_LOW) return {&sc->low, &sc->low, sc->w_low, sc->ht_low, s.masks_low, s.act_low, s.dbg_masks_low, go.flat_low, go.grid_low, nullptr, nullptr, nullptr, nullptr};
     if (role == ROLE_HIGH) return {&sc->high, &sc->low, sc->w_high, sc->ht_high, s.masks_high, s.act_high, s.dbg_masks_high, go.flat_high, go.grid_high, s.list, s.counter, bw.att_g, s.flags};
@@ -3010,17 +3062,152 @@ static int run_decoder_bwd(DecodeBwdArgs a, const NetBwd& n, bool h, const adfp_
                            BinPlan& bp, int options, hipStream_t st) {
     a.g0 = make_grid(*n.grid); a.g1 = make_grid(*n.grid1); a.packed = n.w; a.g_grid = n.g_grid; a.dbg_masks = n.dbg_masks;
     a.list = n.list; a.count_ptr = n.count_ptr; a.att_g = n.att_g;
-    if (h) return run_decode_bwd_h<CDIM, NOUT, ROLE>(a, n.ht, n.masks, n.act, sc->status, state.counter ? state.counter + 8 : nullptr, P, n.count_ptr, n.flat, bw, bp, n.flags, options, st);
-    return n.w ? run_decode_bwd<CDIM, NOUT, ROLE>(a, P, n.count_ptr, n.flat, bw, st) : ADFP_E_ARG;
+    if (h) return run_decode_bwd_h<CDIM, NOUT, ROLE>(a, n, sc->status, skip_flag(state), P, bw, bp, options, st);
+    return n.w ? run_decode_bwd<CDIM, NOUT, ROLE>(a, P, n.flat, bw, st) : ADFP_E_ARG;
+}
+
+// the attention network's f16-split backward over ntiles tiles of the in-band list: leaving the G pieces for k_outer_h (wgrad), or
+// with d/d position (pgrad: only without weight gradients, backward_points' use_h)
+static int launch_attention_bwd_h(const AttBwdHArgs& t, bool wgrad, bool pgrad, int ntiles, hipStream_t st) {
+    const dim3 grid(decode_grid(ntiles, 8, 1)), block(512);
+    if (wgrad) hipLaunchKernelGGL(k_attention_bwd_h<true>, grid, block, 0, st, t);
+    else if (pgrad) hipLaunchKernelGGL((k_attention_bwd_h<false, true>), grid, block, 0, st, t);
+    else hipLaunchKernelGGL(k_attention_bwd_h<false>, grid, block, 0, st, t);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+// ... and its exact backward
+static int launch_attention_bwd(const AttBwdArgs& t, bool wgrad, bool pgrad, int ntiles, hipStream_t st) {
+    const dim3 grid(decode_grid(ntiles, 4, 1)), block(256);
+    if (wgrad && pgrad) hipLaunchKernelGGL((k_attention_bwd<true, true>), grid, block, 0, st, t);
+    else if (wgrad) hipLaunchKernelGGL((k_attention_bwd<true, false>), grid, block, 0, st, t);
+    else if (pgrad) hipLaunchKernelGGL((k_attention_bwd<false, true>), grid, block, 0, st, t);
+    else hipLaunchKernelGGL((k_attention_bwd<false, false>), grid, block, 0, st, t);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+// The attention backward on f16 MFMA (k_attention_bwd_h) over the P points' in-band list: masks, softmax weights and layer inputs from
+// the forward; flat = its weight gradients (or NULL), g_pts = d/d position (or NULL)
+static int attention_bwd_h(const adfp_scene* sc, const adfp_train_state& state, const PtsDev& Pd, int P, const float* g_weight, float* g_pts,
+                           float* flat, const BwdWorkspace& bw, hipStream_t st) {
+    AttBwdHArgs t{};
+    t.packed_t = (const unsigned*)sc->ht_att; t.list = state.list; t.count_ptr = state.counter; t.att_occ = state.att_occ; t.att_u = state.att_u;
+    t.masks = state.masks_att; t.g_weight = g_weight; t.g_raw = bw.g_raw; t.att_g = bw.att_g; t.stage = bw.stage;
+    t.status = sc->status; t.gmax = bw.gmax; t.skip = skip_flag(state);
+    t.P = Pd; t.nt = make_norm(sc->tsdf_bnds); t.t = make_tsdf(sc->tsdf); t.g_pts = g_pts;
+    const int rows_cap = bw.stage_rows * 2;               // the G piece is half a row
+    // ONE chunk (the usual case: STG_ROWS_MAX): the weight-gradient workgroups OVERWRITE their slots and the reduction reads only
+    // the slots in use -- no zero fill of the 256 x 134 KB partial sums (9.5 us + a launch per iteration)
+    const bool one_chunk = P <= rows_cap;
+    // one private gradient copy per workgroup; with one chunk the reduction reads the slots in use, so the launch may leave
+    // compute units to the side lane (num_cu(), after plan_sorted_scatter); several chunks accumulate into all OUTER_NSLOT zero-filled slots
+    const int slots = one_chunk && num_cu() < OUTER_NSLOT ? num_cu() : OUTER_NSLOT;
+    OuterHArgs oh = outer_h_attention(t, state.act_att, flat, one_chunk, bw);
+    int rc;
+    if (flat && !one_chunk) { rc = outer_begin(bw, st); if (rc) return rc; }
+    rc = for_chunks(P, rows_cap, [&](int lo, int hi) -> int {
+        t.chunk_lo = lo; t.chunk_hi = hi;
+        const int rc_ = launch_attention_bwd_h(t, flat != nullptr, g_pts != nullptr, (hi - lo + 31) / 32, st);
+        return rc_ || !flat ? rc_ : launch_outer_h(oh, t.count_ptr, lo, hi, slots, st);       // list-based: the count is on the device
+    });
+    if (rc || !flat) return rc;
+    if (!one_chunk) return outer_end_scaled(bw, AttLayout::F_TOTAL, flat, st);
+    const int nblk = (P + OUTER_RT - 1) / OUTER_RT;
+    hipLaunchKernelGGL(k_reduce_partials_scaled, dim3((AttLayout::F_TOTAL + 31) / 32), dim3(256), 0, st, bw.partial, nblk < slots ? nblk : slots,
+                       bw.part_stride, AttLayout::F_TOTAL, flat, bw.gmax, state.counter, P, 0);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+// the exact attention backward (k_attention_bwd + k_outer_lds), chunked by the staging rows
+static int attention_bwd(const adfp_scene* sc, const adfp_train_state& state, const PtsDev& Pd, int P, const float* g_weight, float* g_pts,
+                         float* flat, const BwdWorkspace& bw, hipStream_t st) {
+    if (!sc->w_att) return ADFP_E_ARG;
+    AttBwdArgs t{};
+    t.packed = sc->w_att; t.list = state.list; t.count_ptr = state.counter; t.att_occ = state.att_occ;
+    t.att_u = state.att_u; t.g_weight = g_weight; t.g_raw = bw.g_raw; t.att_g = bw.att_g; t.stage = bw.stage;
+    t.P = Pd; t.nt = make_norm(sc->tsdf_bnds); t.t = make_tsdf(sc->tsdf); t.g_pts = g_pts;
+    t.skip = skip_flag(state); t.dbg_masks = state.dbg_masks_att;
+    OuterArgs oa{}; attention_jobs(oa);
+    int rc;
+    if (flat) { rc = outer_begin(bw, st); if (rc) return rc; }
+    rc = for_chunks(P, bw.stage_rows, [&](int lo, int hi) -> int {
+        t.chunk_lo = lo; t.chunk_hi = hi;
+        const int rc_ = launch_attention_bwd(t, flat != nullptr, g_pts != nullptr, (hi - lo + 31) / 32, st);
+        return rc_ || !flat ? rc_ : launch_outer(oa, bw, t.count_ptr, lo, hi, flat, st);
+    });
+    if (rc || !flat) return rc;
+    return outer_end(bw, AttLayout::F_TOTAL, flat, st);
+}
+
+// The grid gradients of the decoders that take the f16-split backward are scattered in spatial order (k_scatter_sorted): one
+// radix sort of the points by (coarsest such grid's cell, finest grid's cell inside it), shared by all of them.  cand: those grids
+// (NULL: that decoder has none).  With a plan (bp.ok) this sends off the call's head together with the sort keys (or k_bin_keys alone),
+// has the gradient scale folded, and runs the sort -- on the caller's side lane when there is one.  It then also sets t_cu_reserve:
+// every num_cu() AFTER this function (the attention's slot count, the role-split kernel's workgroups) leaves the lane room, so the
+// plan comes first in backward_points.  Without a plan nothing is launched here.
+static int plan_sorted_scatter(const adfp_grid* const cand[3], const PtsDev& Pd, int P, const NormDev& nb, int options, const BwdWorkspace& bw,
+                               BackwardCall& call, BinPlan& bp, hipStream_t st) {
+    const adfp_grid* fine = nullptr; const adfp_grid* coarse = nullptr;
+    auto vox = [](const adfp_grid& g) { return (long long)g.X * g.Y * g.Z; };
+    for (int k = 0; k < 3; ++k) {
+        if (!cand[k]) continue;
+        if (!fine || vox(*cand[k]) > vox(*fine)) fine = cand[k];
+        if (!coarse || vox(*cand[k]) < vox(*coarse)) coarse = cand[k];
+    }
+    // ADFP_BWD_SCATTER_IN_KERNEL keeps every grid on the in-kernel write-combining scatter (what the tests compare the sorted
+    // scatter against)
+    if (!fine || (options & ADFP_BWD_SCATTER_IN_KERNEL) || coarse->X < 2 || coarse->Y < 2 || coarse->Z < 2 || P <= 0) return 0;
+    int bits = 0;
+    while ((1 << bits) < coarse->X || (1 << bits) < coarse->Y || (1 << bits) < coarse->Z) ++bits;
+    if (bits > ADFP_BIN_MAXBITS) return 0;
+    BinArgs& b = bp.args;
+    b.P = Pd; b.nb = nb; b.CX = coarse->X; b.CY = coarse->Y; b.CZ = coarse->Z; b.RX = fine->X; b.RY = fine->Y; b.RZ = fine->Z;
+    b.key = bw.bin_key; b.val = bw.bin_val;
+    const float* fold_parts = nullptr;            // the per-ray maxima still to be folded: by the sort's first launch when the
+    int fold_n = 0;                               // head carries k_composite_bwd (they are not written yet), else by k_bin_keys
+    int rc;
+    if (call.head_pending) {
+        rc = launch_backward_head(call, &b, P, st); if (rc) return rc;
+        if (call.gmax_pending > 0) { fold_parts = bw.gmax_parts; fold_n = call.gmax_pending; }
+    } else {
+        b.max_parts = call.gmax_pending > 0 ? bw.gmax_parts : nullptr; b.max_n = call.gmax_pending; b.max_out = bw.gmax;
+        hipLaunchKernelGGL(k_bin_keys, dim3((P + 255) / 256 + (b.max_parts ? 1 : 0)), dim3(256), 0, st, b);
+        ADFP_CHECK_LAUNCH();
+    }
+    call.gmax_pending = 0;
+    // stable LSD radix sort (adfp_sort.h), ping-pong between the two buffer pairs -- on the caller's side lane when there is
+    // one: nine short launches nobody but k_scatter_sorted waits for, beside the backward kernels instead of in front of them
+    hipStream_t sort_st = st;
+    if (call.side) {
+        // The gradient scale is folded HERE, on the main stream (one small launch): riding on the sort's first launch it would
+        // make the first backward kernel wait for the side lane -- two cross-stream hops of ~15 us each (measured: 36 us
+        // between k_backward_head's end and k_attention_bwd_h's start).
+        if (fold_parts) {
+            hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, st, fold_parts, fold_n, bw.gmax);
+            ADFP_CHECK_LAUNCH();
+            fold_parts = nullptr; fold_n = 0;
+        }
+        hipError_t e = hipEventRecord(call.side_ev[0], st);                       // the keys exist
+        if (e == hipSuccess) e = hipStreamWaitEvent(call.side, call.side_ev[0], 0);
+        if (e != hipSuccess) return (int)e;
+        sort_st = call.side;
+        call.side_join_pending = true;
+        t_cu_reserve = ADFP_SIDE_CU_RESERVE;          // the whole-CU kernels of the call leave the lane room (backward_points restores it)
+    }
+    rc = radix_sort_pairs(bw.bin_key, bw.bin_val, bw.bin_key_sorted, bw.bin_perm, P, bin_key_bits(coarse->X, coarse->Y, coarse->Z), bw.sort_table, nullptr,
+                          &bp.perm, sort_st, fold_parts, fold_n, bw.gmax);               // perm: the pair the last pass wrote
+    if (rc) return rc;
+    bp.ok = true;
+    return 0;
 }
 
 // DF.forward backward over P points: bw.g_raw holds the cotangent of raw [P,4] (the attention pass reads .w and rewrites it
-// with d/d(high+low)); g_pts (bw.g_pts, zeroed here) receives d/d position when pgrad.
+// with d/d(high+low)); g_pts (bw.g_pts, zeroed here) receives d/d position when pgrad.  The sequence and nothing else: the scatter
+// plan, the call's held-back head and gradient-scale fold, the attention network, the decoders, the deferred launches.
 static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, int P, const adfp_train_state& state, const float* g_weight,
                            const GradOut& go, bool pgrad, int options, const BwdWorkspace& bw, BackwardCall& call, hipStream_t st) {
     int rc;
-    hipError_t e;
-    // whatever path leaves this function: the main stream has waited for the side lane (a capture must see it joined)
+    // whatever path leaves this function: the main stream has waited for the side lane (a capture must see it joined) ...
     struct SideJoin { BackwardCall& call; hipStream_t st;
                       hipError_t join() {
                           if (!call.side_join_pending) return hipSuccess;
@@ -3029,87 +3216,27 @@ static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, in
                           return e_ == hipSuccess ? hipStreamWaitEvent(st, call.side_ev[1], 0) : e_;
                       }
                       ~SideJoin() { (void)join(); } } side_join{call, st};
-    struct CuReserve { int saved; CuReserve() : saved(t_cu_reserve) {} ~CuReserve() { t_cu_reserve = saved; } } cu_reserve;     // see num_cu()
-    const bool fuse = stage != ADFP_STAGE_LOW;
-    DecodeBwdArgs a;
-    a.P = Pd; a.nb = make_norm(sc->bound); fill_bound(a.b, sc->bound);
-    a.list = nullptr; a.count_ptr = nullptr; a.g_raw = bw.g_raw; a.att_g = nullptr; a.stage = nullptr; a.dbg_masks = nullptr;
+    // ... and the compute units plan_sorted_scatter reserved for the lane are the caller's again (see num_cu())
+    struct CuReserve { int saved; CuReserve() : saved(t_cu_reserve) {} ~CuReserve() { t_cu_reserve = saved; } } cu_reserve;
+    const bool fuse = stage != ADFP_STAGE_LOW, with_color = stage == ADFP_STAGE_COLOR;
+    DecodeBwdArgs a{};
+    a.P = Pd; a.nb = make_norm(sc->bound); fill_bound(a.b, sc->bound); a.g_raw = bw.g_raw;
     a.g_pts = pgrad ? bw.g_pts : nullptr;
-    if (pgrad && !(call.head_pending && call.head_zeroes_g_pts)) { e = zero_async(bw.g_pts, (size_t)P * 12, st); if (e != hipSuccess) return (int)e; }
+    if (pgrad && !(call.head_pending && call.head_zeroes_g_pts)) { hipError_t e = zero_async(bw.g_pts, (size_t)P * 12, st); if (e != hipSuccess) return (int)e; }
     // a decoder takes the f16-split backward when its T image and the forward's masks are there and -- if its weight gradients
     // are wanted -- the forward also left the layer inputs.  A position gradient comes from the f16-split kernels only on its own
     // (the Tracker: networks and grids frozen); together with weight or grid gradients (bundle adjustment) the exact kernels run.
     auto use_h = [&](const void* t, const unsigned* masks, const float* act, const float* flat, const float* grid = nullptr) {
         return t && masks && (!flat || act) && (!pgrad || (!flat && !grid));
     };
-    // The grid gradients of the decoders that take the f16-split backward are scattered in spatial order (k_scatter_sorted): one
-    // radix sort of the points by (coarsest such grid's cell, finest grid's cell inside it), shared by all of them.
     const NetBwd low = net_bwd(sc, state, go, bw, ROLE_LOW), high = net_bwd(sc, state, go, bw, ROLE_HIGH), color = net_bwd(sc, state, go, bw, ROLE_COLOR);
     auto net_h = [&](const NetBwd& n) { return use_h(n.ht, n.masks, n.act, n.flat, n.g_grid); };
-    BinPlan bp; bp.ok = false; bp.pend.n_jobs = 0; bp.pgrad.n = 0;
-    {
-        const bool h_low = go.grid_low && net_h(low);
-        const bool h_high = fuse && go.grid_high && net_h(high);
-        const bool h_color = stage == ADFP_STAGE_COLOR && go.grid_color && net_h(color);
-        const adfp_grid* fine = nullptr; const adfp_grid* coarse = nullptr;
-        auto vox = [](const adfp_grid& g) { return (long long)g.X * g.Y * g.Z; };
-        const adfp_grid* cand[3] = {h_low ? &sc->low : nullptr, h_high ? &sc->high : nullptr, h_color ? &sc->color : nullptr};
-        for (int k = 0; k < 3; ++k) {
-            if (!cand[k]) continue;
-            if (!fine || vox(*cand[k]) > vox(*fine)) fine = cand[k];
-            if (!coarse || vox(*cand[k]) < vox(*coarse)) coarse = cand[k];
-        }
-        // ADFP_BWD_SCATTER_IN_KERNEL keeps every grid on the in-kernel write-combining scatter (what the tests compare the sorted
-        // scatter against)
-        const bool force_cache = (options & ADFP_BWD_SCATTER_IN_KERNEL) != 0;
-        if (fine && !force_cache && coarse->X >= 2 && coarse->Y >= 2 && coarse->Z >= 2 && P > 0) {
-            int bits = 0;
-            while ((1 << bits) < coarse->X || (1 << bits) < coarse->Y || (1 << bits) < coarse->Z) ++bits;
-            if (bits <= ADFP_BIN_MAXBITS) {
-                BinArgs& b = bp.args;
-                b.P = Pd; b.nb = a.nb; b.CX = coarse->X; b.CY = coarse->Y; b.CZ = coarse->Z; b.RX = fine->X; b.RY = fine->Y; b.RZ = fine->Z;
-                b.key = bw.bin_key; b.val = bw.bin_val;
-                const float* fold_parts = nullptr;            // the per-ray maxima still to be folded: by the sort's first launch when the
-                int fold_n = 0;                               // head carries k_composite_bwd (they are not written yet), else by k_bin_keys
-                if (call.head_pending) {
-                    rc = launch_backward_head(call, &b, P, st); if (rc) return rc;
-                    if (call.gmax_pending > 0) { fold_parts = bw.gmax_parts; fold_n = call.gmax_pending; }
-                } else {
-                    b.max_parts = call.gmax_pending > 0 ? bw.gmax_parts : nullptr; b.max_n = call.gmax_pending; b.max_out = bw.gmax;
-                    hipLaunchKernelGGL(k_bin_keys, dim3((P + 255) / 256 + (b.max_parts ? 1 : 0)), dim3(256), 0, st, b);
-                    ADFP_CHECK_LAUNCH();
-                }
-                call.gmax_pending = 0;
-                // stable LSD radix sort (adfp_sort.h), ping-pong between the two buffer pairs -- on the caller's side lane when there is
-                // one: nine short launches nobody but k_scatter_sorted waits for, beside the backward kernels instead of in front of them
-                const int* vfin = nullptr;
-                hipStream_t sort_st = st;
-                if (call.side) {
-                    // The gradient scale is folded HERE, on the main stream (one small launch): riding on the sort's first launch it would
-                    // make the first backward kernel wait for the side lane -- two cross-stream hops of ~15 us each (measured: 36 us
-                    // between k_backward_head's end and k_attention_bwd_h's start).
-                    if (fold_parts) {
-                        hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, st, fold_parts, fold_n, bw.gmax);
-                        ADFP_CHECK_LAUNCH();
-                        fold_parts = nullptr; fold_n = 0;
-                    }
-                    e = hipEventRecord(call.side_ev[0], st);                       // the keys exist
-                    if (e == hipSuccess) e = hipStreamWaitEvent(call.side, call.side_ev[0], 0);
-                    if (e != hipSuccess) return (int)e;
-                    sort_st = call.side;
-                    call.side_join_pending = true;
-                    t_cu_reserve = ADFP_SIDE_CU_RESERVE;          // the whole-CU kernels below leave the lane room (restored on return)
-                }
-                rc = radix_sort_pairs(bw.bin_key, bw.bin_val, bw.bin_key_sorted, bw.bin_perm, P, bin_key_bits(coarse->X, coarse->Y, coarse->Z), bw.sort_table, nullptr, &vfin, sort_st,
-                                      fold_parts, fold_n, bw.gmax);
-                if (rc) return rc;
-                const int* vin = vfin;
-                bp.perm = vin;                      // the pair the last pass wrote
-                bp.ok = true;
-            }
-        }
-    }
+    const bool h_low = net_h(low), h_high = net_h(high), h_color = net_h(color);
 
+    BinPlan bp{};
+    const adfp_grid* const sorted[3] = {go.grid_low && h_low ? &sc->low : nullptr, fuse && go.grid_high && h_high ? &sc->high : nullptr,
+                                        with_color && go.grid_color && h_color ? &sc->color : nullptr};
+    rc = plan_sorted_scatter(sorted, Pd, P, a.nb, options, bw, call, bp, st); if (rc) return rc;
     if (call.head_pending) { rc = launch_backward_head(call, nullptr, P, st); if (rc) return rc; }      // no sorted scatter: zero fill + compositing backward
     if (call.gmax_pending > 0) {                       // no sorted scatter in this call: the fold is a launch of its own
         hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, st, bw.gmax_parts, call.gmax_pending, bw.gmax);
@@ -3117,87 +3244,17 @@ static int backward_points(const adfp_scene* sc, int stage, const PtsDev& Pd, in
         call.gmax_pending = 0;
     }
     if (fuse) {
-        const bool att_full_h = use_h(sc->ht_att, state.masks_att, state.act_att, go.flat_att);
-        if (att_full_h) {
-            // the attention backward on f16 MFMA (k_attention_bwd_h): masks, softmax weights and layer inputs from the forward
-            AttBwdHArgs t;
-            t.packed_t = (const unsigned*)sc->ht_att; t.list = state.list; t.count_ptr = state.counter; t.att_occ = state.att_occ; t.att_u = state.att_u;
-            t.masks = state.masks_att; t.g_weight = g_weight; t.g_raw = bw.g_raw; t.att_g = bw.att_g; t.stage = bw.stage;
-            t.status = sc->status; t.gmax = bw.gmax; t.skip = state.counter ? state.counter + 8 : nullptr;
-            t.P = Pd; t.nt = make_norm(sc->tsdf_bnds); t.t = make_tsdf(sc->tsdf); t.g_pts = a.g_pts;
-            OuterHArgs oh; attention_jobs(oh.o);
-            oh.act = state.act_att; oh.nxm4 = 416 / 4; oh.ngm4 = 416 / 4; oh.g_dst4 = 416 / 4; oh.x_gap_at4 = 1 << 20; oh.x_gap4 = 0; oh.x_skip4 = 0; oh.P = PtsDev{}; oh.list = nullptr;
-            oh.masks = nullptr; oh.bm = nullptr; oh.col_se = 0; oh.col_sgp = 0; oh.status = sc->status; oh.skip = t.skip;
-            OuterArgs& oa = oh.o;
-            const int rows_cap = bw.stage_rows * 2;               // the G piece is half a row
-            // ONE chunk (the usual case: STG_ROWS_MAX): the weight-gradient workgroups OVERWRITE their slots and the reduction reads only
-            // the slots in use -- no zero fill of the 256 x 134 KB partial sums (9.5 us + a launch per iteration)
-            const bool one_chunk = P <= rows_cap;
-            oh.overwrite = one_chunk ? 1 : 0;
-            // one private gradient copy per workgroup; with one chunk the reduction reads the slots in use, so the launch may leave
-            // compute units to the side lane (num_cu()); several chunks accumulate into all OUTER_NSLOT zero-filled slots
-            const int att_slots = one_chunk ? (num_cu() < OUTER_NSLOT ? num_cu() : OUTER_NSLOT) : OUTER_NSLOT;
-            if (go.flat_att && !one_chunk) { rc = outer_begin(bw, AttLayout::F_TOTAL, st); if (rc) return rc; }
-            for (int lo = 0; lo < P; lo += rows_cap) {
-                const int hi = lo + rows_cap < P ? lo + rows_cap : P;
-                t.chunk_lo = lo; t.chunk_hi = hi;
-                const int ntiles = (hi - lo + 31) / 32;
-                if (go.flat_att) hipLaunchKernelGGL(k_attention_bwd_h<true>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
-                else if (pgrad) hipLaunchKernelGGL((k_attention_bwd_h<false, true>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
-                else hipLaunchKernelGGL(k_attention_bwd_h<false>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
-                ADFP_CHECK_LAUNCH();
-                if (go.flat_att) {
-                    oa.stage = bw.stage; oa.count_ptr = state.counter; oa.chunk_lo = lo; oa.chunk_hi = hi; oa.flat = go.flat_att;
-                    oa.partial = bw.partial; oa.part_stride = bw.part_stride;
-                    const int nblk = (hi - lo + OUTER_RT - 1) / OUTER_RT;     // list-based: the count is on the device, the kernel splits its rows evenly (even_block)
-                    oa.rows_per_wave = 0;
-                    hipLaunchKernelGGL(k_outer_h, dim3(nblk < att_slots ? nblk : att_slots), dim3(512), 0, st, oh);
-                    ADFP_CHECK_LAUNCH();
-                }
-            }
-            if (go.flat_att) {
-                if (one_chunk) {
-                    const int nblk = (P + OUTER_RT - 1) / OUTER_RT;
-                    hipLaunchKernelGGL(k_reduce_partials_scaled, dim3((AttLayout::F_TOTAL + 31) / 32), dim3(256), 0, st, bw.partial, nblk < att_slots ? nblk : att_slots,
-                                       bw.part_stride, AttLayout::F_TOTAL, go.flat_att, bw.gmax, state.counter, P, 0);
-                    ADFP_CHECK_LAUNCH();
-                } else { rc = outer_end_scaled(bw, AttLayout::F_TOTAL, go.flat_att, st); if (rc) return rc; }
-            }
-        } else {
-        if (!sc->w_att) return ADFP_E_ARG;
-        AttBwdArgs t;
-        t.packed = sc->w_att; t.list = state.list; t.count_ptr = state.counter; t.att_occ = state.att_occ;
-        t.att_u = state.att_u; t.g_weight = g_weight; t.g_raw = bw.g_raw; t.att_g = bw.att_g; t.stage = bw.stage;
-        t.P = Pd; t.nt = make_norm(sc->tsdf_bnds); t.t = make_tsdf(sc->tsdf); t.g_pts = a.g_pts;
-        t.gmax = nullptr; t.skip = state.counter ? state.counter + 8 : nullptr; t.dbg_masks = state.dbg_masks_att;
-        OuterArgs oa; attention_jobs(oa);
-        if (go.flat_att) { rc = outer_begin(bw, AttLayout::F_TOTAL, st); if (rc) return rc; }
-        for (int lo = 0; lo < P; lo += bw.stage_rows) {
-            const int hi = lo + bw.stage_rows < P ? lo + bw.stage_rows : P;
-            t.chunk_lo = lo; t.chunk_hi = hi;
-            const int ntiles = (hi - lo + 31) / 32;
-            if (go.flat_att) {
-                if (pgrad) hipLaunchKernelGGL((k_attention_bwd<true, true>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, t);
-                else hipLaunchKernelGGL((k_attention_bwd<true, false>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, t);
-                ADFP_CHECK_LAUNCH();
-                rc = launch_outer(oa, bw, state.counter, lo, hi, go.flat_att, st);
-                if (rc) return rc;
-            } else {
-                if (pgrad) hipLaunchKernelGGL((k_attention_bwd<false, true>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, t);
-                else hipLaunchKernelGGL((k_attention_bwd<false, false>), dim3(decode_grid(ntiles, 4, 1)), dim3(256), 0, st, t);
-                ADFP_CHECK_LAUNCH();
-            }
-        }
-        if (go.flat_att) { rc = outer_end(bw, AttLayout::F_TOTAL, go.flat_att, st); if (rc) return rc; }
-        }
-        if (go.grid_high || go.flat_high || pgrad) { rc = run_decoder_bwd<64, 1, ROLE_HIGH>(a, high, net_h(high), sc, state, P, bw, bp, options, st); if (rc) return rc; }
+        rc = use_h(sc->ht_att, state.masks_att, state.act_att, go.flat_att) ? attention_bwd_h(sc, state, Pd, P, g_weight, a.g_pts, go.flat_att, bw, st)
+                                                                            : attention_bwd(sc, state, Pd, P, g_weight, a.g_pts, go.flat_att, bw, st);
+        if (rc) return rc;
+        if (go.grid_high || go.flat_high || pgrad) { rc = run_decoder_bwd<64, 1, ROLE_HIGH>(a, high, h_high, sc, state, P, bw, bp, options, st); if (rc) return rc; }
     }
-    if (go.grid_low || go.flat_low || pgrad) { rc = run_decoder_bwd<32, 1, ROLE_LOW>(a, low, net_h(low), sc, state, P, bw, bp, options, st); if (rc) return rc; }
-    if (stage == ADFP_STAGE_COLOR && (go.grid_color || go.flat_color || pgrad)) {
-        rc = run_decoder_bwd<32, 4, ROLE_COLOR>(a, color, net_h(color), sc, state, P, bw, bp, options, st); if (rc) return rc;
+    if (go.grid_low || go.flat_low || pgrad) { rc = run_decoder_bwd<32, 1, ROLE_LOW>(a, low, h_low, sc, state, P, bw, bp, options, st); if (rc) return rc; }
+    if (with_color && (go.grid_color || go.flat_color || pgrad)) {
+        rc = run_decoder_bwd<32, 4, ROLE_COLOR>(a, color, h_color, sc, state, P, bw, bp, options, st); if (rc) return rc;
     }
     rc = flush_pgrad(bp, bw, call, st); if (rc) return rc;
-    e = side_join.join();                            // the sorted order is what k_scatter_sorted reads
+    const hipError_t e = side_join.join();           // the sorted order is what k_scatter_sorted reads
     if (e != hipSuccess) return (int)e;
     return flush_scatter(bp, st);
 }
@@ -3241,10 +3298,9 @@ extern "C" int adfp_render_backward(const adfp_scene* sc, const adfp_backward_ar
             call.head_zeroes_g_pts = true; call.pgrad_separate = true;
         }
         call.head_zero = zb.z; call.head_zero_blocks = zb.blocks;
-        call.head_zero.n = zb.z.n;
         CompositeBwdArgs& c = call.head_comp;
         c.raw = r->raw; c.z = r->z_vals; c.n_rays = r->n_rays; c.S = r->S; c.g_depth = r->g_depth; c.g_var = r->g_uncertainty; c.g_color = r->g_color;
-        c.g_raw = bw.g_raw; c.keep = r->ray_keep; c.gmax = bw.gmax_parts; c.g_weight = r->g_weight; c.skip = r->state.counter ? r->state.counter + 8 : nullptr;
+        c.g_raw = bw.g_raw; c.keep = r->ray_keep; c.gmax = bw.gmax_parts; c.g_weight = r->g_weight; c.skip = skip_flag(r->state);
         call.head_pending = true;
     }
     call.gmax_pending = r->n_rays;                     // folded into bw.gmax by the sort's first launch (or k_max_reduce)
@@ -3254,8 +3310,8 @@ extern "C" int adfp_render_backward(const adfp_scene* sc, const adfp_backward_ar
         for (int k = 0; k < 2; ++k) call.side_ev[k] = (hipEvent_t)r->side_events[k];
     }
 
-    PtsDev Pd;
-    Pd.mode = ADFP_PTS_RAYS; Pd.S = r->S; Pd.n = P; Pd.pts = nullptr; Pd.ro = r->rays_o; Pd.rd = r->rays_d; Pd.z = r->z_vals;
+    PtsDev Pd{};
+    Pd.mode = ADFP_PTS_RAYS; Pd.S = r->S; Pd.n = P; Pd.ro = r->rays_o; Pd.rd = r->rays_d; Pd.z = r->z_vals;
     const bool pgrad = r->g_rays_o || r->g_rays_d;
     rc = backward_points(sc, r->stage, Pd, P, r->state, r->g_weight, go, pgrad, r->options, bw, call, st);
     if (rc) return rc;
@@ -3308,7 +3364,7 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
     rc = zero_grad_outputs(sc, go, r->options, st); if (rc) return rc;
     if (Pd.n == 0) return 0;
     hipLaunchKernelGGL(k_evalpts_bwd_prep, dim3((Pd.n + 255) / 256), dim3(256), 0, st, Pd, r->g_raw, bw.g_raw, sc->bound[0][0], sc->bound[0][1],
-                       sc->bound[1][0], sc->bound[1][1], sc->bound[2][0], sc->bound[2][1], (r->flags & ADFP_EVAL_APPLY_BOUND) ? 1 : 0, bw.gmax_parts, r->g_w, r->state.counter ? r->state.counter + 8 : nullptr);
+                       sc->bound[1][0], sc->bound[1][1], sc->bound[2][0], sc->bound[2][1], (r->flags & ADFP_EVAL_APPLY_BOUND) ? 1 : 0, bw.gmax_parts, r->g_w, skip_flag(r->state));
     ADFP_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, st, bw.gmax_parts, ((Pd.n + 255) / 256) * 4, bw.gmax);
     ADFP_CHECK_LAUNCH();

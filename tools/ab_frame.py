@@ -8,6 +8,10 @@ round times, for A then for B, with device events:
   sample<N>   adfp_sample_rays alone on the first N rays of the frame (no relayout blocks in the launch), us per call:
               200 (a Tracker batch), 1 000, 5 000 (a Mapper batch), 16 384, 38 400 (1/8 frame), 100 000, 307 200 (the frame)
   low_color   adfp_decode_stage(LOW_COLOR) on a 100 000-ray batch (k_decode_lc16), ms per call
+  mapper_bwd  adfp_render_backward (Engine.render_backward on a saved training forward) of 5 000 random rays of the frame x 64 samples,
+              stage colour, every grid and parameter gradient wanted (the Mapper's iteration: the f16-split kernels), us per call
+  ba_bwd      the same with the ray gradients wanted too (bundle adjustment: the exact kernels), us per call
+  tracker_bwd the same entry at 200 rays x 64 samples with the ray gradients only (the Tracker: k_decode_bwd_h_pgrad3), us per call
 Each library has its own Renderer and decoders (nothing one build packed is read by the other).  Give the same file twice (a copy
 under another name) for the A/A spread of the process.  Prints one JSON line: per quantity and side the per-round values, median
 and minimum, and the sha256 of the frame's three images per side."""
@@ -95,10 +99,28 @@ def main():
                                   _lib.ptr(z), _lib.ptr(scratch), st)
         assert rc == 0, rc
 
+    # name -> rays, grids and parameters wanted, rays wanted
+    BWD = {'mapper_bwd_us': (5000, True, False), 'ba_bwd_us': (5000, True, True), 'tracker_bwd_us': (200, False, True)}
+    pick = torch.randperm(n_rays, generator=torch.Generator().manual_seed(4)).to(dev)
+
+    def train_forward(s, n, params):
+        """The saved state of a training forward on n rays and seeded cotangents for its backward."""
+        eng, idx = s.rend._engine, pick[:n]
+        flat = {k: params for k in ('low', 'high', 'color', 'att')}
+        d, u, col, w, saved = eng.render_forward(s.dec, scene.c, ro[idx].contiguous(), rd[idx].contiguous(), gd[idx].contiguous(), scene.tsdf_volume,
+                                                 tsdf_bnds, s.rend.bound, 'color', 48, 16, train=True, need_flat=flat)
+        return saved, (torch.randn_like(d), torch.randn_like(col), torch.randn_like(w).reshape(n, -1))
+
+    def backward(s, q, saved, cot):
+        n, params, rays = BWD[q]
+        want = {k: params for k in ('low', 'high', 'color', 'att')}
+        return s.rend._engine.render_backward(s.dec, scene.c, scene.tsdf_volume, tsdf_bnds, s.rend.bound, 'color', saved, cot[0], None, cot[1], cot[2],
+                                              want, want, rays)
+
     sizes = (200, 1000, 5000, 16384, 38400, 100000, n_rays)
-    quantities = ('frame_ms', 'low_color_ms') + tuple('sample%d_us' % n for n in sizes)
+    quantities = ('frame_ms', 'low_color_ms') + tuple(BWD) + tuple('sample%d_us' % n for n in sizes)
     res = {k: {q: [] for q in quantities} for k in sides}
-    stage = {}
+    stage, trained = {}, {}
     with torch.no_grad():
         for k, s in sides.items():
             s.use()
@@ -119,6 +141,7 @@ def main():
             apts.mode, apts.n_points = _lib.PTS_RAYS, NB * 64
             apts.rays_o, apts.rays_d, apts.z_vals, apts.S = ro.data_ptr(), rd.data_ptr(), z.data_ptr(), 64
             stage[k] = (sc, keep, apts)
+            trained[k] = {q: train_forward(s, BWD[q][0], BWD[q][1]) for q in BWD}
         raw = torch.empty((NB * 64, 4), dtype=torch.float32, device=dev)
         wb = torch.empty((NB * 64,), dtype=torch.float32, device=dev)
         cnt = torch.zeros((4,), dtype=torch.int32, device=dev)
@@ -131,6 +154,8 @@ def main():
                     'low_color_ms': ev_time(lambda: s.L.adfp_decode_stage(C.byref(sc), C.byref(apts), 3, _lib.ptr(raw), _lib.ptr(wb),
                                                                           _lib.ptr(cnt[1:]), st), 5),
                 }
+                for q in BWD:
+                    vals[q] = ev_time(lambda: backward(s, q, *trained[k][q]), 20) * 1e3
                 for n in sizes:
                     vals['sample%d_us' % n] = ev_time(lambda: sample(s, n), 100 if n < 50000 else 20) * 1e3
                 if rnd:
