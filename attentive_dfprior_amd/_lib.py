@@ -441,11 +441,19 @@ SYMBOLS = [
                                 C.c_float, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ('adfp_icp_end', C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    # RGB-D ICP
+    ('adfp_rgbd_workspace_bytes', C.c_size_t, [C.c_int, C.c_int]),
+    ('adfp_rgbd_frame_map', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ('adfp_rgbd_step', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                 C.c_float, C.c_float, C.c_float, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 ]
 
 ICP_SUMS = 29                          # ADFP_ICP_SUMS
 ICP_STATS = 6                          # ADFP_ICP_STATS
 ICP_STATE_BYTES = 272                  # ADFP_ICP_STATE_BYTES
+RGBD_SUMS = 31                         # ADFP_RGBD_SUMS
+RGBD_STATS = 2                         # ADFP_RGBD_STATS
 ICP_STATUS = {'ok': 0, 'few_pairs': 1, 'degenerate': 2, 'rejected': 3}     # ADFP_ICP_OK / _FEW_PAIRS / _DEGENERATE / _REJECTED
 MC_OUT = {'lower': 0, 'higher': 1}      # ADFP_MC_OUT_LOWER / ADFP_MC_OUT_HIGHER
 MC_MAX_TRI = 5                         # ADFP_MC_MAX_TRI

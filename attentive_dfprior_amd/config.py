@@ -24,8 +24,10 @@ def mapping_setting(cfg, key):
 # absent key means); 'icp' = the guess refined by icp.DepthICP, point-to-plane ICP of the whole depth image against the raycast of
 # the TSDF prior -- with tracking.iters: 0 that result is the frame's pose.  tracking.icp: keywords of DepthICP's constructor
 # (strides, iters, dist_tol, cos_tol, min_pivot, min_pairs, max_jump, max_shift, max_angle, near); lengths are metres and are NOT
-# multiplied by `scale`.
-TRACKING_DEFAULTS = {'init': 'guess', 'icp': {}}
+# multiplied by `scale`.  tracking.icp_rgb: {'weight': w, 'tol': t} -- with tracking.init: icp and w > 0 (absent or 0: off) every ICP
+# step adds a photometric term against the last tracked frame, weighted by w, to its normal equations (icp.RgbdICP; t drops pairs
+# whose intensities differ by more, RgbdICP's default when absent).  A weight > 0 without tracking.init: icp is an error.
+TRACKING_DEFAULTS = {'init': 'guess', 'icp': {}, 'icp_rgb': {}}
 TRACKING_INITS = ('guess', 'icp')
 
 

@@ -9,7 +9,9 @@
 //                    to the image: a lane keeps the 29 sums of the normal equations in registers (58 VGPRs), the wave adds them
 //                    with DPP row steps and four readlanes (wave_sum), the four waves meet in 4 x 29 doubles of LDS, and the
 //                    workgroup leaves ONE row of 29 doubles in the caller's workspace.  No atomics.
-//   k_icp_solve      one wave: lane l adds the rows l, l + 64, ... of the workspace in that order, wave_sum adds the lanes, lane 0
+//                    The pair itself (association, gates, r and J: icp_geo_pair), the accumulation (icp_add_pair) and the
+//                    workgroup's reduction (icp_block_sums) are functions that k_rgbd_step (adfp_rgbd.h) calls too.
+//   k_icp_solve<NS>  one wave: lane l adds the rows l, l + 64, ... of the workspace in that order, wave_sum adds the lanes, lane 0
 //                    solves the 6 x 6 system by LDL^T, applies the twist and writes the stats row.  The order of every addition
 //                    is fixed by the launch geometry alone, so two calls on the same inputs give the same bytes.
 //   k_icp_begin / k_icp_end   one lane each: T = guess; the gate on the result, c2w_out, cam_out.
@@ -87,6 +89,83 @@ struct IcpStepArgs {
     double* part;                          // [gridDim.x][ADFP_ICP_SUMS]
 };
 
+// x = T V(u, v, d): the sensor pixel's point in the world
+ADFP_DEV void icp_sensor_point(const IcpStepArgs& a, const double T[12], int us, int vs, double d, double x[3]) {
+    double Vs[3];
+    icp_vertex(us, vs, d, a.fx, a.fy, a.cx, a.cy, Vs);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) x[k] = ((T[4 * k] * Vs[0] + T[4 * k + 1] * Vs[1]) + T[4 * k + 2] * Vs[2]) + T[4 * k + 3];
+}
+
+// The geometric pair of the sensor point x with the sensor normal Ns (camera frame, not zero): projective association into the model
+// image, the gates, then r and J.  false: no pair.  k_icp_step and k_rgbd_step (adfp_rgbd.h) both call this, so that the joint step
+// without a photometric term adds the same numbers in the same order.
+ADFP_DEV bool icp_geo_pair(const IcpStepArgs& a, const double T[12], const double P[12], const double x[3], const double Ns[3], double J[6],
+                           double& r) {
+    double nsw[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) nsw[k] = (T[4 * k] * Ns[0] + T[4 * k + 1] * Ns[1]) + T[4 * k + 2] * Ns[2];
+    const double e[3] = {x[0] - P[3], x[1] - P[7], x[2] - P[11]};
+    double xc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) xc[k] = (P[k] * e[0] + P[4 + k] * e[1]) + P[8 + k] * e[2];
+    const double z = -xc[2];
+    if (!(z > 0.0)) return false;
+    const double pu = floor((((a.fx * xc[0]) / z) + a.cx) + 0.5), pv = floor((((-a.fy * xc[1]) / z) + a.cy) + 0.5);
+    if (!(pu >= 0.0 && pu <= (double)(a.W - 1) && pv >= 0.0 && pv <= (double)(a.H - 1))) return false;
+    const int um = (int)pu, vm = (int)pv;
+    const long long mi = (long long)vm * a.W + um;
+    const double Nm[3] = {(double)a.nm[3 * mi], (double)a.nm[3 * mi + 1], (double)a.nm[3 * mi + 2]};
+    if (Nm[0] == 0.0 && Nm[1] == 0.0 && Nm[2] == 0.0) return false;
+    double Vm[3];
+    icp_vertex(um, vm, (double)a.dm[mi], a.fx, a.fy, a.cx, a.cy, Vm);
+    double m[3], n[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        m[k] = ((P[4 * k] * Vm[0] + P[4 * k + 1] * Vm[1]) + P[4 * k + 2] * Vm[2]) + P[4 * k + 3];
+        n[k] = (P[4 * k] * Nm[0] + P[4 * k + 1] * Nm[1]) + P[4 * k + 2] * Nm[2];
+    }
+    const double g[3] = {m[0] - x[0], m[1] - x[1], m[2] - x[2]};
+    const double dist = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+    if (!(dist <= a.dist_tol)) return false;
+    const double cs = (nsw[0] * n[0] + nsw[1] * n[1]) + nsw[2] * n[2];
+    if (!(cs >= a.cos_tol)) return false;
+    r = (n[0] * g[0] + n[1] * g[1]) + n[2] * g[2];
+    J[0] = x[1] * n[2] - x[2] * n[1]; J[1] = x[2] * n[0] - x[0] * n[2]; J[2] = x[0] * n[1] - x[1] * n[0];
+    J[3] = n[0]; J[4] = n[1]; J[5] = n[2];
+    return true;
+}
+
+// one pair into a lane's sums: acc[0..20] += w J J^T (upper, row by row), acc[21..26] += w J r, acc[tail] += r^2, acc[tail + 1] += 1.
+// WEIGHTED false adds the products themselves (w is not read).
+template <bool WEIGHTED>
+ADFP_DEV void icp_add_pair(double* acc, const double J[6], double r, double w, int tail) {
+    int q = 0;
+#pragma unroll
+    for (int i2 = 0; i2 < 6; ++i2)
+#pragma unroll
+        for (int j2 = i2; j2 < 6; ++j2) { acc[q] += WEIGHTED ? w * (J[i2] * J[j2]) : J[i2] * J[j2]; ++q; }
+#pragma unroll
+    for (int i2 = 0; i2 < 6; ++i2) acc[21 + i2] += WEIGHTED ? w * (J[i2] * r) : J[i2] * r;
+    acc[tail] += r * r;
+    acc[tail + 1] += 1.0;
+}
+
+// the lanes' sums -> one row of NS doubles per workgroup: DPP within the wave, the four waves through LDS
+template <int NS>
+ADFP_DEV void icp_block_sums(double* acc, double (*s_part)[NS], double* __restrict__ part) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) acc[k] = wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s_part[threadIdx.x >> 6][k] = acc[k];
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        const int k = threadIdx.x;
+        part[(long long)blockIdx.x * NS + k] = (s_part[0][k] + s_part[1][k]) + (s_part[2][k] + s_part[3][k]);
+    }
+}
+
 __global__ __launch_bounds__(ADFP_ICP_THREADS) void k_icp_step(IcpStepArgs a) {
     __shared__ double s_part[4][ADFP_ICP_SUMS];
     if (a.state->status != (double)ADFP_ICP_OK) return;          // kernel-uniform: k_icp_solve returns on the same word
@@ -102,61 +181,12 @@ __global__ __launch_bounds__(ADFP_ICP_THREADS) void k_icp_step(IcpStepArgs a) {
         const long long si = (long long)vs * a.W + us;
         const double Ns[3] = {(double)a.ns[3 * si], (double)a.ns[3 * si + 1], (double)a.ns[3 * si + 2]};
         if (Ns[0] == 0.0 && Ns[1] == 0.0 && Ns[2] == 0.0) continue;
-        double Vs[3];
-        icp_vertex(us, vs, (double)a.ds[si], a.fx, a.fy, a.cx, a.cy, Vs);
-        double x[3], nsw[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            x[k] = ((T[4 * k] * Vs[0] + T[4 * k + 1] * Vs[1]) + T[4 * k + 2] * Vs[2]) + T[4 * k + 3];
-            nsw[k] = (T[4 * k] * Ns[0] + T[4 * k + 1] * Ns[1]) + T[4 * k + 2] * Ns[2];
-        }
-        const double e[3] = {x[0] - P[3], x[1] - P[7], x[2] - P[11]};
-        double xc[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xc[k] = (P[k] * e[0] + P[4 + k] * e[1]) + P[8 + k] * e[2];
-        const double z = -xc[2];
-        if (!(z > 0.0)) continue;
-        const double pu = floor((((a.fx * xc[0]) / z) + a.cx) + 0.5), pv = floor((((-a.fy * xc[1]) / z) + a.cy) + 0.5);
-        if (!(pu >= 0.0 && pu <= (double)(a.W - 1) && pv >= 0.0 && pv <= (double)(a.H - 1))) continue;
-        const int um = (int)pu, vm = (int)pv;
-        const long long mi = (long long)vm * a.W + um;
-        const double Nm[3] = {(double)a.nm[3 * mi], (double)a.nm[3 * mi + 1], (double)a.nm[3 * mi + 2]};
-        if (Nm[0] == 0.0 && Nm[1] == 0.0 && Nm[2] == 0.0) continue;
-        double Vm[3];
-        icp_vertex(um, vm, (double)a.dm[mi], a.fx, a.fy, a.cx, a.cy, Vm);
-        double m[3], n[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            m[k] = ((P[4 * k] * Vm[0] + P[4 * k + 1] * Vm[1]) + P[4 * k + 2] * Vm[2]) + P[4 * k + 3];
-            n[k] = (P[4 * k] * Nm[0] + P[4 * k + 1] * Nm[1]) + P[4 * k + 2] * Nm[2];
-        }
-        const double g[3] = {m[0] - x[0], m[1] - x[1], m[2] - x[2]};
-        const double dist = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
-        if (!(dist <= a.dist_tol)) continue;
-        const double cs = (nsw[0] * n[0] + nsw[1] * n[1]) + nsw[2] * n[2];
-        if (!(cs >= a.cos_tol)) continue;
-        const double r = (n[0] * g[0] + n[1] * g[1]) + n[2] * g[2];
-        const double J[6] = {x[1] * n[2] - x[2] * n[1], x[2] * n[0] - x[0] * n[2], x[0] * n[1] - x[1] * n[0], n[0], n[1], n[2]};
-        int q = 0;
-#pragma unroll
-        for (int i2 = 0; i2 < 6; ++i2)
-#pragma unroll
-            for (int j2 = i2; j2 < 6; ++j2) { acc[q] += J[i2] * J[j2]; ++q; }
-#pragma unroll
-        for (int i2 = 0; i2 < 6; ++i2) acc[21 + i2] += J[i2] * r;
-        acc[27] += r * r;
-        acc[28] += 1.0;
+        double x[3], J[6], r;
+        icp_sensor_point(a, T, us, vs, (double)a.ds[si], x);
+        if (!icp_geo_pair(a, T, P, x, Ns, J, r)) continue;
+        icp_add_pair<false>(acc, J, r, 1.0, 27);
     }
-#pragma unroll
-    for (int k = 0; k < ADFP_ICP_SUMS; ++k) acc[k] = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < ADFP_ICP_SUMS; ++k) s_part[threadIdx.x >> 6][k] = acc[k];
-    __syncthreads();
-    if (threadIdx.x < ADFP_ICP_SUMS) {
-        const int k = threadIdx.x;
-        a.part[(long long)blockIdx.x * ADFP_ICP_SUMS + k] = (s_part[0][k] + s_part[1][k]) + (s_part[2][k] + s_part[3][k]);
-    }
+    icp_block_sums<ADFP_ICP_SUMS>(acc, s_part, a.part);
 }
 
 // Exp of the twist (w, t): rotation E[0..8] row-major and translation E[9..11] = V t
@@ -182,30 +212,39 @@ ADFP_DEV void icp_exp(const double w[3], const double t[3], double th, double E[
     for (int i = 0; i < 3; ++i) E[9 + i] = (Vm[3 * i] * t[0] + Vm[3 * i + 1] * t[1]) + Vm[3 * i + 2] * t[2];
 }
 
-// one wave
+// one wave.  NS = ADFP_ICP_SUMS: the depth ICP's 29 sums.  NS = ADFP_RGBD_SUMS: two more, the photometric sum of squares and pair
+// count; the larger of the two pair counts is held against min_pairs, and rgb_row receives (photometric pairs, photometric rmse).
+template <int NS>
 __global__ __launch_bounds__(64) void k_icp_solve(const double* __restrict__ part, int rows, IcpState* state, double min_pivot, double min_pairs,
-                                                  double* __restrict__ stats_row, double* __restrict__ sums_out) {
+                                                  double* __restrict__ stats_row, double* __restrict__ rgb_row, double* __restrict__ sums_out) {
     const int lane = threadIdx.x;
     const double st_in = state->status;
     if (st_in != (double)ADFP_ICP_OK) {                           // a step after a failed one: the row says so, nothing moves
         if (lane < ADFP_ICP_STATS) stats_row[lane] = lane == ADFP_ICP_STATS - 1 ? st_in : 0.0;
-        if (sums_out && lane < ADFP_ICP_SUMS) sums_out[lane] = 0.0;
+        if (NS > ADFP_ICP_SUMS && lane < 2) rgb_row[lane] = 0.0;
+        if (sums_out && lane < NS) sums_out[lane] = 0.0;
         return;
     }
-    double S[ADFP_ICP_SUMS];
+    double S[NS];
 #pragma unroll
-    for (int k = 0; k < ADFP_ICP_SUMS; ++k) S[k] = 0.0;
+    for (int k = 0; k < NS; ++k) S[k] = 0.0;
     for (int r = lane; r < rows; r += 64)
 #pragma unroll
-        for (int k = 0; k < ADFP_ICP_SUMS; ++k) S[k] += part[(long long)r * ADFP_ICP_SUMS + k];
+        for (int k = 0; k < NS; ++k) S[k] += part[(long long)r * NS + k];
 #pragma unroll
-    for (int k = 0; k < ADFP_ICP_SUMS; ++k) S[k] = wave_sum(S[k]);
+    for (int k = 0; k < NS; ++k) S[k] = wave_sum(S[k]);
     if (lane != 0) return;
     if (sums_out)
 #pragma unroll
-        for (int k = 0; k < ADFP_ICP_SUMS; ++k) sums_out[k] = S[k];
+        for (int k = 0; k < NS; ++k) sums_out[k] = S[k];
     const double pairs = S[28];
     const double rmse = pairs > 0.0 ? sqrt(S[27] / pairs) : 0.0;
+    double most = pairs;                                           // what min_pairs is held against
+    if (NS > ADFP_ICP_SUMS) {
+        const double pp = S[NS - 1];
+        rgb_row[0] = pp; rgb_row[1] = pp > 0.0 ? sqrt(S[NS - 2] / pp) : 0.0;
+        most = pp > pairs ? pp : pairs;
+    }
     double A[6][6], b[6];
     {
         int q = 0;
@@ -217,7 +256,7 @@ __global__ __launch_bounds__(64) void k_icp_solve(const double* __restrict__ par
         for (int i = 0; i < 6; ++i) b[i] = S[21 + i];
     }
     double status = (double)ADFP_ICP_OK, ratio = 0.0, wn = 0.0, tn = 0.0;
-    if (pairs < min_pairs) status = (double)ADFP_ICP_FEW_PAIRS;
+    if (most < min_pairs) status = (double)ADFP_ICP_FEW_PAIRS;
     else {
         double dmax = A[0][0];
 #pragma unroll
@@ -421,8 +460,8 @@ extern "C" int adfp_icp_step(const float* depth_s, const float* normals_s, const
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_icp_step, dim3((unsigned)blocks), dim3(ADFP_ICP_THREADS), 0, st, a);
     ADFP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(64), 0, st, (const double*)workspace, (int)blocks, (IcpState*)state, min_pivot, min_pairs,
-                       stats + (long long)row * ADFP_ICP_STATS, sums);
+    hipLaunchKernelGGL((k_icp_solve<ADFP_ICP_SUMS>), dim3(1), dim3(64), 0, st, (const double*)workspace, (int)blocks, (IcpState*)state, min_pivot,
+                       min_pairs, stats + (long long)row * ADFP_ICP_STATS, (double*)nullptr, sums);
     ADFP_CHECK_LAUNCH();
     return 0;
 }

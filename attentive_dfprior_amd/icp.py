@@ -12,7 +12,11 @@ the tracker (``tracking.init: icp``, slam.Tracker).
 
 The rule (normal map, association, normal equations, solve, gate) is stated in include/adfp.h ("Depth ICP") and restated in numpy in
 tests/icp_ref.py.  Everything is decided on the device: a refinement is a fixed sequence of launches with no read-back, and a
-refinement that fails (too few pairs, a direction the pairs do not constrain, a result too far from the guess) returns the guess."""
+refinement that fails (too few pairs, a direction the pairs do not constrain, a result too far from the guess) returns the guess.
+
+RgbdICP (``tracking.icp_rgb``) is DepthICP with a photometric term against the last tracked frame in every step's normal equations
+(adfp_rgbd_frame_map, adfp_rgbd_step, csrc/adfp_rgbd.h; include/adfp.h "RGB-D ICP", tests/rgbd_icp_ref.py): texture constrains what a
+view of one or two walls leaves free, and an empty model image still yields pairs."""
 import ctypes as C
 import math
 
@@ -167,3 +171,137 @@ class DepthICP(object):
             check(lib().adfp_icp_end(ptr(self.state), float('inf'), float('inf'), ptr(self.c2w_out), ptr(self.cam_out), None, 0, 0, st),
                   'adfp_icp_end')
         return sums, self.stats[0].clone(), self.c2w_out.clone(), self.cam_out.clone()
+
+
+RGB_STATS_COLUMNS = ('rgb_pairs', 'rgb_rmse')
+
+
+def _c2w44(c2w, dev):
+    """[4,4] or [3,4], numpy or torch, anywhere -> [4,4] float32 on `dev`"""
+    if isinstance(c2w, np.ndarray):
+        c2w = torch.from_numpy(c2w)
+    g = c2w.detach().to(dev, torch.float32)
+    if tuple(g.shape) == (3, 4):
+        g = torch.cat([g, g.new_tensor([[0., 0., 0., 1.]])], 0)
+    if tuple(g.shape) != (4, 4):
+        raise ValueError(f'c2w: expected [4,4] or [3,4], got {tuple(c2w.shape)}')
+    return g
+
+
+class RgbdICP(DepthICP):
+    """DepthICP whose every step adds a photometric term against the last tracked frame (the "keyframe": its sensor colour, its
+    sensor depth and its final pose) to the geometric normal equations (adfp_rgbd_frame_map, adfp_rgbd_step, csrc/adfp_rgbd.h; the
+    rule: include/adfp.h "RGB-D ICP", tests/rgbd_icp_ref.py).  Texture constrains the directions a view of one or two walls leaves
+    free, and a frame-to-frame term needs no prior, so an empty model image still yields pairs.
+
+        icp = RgbdICP(tsdf_volume, tsdf_bnds, H, W, fx, fy, cx, cy, engine=renderer._engine, rgb_weight=1.0)
+        icp.set_keyframe(c2w0, color0, depth0)             # the first frame
+        cam = icp.refine(guess_c2w, gt_depth, gt_color)    # [7] float32 on the device
+        icp.promote(final_c2w)                             # the frame just refined becomes the keyframe
+
+    rgb_weight multiplies the photometric normal equations (intensities are 0..1, geometric residuals metres), rgb_tol drops pairs
+    whose intensities differ by more; both defaults are the mini scene's and have not been tuned on anything else.  Before the first
+    set_keyframe, and with rgb_weight 0, a step is the depth rule.  Everything is allocated here, once."""
+
+    def __init__(self, tsdf_volume, tsdf_bnds, H, W, fx, fy, cx, cy, engine=None, rgb_weight=1.0, rgb_tol=0.25, **depth_icp_keywords):
+        super().__init__(tsdf_volume, tsdf_bnds, H, W, fx, fy, cx, cy, engine=engine, **depth_icp_keywords)
+        self.rgb_weight, self.rgb_tol = float(rgb_weight), float(rgb_tol)
+        if not self.rgb_weight >= 0 or self.rgb_tol != self.rgb_tol:
+            raise ValueError(f'rgb_weight {rgb_weight!r} must be >= 0 and rgb_tol {rgb_tol!r} a number')
+        dev = self.dev
+        nbytes = int(lib().adfp_rgbd_workspace_bytes(self.H, self.W))
+        self.maps = torch.zeros((2, self.H, self.W, 4), dtype=torch.float32, device=dev)          # current frame, keyframe
+        self.p_key = torch.zeros((4, 4), dtype=torch.float32, device=dev)
+        self.rgb_stats = torch.zeros((self.n_steps + 1, _lib.RGBD_STATS), dtype=torch.float64, device=dev)
+        self.rgbd_workspace = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+        self.has_keyframe = False
+
+    def frame_map(self, color, depth, out=None):
+        """color [H,W,3], depth [H,W] float32 on the device -> [H,W,4] = (I, gx, gy, d) (adfp_rgbd_frame_map, one launch)."""
+        _lib.require_cuda(color, 'color')
+        _lib.require_cuda(depth, 'depth')
+        H, W = self.H, self.W
+        if tuple(color.shape) != (H, W, 3) or tuple(depth.shape) != (H, W) or color.dtype != torch.float32 or depth.dtype != torch.float32:
+            raise ValueError(f'expected float32 color [{H},{W},3] and depth [{H},{W}], got {color.dtype} {tuple(color.shape)} and '
+                             f'{depth.dtype} {tuple(depth.shape)}')
+        color, depth = color.detach().contiguous(), depth.detach().contiguous()
+        with _lib.device_guard(depth.device):
+            if out is None:
+                out = torch.empty((H, W, 4), dtype=torch.float32, device=depth.device)
+            check(lib().adfp_rgbd_frame_map(ptr(color), ptr(depth), H, W, ptr(out), _lib.current_stream(depth.device)), 'adfp_rgbd_frame_map')
+        return out
+
+    def set_keyframe(self, c2w, color, depth):
+        """The frame the photometric term compares with: its pose and one frame-map launch into the keyframe map."""
+        self.p_key.copy_(_c2w44(c2w, self.dev))
+        self.frame_map(color, depth, out=self.maps[1])
+        self.has_keyframe = True
+
+    def promote(self, c2w):
+        """The frame last given to refine becomes the keyframe, at the pose `c2w`.  A copy, not a swap of pointers: a captured graph
+        of run_steps stays valid."""
+        self.p_key.copy_(_c2w44(c2w, self.dev))
+        self.maps[1].copy_(self.maps[0])
+        self.has_keyframe = True
+
+    def _rgbd_step(self, cur, normals, depth_m, p_ref, stride, row, st, sums=None, key=True):
+        key = key and self.has_keyframe
+        check(lib().adfp_rgbd_step(ptr(cur), ptr(normals[0]), ptr(depth_m), ptr(normals[1]), ptr(p_ref), ptr(self.maps[1]) if key else None,
+                                   ptr(self.p_key) if key else None, self.H, self.W, self.fx, self.fy, self.cx, self.cy, int(stride),
+                                   self.dist_tol, self.cos_tol, self.rgb_weight, self.rgb_tol, self.min_pivot, self.pairs_needed(stride),
+                                   ptr(self.state), ptr(self.stats), ptr(self.rgb_stats), self.stats.shape[0], int(row), ptr(sums),
+                                   ptr(self.rgbd_workspace), self.rgbd_workspace.numel() * 8, st), 'adfp_rgbd_step')
+
+    def run_steps(self):
+        """DepthICP.run_steps with adfp_rgbd_step on the maps this object holds.  Returns cam_out [7]."""
+        with _lib.device_guard(self.dev):
+            st = _lib.current_stream(self.dev)
+            self._begin(self.p_ref, st)
+            row = 0
+            for stride, n in zip(self.strides, self.iters):
+                for _ in range(n):
+                    self._rgbd_step(self.maps[0], self.normals, self.depth[1], self.p_ref, stride, row, st)
+                    row += 1
+            self._end(row, st)
+        return self.cam_out
+
+    def refine(self, guess_c2w, gt_depth, gt_color):
+        """DepthICP.refine with the frame's colour [H,W,3]: the parent's set_frame, one frame-map launch, the joint steps."""
+        self.set_frame(guess_c2w, gt_depth)
+        self.frame_map(gt_color, self.depth[0], out=self.maps[0])
+        return self.run_steps()
+
+    def last_rgb_stats(self):
+        """The photometric (pairs, rmse) of the last refinement's steps on the host, row for row beside last_stats (the gate's row: 0)."""
+        return self.rgb_stats.cpu()
+
+    def step_system_rgbd(self, c2w, cur_map, normals_s, depth_m, normals_m, p_ref, key_map=None, p_key=None, stride=1):
+        """One joint step from the estimate `c2w` on the caller's maps (key_map None: no photometric term): -> (sums [31] float64,
+        stats row [6], rgb stats row [2], estimate after the step [4,4] float32, its camera tensor [7]), all on the device.  For
+        tests, in the manner of step_system.  The keyframe this object holds is left as it was."""
+        dev = self.dev
+        c2w, p_ref = _c2w44(c2w, dev).contiguous(), _c2w44(p_ref, dev).contiguous()
+        cur = cur_map.to(dev, torch.float32).contiguous()
+        normals = torch.stack([normals_s.to(dev, torch.float32), normals_m.to(dev, torch.float32)]).contiguous()
+        depth_m = depth_m.to(dev, torch.float32).contiguous()
+        if tuple(cur.shape) != (self.H, self.W, 4) or tuple(normals.shape) != (2, self.H, self.W, 3) or tuple(depth_m.shape) != (self.H, self.W):
+            raise ValueError(f'maps: expected a [{self.H},{self.W},4] map, a [{self.H},{self.W}] depth and [{self.H},{self.W},3] normals')
+        if (key_map is None) != (p_key is None):
+            raise ValueError('key_map and p_key: both or neither')
+        saved = (self.maps[1].clone(), self.p_key.clone(), self.has_keyframe)
+        if key_map is not None:
+            self.maps[1].copy_(key_map.to(dev, torch.float32))
+            self.p_key.copy_(_c2w44(p_key, dev))
+        self.has_keyframe = key_map is not None
+        sums = torch.zeros((_lib.RGBD_SUMS,), dtype=torch.float64, device=dev)
+        with _lib.device_guard(dev):
+            st = _lib.current_stream(dev)
+            self._begin(c2w, st)
+            self._rgbd_step(cur, normals, depth_m, p_ref, stride, 0, st, sums=sums)
+            check(lib().adfp_icp_end(ptr(self.state), float('inf'), float('inf'), ptr(self.c2w_out), ptr(self.cam_out), None, 0, 0, st),
+                  'adfp_icp_end')
+        out = sums, self.stats[0].clone(), self.rgb_stats[0].clone(), self.c2w_out.clone(), self.cam_out.clone()
+        self.maps[1].copy_(saved[0])
+        self.p_key.copy_(saved[1])
+        self.has_keyframe = saved[2]
+        return out

@@ -3,6 +3,7 @@
     python -m attentive_dfprior_amd.run CONFIG [--input_folder ..] [--output ..] [--tsdf_volume PATH --tsdf_bounds PATH]
                                                [--prior file|online] [--prior_voxel_size M] [--seed N] [--last_frame N]
                                                [--no_prefetch] [--default_config PATH] [--tracking_init guess|icp]
+                                               [--tracking_rgb_weight W]
 
 The prior TSDF volume comes from the files ``python -m attentive_dfprior_amd.get_tsdf CONFIG`` writes
 (``<dataset>_tsdf_volume/<scene>_tsdf_volume.pt`` and ``_bounds.pt``, or the two paths given), or with ``--prior online`` is fused
@@ -32,6 +33,9 @@ def parse_args(argv=None):
     parser.add_argument('--tracking_init', choices=('guess', 'icp'),
                         help="replaces the config's tracking.init: guess = the constant-speed guess as it is; icp = the guess refined by "
                              'point-to-plane ICP of the depth image against the TSDF prior (icp.DepthICP)')
+    parser.add_argument('--tracking_rgb_weight', type=float, metavar='W',
+                        help="replaces the config's tracking.icp_rgb.weight: W > 0 adds a photometric term against the last tracked frame "
+                             'to every ICP step (icp.RgbdICP; needs tracking.init icp), 0 turns it off')
     return parser.parse_args(argv)
 
 
@@ -40,6 +44,9 @@ def main(argv=None):
     cfg = load_config(args.config, args.default_config if os.path.exists(args.default_config) else None)
     if args.tracking_init is not None:
         cfg.setdefault('tracking', {})['init'] = args.tracking_init
+    if args.tracking_rgb_weight is not None:
+        t = cfg.setdefault('tracking', {})
+        t['icp_rgb'] = dict(t.get('icp_rgb') or {}, weight=args.tracking_rgb_weight)
     if args.seed is not None:
         setup_seed(args.seed)
     slam = DF_Prior(cfg, args)

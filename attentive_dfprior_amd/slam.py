@@ -505,6 +505,18 @@ class Tracker(object):
         if self.init not in TRACKING_INITS:
             raise ValueError(f'tracking.init {self.init!r}: one of {TRACKING_INITS}')
         self.icp_kwargs = dict(tracking_setting(cfg, 'icp') or {})
+        # tracking.icp_rgb: {weight, tol} -- a weight > 0 adds the photometric term against the last tracked frame (icp.RgbdICP)
+        rgb = dict(tracking_setting(cfg, 'icp_rgb') or {})
+        unknown = set(rgb) - {'weight', 'tol'}
+        if unknown:
+            raise ValueError(f'tracking.icp_rgb: unknown keys {sorted(unknown)} (weight, tol)')
+        self.icp_rgb_weight = float(rgb.get('weight') or 0.0)
+        self.icp_rgb_tol = rgb.get('tol')
+        if self.icp_rgb_weight < 0 or self.icp_rgb_weight != self.icp_rgb_weight:
+            raise ValueError(f'tracking.icp_rgb.weight {self.icp_rgb_weight!r}: a number >= 0')
+        if self.icp_rgb_weight > 0 and self.init != 'icp':
+            raise ValueError('tracking.icp_rgb.weight > 0 needs tracking.init: icp')
+        self.icp_rgb = self.init == 'icp' and self.icp_rgb_weight > 0
         self._icp = None
         self.icp_status = []
 
@@ -512,7 +524,13 @@ class Tracker(object):
     def _new_icp(self):
         """The raycaster inside shares the Renderer's Engine: its empty-space bitmap is keyed on the prior volume's version counter
         (--prior online integrates through PyTorch, which bumps it) and dropped by the Renderer's invalidate_tsdf."""
-        from .icp import DepthICP
+        from .icp import DepthICP, RgbdICP
+        if self.icp_rgb:
+            kw = dict(self.icp_kwargs, rgb_weight=self.icp_rgb_weight)
+            if self.icp_rgb_tol is not None:
+                kw['rgb_tol'] = float(self.icp_rgb_tol)
+            return RgbdICP(self.tsdf_volume_shared, self.tsdf_bnds, self.H, self.W, self.fx, self.fy, self.cx, self.cy,
+                           engine=self.renderer._engine, **kw)
         return DepthICP(self.tsdf_volume_shared, self.tsdf_bnds, self.H, self.W, self.fx, self.fy, self.cx, self.cy,
                         engine=self.renderer._engine, **self.icp_kwargs)
 
@@ -583,8 +601,13 @@ class Tracker(object):
             c2w = gt_c2w.detach().cpu()
             if not self.no_vis_on_first_frame:
                 self.visualizer.vis(idx, 0, gt_depth, gt_color, c2w.to(self.device), self.c, self.decoders, tsdf_volume, tsdf_bnds)
+            if self.icp_rgb:
+                self.icp.set_keyframe(c2w, gt_color, gt_depth)                           # what the next tracked frame is compared with
         else:
-            if self.init == 'icp':
+            if self.icp_rgb:
+                # the same, with the photometric term against the last tracked frame in every step's normal equations
+                camera_tensor = self.icp.refine(self.guess(idx).detach(), gt_depth, gt_color)
+            elif self.init == 'icp':
                 # the guess aligned with the prior's surface over the whole depth image; the guess itself when that fails.  On the
                 # device, no read-back: the iterations below are queued behind it
                 camera_tensor = self.icp.refine(self.guess(idx).detach(), gt_depth)
@@ -609,6 +632,13 @@ class Tracker(object):
                     step = last[-1].tolist() if len(last) else [0.0] * 6
                     print(f'ICP frame {idx}: {STATUS_NAMES[self.icp_status[-1]]}, last step {step[0]:.0f} pairs, rmse {step[1]:.5f} m, '
                           f'pivot ratio {step[2]:.2e}; moved {stats[-1, 4].item():.4f} m {stats[-1, 3].item():.4f} rad from the guess')
+                    if self.icp_rgb:
+                        rgb = self.icp.last_rgb_stats()[:-1]
+                        rgb = rgb[rgb[:, 0] > 0]
+                        last_rgb = rgb[-1].tolist() if len(rgb) else [0.0, 0.0]
+                        print(f'ICP frame {idx}: photometric term, last step {last_rgb[0]:.0f} pairs, rmse {last_rgb[1]:.5f}')
+                if self.icp_rgb:
+                    self.icp.promote(c2w)                                                # the pose is final: this frame is the next keyframe
 
         self.estimate_c2w_list[idx] = c2w.clone()
         self.gt_c2w_list[idx] = gt_c2w.clone().cpu()

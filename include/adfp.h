@@ -1547,6 +1547,51 @@ int adfp_icp_step(const float* depth_s, const float* normals_s, const float* dep
 int adfp_icp_end(void* state, double max_shift, double max_angle, float* c2w_out /*[16]*/, float* cam_out /*[7]*/,
                  double* stats /*or NULL*/, int stats_rows, int row, void* stream);
 
+/* ---- RGB-D ICP (icp.RgbdICP, tracking.icp_rgb: the depth ICP's step with a photometric term against the last tracked frame, the
+ * "keyframe" -- its sensor colour, its sensor depth, its final pose -- added to the same normal equations, as Kintinuous,
+ * ElasticFusion and DVO pair the two; no counterpart in the reference) ----  tests/rgbd_icp_ref.py states the rule in numpy.
+ * Conventions are "Depth ICP"'s: the camera point V(u, v, d), f64 arithmetic on f32 loads, a depth is valid when d > 0 and finite.
+ * Every gate is written as !(... <= ...), so a NaN drops the pair.
+ * Frame map (adfp_rgbd_frame_map, one launch): colour [H][W][3] f32 (0..1) and depth [H][W] f32 -> map [H][W][4] f32 = (I, gx, gy, d).
+ *   I = (0.299 r + 0.587 g) + 0.114 b in f64; gx = (I(u + 1, v) - I(u - 1, v)) / 2 and gy = (I(u, v + 1) - I(u, v - 1)) / 2 from the
+ *   UNROUNDED f64 intensities, one rounding at the store; gx = 0 in the first and the last column, gy = 0 in the first and the last
+ *   row; d is the depth's own bits.  A NaN colour gives a NaN.  The 16-byte texel makes each pixel of a bilinear footprint one load.
+ * Photometric pairs of a step.  T is the estimate, p_key (f32 [16]) the keyframe's pose, key its map, cur the current frame's map.
+ *   For every pixel with u % stride == 0, v % stride == 0, a valid d_s = cur.d and a finite I_s = cur.I (no sensor normal is needed):
+ *     x = T V_s;  y = R_key^T (x - t_key);  z = -y.z, required > 0;
+ *     a = (fx y.x) / z + cx, b = (-fy y.y) / z + cy;  u0 = floor(a), v0 = floor(b), required 1 <= u0 <= W - 3 and 1 <= v0 <= H - 3 (all
+ *     four footprint pixels carry central differences);  s = a - u0, t = b - v0;
+ *     each of the four keyframe texels M_ji = key(v0 + j, u0 + i) needs a valid depth with |d_key - z| <= dist_tol (the occlusion gate);
+ *     (I, gx, gy) = ((1-s)(1-t) M_00 + s(1-t) M_01) + ((1-s) t M_10 + s t M_11), in that order of addition;
+ *     r = I_s - I, kept if |r| <= rgb_tol;
+ *     c = ((gx fx) / z, -(gy fy) / z, ((gx fx) y.x - (gy fy) y.y) / z^2);  n = R_key c;  J = [x x n, n], the point-to-plane form for the
+ *     same left twist.
+ * Sums (ADFP_RGBD_SUMS = 31 f64): the 21 upper entries of sum_g J J^T + w sum_p J J^T, the 6 of sum_g J r + w sum_p J r, then sum r_g^2,
+ *   the geometric pair count, sum r_p^2, the photometric pair count (the last four unweighted).  w = rgb_weight >= 0; a photometric
+ *   pair adds w (J_i J_j) and w (J_i r).  Geometric pairs follow adfp_icp_step's rule exactly (the sensor depth is cur's fourth
+ *   channel); per pixel the geometric contribution is added first.  With w = 0 or key_map NULL no photometric pair is evaluated, sums
+ *   29 and 30 are 0, and sums 0..28 are adfp_icp_step's bytes on the same inputs (same grid, same order of addition).
+ * Solve: max(geometric pairs, photometric pairs) < min_pairs gives ADFP_ICP_FEW_PAIRS; otherwise adfp_icp_step's LDL^T, min_pivot
+ *   gate, Exp and state block.  adfp_icp_begin and adfp_icp_end bracket the steps unchanged.  The stats row keeps its meaning (pairs
+ *   and rmse are the geometric ones); rgb_stats [stats_rows][ADFP_RGBD_STATS = 2] receives (photometric pairs, photometric rmse) in
+ *   the same row, zeros from a step after a failed one.  sums (device [31], or NULL) receives the step's sums.
+ * workspace: adfp_rgbd_workspace_bytes(H, W) = the workgroups of adfp_icp_workspace_bytes x 31 x 8 (0 for H or W outside [1, 32768]).
+ * Asynchronous on `stream`, no allocation, no pointer kept, no read-back, graph-capturable; adfp_rgbd_step is two launches.  Errors,
+ * all before any launch: ADFP_E_ARG for a null pointer (sums may be NULL; key_map and p_key are both given or both NULL), a map that
+ * is not 16-byte aligned, a block that is not 8-byte aligned, a NaN or negative rgb_weight, a NaN rgb_tol, tolerance or intrinsic, fx
+ * or fy 0, H, W or stride < 1, a workspace below adfp_rgbd_workspace_bytes, a stats row outside [0, stats_rows); ADFP_E_UNSUPPORTED
+ * for H or W above 32768. */
+#define ADFP_RGBD_SUMS 31
+#define ADFP_RGBD_STATS 2
+size_t adfp_rgbd_workspace_bytes(int H, int W);
+int adfp_rgbd_frame_map(const float* color /*[H][W][3]*/, const float* depth /*[H][W]*/, int H, int W, float* map /*[H][W][4], 16-byte aligned*/,
+                        void* stream);
+int adfp_rgbd_step(const float* cur_map, const float* normals_s, const float* depth_m, const float* normals_m, const float* p_ref /*[16]*/,
+                   const float* key_map /*or NULL*/, const float* p_key /*[16], NULL iff key_map is*/, int H, int W, float fx, float fy, float cx,
+                   float cy, int stride, double dist_tol, double cos_tol, double rgb_weight, double rgb_tol, double min_pivot, double min_pairs,
+                   void* state, double* stats /*[stats_rows][6]*/, double* rgb_stats /*[stats_rows][2]*/, int stats_rows, int row,
+                   double* sums /*[31] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -511,6 +511,36 @@ def main(template, d):
                                thousands(ic['valid_model_normals']), ic['pivot_ratio_min'], ic['refine_over_track10']))
     else:
         v['icp_numbers'] = 'No run of `tools/icp_bench.py` is in `profiles/`: not measured.'
+    # RGB-D ICP beside the depth ICP (tools/icp_bench.py --rgbd-json)
+    rg_path = Q('rgbd_icp_bench.json')
+    if os.path.exists(rg_path):
+        rg = json.load(open(rg_path))
+        cell3 = lambda s, f='%.3f': (f + ' (' + f + ', ' + f + ')') % (s['median_ms'], s['min_ms'], s['max_ms'])
+        rows = ['| leg | ms, median (min, max) |', '|---|---|']
+        for label, key in (('frame map of one frame (`adfp_rgbd_frame_map`)', 'frame_map'),
+                           ('one joint step at stride 4 (with `adfp_icp_begin`)', 'joint_s4'), ('… the depth-only step beside it', 'step_s4'),
+                           ('one joint step at stride 2', 'joint_s2'), ('… the depth-only step beside it', 'step_s2'),
+                           ('one joint step at stride 1', 'joint_s1'), ('… the depth-only step beside it', 'step_s1'),
+                           ('`promote` (the map\'s copy, the pose\'s upload)', 'promote'),
+                           ('`RgbdICP.refine` as a whole (with `set_keyframe` before it)', 'rgbd_refine'), ('`DepthICP.refine` beside it', 'refine')):
+            rows.append('| %s | %s |' % (label, cell3(rg[key])))
+        v['rgbd_numbers'] = ('Measured on one MI355X (`profiles/rgbd_icp_bench.json`, one run of `tools/icp_bench.py --reps %d --rgbd-json`): section 5.13\'s '
+                             'frame, %d × %d, the colour `tests/test_gpu_slam_run.py`\'s rule at every pixel\'s world point, the keyframe the scene seen from '
+                             '%.0f mm and %.0f mrad away, `rgb_weight` %g, `rgb_tol` %g.  Device events around each leg, the legs alternating within a '
+                             'repetition:\n\n'
+                             % (rg['reps'], rg['frame'][0], rg['frame'][1], rg['keyframe_distance_m_rad'][0] * 1e3, rg['keyframe_distance_m_rad'][1] * 1e3,
+                                rg['rgb_weight'], rg['rgb_tol'])
+                             + '\n'.join(rows) + '\n\n'
+                             + 'The refinement ended with status %d (0 = OK) %.2f mm and %.3f° from the true pose (the guess: %.1f mm, %.2f°), on %s to %s '
+                               'geometric and %s to %s photometric pairs per step, smallest pivot ratio %.1e.  `RgbdICP.refine` takes %.2f × the time of '
+                               '`DepthICP.refine`.  No threshold is set and no speed target: these are the first times of this path.'
+                             % (rg['status'], rg['error_after_m_rad'][0] * 1e3, rg['error_after_m_rad'][1] * 57.29577951308232,
+                                rg['error_before_m_rad'][0] * 1e3, rg['error_before_m_rad'][1] * 57.29577951308232,
+                                thousands(int(min(rg['pairs_per_step']))), thousands(int(max(rg['pairs_per_step']))),
+                                thousands(int(min(rg['rgb_pairs_per_step']))), thousands(int(max(rg['rgb_pairs_per_step']))), rg['pivot_ratio_min'],
+                                rg['rgbd_refine_over_refine']))
+    else:
+        v['rgbd_numbers'] = 'No run of `tools/icp_bench.py --rgbd-json` is in `profiles/`: the times of this path have not been measured.'
     s = open(template).read()
     out = re.sub(r'@@(\w+)@@', lambda m: v.get(m.group(1), m.group(0)), s)
     sys.stdout.write(out)

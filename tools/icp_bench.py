@@ -8,10 +8,18 @@ a corner-facing pose inside the room with the guess 35 mm / 1.5 degrees off.  Th
   refine     DepthICP.refine as a whole: upload of the guess, copy of the sensor depth, raycast, normals, steps
   track10    ten TrackerIteration.step replays of 200 pixels after a new_frame: the tracking the refinement precedes
 
-Device events around each leg, median (min, max) of `--reps` repetitions after a warm-up; the legs alternate within a repetition.  No
-thresholds: the numbers go into DESIGN.md section 5.13.
+The RGB-D ICP (icp.RgbdICP, csrc/adfp_rgbd.h) on the same frame, the colour test_gpu_slam_run's rule at every pixel's world point, the
+keyframe the scene seen from 36 mm / 27 mrad away (tests/rgbd_icp_ref.py's KEY_TWIST):
 
-    python tools/icp_bench.py [--reps 7] [--json profiles/icp_bench.json]
+  frame_map      adfp_rgbd_frame_map of one frame
+  joint_sN       one adfp_rgbd_step over every N-th pixel, beside step_sN
+  promote        RgbdICP.promote: the map's copy and the pose's upload
+  rgbd_refine    RgbdICP.refine as a whole, beside refine
+
+Device events around each leg, median (min, max) of `--reps` repetitions after a warm-up; the legs alternate within a repetition.  No
+thresholds: the numbers go into DESIGN.md sections 5.13 and 5.13.1.
+
+    python tools/icp_bench.py [--reps 7] [--json profiles/icp_bench.json] [--rgbd-json profiles/rgbd_icp_bench.json]
 """
 import argparse
 import json
@@ -25,9 +33,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import icp_ref                                                 # noqa: E402
+import rgbd_icp_ref                                            # noqa: E402
 import attentive_dfprior_amd as A                              # noqa: E402
 from attentive_dfprior_amd import _lib, common, synthetic      # noqa: E402
-from attentive_dfprior_amd.icp import DepthICP                 # noqa: E402
+from attentive_dfprior_amd.icp import DepthICP, RgbdICP        # noqa: E402
 from attentive_dfprior_amd.tracking import TrackerIteration    # noqa: E402
 
 DEV = 'cuda:0'
@@ -54,6 +63,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--json', default=None)
+    ap.add_argument('--rgbd-json', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'icp_bench needs a GPU'
     assert a.reps >= 5, 'at least 5 repetitions'
@@ -91,10 +101,38 @@ def main():
         for _ in range(10):
             fused.step(200)
 
+    # the RGB-D ICP on the same frame
+    rgbd = RgbdICP(sc.tsdf_volume, tb, *GEO, engine=rend._engine)
+    Pn = P.cpu().numpy()
+    Kn = rgbd_icp_ref.key_pose(Pn)
+    key_depth = icp.raycaster.render_depth(torch.from_numpy(Kn), *GEO)
+    paint = lambda d, c2w: torch.from_numpy(rgbd_icp_ref.color_of(d.cpu().numpy(), c2w, *GEO[2:])).to(DEV)
+    sensor_color, key_color = paint(sensor, Pn), paint(key_depth, Kn)
+    rgbd.set_keyframe(torch.from_numpy(Kn), key_color, key_depth)
+    rgbd.refine(G, sensor, sensor_color)
+    rgbd_rows, rgbd_rgb, rgbd_got = rgbd.last_stats().numpy(), rgbd.last_rgb_stats().numpy(), rgbd.c2w_out.cpu().numpy()
+    rgbd_e1 = icp_ref.pose_error(rgbd_got, Pn)
+    rgbd_final = rgbd.c2w_out.clone()
+
+    def joint_step(stride):
+        def fn():
+            rgbd._begin(rgbd.p_ref, st)
+            rgbd._rgbd_step(rgbd.maps[0], rgbd.normals, rgbd.depth[1], rgbd.p_ref, stride, 0, st)
+        return fn
+
+    def rgbd_refine():
+        rgbd.set_keyframe(torch.from_numpy(Kn), key_color, key_depth)      # not timed apart: one frame_map launch and a pose upload
+        rgbd.refine(G, sensor, sensor_color)
+
+    rgbd_legs = {'frame_map': lambda: rgbd.frame_map(sensor_color, sensor, out=rgbd.maps[0]),
+                 'joint_s4': joint_step(4), 'joint_s2': joint_step(2), 'joint_s1': joint_step(1),
+                 'promote': lambda: rgbd.promote(rgbd_final), 'rgbd_refine': rgbd_refine}
+
     legs = {'raycast': lambda: icp.raycaster.render_depth(icp.p_ref, *GEO, out=icp.depth[1:2]),
             'normals': lambda: icp.compute_normals(icp.depth, out=icp.normals),
             'step_s4': one_step(4), 'step_s2': one_step(2), 'step_s1': one_step(1),
             'steps': icp.run_steps, 'refine': lambda: icp.refine(G, sensor), 'track10': track10}
+    legs.update(rgbd_legs)
     for fn in legs.values():
         fn()
     torch.cuda.synchronize()
@@ -111,13 +149,25 @@ def main():
     res.update({k: stats(v) for k, v in t.items()})
     res['refine_over_track10'] = res['refine']['median_ms'] / res['track10']['median_ms']
     for k in legs:
-        print(f'{k:8s} {res[k]["median_ms"]:.3f} ({res[k]["min_ms"]:.3f}, {res[k]["max_ms"]:.3f}) ms', flush=True)
+        print(f'{k:11s} {res[k]["median_ms"]:.3f} ({res[k]["min_ms"]:.3f}, {res[k]["max_ms"]:.3f}) ms', flush=True)
     print(f'status {res["status"]}, pairs {rows[0, 0]:.0f} .. {rows[-2, 0]:.0f}, error {e0[0] * 1e3:.1f} mm {np.degrees(e0[1]):.2f} deg -> '
           f'{e1[0] * 1e3:.2f} mm {np.degrees(e1[1]):.3f} deg; refine / ten tracking iterations = {res["refine_over_track10"]:.2f}')
     assert common.get_camera_from_tensor(cam).shape == (3, 4)
     if a.json:
         with open(a.json, 'w') as f:
-            json.dump(res, f, indent=1)
+            json.dump({k: v for k, v in res.items() if k not in rgbd_legs}, f, indent=1)
+            f.write('\n')
+    if a.rgbd_json:
+        out = {k: res[k] for k in ('device', 'reps', 'frame', 'volume', 'levels', 'begin_is_timed_with_each_step', 'step_s4', 'step_s2', 'step_s1',
+                                   'refine')}
+        out.update({k: res[k] for k in rgbd_legs})
+        out.update({'rgb_weight': rgbd.rgb_weight, 'rgb_tol': rgbd.rgb_tol, 'rgbd_refine_sets_the_keyframe_too': True,
+                    'keyframe_distance_m_rad': list(icp_ref.pose_error(Kn, Pn)), 'status': int(rgbd_rows[-1, 5]),
+                    'pairs_per_step': rgbd_rows[:-1, 0].tolist(), 'rgb_pairs_per_step': rgbd_rgb[:-1, 0].tolist(),
+                    'pivot_ratio_min': float(rgbd_rows[:-1, 2].min()), 'error_before_m_rad': list(e0), 'error_after_m_rad': list(rgbd_e1),
+                    'rgbd_refine_over_refine': res['rgbd_refine']['median_ms'] / res['refine']['median_ms']})
+        with open(a.rgbd_json, 'w') as f:
+            json.dump(out, f, indent=1)
             f.write('\n')
     return 0
 
