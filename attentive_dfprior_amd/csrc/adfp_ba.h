@@ -8,10 +8,11 @@
 //                             (k_camera_from_tensor_bwd) [-> the Adam step of its 7 parameters]
 //   k_cameras_from_tensors    camera tensors -> c2w at F destinations (the write-back into the keyframe store's rows)
 //
-// The arithmetic is that of the per-frame kernels named above, operation by operation and in their summation order, so the
-// results are equal bit for bit to calling those entries frame by frame, and reproducible from run to run.
+// Each step is the function of adfp_camera.h that the per-frame kernel named above calls, so the results are equal bit for bit to
+// calling those entries frame by frame, and reproducible from run to run.
 #pragma once
 #include "adfp_device.h"
+#include "adfp_camera.h"
 
 __global__ __launch_bounds__(256) void k_ba_head(adfp_ba_head_args a) {
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -29,25 +30,13 @@ __global__ __launch_bounds__(256) void k_ba_head(adfp_ba_head_args a) {
 #pragma unroll
         for (int m = 0; m < 16; ++m) a.c2w[16 * f + m] = c2w[m];
     }
-    // k_sample_keyframes
-    const int Ww = a.W1 - a.W0;
-    const long long k = fr.idx[r];
-    const int row = a.H0 + (int)(k / Ww), col = a.W0 + (int)(k % Ww);
-    const long long p = (long long)row * a.W + col;
-    a.gt_depth[t] = fr.depth_img[p];
-    a.gt_color[3 * t] = fr.color_img[3 * p]; a.gt_color[3 * t + 1] = fr.color_img[3 * p + 1]; a.gt_color[3 * t + 2] = fr.color_img[3 * p + 2];
-    const float pi = (float)col, pj = (float)row;
+    float pi, pj;
+    a.gt_depth[t] = window_sample(fr.idx[r], a.H0, a.W0, a.W1 - a.W0, a.W, fr.depth_img, fr.color_img, pi, pj, a.gt_color + 3 * t);
     a.pix_i[t] = pi; a.pix_j[t] = pj;
-    const float dx = (pi - a.cx) / a.fx, dy = -(pj - a.cy) / a.fy, dz = -1.f;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        a.rays_d[3 * t + m] = __fadd_rn(__fadd_rn(__fmul_rn(dx, c2w[4 * m]), __fmul_rn(dy, c2w[4 * m + 1])), __fmul_rn(dz, c2w[4 * m + 2]));
-        a.rays_o[3 * t + m] = c2w[4 * m + 3];
-    }
+    ray_from_uv(pi, pj, a.fx, a.fy, a.cx, a.cy, c2w, a.rays_o + 3 * t, a.rays_d + 3 * t);
 }
 
-// Workgroup f reduces rows [f n, (f + 1) n) with k_tracker_tail's partition (thread j takes rows j, j + 256, ... of the segment, then
-// wave_sum, then the four waves' sums pairwise), so frame f's g_c2w / g_cam are what the single-frame entries give for that segment.
+// Workgroup f reduces rows [f n, (f + 1) n), so frame f's g_c2w / g_cam are what the single-frame entries give for that segment.
 __global__ __launch_bounds__(256) void k_ba_tail(adfp_ba_tail_args a) {
     __shared__ float s[4][12];
     __shared__ float s_g[16];
@@ -58,31 +47,8 @@ __global__ __launch_bounds__(256) void k_ba_tail(adfp_ba_tail_args a) {
         return;
     }
     const long long base = (long long)f * a.n;
-    const float* pix_i = a.pix_i + base; const float* pix_j = a.pix_j + base;
-    const float* g_o = a.g_rays_o + 3 * base; const float* g_d = a.g_rays_d + 3 * base;
-    float acc[12];
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = 0.f;
-    for (int i = threadIdx.x; i < a.n; i += 256) {
-        const float dir[3] = {(pix_i[i] - a.cx) / a.fx, -(pix_j[i] - a.cy) / a.fy, -1.f};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float gd = g_d[3 * i + k];
-#pragma unroll
-            for (int m = 0; m < 3; ++m) acc[4 * k + m] = fmaf(gd, dir[m], acc[4 * k + m]);
-            acc[4 * k + 3] += g_o[3 * i + k];
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = wave_sum(acc[t]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int t = 0; t < 12; ++t) s[threadIdx.x >> 6][t] = acc[t];
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        const float v = threadIdx.x < 12 ? (s[0][threadIdx.x] + s[1][threadIdx.x]) + (s[2][threadIdx.x] + s[3][threadIdx.x]) : 0.f;
-        s_g[threadIdx.x] = v; a.g_c2w[16 * f + threadIdx.x] = v;
-    }
+    const float v = ray_cotangents_to_c2w(a.pix_i + base, a.pix_j + base, a.n, a.fx, a.fy, a.cx, a.cy, a.g_rays_o + 3 * base, a.g_rays_d + 3 * base, s);
+    if (threadIdx.x < 16) { s_g[threadIdx.x] = v; a.g_c2w[16 * f + threadIdx.x] = v; }
     __syncthreads();
     if (threadIdx.x != 0) return;
     // one thread from here on: 7 parameters
@@ -93,12 +59,7 @@ __global__ __launch_bounds__(256) void k_ba_tail(adfp_ba_tail_args a) {
 #pragma unroll
     for (int k = 0; k < 7; ++k) g_cam[k] = g[k];
     if (!a.step || (a.skip_flag && *a.skip_flag)) return;
-    const float step_size = a.derived[0], sqrt_bc2 = a.derived[1];
-    if (sqrt_bc2 == 0.f) return;                            // adam_prep_group's "skip this iteration"
-    AdamArgs ad;
-    ad.param = cam; ad.grad = g_cam; ad.exp_avg = a.exp_avg + 7 * f; ad.exp_avg_sq = a.exp_avg_sq + 7 * f; ad.mask = nullptr;
-    ad.nvox = 7; ad.C = 1; ad.beta1 = a.beta1; ad.beta2 = a.beta2; ad.eps = a.eps; ad.step_size = 0.f; ad.sqrt_bc2 = 1.f; ad.derived = nullptr;
-    for (int k = 0; k < 7; ++k) adam_one(ad, k, step_size, sqrt_bc2);
+    pose_adam(cam, g_cam, a.exp_avg + 7 * f, a.exp_avg_sq + 7 * f, 0, 7, a.derived[0], a.derived[1], a.beta1, a.beta2, a.eps);
 }
 
 struct CamerasJobs { const float* cam; float* dst[ADFP_KEYFRAMES_MAX]; int n_frames; };
@@ -110,7 +71,7 @@ __global__ void k_cameras_from_tensors(CamerasJobs a) {
 
 extern "C" int adfp_ba_head(const adfp_ba_head_args* a, void* stream) {
     if (!a || a->n_frames < 1 || a->n_frames > ADFP_KEYFRAMES_MAX || a->n < 1) return ADFP_E_ARG;
-    if (a->H0 < 0 || a->W0 < 0 || a->H1 > a->H || a->W1 > a->W || a->H1 <= a->H0 || a->W1 <= a->W0) return ADFP_E_ARG;
+    if (bad_window(a->H0, a->H1, a->W0, a->W1, a->H, a->W)) return ADFP_E_ARG;
     if (!a->cam || !a->c2w || !a->pix_i || !a->pix_j || !a->rays_o || !a->rays_d || !a->gt_depth || !a->gt_color) return ADFP_E_ARG;
     for (int f = 0; f < a->n_frames; ++f) {
         const adfp_ba_frame& k = a->frames[f];

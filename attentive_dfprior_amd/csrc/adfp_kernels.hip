@@ -252,70 +252,33 @@ __global__ void k_pack_attention(const float* __restrict__ flat, float* __restri
 // =====================================================================================
 // a1: get_rays (common.py:254-272)
 // =====================================================================================
+#include "adfp_camera.h"        // the pixel, ray, bound and pose rules that a1-a3, the first launch and the Tracker / Mapper glue share
 __global__ void k_get_rays(int H, int W, float fx, float fy, float cx, float cy, const float* __restrict__ c2w,
                            float* __restrict__ ro, float* __restrict__ rd) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
     const int j = idx / W, i = idx - j * W;
-    // torch.linspace(0, W-1, W) is exactly the integers; dirs = ((i-cx)/fx, -(j-cy)/fy, -1)
-    const float dx = ((float)i - cx) / fx, dy = -((float)j - cy) / fy, dz = -1.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        // torch.sum(dirs * c2w[:3,:3], -1): products then left-to-right adds
-        const float s = __fadd_rn(__fadd_rn(__fmul_rn(dx, c2w[4 * k + 0]), __fmul_rn(dy, c2w[4 * k + 1])),
-                                  __fmul_rn(dz, c2w[4 * k + 2]));
-        rd[3 * idx + k] = s;
-        ro[3 * idx + k] = c2w[4 * k + 3];
-    }
+    // torch.linspace(0, W-1, W) is exactly the integers
+    ray_from_uv((float)i, (float)j, fx, fy, cx, cy, c2w, ro + 3 * idx, rd + 3 * idx);
 }
 
 // =====================================================================================
 // a2: get_rays_from_uv (common.py:76-91): the rays through n given pixels, and the gradient w.r.t. the camera pose that
 // the Tracker and the Mapper's bundle adjustment take through them (src/Tracker.py:97, src/Mapper.py:425)
 // =====================================================================================
-// The ray through pixel (pi, pj) (column, row) of the camera c2w (rows 0-2 of a row-major [4,4] or [3,4]); also the sample points of
-// the Mapper's keyframe selection (adfp_keyframes.h)
-ADFP_DEV void ray_from_uv(float pi, float pj, float fx, float fy, float cx, float cy, const float* __restrict__ c2w, float* ro, float* rd) {
-    const float dx = (pi - cx) / fx, dy = -(pj - cy) / fy, dz = -1.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        // torch.sum(dirs * c2w[:3,:3], -1): products then left-to-right adds
-        rd[k] = __fadd_rn(__fadd_rn(__fmul_rn(dx, c2w[4 * k + 0]), __fmul_rn(dy, c2w[4 * k + 1])), __fmul_rn(dz, c2w[4 * k + 2]));
-        ro[k] = c2w[4 * k + 3];
-    }
-}
 __global__ void k_rays_from_uv(const float* __restrict__ pi, const float* __restrict__ pj, int n, float fx, float fy, float cx, float cy,
                                const float* __restrict__ c2w, float* __restrict__ ro, float* __restrict__ rd) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     ray_from_uv(pi[idx], pj[idx], fx, fy, cx, cy, c2w, ro + 3 * idx, rd + 3 * idx);
 }
-// g_c2w[k][m] = sum_n g_d[n][k] * dirs[n][m] (m < 3), g_c2w[k][3] = sum_n g_o[n][k]; rows 3 of the 4x4 get zero.
 // One workgroup: pixel batches are a few hundred to a few thousand rays.
 __global__ __launch_bounds__(256) void k_rays_from_uv_bwd(const float* __restrict__ pi, const float* __restrict__ pj, int n, float fx, float fy,
                                                           float cx, float cy, const float* __restrict__ g_o, const float* __restrict__ g_d,
                                                           float* __restrict__ g_c2w) {
     __shared__ float s[4][12];
-    float acc[12];
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float dir[3] = {(pi[i] - cx) / fx, -(pj[i] - cy) / fy, -1.f};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float gd = g_d ? g_d[3 * i + k] : 0.f;
-#pragma unroll
-            for (int m = 0; m < 3; ++m) acc[4 * k + m] = fmaf(gd, dir[m], acc[4 * k + m]);
-            acc[4 * k + 3] += g_o ? g_o[3 * i + k] : 0.f;
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = wave_sum(acc[t]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int t = 0; t < 12; ++t) s[threadIdx.x >> 6][t] = acc[t];
-    __syncthreads();
-    if (threadIdx.x < 16) g_c2w[threadIdx.x] = threadIdx.x < 12 ? (s[0][threadIdx.x] + s[1][threadIdx.x]) + (s[2][threadIdx.x] + s[3][threadIdx.x]) : 0.f;
+    const float v = ray_cotangents_to_c2w(pi, pj, n, fx, fy, cx, cy, g_o, g_d, s);
+    if (threadIdx.x < 16) g_c2w[threadIdx.x] = v;
 }
 
 // =====================================================================================
@@ -338,19 +301,7 @@ __global__ __launch_bounds__(1024) void k_prefilter(const float* __restrict__ ro
     __syncthreads();
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + threadIdx.x;
-        bool keep = false;
-        if (i < n) {
-            double t = INFINITY; bool nan = false;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double o = (double)ro[3 * i + k], d = (double)rd[3 * i + k];
-                const double t0 = (b[2 * k] - o) / d, t1 = (b[2 * k + 1] - o) / d;
-                nan |= (t0 != t0) | (t1 != t1);            // torch.max / torch.min propagate NaN
-                const double tm = t0 > t1 ? t0 : t1;
-                t = tm < t ? tm : t;
-            }
-            keep = !nan && (t >= (double)depth[i]);
-        }
+        const bool keep = i < n && ray_in_bound(b, ro + 3 * i, rd + 3 * i, depth[i]);
         const unsigned long long m = __ballot(keep);
         if (lane == 0) s_w[wv] = __popcll(m);
         __syncthreads();
@@ -1358,13 +1309,13 @@ __global__ __launch_bounds__(256) void k_pack_multi(PackJobs j) { pack_multi_blo
 // the first launch of a render call: the weight images it was handed to pack (adfp_render_args.pack_jobs) and the zero fill of its
 // device words
 // ... and, since round 6, two more kinds of blocks, so that a frame (or a rank's share of one) needs no launch of its own for either:
-//   rays:   the rays of pixels [first, first + n) of an H x W frame (k_get_rays' arithmetic, src/common.py:254-272)
+//   rays:   the rays of pixels [first, first + n) of an H x W frame (what k_get_rays gives for them, src/common.py:254-272)
 //   segmax: SEGMAX_PARTS partial maxima of gt_depth per segment of `seg` rays, as ordered uints, plain stores (no atomics: nothing
 //           has to be zeroed before this launch); k_sample's lanes fold them.  Block (s, p) takes the p-th sixteenth of segment s.
 struct RayJob { const float* c2w; int W; float fx, fy, cx, cy; int first, n; float* ro; float* rd; };
 struct SegJob { const float* d; int n, seg, nseg; unsigned* parts;
                 // pre-filter mode (adfp_render_args.prefilter_bound): the maximum is taken over the rays the Mapper's bounding-box test keeps,
-                // and the test's verdict is written to keep[ray] -- k_prefilter_mask's arithmetic (adfp_mapper_iter.h)
+                // and the test's verdict is written to keep[ray], like k_prefilter_mask does (adfp_mapper_iter.h)
                 const float* ro; const float* rd; const double* bnd; unsigned char* keep; };
 struct ForwardHeadArgs { PackJobs p; ZeroJobs z; int nb_pack, nb_zero, nb_rays; RayJob rj; SegJob sj; };
 __device__ inline void rays_block(const RayJob& j, unsigned blk) {
@@ -1372,13 +1323,7 @@ __device__ inline void rays_block(const RayJob& j, unsigned blk) {
     if (k >= j.n) return;
     const int idx = j.first + k;
     const int row = idx / j.W, col = idx - row * j.W;
-    const float dx = ((float)col - j.cx) / j.fx, dy = -((float)row - j.cy) / j.fy, dz = -1.f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float s = __fadd_rn(__fadd_rn(__fmul_rn(dx, j.c2w[4 * a + 0]), __fmul_rn(dy, j.c2w[4 * a + 1])), __fmul_rn(dz, j.c2w[4 * a + 2]));
-        j.rd[3 * k + a] = s;
-        j.ro[3 * k + a] = j.c2w[4 * a + 3];
-    }
+    ray_from_uv((float)col, (float)row, j.fx, j.fy, j.cx, j.cy, j.c2w, j.ro + 3 * k, j.rd + 3 * k);
 }
 __device__ inline void segmax_block(const SegJob& j, unsigned blk) {
     __shared__ unsigned s_m[4];
@@ -1393,17 +1338,8 @@ __device__ inline void segmax_block(const SegJob& j, unsigned blk) {
         for (int k = 0; k < 6; ++k) b[k] = j.bnd[k];
         float mx = -INFINITY;                           // k_prefilter_mask's start value: no kept ray -> -inf
         for (long long i = lo + threadIdx.x; i < hi; i += 256) {
-            double t = INFINITY; bool nan = false;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double o = (double)j.ro[3 * i + k], d = (double)j.rd[3 * i + k];
-                const double t0 = (b[2 * k] - o) / d, t1 = (b[2 * k + 1] - o) / d;
-                nan |= (t0 != t0) | (t1 != t1);        // torch.max / torch.min propagate NaN
-                const double tm = t0 > t1 ? t0 : t1;
-                t = tm < t ? tm : t;
-            }
             const float dep = j.d[i];
-            const bool k_ = !nan && (t >= (double)dep);
+            const bool k_ = ray_in_bound(b, j.ro + 3 * i, j.rd + 3 * i, dep);
             j.keep[i] = k_ ? 1 : 0;
             if (k_) mx = dep > mx ? dep : mx;
         }
@@ -2180,13 +2116,6 @@ int adfp_adam_step(int n_cl_groups, const adfp_adam_cl_group* cl_groups, int n_g
     ADFP_CHECK_LAUNCH();
     return 0;
 }
-int adfp_prefilter_mask(const float* rays_o, const float* rays_d, const float* gt_depth, int n_rays, const double* bound_dev,
-                        unsigned char* keep, float* depth_max, void* stream) {
-    if (!rays_o || !rays_d || !gt_depth || !bound_dev || !keep || !depth_max || n_rays <= 0) return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_prefilter_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, rays_o, rays_d, gt_depth, n_rays, bound_dev, keep, depth_max);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
 static int mapper_loss_impl(const adfp_loss_args* l, const AdamPrepArgs* prep, double* scratch, void* stream);
 int adfp_mapper_loss(const adfp_loss_args* l, void* stream) { return mapper_loss_impl(l, nullptr, nullptr, stream); }
 int adfp_mapper_loss_step(const adfp_loss_args* l, void* scratch, size_t scratch_bytes, int* steps, float* derived, int n_groups, const float* lr,
@@ -2212,198 +2141,6 @@ static int mapper_loss_impl(const adfp_loss_args* l, const AdamPrepArgs* prep, d
     a.scratch = scratch; a.prep.n = 0;
     if (prep) a.prep = *prep;
     hipLaunchKernelGGL(k_mapper_loss, dim3((l->n_rays + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);      // one thread per ray
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-
-}  // extern "C"
-// ---- the Tracker iteration's head and tail, one workgroup each (adfp_tracker_head / adfp_tracker_tail) ----------------------------
-__global__ __launch_bounds__(1024) void k_tracker_head(adfp_tracker_head_args a) {
-    __shared__ float s_m[16];
-    float c2w[16];
-    camera_from_tensor_dev(a.cam, c2w);                     // every thread: 30 operations, the same values
-    if (threadIdx.x < 16) a.c2w[threadIdx.x] = c2w[threadIdx.x];
-    double b[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) b[k] = a.bound[k];
-    const int Ww = a.W1 - a.W0;
-    float mx = -INFINITY;
-    for (int t = threadIdx.x; t < a.n; t += 1024) {
-        // k_select_pixels
-        const long long k = a.idx[t];
-        const int row = a.H0 + (int)(k / Ww), col = a.W0 + (int)(k % Ww);
-        const float pi = (float)col, pj = (float)row;
-        a.pix_i[t] = pi; a.pix_j[t] = pj;
-        const long long p = (long long)row * a.W + col;
-        const float dep = a.depth_img[p];
-        a.gt_depth[t] = dep;
-        a.gt_color[3 * t] = a.color_img[3 * p]; a.gt_color[3 * t + 1] = a.color_img[3 * p + 1]; a.gt_color[3 * t + 2] = a.color_img[3 * p + 2];
-        // k_rays_from_uv
-        const float dx = (pi - a.cx) / a.fx, dy = -(pj - a.cy) / a.fy, dz = -1.f;
-        float ro[3], rd[3];
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-            rd[m] = __fadd_rn(__fadd_rn(__fmul_rn(dx, c2w[4 * m + 0]), __fmul_rn(dy, c2w[4 * m + 1])), __fmul_rn(dz, c2w[4 * m + 2]));
-            ro[m] = c2w[4 * m + 3];
-            a.rays_d[3 * t + m] = rd[m]; a.rays_o[3 * t + m] = ro[m];
-        }
-        // k_prefilter_mask
-        double tt = INFINITY; bool nan = false;
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-            const double o = (double)ro[m], d = (double)rd[m];
-            const double t0 = (b[2 * m] - o) / d, t1 = (b[2 * m + 1] - o) / d;
-            nan |= (t0 != t0) | (t1 != t1);
-            const double tm = t0 > t1 ? t0 : t1;
-            tt = tm < tt ? tm : tt;
-        }
-        const bool k_ = !nan && (tt >= (double)dep);
-        a.keep[t] = k_ ? 1 : 0;
-        if (k_) mx = dep > mx ? dep : mx;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float v = __shfl_xor(mx, o); mx = v > mx ? v : mx; }
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = s_m[0];
-        for (int w = 1; w < 16; ++w) m = s_m[w] > m ? s_m[w] : m;
-        *a.depth_max = m;
-    }
-}
-__global__ __launch_bounds__(256) void k_tracker_tail(adfp_tracker_tail_args a) {
-    __shared__ float s[4][12];
-    __shared__ float s_g[16];
-    // k_rays_from_uv_bwd
-    float acc[12];
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = 0.f;
-    for (int i = threadIdx.x; i < a.n; i += 256) {
-        const float dir[3] = {(a.pix_i[i] - a.cx) / a.fx, -(a.pix_j[i] - a.cy) / a.fy, -1.f};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float gd = a.g_rays_d ? a.g_rays_d[3 * i + k] : 0.f;
-#pragma unroll
-            for (int m = 0; m < 3; ++m) acc[4 * k + m] = fmaf(gd, dir[m], acc[4 * k + m]);
-            acc[4 * k + 3] += a.g_rays_o ? a.g_rays_o[3 * i + k] : 0.f;
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = wave_sum(acc[t]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int t = 0; t < 12; ++t) s[threadIdx.x >> 6][t] = acc[t];
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        const float v = threadIdx.x < 12 ? (s[0][threadIdx.x] + s[1][threadIdx.x]) + (s[2][threadIdx.x] + s[3][threadIdx.x]) : 0.f;
-        s_g[threadIdx.x] = v; a.g_c2w[threadIdx.x] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    // one thread from here on: 7 parameters
-    float g_cam[7];
-    camera_from_tensor_bwd_dev(a.cam, s_g, g_cam);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) a.g_cam[k] = g_cam[k];
-    if (!a.step) return;
-    const bool better_before = *a.loss < *a.best_loss;
-    if (a.n_groups == 2 && better_before) {                 // k_keep_best before the step
-#pragma unroll
-        for (int k = 0; k < 7; ++k) a.best_cam[k] = a.cam[k];
-        *a.best_loss = *a.loss;
-    }
-    AdamPrepArgs pa;
-    pa.steps = a.steps; pa.derived = a.derived; pa.n = a.n_groups; pa.beta1 = a.beta1; pa.beta2 = a.beta2; pa.skip = a.skip_flag;
-    for (int g = 0; g < ADFP_ADAM_MAX_GROUPS; ++g) pa.lr[g] = g < a.n_groups ? a.lr[g] : -1.f;
-    for (int g = 0; g < a.n_groups; ++g) adam_prep_group(pa, g);
-    for (int g = 0; g < a.n_groups; ++g) {
-        const int off = a.n_groups == 2 ? (g == 0 ? 4 : 0) : 0, cnt = a.n_groups == 2 ? (g == 0 ? 3 : 4) : 7;
-        const float step_size = a.derived[2 * g], sqrt_bc2 = a.derived[2 * g + 1];
-        if (sqrt_bc2 == 0.f) continue;                      // adam_prep_group's "skip this iteration"
-        AdamArgs ad;
-        ad.param = a.cam + off; ad.grad = a.g_cam + off; ad.exp_avg = a.exp_avg + off; ad.exp_avg_sq = a.exp_avg_sq + off; ad.mask = nullptr;
-        ad.nvox = cnt; ad.C = 1; ad.beta1 = a.beta1; ad.beta2 = a.beta2; ad.eps = a.eps; ad.step_size = 0.f; ad.sqrt_bc2 = 1.f; ad.derived = nullptr;
-        for (int k = 0; k < cnt; ++k) adam_one(ad, k, step_size, sqrt_bc2);
-    }
-    if (a.n_groups == 1 && better_before) {                 // k_keep_best after the step: the stepped pose, this iteration's loss
-#pragma unroll
-        for (int k = 0; k < 7; ++k) a.best_cam[k] = a.cam[k];
-        *a.best_loss = *a.loss;
-    }
-}
-extern "C" {
-int adfp_tracker_head(const adfp_tracker_head_args* a, void* stream) {
-    if (!a || a->n < 0 || a->H0 < 0 || a->W0 < 0 || a->H1 > a->H || a->W1 > a->W || a->H1 <= a->H0 || a->W1 <= a->W0) return ADFP_E_ARG;
-    if (!a->cam || !a->c2w || !a->bound || !a->keep || !a->depth_max) return ADFP_E_ARG;
-    if (a->n > 0 && (!a->idx || !a->depth_img || !a->color_img || !a->pix_i || !a->pix_j || !a->gt_depth || !a->gt_color || !a->rays_o || !a->rays_d)) return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_tracker_head, dim3(1), dim3(1024), 0, (hipStream_t)stream, *a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-int adfp_tracker_tail(const adfp_tracker_tail_args* a, void* stream) {
-    if (!a || a->n < 0 || !a->cam || !a->g_c2w || !a->g_cam) return ADFP_E_ARG;
-    if (a->n > 0 && (!a->pix_i || !a->pix_j)) return ADFP_E_ARG;
-    if (a->step && (!a->exp_avg || !a->exp_avg_sq || !a->steps || !a->derived || a->n_groups < 1 || a->n_groups > 2 || !a->loss || !a->best_loss || !a->best_cam))
-        return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_tracker_tail, dim3(1), dim3(256), 0, (hipStream_t)stream, *a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-int adfp_camera_from_tensor(const float* cam, float* c2w, void* stream) {
-    if (!cam || !c2w) return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_camera_from_tensor, dim3(1), dim3(64), 0, (hipStream_t)stream, cam, c2w);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-int adfp_camera_from_tensor_backward(const float* cam, const float* g_c2w, float* g_cam, void* stream) {
-    if (!cam || !g_c2w || !g_cam) return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_camera_from_tensor_bwd, dim3(1), dim3(64), 0, (hipStream_t)stream, cam, g_c2w, g_cam);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-int adfp_select_pixels(const long long* idx, int n, int H0, int H1, int W0, int W1, int H, int W, const float* depth_img, const float* color_img,
-                       float* pix_i, float* pix_j, float* gt_depth, float* gt_color, void* stream) {
-    if (n < 0 || H0 < 0 || W0 < 0 || H1 > H || W1 > W || H1 <= H0 || W1 <= W0) return ADFP_E_ARG;
-    if (n == 0) return 0;
-    if (!idx || !depth_img || !color_img || !pix_i || !pix_j || !gt_depth || !gt_color) return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_select_pixels, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, idx, n, H0, W0, W1 - W0, W, depth_img, color_img,
-                       pix_i, pix_j, gt_depth, gt_color);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-int adfp_sample_keyframes(int n_frames, const adfp_keyframe* frames, int n, int H0, int H1, int W0, int W1, int H, int W, float fx, float fy, float cx,
-                          float cy, float* rays_o, float* rays_d, float* gt_depth, float* gt_color, void* stream) {
-    if (n_frames < 0 || n_frames > ADFP_KEYFRAMES_MAX || n < 0 || H0 < 0 || W0 < 0 || H1 > H || W1 > W || H1 <= H0 || W1 <= W0) return ADFP_E_ARG;
-    if (n_frames == 0 || n == 0) return 0;
-    if (!frames || !rays_o || !rays_d || !gt_depth || !gt_color) return ADFP_E_ARG;
-    if ((long long)n_frames * n > 0x7fffffffll) return ADFP_E_UNSUPPORTED;
-    KeyframeJobs a;
-    for (int f = 0; f < ADFP_KEYFRAMES_MAX; ++f) {
-        const adfp_keyframe& k = frames[f < n_frames ? f : 0];
-        if (f < n_frames && (!k.idx || !k.depth_img || !k.color_img)) return ADFP_E_ARG;
-        a.idx[f] = k.idx; a.c2w[f] = k.c2w; a.depth[f] = k.depth_img; a.color[f] = k.color_img;
-        for (int m = 0; m < 12; ++m) a.pose[f][m] = k.c2w_host[m];
-    }
-    a.n_frames = n_frames; a.n = n; a.H0 = H0; a.W0 = W0; a.Ww = W1 - W0; a.W = W; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
-    a.ro = rays_o; a.rd = rays_d; a.gd = gt_depth; a.gc = gt_color;
-    hipLaunchKernelGGL(k_sample_keyframes, dim3((n_frames * n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-int adfp_track_keep_best(const double* loss, const float* cam, double* best_loss, float* best_cam, void* stream) {
-    if (!loss || !cam || !best_loss || !best_cam) return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_keep_best, dim3(1), dim3(64), 0, (hipStream_t)stream, loss, cam, best_loss, best_cam);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-int adfp_tracker_loss(const adfp_track_loss_args* l, void* stream) {
-    if (!l || !l->depth || !l->uncertainty || !l->color || !l->gt_depth || !l->gt_color || !l->g_depth || !l->g_color || !l->loss || l->n_rays < 0) return ADFP_E_ARG;
-    if (l->n_rays > ADFP_TRACK_MAX_RAYS) return ADFP_E_UNSUPPORTED;
-    TrackLossArgs a;
-    a.n = l->n_rays; a.handle_dynamic = l->handle_dynamic; a.w_color = l->w_color_loss;
-    a.depth = l->depth; a.unc = l->uncertainty; a.color = l->color; a.gd = l->gt_depth; a.gc = l->gt_color; a.keep = l->keep;
-    a.loss = l->loss; a.g_depth = l->g_depth; a.g_color = l->g_color;
-    hipLaunchKernelGGL(k_tracker_loss, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
     ADFP_CHECK_LAUNCH();
     return 0;
 }

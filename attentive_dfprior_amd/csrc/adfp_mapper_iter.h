@@ -9,41 +9,34 @@
 //   k_mapper_loss      the three L1 terms of src/Mapper.py:457-469 and their cotangents (torch's abs backward = sign)
 //   k_adam_prep        step += 1 and the bias corrections of torch.optim.Adam for every parameter group, on the device
 //   k_masked_adam_dev  k_masked_adam with the step-dependent scalars read from device memory
+//
+// k_prefilter_mask's entry (adfp_prefilter_mask) follows its kernel; the loss and Adam entries are with the C ABI in adfp_kernels.hip.
+// The keep test and the workgroup's maximum are adfp_camera.h's.
 #pragma once
 #include "adfp_device.h"
+#include "adfp_camera.h"
 
 __global__ __launch_bounds__(1024) void k_prefilter_mask(const float* __restrict__ ro, const float* __restrict__ rd,
                                                          const float* __restrict__ depth, int n, const double* __restrict__ bnd,
                                                          unsigned char* __restrict__ keep, float* __restrict__ depth_max) {
-    __shared__ float s_m[16];
     double b[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) b[k] = bnd[k];
     float mx = -INFINITY;
     for (int i = threadIdx.x; i < n; i += 1024) {
-        double t = INFINITY; bool nan = false;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double o = (double)ro[3 * i + k], d = (double)rd[3 * i + k];
-            const double t0 = (b[2 * k] - o) / d, t1 = (b[2 * k + 1] - o) / d;
-            nan |= (t0 != t0) | (t1 != t1);            // torch.max / torch.min propagate NaN
-            const double tm = t0 > t1 ? t0 : t1;
-            t = tm < t ? tm : t;
-        }
         const float dep = depth[i];
-        const bool k_ = !nan && (t >= (double)dep);
+        const bool k_ = ray_in_bound(b, ro + 3 * i, rd + 3 * i, dep);
         keep[i] = k_ ? 1 : 0;
         if (k_) mx = dep > mx ? dep : mx;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float v = __shfl_xor(mx, o); mx = v > mx ? v : mx; }
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = s_m[0];
-        for (int w = 1; w < 16; ++w) m = s_m[w] > m ? s_m[w] : m;
-        *depth_max = m;
-    }
+    kept_depth_max_1024(mx, depth_max);
+}
+extern "C" int adfp_prefilter_mask(const float* rays_o, const float* rays_d, const float* gt_depth, int n_rays, const double* bound_dev,
+                                   unsigned char* keep, float* depth_max, void* stream) {
+    if (!rays_o || !rays_d || !gt_depth || !bound_dev || !keep || !depth_max || n_rays <= 0) return ADFP_E_ARG;
+    hipLaunchKernelGGL(k_prefilter_mask, dim3(1), dim3(1024), 0, (hipStream_t)stream, rays_o, rays_d, gt_depth, n_rays, bound_dev, keep, depth_max);
+    ADFP_CHECK_LAUNCH();
+    return 0;
 }
 
 #define ADFP_ADAM_MAX_GROUPS 8

@@ -4,73 +4,40 @@
 //
 //   k_camera_from_tensor(_bwd)   quaternion + translation -> camera-to-world and back (src/common.py:139-178)
 //   k_select_pixels              the sampled pixels' coordinates, sensor depth and colour (src/common.py:94-124)
+//   k_sample_keyframes           the same and the rays, for every keyframe of the Mapper's window
 //   k_tracker_loss               the tracking loss with its median-based outlier mask and the cotangents (src/Tracker.py:116-129)
 //   k_keep_best                  the running "candidate_cam_tensor" of the iteration loop (src/Tracker.py:261-263)
+//   k_tracker_head               one workgroup: camera tensor -> c2w, the drawn pixels, their rays, the pre-filter and its max depth
+//   k_tracker_tail               one workgroup: ray cotangents -> g_c2w -> g_cam [-> keep-best, the Adam preparation and step]
 //
-// The rays (adfp_rays_from_uv), the pre-filter (adfp_prefilter_mask), the render forward / backward with ray gradients and the
-// Adam step (adfp_adam_prep + adfp_masked_adam_multi on the 7 pose parameters) are the existing entries.
+// and their entries, at the end.  Head and tail merge the steps that are also entries of their own (adfp_select_pixels,
+// adfp_rays_from_uv, adfp_prefilter_mask; adfp_rays_from_uv_backward, adfp_camera_from_tensor_backward, adfp_track_keep_best,
+// adfp_adam_prep, adfp_masked_adam_multi on the 7 pose parameters) by calling the same functions of adfp_camera.h, so the two routes
+// are equal bit for bit.  The render forward / backward with ray gradients between head and tail is the existing entry.
 #pragma once
 #include "adfp_device.h"
+#include "adfp_camera.h"
+#include "adfp_mapper_iter.h"    // AdamPrepArgs, adam_prep_group
 
-// R = I + two_s M(q), two_s = 2 / |q|^2, q = (r, i, j, k): quad2rotation of src/common.py:139-163, float32 like the reference
-ADFP_DEV void quat_terms(const float* q, float& two_s, float M[9]) {
-    const float qr = q[0], qi = q[1], qj = q[2], qk = q[3];
-    two_s = 2.0f / (((qr * qr + qi * qi) + qj * qj) + qk * qk);
-    M[0] = -(qj * qj + qk * qk); M[1] = qi * qj - qk * qr;   M[2] = qi * qk + qj * qr;
-    M[3] = qi * qj + qk * qr;    M[4] = -(qi * qi + qk * qk); M[5] = qj * qk - qi * qr;
-    M[6] = qi * qk - qj * qr;    M[7] = qj * qk + qi * qr;   M[8] = -(qi * qi + qj * qj);
-}
-ADFP_DEV void camera_from_tensor_dev(const float* __restrict__ cam, float* c2w /*[16]*/) {
-    float two_s, M[9];
-    quat_terms(cam, two_s, M);
-    for (int a = 0; a < 3; ++a) {
-        for (int b = 0; b < 3; ++b) c2w[4 * a + b] = (a == b ? 1.0f : 0.0f) + two_s * M[3 * a + b];
-        c2w[4 * a + 3] = cam[4 + a];
-    }
-    c2w[12] = 0.f; c2w[13] = 0.f; c2w[14] = 0.f; c2w[15] = 1.f;
-}
 __global__ void k_camera_from_tensor(const float* __restrict__ cam, float* __restrict__ c2w) {
     if (blockIdx.x || threadIdx.x) return;
     camera_from_tensor_dev(cam, c2w);
 }
-// g_cam[0..3] = dL/dq, g_cam[4..6] = dL/dT from dL/d c2w (rows 0-2):
-//   dL/dq_m = two_s sum_ab G_ab dM_ab/dq_m - two_s^2 q_m sum_ab G_ab M_ab       (d two_s / d q_m = -two_s^2 q_m)
-ADFP_DEV void camera_from_tensor_bwd_dev(const float* __restrict__ cam, const float* g_c2w, float* g_cam);
 __global__ void k_camera_from_tensor_bwd(const float* __restrict__ cam, const float* __restrict__ g_c2w, float* __restrict__ g_cam) {
     if (blockIdx.x || threadIdx.x) return;
     camera_from_tensor_bwd_dev(cam, g_c2w, g_cam);
 }
-ADFP_DEV void camera_from_tensor_bwd_dev(const float* __restrict__ cam, const float* g_c2w, float* g_cam) {
-    float two_s, M[9], G[9];
-    quat_terms(cam, two_s, M);
-    float gm = 0.f;
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { G[3 * a + b] = g_c2w[4 * a + b]; gm += G[3 * a + b] * M[3 * a + b]; }
-    const float qr = cam[0], qi = cam[1], qj = cam[2], qk = cam[3];
-    const float dr = -qk * G[1] + qj * G[2] + qk * G[3] - qi * G[5] - qj * G[6] + qi * G[7];
-    const float di = qj * G[1] + qk * G[2] + qj * G[3] - 2.f * qi * G[4] - qr * G[5] + qk * G[6] + qr * G[7] - 2.f * qi * G[8];
-    const float dj = -2.f * qj * G[0] + qi * G[1] + qr * G[2] + qi * G[3] + qk * G[5] - qr * G[6] + qk * G[7] - 2.f * qj * G[8];
-    const float dk = -2.f * qk * G[0] - qr * G[1] + qi * G[2] + qr * G[3] - 2.f * qk * G[4] + qj * G[5] + qi * G[6] + qj * G[7];
-    const float t2 = two_s * two_s * gm;
-    g_cam[0] = two_s * dr - t2 * qr; g_cam[1] = two_s * di - t2 * qi; g_cam[2] = two_s * dj - t2 * qj; g_cam[3] = two_s * dk - t2 * qk;
-    g_cam[4] = g_c2w[3]; g_cam[5] = g_c2w[7]; g_cam[6] = g_c2w[11];
-}
 
-// pixel k of the window [H0, H0 + Hw) x [W0, W0 + Ww) in row-major order (get_sample_uv's meshgrid flattened, src/common.py:112-124)
 __global__ __launch_bounds__(256) void k_select_pixels(const long long* __restrict__ idx, int n, int H0, int W0, int Ww, int W,
                                                        const float* __restrict__ depth, const float* __restrict__ color,
                                                        float* __restrict__ pi, float* __restrict__ pj, float* __restrict__ gd, float* __restrict__ gc) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
-    const long long k = idx[t];
-    const int row = H0 + (int)(k / Ww), col = W0 + (int)(k % Ww);
-    pi[t] = (float)col; pj[t] = (float)row;
-    const long long p = (long long)row * W + col;
-    gd[t] = depth[p];
-    gc[3 * t] = color[3 * p]; gc[3 * t + 1] = color[3 * p + 1]; gc[3 * t + 2] = color[3 * p + 2];
+    gd[t] = window_sample(idx[t], H0, W0, Ww, W, depth, color, pi[t], pj[t], gc + 3 * t);
 }
 
-// k_select_pixels + k_rays_from_uv for every keyframe of the Mapper's window in one launch (adfp_sample_keyframes): thread t = ray
-// t % n of frame t / n.  The ray arithmetic is k_rays_from_uv's, operation by operation.
+// The pixels and their rays for every keyframe of the Mapper's window in one launch (adfp_sample_keyframes): thread t = ray t % n
+// of frame t / n, with the frame's pose from device memory (c2w[f]) or, where that is null, from the launch's arguments (pose[f]).
 struct KeyframeJobs {
     const long long* idx[ADFP_KEYFRAMES_MAX]; const float* c2w[ADFP_KEYFRAMES_MAX]; const float* depth[ADFP_KEYFRAMES_MAX];
     const float* color[ADFP_KEYFRAMES_MAX]; float pose[ADFP_KEYFRAMES_MAX][12];
@@ -81,21 +48,11 @@ __global__ __launch_bounds__(256) void k_sample_keyframes(KeyframeJobs a) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= a.n_frames * a.n) return;
     const int f = t / a.n;
-    const long long k = a.idx[f][t - f * a.n];
-    const int row = a.H0 + (int)(k / a.Ww), col = a.W0 + (int)(k % a.Ww);
-    const long long p = (long long)row * a.W + col;
-    a.gd[t] = a.depth[f][p];
-    a.gc[3 * t] = a.color[f][3 * p]; a.gc[3 * t + 1] = a.color[f][3 * p + 1]; a.gc[3 * t + 2] = a.color[f][3 * p + 2];
-    const float pi = (float)col, pj = (float)row;
-    const float dx = (pi - a.cx) / a.fx, dy = -(pj - a.cy) / a.fy, dz = -1.f;
+    float pi, pj, c2w[12];
+    a.gd[t] = window_sample(a.idx[f][t - f * a.n], a.H0, a.W0, a.Ww, a.W, a.depth[f], a.color[f], pi, pj, a.gc + 3 * t);
 #pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        float c0, c1, c2, c3;
-        if (a.c2w[f]) { c0 = a.c2w[f][4 * m]; c1 = a.c2w[f][4 * m + 1]; c2 = a.c2w[f][4 * m + 2]; c3 = a.c2w[f][4 * m + 3]; }
-        else { c0 = a.pose[f][4 * m]; c1 = a.pose[f][4 * m + 1]; c2 = a.pose[f][4 * m + 2]; c3 = a.pose[f][4 * m + 3]; }
-        a.rd[3 * t + m] = __fadd_rn(__fadd_rn(__fmul_rn(dx, c0), __fmul_rn(dy, c1)), __fmul_rn(dz, c2));
-        a.ro[3 * t + m] = c3;
-    }
+    for (int m = 0; m < 12; ++m) c2w[m] = a.c2w[f] ? a.c2w[f][m] : a.pose[f][m];
+    ray_from_uv(pi, pj, a.fx, a.fy, a.cx, a.cy, c2w, a.ro + 3 * t, a.rd + 3 * t);
 }
 
 // loss = sum_mask |gt_d - d| / sqrt(unc + 1e-10)  +  w_color sum_mask |gt_c - c|,   mask = kept & (gt_d > 0) [& tmp < 10 median(tmp)]
@@ -224,4 +181,136 @@ __global__ void k_keep_best(const double* __restrict__ loss, const float* __rest
     if (!better) return;
     best_cam[threadIdx.x] = v;
     if (threadIdx.x == 0) *best_loss = *loss;
+}
+
+// ---- the Tracker iteration's head and tail, one workgroup each ---------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_tracker_head(adfp_tracker_head_args a) {
+    float c2w[16];
+    camera_from_tensor_dev(a.cam, c2w);                     // every thread: 30 operations, the same values
+    if (threadIdx.x < 16) a.c2w[threadIdx.x] = c2w[threadIdx.x];
+    double b[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] = a.bound[k];
+    float mx = -INFINITY;
+    for (int t = threadIdx.x; t < a.n; t += 1024) {
+        float pi, pj, ro[3], rd[3];
+        const float dep = window_sample(a.idx[t], a.H0, a.W0, a.W1 - a.W0, a.W, a.depth_img, a.color_img, pi, pj, a.gt_color + 3 * t);
+        a.pix_i[t] = pi; a.pix_j[t] = pj; a.gt_depth[t] = dep;
+        ray_from_uv(pi, pj, a.fx, a.fy, a.cx, a.cy, c2w, ro, rd);
+#pragma unroll
+        for (int m = 0; m < 3; ++m) { a.rays_d[3 * t + m] = rd[m]; a.rays_o[3 * t + m] = ro[m]; }
+        const bool k_ = ray_in_bound(b, ro, rd, dep);
+        a.keep[t] = k_ ? 1 : 0;
+        if (k_) mx = dep > mx ? dep : mx;
+    }
+    kept_depth_max_1024(mx, a.depth_max);
+}
+__global__ __launch_bounds__(256) void k_tracker_tail(adfp_tracker_tail_args a) {
+    __shared__ float s[4][12];
+    __shared__ float s_g[16];
+    const float v = ray_cotangents_to_c2w(a.pix_i, a.pix_j, a.n, a.fx, a.fy, a.cx, a.cy, a.g_rays_o, a.g_rays_d, s);
+    if (threadIdx.x < 16) { s_g[threadIdx.x] = v; a.g_c2w[threadIdx.x] = v; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    // one thread from here on: 7 parameters
+    float g_cam[7];
+    camera_from_tensor_bwd_dev(a.cam, s_g, g_cam);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) a.g_cam[k] = g_cam[k];
+    if (!a.step) return;
+    const bool better_before = *a.loss < *a.best_loss;
+    if (a.n_groups == 2 && better_before) {                 // separate learning rates: the candidate is kept BEFORE the step
+#pragma unroll
+        for (int k = 0; k < 7; ++k) a.best_cam[k] = a.cam[k];
+        *a.best_loss = *a.loss;
+    }
+    AdamPrepArgs pa;
+    pa.steps = a.steps; pa.derived = a.derived; pa.n = a.n_groups; pa.beta1 = a.beta1; pa.beta2 = a.beta2; pa.skip = a.skip_flag;
+    for (int g = 0; g < ADFP_ADAM_MAX_GROUPS; ++g) pa.lr[g] = g < a.n_groups ? a.lr[g] : -1.f;
+    for (int g = 0; g < a.n_groups; ++g) adam_prep_group(pa, g);
+    for (int g = 0; g < a.n_groups; ++g) {                  // two groups: the translation (4..6), then the quaternion (0..3)
+        const int off = a.n_groups == 2 ? (g == 0 ? 4 : 0) : 0, cnt = a.n_groups == 2 ? (g == 0 ? 3 : 4) : 7;
+        pose_adam(a.cam, a.g_cam, a.exp_avg, a.exp_avg_sq, off, cnt, a.derived[2 * g], a.derived[2 * g + 1], a.beta1, a.beta2, a.eps);
+    }
+    if (a.n_groups == 1 && better_before) {                 // one group: kept after the step, the stepped pose with this iteration's loss
+#pragma unroll
+        for (int k = 0; k < 7; ++k) a.best_cam[k] = a.cam[k];
+        *a.best_loss = *a.loss;
+    }
+}
+
+extern "C" int adfp_tracker_head(const adfp_tracker_head_args* a, void* stream) {
+    if (!a || a->n < 0 || bad_window(a->H0, a->H1, a->W0, a->W1, a->H, a->W)) return ADFP_E_ARG;
+    if (!a->cam || !a->c2w || !a->bound || !a->keep || !a->depth_max) return ADFP_E_ARG;
+    if (a->n > 0 && (!a->idx || !a->depth_img || !a->color_img || !a->pix_i || !a->pix_j || !a->gt_depth || !a->gt_color || !a->rays_o || !a->rays_d)) return ADFP_E_ARG;
+    hipLaunchKernelGGL(k_tracker_head, dim3(1), dim3(1024), 0, (hipStream_t)stream, *a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int adfp_tracker_tail(const adfp_tracker_tail_args* a, void* stream) {
+    if (!a || a->n < 0 || !a->cam || !a->g_c2w || !a->g_cam) return ADFP_E_ARG;
+    if (a->n > 0 && (!a->pix_i || !a->pix_j)) return ADFP_E_ARG;
+    if (a->step && (!a->exp_avg || !a->exp_avg_sq || !a->steps || !a->derived || a->n_groups < 1 || a->n_groups > 2 || !a->loss || !a->best_loss || !a->best_cam))
+        return ADFP_E_ARG;
+    hipLaunchKernelGGL(k_tracker_tail, dim3(1), dim3(256), 0, (hipStream_t)stream, *a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int adfp_camera_from_tensor(const float* cam, float* c2w, void* stream) {
+    if (!cam || !c2w) return ADFP_E_ARG;
+    hipLaunchKernelGGL(k_camera_from_tensor, dim3(1), dim3(64), 0, (hipStream_t)stream, cam, c2w);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int adfp_camera_from_tensor_backward(const float* cam, const float* g_c2w, float* g_cam, void* stream) {
+    if (!cam || !g_c2w || !g_cam) return ADFP_E_ARG;
+    hipLaunchKernelGGL(k_camera_from_tensor_bwd, dim3(1), dim3(64), 0, (hipStream_t)stream, cam, g_c2w, g_cam);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int adfp_select_pixels(const long long* idx, int n, int H0, int H1, int W0, int W1, int H, int W, const float* depth_img, const float* color_img,
+                                  float* pix_i, float* pix_j, float* gt_depth, float* gt_color, void* stream) {
+    if (n < 0 || bad_window(H0, H1, W0, W1, H, W)) return ADFP_E_ARG;
+    if (n == 0) return 0;
+    if (!idx || !depth_img || !color_img || !pix_i || !pix_j || !gt_depth || !gt_color) return ADFP_E_ARG;
+    hipLaunchKernelGGL(k_select_pixels, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, idx, n, H0, W0, W1 - W0, W, depth_img, color_img,
+                       pix_i, pix_j, gt_depth, gt_color);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int adfp_sample_keyframes(int n_frames, const adfp_keyframe* frames, int n, int H0, int H1, int W0, int W1, int H, int W, float fx, float fy,
+                                     float cx, float cy, float* rays_o, float* rays_d, float* gt_depth, float* gt_color, void* stream) {
+    if (n_frames < 0 || n_frames > ADFP_KEYFRAMES_MAX || n < 0 || bad_window(H0, H1, W0, W1, H, W)) return ADFP_E_ARG;
+    if (n_frames == 0 || n == 0) return 0;
+    if (!frames || !rays_o || !rays_d || !gt_depth || !gt_color) return ADFP_E_ARG;
+    if ((long long)n_frames * n > 0x7fffffffll) return ADFP_E_UNSUPPORTED;
+    KeyframeJobs a;
+    for (int f = 0; f < ADFP_KEYFRAMES_MAX; ++f) {
+        const adfp_keyframe& k = frames[f < n_frames ? f : 0];
+        if (f < n_frames && (!k.idx || !k.depth_img || !k.color_img)) return ADFP_E_ARG;
+        a.idx[f] = k.idx; a.c2w[f] = k.c2w; a.depth[f] = k.depth_img; a.color[f] = k.color_img;
+        for (int m = 0; m < 12; ++m) a.pose[f][m] = k.c2w_host[m];
+    }
+    a.n_frames = n_frames; a.n = n; a.H0 = H0; a.W0 = W0; a.Ww = W1 - W0; a.W = W; a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.ro = rays_o; a.rd = rays_d; a.gd = gt_depth; a.gc = gt_color;
+    hipLaunchKernelGGL(k_sample_keyframes, dim3((n_frames * n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int adfp_track_keep_best(const double* loss, const float* cam, double* best_loss, float* best_cam, void* stream) {
+    if (!loss || !cam || !best_loss || !best_cam) return ADFP_E_ARG;
+    hipLaunchKernelGGL(k_keep_best, dim3(1), dim3(64), 0, (hipStream_t)stream, loss, cam, best_loss, best_cam);
+    ADFP_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int adfp_tracker_loss(const adfp_track_loss_args* l, void* stream) {
+    if (!l || !l->depth || !l->uncertainty || !l->color || !l->gt_depth || !l->gt_color || !l->g_depth || !l->g_color || !l->loss || l->n_rays < 0) return ADFP_E_ARG;
+    if (l->n_rays > ADFP_TRACK_MAX_RAYS) return ADFP_E_UNSUPPORTED;
+    TrackLossArgs a;
+    a.n = l->n_rays; a.handle_dynamic = l->handle_dynamic; a.w_color = l->w_color_loss;
+    a.depth = l->depth; a.unc = l->uncertainty; a.color = l->color; a.gd = l->gt_depth; a.gc = l->gt_color; a.keep = l->keep;
+    a.loss = l->loss; a.g_depth = l->g_depth; a.g_color = l->g_color;
+    hipLaunchKernelGGL(k_tracker_loss, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    ADFP_CHECK_LAUNCH();
+    return 0;
 }

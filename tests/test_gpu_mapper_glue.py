@@ -93,9 +93,17 @@ def run_prefilter(ro, rd, gd, bound):
     ro_d, rd_d, gd_d, b_d = t(ro, torch.float32), t(rd, torch.float32), t(gd, torch.float32), t(bound, torch.float64)
     keep, dmax = Guarded((N,), torch.uint8), Guarded((1,), torch.float32)
     check(lib().adfp_prefilter_mask(ptr(ro_d), ptr(rd_d), ptr(gd_d), N, ptr(b_d), keep.ptr, dmax.ptr, stream()), 'adfp_prefilter_mask')
+    # the compacting entry on the same batch: its ordered index list is nonzero(keep), its count the number of kept rays
+    index, count = Guarded((N,), torch.int32), Guarded((1,), torch.int32)
+    check(lib().adfp_prefilter_rays(ptr(ro_d), ptr(rd_d), ptr(gd_d), N, ptr(b_d), index.ptr, count.ptr, stream()), 'adfp_prefilter_rays')
     torch.cuda.synchronize()
     k = keep.check('keep')
     assert k.max() <= 1
+    kept = np.nonzero(k)[0]
+    assert int(count.check('count')[0]) == kept.size
+    got = index.check('index', written=False)
+    assert np.array_equal(got[:kept.size], kept), 'adfp_prefilter_rays and adfp_prefilter_mask keep different rays'
+    assert (got[kept.size:] == SENTINEL[torch.int32]).all(), 'adfp_prefilter_rays wrote behind its count'
     return k.astype(bool), dmax.check('depth_max')[0]
 
 
