@@ -23,8 +23,9 @@ def mapping_setting(cfg, key):
 # tracking.init: what a tracked frame starts from.  'guess' = the constant-speed guess as it is (the reference's path, and what an
 # absent key means); 'icp' = the guess refined by icp.DepthICP, point-to-plane ICP of the whole depth image against the raycast of
 # the TSDF prior -- with tracking.iters: 0 that result is the frame's pose.  tracking.icp: keywords of DepthICP's constructor
-# (strides, iters, dist_tol, cos_tol, min_pivot, min_pairs, max_jump, max_shift, max_angle, near); lengths are metres and are NOT
-# multiplied by `scale`.  tracking.icp_rgb: {'weight': w, 'tol': t} -- with tracking.init: icp and w > 0 (absent or 0: off) every ICP
+# (strides, iters, dist_tol, cos_tol, min_pivot, min_pairs, max_jump, max_shift, max_angle, near, bilateral); lengths are metres and
+# are NOT multiplied by `scale`.  tracking.icp.bilateral: {radius, sigma_space, sigma_depth, sigma_depth_z2, points} -- the ICP reads
+# the sensor depth through icp.depth_bilateral ({}: its defaults; absent, None or False: off).  tracking.icp_rgb: {'weight': w, 'tol': t} -- with tracking.init: icp and w > 0 (absent or 0: off) every ICP
 # step adds a photometric term against the last tracked frame, weighted by w, to its normal equations (icp.RgbdICP; t drops pairs
 # whose intensities differ by more, RgbdICP's default when absent).  A weight > 0 without tracking.init: icp is an error.
 TRACKING_DEFAULTS = {'init': 'guess', 'icp': {}, 'icp_rgb': {}}

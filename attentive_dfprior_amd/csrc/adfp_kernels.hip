@@ -3134,3 +3134,4 @@ extern "C" int adfp_eval_points_backward(const adfp_scene* sc, const adfp_points
 #include "adfp_tsdfcast.h"      // TSDF raycast
 #include "adfp_icp.h"           // depth ICP against the TSDF raycast
 #include "adfp_rgbd.h"          // RGB-D ICP: the depth ICP's step with a photometric term against the last tracked frame
+#include "adfp_depthfilter.h"   // bilateral filter of the sensor depth ahead of the depth ICP's normal map

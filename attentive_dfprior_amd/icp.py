@@ -16,8 +16,13 @@ refinement that fails (too few pairs, a direction the pairs do not constrain, a 
 
 RgbdICP (``tracking.icp_rgb``) is DepthICP with a photometric term against the last tracked frame in every step's normal equations
 (adfp_rgbd_frame_map, adfp_rgbd_step, csrc/adfp_rgbd.h; include/adfp.h "RGB-D ICP", tests/rgbd_icp_ref.py): texture constrains what a
-view of one or two walls leaves free, and an empty model image still yields pairs."""
+view of one or two walls leaves free, and an empty model image still yields pairs.
+
+depth_bilateral (adfp_depth_bilateral, csrc/adfp_depthfilter.h; include/adfp.h "Depth bilateral filter", tests/depth_filter_ref.py) is
+the filter KinectFusion applies to the raw depth before anything else, and ``DepthICP(bilateral={...})`` (``tracking.icp.bilateral``)
+puts it in front of the sensor's normal map: the normals are one-pixel differences of the depth, and a noisy normal fails cos_tol."""
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -30,6 +35,69 @@ from .tsdf_raycast import TsdfRaycaster
 OK, FEW_PAIRS, DEGENERATE, REJECTED = 0, 1, 2, 3
 STATUS_NAMES = {v: k for k, v in _lib.ICP_STATUS.items()}
 STATS_COLUMNS = ('pairs', 'rmse', 'pivot_ratio', 'omega', 'shift', 'status')
+BILATERAL_DEFAULTS = {'radius': 2, 'sigma_space': 1.5, 'sigma_depth': 0.05, 'sigma_depth_z2': 0.0, 'points': True}
+BILATERAL_MAX_RADIUS = 8               # ADFP_BILATERAL_MAX_RADIUS
+
+
+def _bilateral_numbers(radius, sigma_space, sigma_depth, sigma_depth_z2):
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= BILATERAL_MAX_RADIUS:
+        raise ValueError(f'bilateral radius {radius!r}: an integer in 1 .. {BILATERAL_MAX_RADIUS}')
+    ss, sd, sz = float(sigma_space), float(sigma_depth), float(sigma_depth_z2)
+    if not ss > 0 or not sd > 0 or not sz >= 0:
+        raise ValueError(f'bilateral sigma_space {sigma_space!r} and sigma_depth {sigma_depth!r} must be > 0, sigma_depth_z2 '
+                         f'{sigma_depth_z2!r} >= 0')
+    return int(radius), ss, sd, sz
+
+
+def bilateral_config(bilateral, points=True):
+    """The ``bilateral`` keyword -> None (off) or the full dict; `points` is the default of the key of that name."""
+    if bilateral is None or bilateral is False:
+        return None
+    if not isinstance(bilateral, dict):
+        raise ValueError(f'bilateral: None, False or a dict with keys from {sorted(BILATERAL_DEFAULTS)}, got {bilateral!r}')
+    unknown = sorted(set(bilateral) - set(BILATERAL_DEFAULTS))
+    if unknown:
+        raise ValueError(f'bilateral: unknown keys {unknown}; the keys are {sorted(BILATERAL_DEFAULTS)}')
+    cfg = dict(BILATERAL_DEFAULTS, points=points)
+    cfg.update(bilateral)
+    cfg['radius'], cfg['sigma_space'], cfg['sigma_depth'], cfg['sigma_depth_z2'] = _bilateral_numbers(
+        cfg['radius'], cfg['sigma_space'], cfg['sigma_depth'], cfg['sigma_depth_z2'])
+    if not isinstance(cfg['points'], bool):
+        raise ValueError(f"bilateral points {cfg['points']!r}: True or False")
+    return cfg
+
+
+def depth_bilateral(depth, radius=2, sigma_space=1.5, sigma_depth=0.05, sigma_depth_z2=0.0, out=None):
+    """Bilateral filter of depth images, [V,H,W] or [H,W] float32 on the device -> the same shape (adfp_depth_bilateral, one launch;
+    `out`: where to, not `depth` itself).  A (2 radius + 1)^2 window, sigma_space in pixels, the range term sigma_depth +
+    sigma_depth_z2 d^2 in metres at the centre's depth d, neighbours further than three of it in depth left out; an invalid pixel
+    (<= 0 or not finite) stays 0 and takes no part.  The defaults are the mini scene's (48 x 64, depths 0.3-1.2 m) and, like the
+    ICP's other defaults, have not been tuned on anything else."""
+    _lib.require_cuda(depth, 'depth')
+    if depth.dtype != torch.float32 or depth.dim() not in (2, 3) or not depth.is_contiguous():
+        raise ValueError(f'depth: expected contiguous float32 [V,H,W] or [H,W], got {depth.dtype} {tuple(depth.shape)}')
+    radius, ss, sd, sz = _bilateral_numbers(radius, sigma_space, sigma_depth, sigma_depth_z2)
+    H, W = depth.shape[-2:]
+    V = depth.shape[0] if depth.dim() == 3 else 1
+    with _lib.device_guard(depth.device):
+        if out is None:
+            out = torch.empty_like(depth)
+        elif out.dtype != torch.float32 or out.shape != depth.shape or not out.is_contiguous() or out.device != depth.device:
+            raise ValueError(f'out: expected contiguous float32 {tuple(depth.shape)} on {depth.device}, got {out.dtype} {tuple(out.shape)}')
+        check(lib().adfp_depth_bilateral(ptr(depth), V, H, W, radius, ss, sd, sz, ptr(out), _lib.current_stream(depth.device)),
+              'adfp_depth_bilateral')
+    return out
+
+
+def _takes_bilateral(init):
+    """DepthICP(..., bilateral=None): the keyword is taken and validated here, ahead of the constructor proper, whose own keyword list
+    (what inspect.signature reports through __wrapped__, and what tests/test_icp_api_signatures.py pins) is the one the ICP had
+    before the filter.  The wrapper's __kwdefaults__ carry the new keyword and its default."""
+    @functools.wraps(init)
+    def __init__(self, *args, bilateral=None, **keywords):
+        self.bilateral = bilateral_config(bilateral, points=self._BILATERAL_POINTS)
+        init(self, *args, **keywords)
+    return __init__
 
 
 class DepthICP(object):
@@ -42,8 +110,17 @@ class DepthICP(object):
     depth, 0: from the camera) is where the model's raycast starts marching -- a ray whose first sample lies in unobserved space
     (-1 in a fused volume, which the camera's own voxel is unless another frame saw it) reports no surface.  `engine`: share a
     Renderer's Engine, so that one invalidate_tsdf serves both.  All buffers are allocated here, once; refine() allocates only the
-    raycaster's scratch and synchronises nothing."""
+    raycaster's scratch and synchronises nothing.
 
+    bilateral: None or False (off: nothing changes), or a dict with any of radius, sigma_space, sigma_depth, sigma_depth_z2 (the
+    arguments of depth_bilateral, with its defaults and its caveat: the mini scene's, tuned on nothing else) and points.  set_frame
+    then filters the sensor image (one more launch, between the raycast and the normals; the model image is not filtered) and the
+    sensor's normals come from the filtered image.  points True (the default, as KinectFusion does): so do the sensor's points;
+    points False: the points are the raw image's, since on clean depth at a small resolution the filter rounds the corners of a room
+    and costs a millimetre or two of the final pose."""
+    _BILATERAL_POINTS = True           # the default of bilateral's `points`
+
+    @_takes_bilateral
     def __init__(self, tsdf_volume, tsdf_bnds, H, W, fx, fy, cx, cy, engine=None, strides=(4, 2, 1), iters=(4, 3, 3), dist_tol=0.1,
                  cos_tol=0.8, min_pivot=1e-6, min_pairs=0.05, max_jump=0.0, max_shift=0.5, max_angle=0.5, near=0.0):
         self.raycaster = TsdfRaycaster(tsdf_volume, tsdf_bnds, engine=engine)
@@ -59,7 +136,14 @@ class DepthICP(object):
         nbytes = int(lib().adfp_icp_workspace_bytes(self.H, self.W))
         if nbytes == 0:
             raise RuntimeError(f'adfp_icp_workspace_bytes refuses a {self.H} x {self.W} image')
-        self.depth = torch.zeros((2, self.H, self.W), dtype=torch.float32, device=dev)             # sensor, model
+        if self.bilateral is None:
+            self.depth = torch.zeros((2, self.H, self.W), dtype=torch.float32, device=dev)         # sensor, model
+            self.raw_depth = self.points_depth = self.depth[0]
+        else:                                              # raw sensor, filtered sensor, model: the last two are the normals' launch
+            self._depth3 = torch.zeros((3, self.H, self.W), dtype=torch.float32, device=dev)
+            self.depth = self._depth3[1:]
+            self.raw_depth = self._depth3[0]
+            self.points_depth = self.depth[0] if self.bilateral['points'] else self.raw_depth
         self.normals = torch.zeros((2, self.H, self.W, 3), dtype=torch.float32, device=dev)
         self.p_ref = torch.zeros((4, 4), dtype=torch.float32, device=dev)
         self.state = torch.zeros((_lib.ICP_STATE_BYTES // 8,), dtype=torch.float64, device=dev)
@@ -95,9 +179,11 @@ class DepthICP(object):
     def _begin(self, guess, st):
         check(lib().adfp_icp_begin(ptr(guess), ptr(self.state), st), 'adfp_icp_begin')
 
-    def _step(self, maps, p_ref, stride, row, st, sums=None):
+    def _step(self, maps, p_ref, stride, row, st, sums=None, points=None):
+        """points: the image the sensor's points come from when it is not the one its normals were taken of (maps' first)"""
         depth, normals = maps
-        check(lib().adfp_icp_step(ptr(depth[0]), ptr(normals[0]), ptr(depth[1]), ptr(normals[1]), ptr(p_ref), self.H, self.W, self.fx, self.fy,
+        depth_s = depth[0] if points is None else points
+        check(lib().adfp_icp_step(ptr(depth_s), ptr(normals[0]), ptr(depth[1]), ptr(normals[1]), ptr(p_ref), self.H, self.W, self.fx, self.fy,
                                   self.cx, self.cy, int(stride), self.dist_tol, self.cos_tol, self.min_pivot, self.pairs_needed(stride),
                                   ptr(self.state), ptr(self.stats), self.stats.shape[0], int(row), ptr(sums), ptr(self.workspace),
                                   self.workspace.numel() * 8, st), 'adfp_icp_step')
@@ -115,13 +201,14 @@ class DepthICP(object):
             row = 0
             for stride, n in zip(self.strides, self.iters):
                 for _ in range(n):
-                    self._step((self.depth, self.normals), self.p_ref, stride, row, st)
+                    self._step((self.depth, self.normals), self.p_ref, stride, row, st, points=self.points_depth)
                     row += 1
             self._end(row, st)
         return self.cam_out
 
     def set_frame(self, guess_c2w, gt_depth):
-        """The refinement's inputs: the sensor depth, the raycast of the prior from the guess, both normal maps (one launch)."""
+        """The refinement's inputs: the sensor depth, the raycast of the prior from the guess, with `bilateral` the filtered sensor
+        depth (one launch), both normal maps (one launch)."""
         if isinstance(guess_c2w, np.ndarray):
             guess_c2w = torch.from_numpy(guess_c2w)
         g = guess_c2w.detach().to(self.dev, torch.float32)
@@ -133,8 +220,11 @@ class DepthICP(object):
             raise ValueError(f'gt_depth: expected [{self.H},{self.W}], got {tuple(gt_depth.shape)}')
         _lib.require_cuda(gt_depth, 'gt_depth')
         self.p_ref.copy_(g)
-        self.depth[0].copy_(gt_depth)
+        self.raw_depth.copy_(gt_depth)
         self.raycaster.render_depth(self.p_ref, self.H, self.W, self.fx, self.fy, self.cx, self.cy, near=self.near, out=self.depth[1:2])
+        if self.bilateral is not None:
+            b = self.bilateral
+            depth_bilateral(self.raw_depth, b['radius'], b['sigma_space'], b['sigma_depth'], b['sigma_depth_z2'], out=self.depth[0])
         self.compute_normals(self.depth, out=self.normals)
 
     def refine(self, guess_c2w, gt_depth):
@@ -201,10 +291,18 @@ class RgbdICP(DepthICP):
 
     rgb_weight multiplies the photometric normal equations (intensities are 0..1, geometric residuals metres), rgb_tol drops pairs
     whose intensities differ by more; both defaults are the mini scene's and have not been tuned on anything else.  Before the first
-    set_keyframe, and with rgb_weight 0, a step is the depth rule.  Everything is allocated here, once."""
+    set_keyframe, and with rgb_weight 0, a step is the depth rule.  Everything is allocated here, once.
+
+    bilateral (DepthICP's keyword): the sensor's normals come from the filtered image.  The frame map is always built from the raw
+    sensor depth, so maps[0], and after promote the keyframe's map, are the bytes they are without the filter; a step reads the
+    sensor's depth from that map, so the points are the raw image's: `points` defaults to False here and True is refused."""
+    _BILATERAL_POINTS = False
 
     def __init__(self, tsdf_volume, tsdf_bnds, H, W, fx, fy, cx, cy, engine=None, rgb_weight=1.0, rgb_tol=0.25, **depth_icp_keywords):
         super().__init__(tsdf_volume, tsdf_bnds, H, W, fx, fy, cx, cy, engine=engine, **depth_icp_keywords)
+        if self.bilateral is not None and self.bilateral['points']:
+            raise ValueError('RgbdICP: bilateral points True is not available, a joint step reads the sensor depth from the frame map, '
+                             'which is built from the raw depth')
         self.rgb_weight, self.rgb_tol = float(rgb_weight), float(rgb_tol)
         if not self.rgb_weight >= 0 or self.rgb_tol != self.rgb_tol:
             raise ValueError(f'rgb_weight {rgb_weight!r} must be >= 0 and rgb_tol {rgb_tol!r} a number')
@@ -268,7 +366,7 @@ class RgbdICP(DepthICP):
     def refine(self, guess_c2w, gt_depth, gt_color):
         """DepthICP.refine with the frame's colour [H,W,3]: the parent's set_frame, one frame-map launch, the joint steps."""
         self.set_frame(guess_c2w, gt_depth)
-        self.frame_map(gt_color, self.depth[0], out=self.maps[0])
+        self.frame_map(gt_color, self.raw_depth, out=self.maps[0])
         return self.run_steps()
 
     def last_rgb_stats(self):

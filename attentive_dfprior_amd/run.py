@@ -3,7 +3,7 @@
     python -m attentive_dfprior_amd.run CONFIG [--input_folder ..] [--output ..] [--tsdf_volume PATH --tsdf_bounds PATH]
                                                [--prior file|online] [--prior_voxel_size M] [--seed N] [--last_frame N]
                                                [--no_prefetch] [--default_config PATH] [--tracking_init guess|icp]
-                                               [--tracking_rgb_weight W]
+                                               [--tracking_rgb_weight W] [--tracking_icp_bilateral]
 
 The prior TSDF volume comes from the files ``python -m attentive_dfprior_amd.get_tsdf CONFIG`` writes
 (``<dataset>_tsdf_volume/<scene>_tsdf_volume.pt`` and ``_bounds.pt``, or the two paths given), or with ``--prior online`` is fused
@@ -36,6 +36,9 @@ def parse_args(argv=None):
     parser.add_argument('--tracking_rgb_weight', type=float, metavar='W',
                         help="replaces the config's tracking.icp_rgb.weight: W > 0 adds a photometric term against the last tracked frame "
                              'to every ICP step (icp.RgbdICP; needs tracking.init icp), 0 turns it off')
+    parser.add_argument('--tracking_icp_bilateral', action='store_true',
+                        help="sets the config's tracking.icp.bilateral to its defaults where the config has none: the sensor depth goes "
+                             'through a bilateral filter before the ICP takes its normals (icp.depth_bilateral; needs tracking.init icp)')
     return parser.parse_args(argv)
 
 
@@ -47,6 +50,13 @@ def main(argv=None):
     if args.tracking_rgb_weight is not None:
         t = cfg.setdefault('tracking', {})
         t['icp_rgb'] = dict(t.get('icp_rgb') or {}, weight=args.tracking_rgb_weight)
+    if args.tracking_icp_bilateral:
+        t = cfg.setdefault('tracking', {})
+        if t.get('init', 'guess') != 'icp':
+            raise ValueError('--tracking_icp_bilateral needs tracking.init: icp')
+        t['icp'] = dict(t.get('icp') or {})
+        if not t['icp'].get('bilateral'):
+            t['icp']['bilateral'] = {}
     if args.seed is not None:
         setup_seed(args.seed)
     slam = DF_Prior(cfg, args)

@@ -22,6 +22,10 @@ Deliberate differences from the reference:
   * ``tracking.init: icp`` (default ``guess``): the constant-speed guess is refined by point-to-plane ICP of the frame's whole depth
     image against the raycast of the TSDF prior (``icp.DepthICP``) before the iterations start from it; with ``tracking.iters: 0``
     the refined pose is the frame's pose.  ``Tracker.icp_status`` holds one status per tracked frame.
+  * ``tracking.icp.bilateral: {radius, sigma_space, sigma_depth, sigma_depth_z2, points}`` (absent, null or false: off; ``{}``: the
+    defaults 2, 1.5 px, 0.05 m, 0, true): the ICP takes the sensor's normals, and with ``points`` its points, from the bilaterally
+    filtered sensor depth (``icp.depth_bilateral``).  Only the ICP sees the filtered image: the iterations, the Mapper and the
+    online prior's fusion read the raw depth.  ``--tracking_icp_bilateral`` switches it on with the defaults.
 """
 import logging
 import os

@@ -181,6 +181,41 @@ def make_ray_batch(scene, n_rays, seed=1, zero_frac=0.1, noise=0.02, poses=2, de
     return rays_o.to(device), rays_d.to(device), depth.to(device), color.to(device)
 
 
+def sensor_depth(depth, seed, a=0.0012, b=0.0019, z0=0.4, scale=1.0, quantum=0.0, edge_jump=0.0):
+    """A depth sensor's view of a clean depth image ([..., H, W], numpy or torch; metres, <= 0 or not finite: invalid), on the host,
+    seeded by numpy's default_rng(seed): -> float32 of the same kind and shape.
+
+    Valid depths get N(0, (scale (a + b (z - z0)^2))^2) added; the defaults are the axial noise fitted to the Kinect (Nguyen, Izadi,
+    Lovell: "Modeling Kinect sensor noise for improved 3D reconstruction and tracking", 3DIMPVT 2012), a = 0, z0 = 0 gives
+    sigma = b z^2.  quantum > 0: the noisy depth is rounded to a multiple of it.  edge_jump > 0: a pixel whose CLEAN depth differs
+    from a valid 4-neighbour's by more than edge_jump becomes 0, the holes a sensor leaves at depth edges.  Invalid depths stay 0,
+    and a result that is not > 0 becomes 0.  One normal deviate is drawn per pixel, valid or not, so a hole moves no other pixel's
+    noise."""
+    import numpy as np
+    is_torch = isinstance(depth, torch.Tensor)
+    z = (depth.detach().cpu().numpy() if is_torch else np.asarray(depth)).astype(np.float64)
+    if z.ndim < 2:
+        raise ValueError(f'depth: expected [..., H, W], got {z.shape}')
+    ok = np.isfinite(z) & (z > 0)
+    z = np.where(ok, z, 0.0)
+    rng = np.random.default_rng(seed)
+    sigma = float(scale) * (float(a) + float(b) * (z - float(z0)) ** 2)
+    out = z + sigma * rng.standard_normal(z.shape)
+    if quantum > 0:
+        out = np.round(out / quantum) * quantum
+    hole = np.zeros(z.shape, dtype=bool)
+    if edge_jump > 0:
+        for axis in (-2, -1):
+            lo, hi = [slice(None)] * z.ndim, [slice(None)] * z.ndim
+            lo[axis], hi[axis] = slice(0, -1), slice(1, None)
+            lo, hi = tuple(lo), tuple(hi)
+            jump = ok[lo] & ok[hi] & (np.abs(z[lo] - z[hi]) > edge_jump)
+            hole[lo] |= jump
+            hole[hi] |= jump
+    out = np.where(ok & ~hole & (out > 0), out, 0.0).astype(np.float32)
+    return torch.from_numpy(out).to(depth.device) if is_torch else out
+
+
 def seeded_state_dict(seed=0, bias_scale=0.05, occ_bias=-0.5, out_scale=0.15):
     """Seeded decoder weights (pretrained/low_high.pt is missing from the reference snapshot):
     the reference's init distributions (xavier-uniform DenseLayers, N(0,25^2) Fourier matrices,

@@ -1592,6 +1592,23 @@ int adfp_rgbd_step(const float* cur_map, const float* normals_s, const float* de
                    void* state, double* stats /*[stats_rows][6]*/, double* rgb_stats /*[stats_rows][2]*/, int stats_rows, int row,
                    double* sums /*[31] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Depth bilateral filter (icp.depth_bilateral, DepthICP(bilateral=...), tracking.icp.bilateral: the filter of the raw sensor depth
+ * that KinectFusion's pipeline starts with, ahead of the normal map; no counterpart in the reference) ----  tests/depth_filter_ref.py
+ * states the rule in numpy.  Conventions are "Depth ICP"'s: f64 arithmetic on f32 loads, a depth is valid when d > 0 and finite.
+ * For a pixel p = (u, v) of image k with an invalid depth d_p, out = +0.0f: holes are not filled.  With a valid d_p:
+ *     s_p = sigma_depth + sigma_depth_z2 (d_p d_p);  a = 1 / ((2 sigma_space) sigma_space);  b = 1 / ((2 s_p) s_p);
+ *     q runs over the (2 radius + 1)^2 window around p clipped to the image, rows ascending, within a row columns ascending; a q takes
+ *     part when d_q is valid and !(|d_q - d_p| > 3 s_p);  w_q = exp(-((du du + dv dv) a + ((d_q - d_p) (d_q - d_p)) b)) with the integer
+ *     offsets du, dv: one f64 exp per tap;  num = sum w_q d_q, den = sum w_q, both added in q's order;  out = (float)(num / den).
+ *   The centre's own weight is 1, so den >= 1.  sigma_depth_z2 > 0 widens the range term with the square of the depth, as the axial
+ *   noise of a structured-light or time-of-flight sensor grows.
+ * One launch, no atomics: the same inputs give the same bytes.  Asynchronous on `stream`, no allocation, no pointer kept, no
+ * read-back, graph-capturable.  Errors, all before any launch: ADFP_E_ARG for a null pointer, out == depth, V, H, W or radius < 1, a
+ * NaN or <= 0 sigma_space or sigma_depth, a NaN or < 0 sigma_depth_z2; ADFP_E_UNSUPPORTED for radius above 8, H or W above 32768, V
+ * above 65535. */
+int adfp_depth_bilateral(const float* depth /*[V][H][W]*/, int V, int H, int W, int radius, double sigma_space, double sigma_depth,
+                         double sigma_depth_z2, float* out /*[V][H][W]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

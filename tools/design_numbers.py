@@ -541,6 +541,45 @@ def main(template, d):
                                 rg['rgbd_refine_over_refine']))
     else:
         v['rgbd_numbers'] = 'No run of `tools/icp_bench.py --rgbd-json` is in `profiles/`: the times of this path have not been measured.'
+    # the depth bilateral filter alone and in front of the refinement (tools/icp_bench.py --filter-json)
+    fl_path = Q('icp_filter_bench.json')
+    if os.path.exists(fl_path):
+        fl = json.load(open(fl_path))
+        cell3 = lambda s, f='%.3f': (f + ' (' + f + ', ' + f + ')') % (s['median_ms'], s['min_ms'], s['max_ms'])
+        rows = ['| leg | ms, median (min, max) |', '|---|---|']
+        for label, key in (('the filter alone, %d × %d, radius 2' % tuple(fl['frame']), 'filter_r2'), ('… radius 3', 'filter_r3'),
+                           ('the filter alone, %d × %d (TUM RGB-D), radius 2' % tuple(fl['tum_frame']), 'filter_tum_r2'),
+                           ('… radius 3', 'filter_tum_r3'), ('clean depth: `DepthICP.refine` without the filter (the comparator)', 'refine'),
+                           ('clean depth: `DepthICP(bilateral={}).refine`', 'refine_bilateral'),
+                           ('noisy depth: `DepthICP.refine` without the filter', 'refine_noisy'),
+                           ('noisy depth: `DepthICP(bilateral={}).refine`', 'refine_noisy_bilateral'),
+                           ('noisy depth: … with `points: false`', 'refine_noisy_bilateral_raw_points')):
+            rows.append('| %s | %s |' % (label, cell3(fl[key])))
+        off, on, cl = fl['refine_noisy'], fl['refine_noisy_bilateral'], fl['refine_bilateral']
+        deg = 57.29577951308232
+        v['filter_numbers'] = ('Measured on one MI355X (`profiles/icp_filter_bench.json`, one run of `tools/icp_bench.py --reps %d --filter-json`): section '
+                               '5.13\'s frame and pose, clean (the raycast at the true pose) and through `synthetic.sensor_depth`\'s default model '
+                               '(depths %.2f – %.2f m), and the same scene at TUM RGB-D\'s frame; the filter\'s defaults but for the radius.  Device events '
+                               'around each leg, the legs alternating within a repetition; the clean refinement without the filter is the path before '
+                               'this section, timed in the same run:\n\n' % (fl['reps'], fl['sensor_depth_range_m'][0], fl['sensor_depth_range_m'][1])
+                               + '\n'.join(rows) + '\n\n'
+                               + 'On clean depth both refinements go through all ten steps: the filter\'s launch at radius 2 is %.1f %% of the filtered '
+                                 '`refine`, which takes %.2f × the unfiltered one (%+.3f ms) and ends with status %d (0 = OK) %.2f mm and %.3f° from the true '
+                                 'pose against %.2f mm and %.3f° unfiltered -- the clean-depth cost again.  On the noisy frame the unfiltered refinement '
+                                 'ended with status %d on %s pairs in its first step (a refinement that fails does nothing in its remaining steps, hence '
+                                 'its short time) and returned the guess, %.1f mm and %.2f° off; the filtered one ended with status %d on %s to %s pairs '
+                                 'per step, %.2f mm and %.3f° from the true pose, and with `points: false` %.2f mm and %.3f°.  No threshold is set and no '
+                                 'speed target: these are the first times of this path.'
+                               % (100 * fl['filter_share_of_refine'], fl['refine_bilateral_over_refine'], fl['refine_bilateral_minus_refine_ms'],
+                                  cl['status'], cl['error_after_m_rad'][0] * 1e3, cl['error_after_m_rad'][1] * deg,
+                                  fl['refine']['error_after_m_rad'][0] * 1e3, fl['refine']['error_after_m_rad'][1] * deg,
+                                  off['status'], thousands(int(off['pairs_per_step'][0])), fl['error_before_m_rad'][0] * 1e3, fl['error_before_m_rad'][1] * deg,
+                                  on['status'], thousands(int(min(on['pairs_per_step']))), thousands(int(max(on['pairs_per_step']))),
+                                  on['error_after_m_rad'][0] * 1e3, on['error_after_m_rad'][1] * deg,
+                                  fl['refine_noisy_bilateral_raw_points']['error_after_m_rad'][0] * 1e3,
+                                  fl['refine_noisy_bilateral_raw_points']['error_after_m_rad'][1] * deg))
+    else:
+        v['filter_numbers'] = 'No run of `tools/icp_bench.py --filter-json` is in `profiles/`: the times of this path have not been measured.'
     s = open(template).read()
     out = re.sub(r'@@(\w+)@@', lambda m: v.get(m.group(1), m.group(0)), s)
     sys.stdout.write(out)

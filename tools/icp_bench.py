@@ -16,10 +16,22 @@ keyframe the scene seen from 36 mm / 27 mrad away (tests/rgbd_icp_ref.py's KEY_T
   promote        RgbdICP.promote: the map's copy and the pose's upload
   rgbd_refine    RgbdICP.refine as a whole, beside refine
 
+The depth bilateral filter (icp.depth_bilateral, csrc/adfp_depthfilter.h) and DepthICP(bilateral={...}); the sensor depth of these
+legs is the same frame through synthetic.sensor_depth's default noise model:
+
+  filter_rN / filter_tum_rN      the filter's launch alone at radius N = 2, 3, on this frame and on TUM RGB-D's (480 x 640)
+  refine_bilateral               DepthICP(bilateral={}).refine on the CLEAN frame, beside `refine`, the path before the filter: both go
+                                 through all ten steps, so their difference is the filter's launch and what it changes in the steps
+  refine_noisy                   DepthICP.refine without the filter on the noisy frame (a refinement that fails does nothing in its
+                                 remaining steps, so a failed leg is short: read its status beside its time)
+  refine_noisy_bilateral         DepthICP(bilateral={}).refine on the same frame (points and normals of the filtered image)
+  refine_noisy_bilateral_raw_points    the same with points: False
+
 Device events around each leg, median (min, max) of `--reps` repetitions after a warm-up; the legs alternate within a repetition.  No
-thresholds: the numbers go into DESIGN.md sections 5.13 and 5.13.1.
+thresholds: the numbers go into DESIGN.md sections 5.13, 5.13.1 and 5.13.2.
 
     python tools/icp_bench.py [--reps 7] [--json profiles/icp_bench.json] [--rgbd-json profiles/rgbd_icp_bench.json]
+                              [--filter-json profiles/icp_filter_bench.json]
 """
 import argparse
 import json
@@ -36,11 +48,12 @@ import icp_ref                                                 # noqa: E402
 import rgbd_icp_ref                                            # noqa: E402
 import attentive_dfprior_amd as A                              # noqa: E402
 from attentive_dfprior_amd import _lib, common, synthetic      # noqa: E402
-from attentive_dfprior_amd.icp import DepthICP, RgbdICP        # noqa: E402
+from attentive_dfprior_amd.icp import DepthICP, RgbdICP, depth_bilateral        # noqa: E402
 from attentive_dfprior_amd.tracking import TrackerIteration    # noqa: E402
 
 DEV = 'cuda:0'
 GEO = (680, 1200, 600.0, 600.0, 599.5, 339.5)                  # configs/Replica/replica.yaml
+GEO_TUM = (480, 640, 517.3, 516.5, 318.6, 255.3)               # TUM RGB-D, freiburg1
 CFG = {'rendering': {'lindisp': False, 'perturb': 0.0, 'N_samples': 48, 'N_surface': 16, 'N_importance': 0},
        'scale': 1, 'occupancy': True, 'meshing': {'resolution': 256}}
 
@@ -64,6 +77,7 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--json', default=None)
     ap.add_argument('--rgbd-json', default=None)
+    ap.add_argument('--filter-json', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'icp_bench needs a GPU'
     assert a.reps >= 5, 'at least 5 repetitions'
@@ -133,6 +147,21 @@ def main():
             'step_s4': one_step(4), 'step_s2': one_step(2), 'step_s1': one_step(1),
             'steps': icp.run_steps, 'refine': lambda: icp.refine(G, sensor), 'track10': track10}
     legs.update(rgbd_legs)
+
+    # the bilateral filter alone and in front of the refinement, on the frame through the sensor model
+    noisy = synthetic.sensor_depth(sensor, 0)
+    tum_noisy = synthetic.sensor_depth(icp.raycaster.render_depth(P, *GEO_TUM), 1)
+    filt_out, tum_out = torch.empty_like(noisy), torch.empty_like(tum_noisy)
+    filt = DepthICP(sc.tsdf_volume, tb, *GEO, engine=rend._engine, bilateral={})
+    filt_raw = DepthICP(sc.tsdf_volume, tb, *GEO, engine=rend._engine, bilateral={'points': False})
+    plain = DepthICP(sc.tsdf_volume, tb, *GEO, engine=rend._engine)
+    filter_legs = {'filter_r2': lambda: depth_bilateral(noisy, radius=2, out=filt_out), 'filter_r3': lambda: depth_bilateral(noisy, radius=3, out=filt_out),
+                   'filter_tum_r2': lambda: depth_bilateral(tum_noisy, radius=2, out=tum_out),
+                   'filter_tum_r3': lambda: depth_bilateral(tum_noisy, radius=3, out=tum_out),
+                   'refine_bilateral': lambda: filt.refine(G, sensor), 'refine_noisy': lambda: plain.refine(G, noisy), 'refine_noisy_bilateral': lambda: filt.refine(G, noisy),
+                   'refine_noisy_bilateral_raw_points': lambda: filt_raw.refine(G, noisy)}
+    if a.filter_json:
+        legs.update(filter_legs)
     for fn in legs.values():
         fn()
     torch.cuda.synchronize()
@@ -155,7 +184,31 @@ def main():
     assert common.get_camera_from_tensor(cam).shape == (3, 4)
     if a.json:
         with open(a.json, 'w') as f:
-            json.dump({k: v for k, v in res.items() if k not in rgbd_legs}, f, indent=1)
+            json.dump({k: v for k, v in res.items() if k not in rgbd_legs and k not in filter_legs}, f, indent=1)
+            f.write('\n')
+    if a.filter_json:
+        fo = {k: res[k] for k in ('device', 'reps', 'frame', 'volume', 'levels', 'refine')}
+        filt.refine(G, sensor)
+        st = filt.last_stats().numpy()
+        res['refine_bilateral'].update({'status': int(st[-1, 5]), 'pairs_per_step': st[:-1, 0].tolist(),
+                                        'error_after_m_rad': list(icp_ref.pose_error(filt.c2w_out.cpu().numpy(), P.cpu().numpy()))})
+        fo['refine'] = dict(fo['refine'], status=res['status'], pairs_per_step=res['pairs_per_step'], error_after_m_rad=res['error_after_m_rad'])
+        fo.update({k: res[k] for k in filter_legs})
+        Pn_ = P.cpu().numpy()
+        for name, obj in (('refine_noisy', plain), ('refine_noisy_bilateral', filt), ('refine_noisy_bilateral_raw_points', filt_raw)):
+            obj.refine(G, noisy)
+            st = obj.last_stats().numpy()
+            fo[name].update({'status': int(st[-1, 5]), 'pairs_per_step': st[:-1, 0].tolist(),
+                             'error_after_m_rad': list(icp_ref.pose_error(obj.c2w_out.cpu().numpy(), Pn_)),
+                             'valid_sensor_normals': int((obj.normals[0] != 0).any(-1).sum())})
+        fo.update({'tum_frame': list(GEO_TUM[:2]), 'bilateral': dict(filt.bilateral), 'error_before_m_rad': list(e0),
+                   'sensor_model': 'synthetic.sensor_depth defaults: sigma = 0.0012 + 0.0019 (z - 0.4)^2 m',
+                   'sensor_depth_range_m': [float(noisy[noisy > 0].min()), float(noisy.max())],
+                   'filter_share_of_refine': res['filter_r2']['median_ms'] / res['refine_bilateral']['median_ms'],
+                   'refine_bilateral_over_refine': res['refine_bilateral']['median_ms'] / res['refine']['median_ms'],
+                   'refine_bilateral_minus_refine_ms': res['refine_bilateral']['median_ms'] - res['refine']['median_ms']})
+        with open(a.filter_json, 'w') as f:
+            json.dump(fo, f, indent=1)
             f.write('\n')
     if a.rgbd_json:
         out = {k: res[k] for k in ('device', 'reps', 'frame', 'volume', 'levels', 'begin_is_timed_with_each_step', 'step_s4', 'step_s2', 'step_s1',
