@@ -837,9 +837,9 @@ class Engine(object):
             try:
                 a = _lib.AdfpRenderArgs()
                 if owed is not None:                     # this call's first launch packs them beside its zero fill
-                    a.pack_jobs, a.n_pack_jobs = C.cast(owed[0], C.c_void_p), owed[1]
+                    a.pack_jobs, a.n_pack_jobs = owed[0], owed[1]
                 if owed_rl is not None:                  # ... and converts the grids
-                    a.relayout_jobs, a.n_relayout_jobs = C.cast(owed_rl[0], C.c_void_p), owed_rl[1]
+                    a.relayout_jobs, a.n_relayout_jobs = owed_rl[0], owed_rl[1]
                 a.stage = _lib.STAGE[stage]
                 a.n_rays = N
                 a.n_samples = n_samples

@@ -816,7 +816,7 @@ int adfp_nn_build(const double* ref, long long n_ref, void* index, size_t index_
  * n_ref = 0 with queries is ADFP_E_ARG. */
 #define ADFP_NN_SORT_QUERIES 1
 size_t adfp_nn_query_workspace_bytes(long long n_query, int flags);
-int adfp_nn_query(const void* index, size_t index_bytes, long long n_ref, const double* query, long long n_query, const double* transform,
+int adfp_nn_query(const void* index, size_t index_bytes, long long n_ref, const double* query, long long n_query, const double transform[12],
                   double radius, int flags, void* workspace, size_t workspace_bytes, double* dist, int* idx, void* stream);
 /* Workspace of the two reductions below: 8 * 17 * min(max(ceil(n / 256), 1), 1024) bytes for n elements. */
 size_t adfp_recon_reduce_workspace_bytes(long long n);
@@ -827,7 +827,7 @@ int adfp_nn_metric_sums(const double* dist, long long n, double threshold, void*
  * correspondences i with idx[i] in [0, n_tgt) (an adfp_nn_query of src under the same transform): with p = T src_i - origin,
  * q = tgt[idx[i]] - origin, out (device f64 [17]) = count, sum d^2 (d^2 as the query computes it), sum p [3], sum q [3],
  * sum p q^T [3][3] row-major.  transform [12] and origin [3] are HOST arrays. */
-int adfp_icp_moments(const double* src, long long n_src, const double* transform, const double* origin, const double* tgt, long long n_tgt,
+int adfp_icp_moments(const double* src, long long n_src, const double transform[12], const double origin[3], const double* tgt, long long n_tgt,
                      const int* idx, void* workspace, size_t workspace_bytes, double* out, void* stream);
 /* trimesh.sample.sample_surface(mesh, count) (eval_recon.py:115-118) on caller-drawn uniforms u_face [count], u_bary [count][2]
  * (f64): face areas |cross(v1 - v0, v2 - v0)| / 2, their inclusive scan cum (fixed order; where the parallel scan's rounding

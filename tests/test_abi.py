@@ -59,54 +59,25 @@ def test_host_side_argument_errors_need_no_gpu():
 
 @pytest.mark.skipif(subprocess.call(['which', 'gcc'], stdout=subprocess.DEVNULL) != 0, reason='no gcc')
 def test_ctypes_struct_layout_matches_c(tmp_path):
+    """gcc is the judge of the binding's header parser: sizeof of every struct class _lib built and offsetof + size of every field
+    of it, from a generated C program compiled against include/adfp.h."""
+    structs = _lib.STRUCTS
+    assert len(structs) == 25 and all(getattr(_lib, cls.__name__) is cls for cls in structs.values())
+    lines = []
+    for name, cls in structs.items():
+        lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'printf("{name}.{f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f, _ in cls._fields_]
     prog = tmp_path / 'layout.c'
-    prog.write_text('''
-#include <stdio.h>
-#include <stddef.h>
-#include "adfp.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(adfp_grid), sizeof(adfp_tsdf), sizeof(adfp_scene), sizeof(adfp_points),
-         sizeof(adfp_render_args), sizeof(adfp_train_state), sizeof(adfp_backward_args), sizeof(adfp_loss_args));
-  printf("%zu %zu %zu %zu %zu\\n", offsetof(adfp_scene, low), offsetof(adfp_scene, tsdf), offsetof(adfp_scene, w_low),
-         offsetof(adfp_scene, w_att), offsetof(adfp_scene, status));
-  printf("%zu %zu %zu\\n", offsetof(adfp_points, pts), offsetof(adfp_points, z_vals), offsetof(adfp_points, S));
-  printf("%zu %zu %zu %zu %zu\\n", offsetof(adfp_render_args, perturb), offsetof(adfp_render_args, rays_o),
-         offsetof(adfp_render_args, workspace), offsetof(adfp_render_args, workspace_bytes), offsetof(adfp_render_args, state));
-  printf("%zu %zu %zu %zu %zu\\n", offsetof(adfp_backward_args, rays_o), offsetof(adfp_backward_args, state),
-         offsetof(adfp_backward_args, g_depth), offsetof(adfp_backward_args, g_rays_d), offsetof(adfp_backward_args, workspace_bytes));
-  printf("%zu %zu %zu %zu\\n", offsetof(adfp_backward_args, ray_keep), offsetof(adfp_loss_args, w_color_loss), offsetof(adfp_loss_args, depth),
-         offsetof(adfp_loss_args, g_weight));
-  printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(adfp_adam_group), offsetof(adfp_adam_group, mask), offsetof(adfp_adam_group, channels),
-         offsetof(adfp_adam_group, derived), offsetof(adfp_scene, ht_low), offsetof(adfp_train_state, masks_low),
-         offsetof(adfp_train_state, act_color));
-  printf("%zu %zu %zu %zu %zu\\n", sizeof(adfp_frame_job), offsetof(adfp_frame_job, fx), offsetof(adfp_frame_job, depth),
-         offsetof(adfp_frame_job, rays_d), offsetof(adfp_render_args, frame));
-  return 0;
-}''')
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "adfp.h"\nint main(void) {\n' + '\n'.join(lines) + '\nreturn 0;\n}\n')
     exe = tmp_path / 'layout'
     subprocess.check_call(['gcc', '-std=c99', '-I', os.path.join(ROOT, 'include'), str(prog), '-o', str(exe)])
-    out = subprocess.check_output([str(exe)]).decode().split('\n')
-    sz = list(map(int, out[0].split()))
-    assert sz == [ctypes.sizeof(_lib.AdfpGrid), ctypes.sizeof(_lib.AdfpTsdf), ctypes.sizeof(_lib.AdfpScene),
-                  ctypes.sizeof(_lib.AdfpPoints), ctypes.sizeof(_lib.AdfpRenderArgs),
-                  ctypes.sizeof(_lib.AdfpTrainState), ctypes.sizeof(_lib.AdfpBackwardArgs), ctypes.sizeof(_lib.AdfpLossArgs)]
-    S = _lib.AdfpScene
-    assert list(map(int, out[1].split())) == [S.low.offset, S.tsdf.offset, S.w_low.offset, S.w_att.offset, S.status.offset]
-    P = _lib.AdfpPoints
-    assert list(map(int, out[2].split())) == [P.pts.offset, P.z_vals.offset, P.S.offset]
-    R = _lib.AdfpRenderArgs
-    assert list(map(int, out[3].split())) == [R.perturb.offset, R.rays_o.offset, R.workspace.offset,
-                                              R.workspace_bytes.offset, R.state.offset]
-    B = _lib.AdfpBackwardArgs
-    assert list(map(int, out[4].split())) == [B.rays_o.offset, B.state.offset, B.g_depth.offset, B.g_rays_d.offset,
-                                              B.workspace_bytes.offset]
-    Lo = _lib.AdfpLossArgs
-    assert list(map(int, out[5].split())) == [B.ray_keep.offset, Lo.w_color_loss.offset, Lo.depth.offset, Lo.g_weight.offset]
-    G, T = _lib.AdfpAdamGroup, _lib.AdfpTrainState
-    assert list(map(int, out[6].split())) == [ctypes.sizeof(G), G.mask.offset, G.channels.offset, G.derived.offset, S.ht_low.offset,
-                                              T.masks_low.offset, T.act_color.offset]
-    F = _lib.AdfpFrameJob
-    assert list(map(int, out[7].split())) == [ctypes.sizeof(F), F.fx.offset, F.depth.offset, F.rays_d.offset, R.frame.offset]
+    c_says = {k: list(map(int, v)) for k, *v in (line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())}
+    ctypes_says = {}
+    for name, cls in structs.items():
+        ctypes_says[name] = [ctypes.sizeof(cls)]
+        ctypes_says.update({f'{name}.{f}': [getattr(cls, f).offset, getattr(cls, f).size] for f, _ in cls._fields_})
+    assert len(c_says) == len(lines) > 300
+    assert ctypes_says == c_says, sorted(k for k in c_says if ctypes_says.get(k) != c_says[k])
 
 
 def test_reference_fusion_kernel_builds_as_a_checker():
