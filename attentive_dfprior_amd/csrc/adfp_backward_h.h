@@ -96,8 +96,6 @@ ADFP_DEV void pack_decoder_ht_block(int blk, const float* __restrict__ flat, uns
     else { x = (_Float16)(a - ah); y = (_Float16)(b - bh); }
     packed[t] = (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
 }
-template <int CDIM, int NOUT>
-__global__ void k_pack_decoder_ht(const float* __restrict__ flat, unsigned* __restrict__ packed, int* __restrict__ status, int bit) { pack_decoder_ht_block<CDIM, NOUT>((int)blockIdx.x, flat, packed, status, bit); }
 
 struct DecodeBwdHArgs {
     PtsDev P; NormDev nb;
@@ -898,7 +896,6 @@ ADFP_DEV void pack_attention_ht_block(int blk, const float* __restrict__ flat, u
     else { x = (_Float16)(a - ah); y = (_Float16)(b - bh); }
     packed[t] = (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
 }
-__global__ void k_pack_attention_ht(const float* __restrict__ flat, unsigned* __restrict__ packed, int* __restrict__ status) { pack_attention_ht_block((int)blockIdx.x, flat, packed, status); }
 
 struct AttBwdHArgs {
     const unsigned* packed_t; const int* list; const int* count_ptr;

@@ -113,8 +113,6 @@ ADFP_DEV void pack_decoder_g_block(int blk, const float* __restrict__ flat, unsi
     else { x = (_Float16)(a - ah); y = (_Float16)(b - bh); }
     packed[t] = (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
 }
-template <int CDIM, int NOUT>
-__global__ void k_pack_decoder_g(const float* __restrict__ flat, unsigned* __restrict__ packed, int* __restrict__ status, int bit) { pack_decoder_g_block<CDIM, NOUT>((int)blockIdx.x, flat, packed, status, bit); }
 
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 
@@ -656,7 +654,6 @@ ADFP_DEV void pack_attention_g_block(int blk, const float* __restrict__ flat, un
     else { x = (_Float16)(a - ah); y = (_Float16)(b - bh); }
     packed[t] = (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
 }
-__global__ void k_pack_attention_g(const float* __restrict__ flat, unsigned* __restrict__ packed, int* __restrict__ status) { pack_attention_g_block((int)blockIdx.x, flat, packed, status); }
 
 // AttArgs is k_attention_h's; a.packed points at the G image
 template <int NT>

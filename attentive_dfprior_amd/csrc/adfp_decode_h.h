@@ -138,8 +138,6 @@ ADFP_DEV void pack_decoder_h_block(int blk, const float* __restrict__ flat, unsi
     else { x = (_Float16)(a - ah); y = (_Float16)(b - bh); }
     packed[t] = (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
 }
-template <int CDIM, int NOUT>
-__global__ void k_pack_decoder_h(const float* __restrict__ flat, unsigned* __restrict__ packed, int* __restrict__ status, int bit) { pack_decoder_h_block<CDIM, NOUT>((int)blockIdx.x, flat, packed, status, bit); }
 
 // 8 f32 -> 8 hi halves + 8 lo halves.  `amax` tracks max |x| of everything that was split (one v_max3_f32 per
 // pair): an operand at or beyond the f16 range (65504) cannot be split -- cvt_pkrtz saturates it -- so the kernels
@@ -421,7 +419,6 @@ ADFP_DEV void pack_attention_h_block(int blk, const float* __restrict__ flat, un
     else { x = (_Float16)(a - ah); y = (_Float16)(b - bh); }
     packed[t] = (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
 }
-__global__ void k_pack_attention_h(const float* __restrict__ flat, unsigned* __restrict__ packed, int* __restrict__ status) { pack_attention_h_block((int)blockIdx.x, flat, packed, status); }
 
 // relu(v) with its activity bit shifted into `m` (see relu_bias_mask)
 ADFP_DEV float relu_mask(float v, unsigned& m) {

@@ -1269,19 +1269,51 @@ static Workspace layout_forward(Arena& A, long long P) {
     return w;
 }
 
+// ---- the weight images of a network: every size, block count and kernel that depends on WHICH network is named HERE and nowhere
+// else on the host.  L / LH / LG / LT: the layouts of the exact f32 image, of the H and the G part of the f16-split image (G lies
+// behind H in one buffer) and of the transposed image; the pack job of H and of G has one block per range-flag word, that of the
+// f32 and the transposed image one thread per word.  (The job kernel's own dispatch is pack_multi_block below.)
+template <class L, class LH, class LG, class LT, int BIT, int ACT, void (*PACK_F32)(const float*, float*)>
+struct NetImagesOf {
+    static constexpr int FLAT_FLOATS = L::F_TOTAL, F32_FLOATS = L::P_TOTAL, F32_BLOCKS = (L::P_TOTAL + 255) / 256;
+    static constexpr int H_WORDS = LH::P_TOTAL, H_BLOCKS = LH::NFLAG, G_WORDS = LG::P_TOTAL, G_BLOCKS = LG::NFLAG;
+    static constexpr int HT_WORDS = LT::P_TOTAL, HT_BLOCKS = (LT::P_TOTAL + 255) / 256;
+    static constexpr int STATUS_BIT = BIT;
+    static constexpr int TRAIN_ACT_FLOATS = ACT;         // decoders: the layer inputs a training forward keeps per point
+    static constexpr auto pack_f32 = PACK_F32;
+};
+template <int CDIM, int NOUT, int BIT>
+using DecImages = NetImagesOf<DecLayout<CDIM, NOUT>, DecLayoutH<CDIM, NOUT>, DecLayoutG<CDIM, NOUT>, DecLayoutHT<CDIM, NOUT>, BIT,
+                              DecStage<CDIM>::NXM, k_pack_decoder<CDIM, NOUT>>;
+using LowImages = DecImages<32, 1, ADFP_STATUS_F16_RANGE_LOW>;
+using HighImages = DecImages<64, 1, ADFP_STATUS_F16_RANGE_HIGH>;
+using ColorImages = DecImages<32, 4, ADFP_STATUS_F16_RANGE_COLOR>;
+using AttImages = NetImagesOf<AttLayout, AttLayoutH, AttLayoutG, AttLayoutHT, ADFP_STATUS_F16_RANGE_ATT, 0, k_pack_attention>;
+// f(the images of network `net`), or ADFP_E_ARG for an id that names none; with_decoder: the same for a decoder kind
+template <class F>
+static long long with_net(int net, F f) {
+    switch (net) {
+        case ADFP_DEC_LOW: return f(LowImages{});
+        case ADFP_DEC_HIGH: return f(HighImages{});
+        case ADFP_DEC_COLOR: return f(ColorImages{});
+        case ADFP_NET_ATT: return f(AttImages{});
+    }
+    return ADFP_E_ARG;
+}
+template <class F>
+static long long with_decoder(int kind, F f) { return kind == ADFP_NET_ATT ? ADFP_E_ARG : with_net(kind, f); }
+// the G part of network N's f16-split image
+template <class N>
+static const unsigned* g_image(const void* split) { return (const unsigned*)split + N::H_WORDS; }
+
 // Several images in ONE launch: a training iteration re-packs four per step (the trained networks' forward and transposed images) and
 // a pack kernel is ~5 us inside a graph replay whatever it packs.  A workgroup belongs to one job (its first block is in `first`).
 struct PackJobs { int n; int first[ADFP_PACK_MAX_JOBS + 1]; int net[ADFP_PACK_MAX_JOBS]; int fmt[ADFP_PACK_MAX_JOBS];
                   const float* flat[ADFP_PACK_MAX_JOBS]; unsigned* out[ADFP_PACK_MAX_JOBS]; int* status; };
 static int pack_job_blocks(int net, int fmt) {
-    const bool h = fmt == ADFP_IMAGE_H, g = fmt == ADFP_IMAGE_G, t = fmt == ADFP_IMAGE_HT;
-    switch (net) {
-        case ADFP_DEC_LOW: return h ? DecLayoutH<32, 1>::NFLAG : (g ? DecLayoutG<32, 1>::NFLAG : (t ? (DecLayoutHT<32, 1>::P_TOTAL + 255) / 256 : -1));
-        case ADFP_DEC_HIGH: return h ? DecLayoutH<64, 1>::NFLAG : (g ? DecLayoutG<64, 1>::NFLAG : (t ? (DecLayoutHT<64, 1>::P_TOTAL + 255) / 256 : -1));
-        case ADFP_DEC_COLOR: return h ? DecLayoutH<32, 4>::NFLAG : (g ? DecLayoutG<32, 4>::NFLAG : (t ? (DecLayoutHT<32, 4>::P_TOTAL + 255) / 256 : -1));
-        case ADFP_NET_ATT: return h ? AttLayoutH::NFLAG : (g ? AttLayoutG::NFLAG : (t ? (AttLayoutHT::P_TOTAL + 255) / 256 : -1));
-    }
-    return -1;
+    return (int)with_net(net, [fmt](auto n) -> long long {
+        return fmt == ADFP_IMAGE_H ? n.H_BLOCKS : (fmt == ADFP_IMAGE_G ? n.G_BLOCKS : (fmt == ADFP_IMAGE_HT ? n.HT_BLOCKS : -1));
+    });
 }
 template <int CDIM, int NOUT>
 ADFP_DEV void pack_decoder_any(int fmt, int blk, const float* flat, unsigned* out, int* status, int bit) {
@@ -1382,6 +1414,23 @@ static int pack_jobs_table(int n_jobs, const adfp_pack_job* jobs, int* status, P
     }
     return 0;
 }
+// the single-image entries: the parts (ADFP_IMAGE_* bits) of one network's images as the jobs of one adfp_pack_images launch
+static int pack_parts(int net, int parts, const float* flat, void* packed, int* status, void* stream) {
+    adfp_pack_job jobs[3];
+    int n = 0;
+    for (int fmt : {ADFP_IMAGE_H, ADFP_IMAGE_G, ADFP_IMAGE_HT})
+        if (parts & fmt) jobs[n++] = {net, fmt, flat, packed};
+    return n ? adfp_pack_images(n, jobs, status, stream) : ADFP_E_ARG;
+}
+// the exact f32 image: float output and no status word, a kernel of its own per network
+static int pack_f32_image(int net, const float* flat, float* packed, void* stream) {
+    if (!flat || !packed) return ADFP_E_ARG;
+    return (int)with_net(net, [=](auto n) -> long long {
+        hipLaunchKernelGGL(decltype(n)::pack_f32, dim3(n.F32_BLOCKS), dim3(256), 0, (hipStream_t)stream, flat, packed);
+        ADFP_CHECK_LAUNCH();
+        return 0;
+    });
+}
 static int decode_grid(int ntiles, int waves_per_wg, int wg_per_cu) {
     int g = (ntiles + waves_per_wg - 1) / waves_per_wg;
     const int cap = num_cu() * wg_per_cu;
@@ -1418,7 +1467,7 @@ static int launch_decoder(DecodeArgs a, const NetImages& n, hipStream_t st) {
         else hipLaunchKernelGGL((k_decode_h<CDIM, NOUT, ROLE, 512, 1>), dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, a);
     } else if constexpr (ROLE == ROLE_HIGH) {
         if (n.h && !a.single) {
-            a.packed = (const float*)((const unsigned*)n.h + DecLayoutH<64, 1>::P_TOTAL);          // the G image
+            a.packed = (const float*)g_image<HighImages>(n.h);
             a.pool = pool;
             if (a.P.mode == ADFP_PTS_RAYS) hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT, true>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
             else hipLaunchKernelGGL((k_decode_high_g<ADFP_HIGH_NT, false>), dim3(decode_grid(ntiles, ADFP_HIGH_NT / 64, 1)), dim3(ADFP_HIGH_NT), 0, st, a);
@@ -1440,7 +1489,7 @@ static int launch_low_color(const adfp_scene* sc, const PtsDev& P, const unsigne
     DecodeLCArgs& f = t.f;
     f.P = P; f.nb = make_norm(sc->bound); fill_bound(f.b, sc->bound);
     f.g_low = make_grid(sc->low); f.g_color = make_grid(sc->color);
-    f.packed_low = (const unsigned*)sc->h_low + DecLayoutH<32, 1>::P_TOTAL; f.packed_color = (const unsigned*)sc->h_color + DecLayoutH<32, 4>::P_TOTAL;   // the G images
+    f.packed_low = g_image<LowImages>(sc->h_low); f.packed_color = g_image<ColorImages>(sc->h_color);
     f.flags = flags; f.raw = raw; f.w = w; f.write_w = 1; f.apply_bound = apply_bound; f.status = sc->status; f.call_flag = call_flag;
     const int ntiles = (P.n + 31) / 32;
     if (!state) {
@@ -1471,7 +1520,7 @@ static int launch_attention(AttArgs t, const adfp_scene* sc, int ntiles, hipStre
     else {
         t.masks = nullptr; t.act = nullptr;
         if (sc->h_att && t.count_ptr) {
-            t.packed = (const float*)((const unsigned*)sc->h_att + AttLayoutH::P_TOTAL);                 // the G image
+            t.packed = (const float*)g_image<AttImages>(sc->h_att);
             t.pool = pool;
             hipLaunchKernelGGL(k_attention_g<512>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
         } else if (sc->h_att) hipLaunchKernelGGL(k_attention_h<0>, dim3(decode_grid(ntiles, 8, 1)), dim3(512), 0, st, t);
@@ -1485,24 +1534,10 @@ extern "C" {
 
 int adfp_version(void) { return ADFP_VERSION; }
 
-long long adfp_decoder_flat_floats(int kind) {
-    switch (kind) {
-        case ADFP_DEC_LOW: return DecLayout<32, 1>::F_TOTAL;
-        case ADFP_DEC_HIGH: return DecLayout<64, 1>::F_TOTAL;
-        case ADFP_DEC_COLOR: return DecLayout<32, 4>::F_TOTAL;
-    }
-    return ADFP_E_ARG;
-}
-long long adfp_decoder_packed_floats(int kind) {
-    switch (kind) {
-        case ADFP_DEC_LOW: return DecLayout<32, 1>::P_TOTAL;
-        case ADFP_DEC_HIGH: return DecLayout<64, 1>::P_TOTAL;
-        case ADFP_DEC_COLOR: return DecLayout<32, 4>::P_TOTAL;
-    }
-    return ADFP_E_ARG;
-}
-long long adfp_attention_flat_floats(void) { return AttLayout::F_TOTAL; }
-long long adfp_attention_packed_floats(void) { return AttLayout::P_TOTAL; }
+long long adfp_decoder_flat_floats(int kind) { return with_decoder(kind, [](auto n) -> long long { return n.FLAT_FLOATS; }); }
+long long adfp_decoder_packed_floats(int kind) { return with_decoder(kind, [](auto n) -> long long { return n.F32_FLOATS; }); }
+long long adfp_attention_flat_floats(void) { return AttImages::FLAT_FLOATS; }
+long long adfp_attention_packed_floats(void) { return AttImages::F32_FLOATS; }
 
 size_t adfp_workspace_bytes(long long n_points) {
     if (n_points < 0) return 0;
@@ -1547,61 +1582,19 @@ int adfp_relayout_grid_back(const float* src, float* dst, int C, int Z, int Y, i
     return 0;
 }
 
+// Every single-image entry below is a wrapper: the exact f32 images of pack_f32_image, the f16-split and the transposed images of
+// adfp_pack_images (ONE pack kernel: what the engine's job tables run is what a C caller of these entries runs).
 int adfp_pack_decoder(int kind, const float* flat, float* packed, void* stream) {
-    if (!flat || !packed) return ADFP_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    switch (kind) {
-        case ADFP_DEC_LOW:
-            hipLaunchKernelGGL((k_pack_decoder<32, 1>), dim3((DecLayout<32, 1>::P_TOTAL + 255) / 256), dim3(256), 0, st, flat, packed);
-            break;
-        case ADFP_DEC_HIGH:
-            hipLaunchKernelGGL((k_pack_decoder<64, 1>), dim3((DecLayout<64, 1>::P_TOTAL + 255) / 256), dim3(256), 0, st, flat, packed);
-            break;
-        case ADFP_DEC_COLOR:
-            hipLaunchKernelGGL((k_pack_decoder<32, 4>), dim3((DecLayout<32, 4>::P_TOTAL + 255) / 256), dim3(256), 0, st, flat, packed);
-            break;
-        default: return ADFP_E_ARG;
-    }
-    ADFP_CHECK_LAUNCH();
-    return 0;
+    return kind == ADFP_NET_ATT ? ADFP_E_ARG : pack_f32_image(kind, flat, packed, stream);
 }
-// The split image of a 32-channel decoder is TWO images back to back: the "H" image (32x32x16 operand order: the training forward,
-// the single-network kernels) and the "G" image (16x16x32 operand order, adfp_decode_g.h: the fused low + colour inference launch).
-long long adfp_decoder_packed_h_words(int kind) {
-    switch (kind) {
-        case ADFP_DEC_LOW: return DecLayoutH<32, 1>::P_TOTAL + DecLayoutG<32, 1>::P_TOTAL;
-        case ADFP_DEC_HIGH: return DecLayoutH<64, 1>::P_TOTAL + DecLayoutG<64, 1>::P_TOTAL;
-        case ADFP_DEC_COLOR: return DecLayoutH<32, 4>::P_TOTAL + DecLayoutG<32, 4>::P_TOTAL;
-    }
-    return ADFP_E_ARG;
-}
-int adfp_pack_split_image(int net, int which, const float* flat, void* packed, int* status, void* stream) {
-    if (!flat || !packed || !(which & (ADFP_IMAGE_H | ADFP_IMAGE_G)) || (which & ~(ADFP_IMAGE_H | ADFP_IMAGE_G))) return ADFP_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned* out = (unsigned*)packed;
-    const bool H = which & ADFP_IMAGE_H, G = which & ADFP_IMAGE_G;
-    switch (net) {
-        case ADFP_DEC_LOW:
-            if (H) hipLaunchKernelGGL((k_pack_decoder_h<32, 1>), dim3(DecLayoutH<32, 1>::NFLAG), dim3(256), 0, st, flat, out, status, ADFP_STATUS_F16_RANGE_LOW);
-            if (G) hipLaunchKernelGGL((k_pack_decoder_g<32, 1>), dim3(DecLayoutG<32, 1>::NFLAG), dim3(256), 0, st, flat, out + DecLayoutH<32, 1>::P_TOTAL, status, ADFP_STATUS_F16_RANGE_LOW);
-            break;
-        case ADFP_DEC_HIGH:
-            if (H) hipLaunchKernelGGL((k_pack_decoder_h<64, 1>), dim3(DecLayoutH<64, 1>::NFLAG), dim3(256), 0, st, flat, out, status, ADFP_STATUS_F16_RANGE_HIGH);
-            if (G) hipLaunchKernelGGL((k_pack_decoder_g<64, 1>), dim3(DecLayoutG<64, 1>::NFLAG), dim3(256), 0, st, flat, out + DecLayoutH<64, 1>::P_TOTAL, status, ADFP_STATUS_F16_RANGE_HIGH);
-            break;
-        case ADFP_DEC_COLOR:
-            if (H) hipLaunchKernelGGL((k_pack_decoder_h<32, 4>), dim3(DecLayoutH<32, 4>::NFLAG), dim3(256), 0, st, flat, out, status, ADFP_STATUS_F16_RANGE_COLOR);
-            if (G) hipLaunchKernelGGL((k_pack_decoder_g<32, 4>), dim3(DecLayoutG<32, 4>::NFLAG), dim3(256), 0, st, flat, out + DecLayoutH<32, 4>::P_TOTAL, status, ADFP_STATUS_F16_RANGE_COLOR);
-            break;
-        case ADFP_NET_ATT:
-            if (H) hipLaunchKernelGGL(k_pack_attention_h, dim3(AttLayoutH::NFLAG), dim3(256), 0, st, flat, out, status);
-            if (G) hipLaunchKernelGGL(k_pack_attention_g, dim3(AttLayoutG::NFLAG), dim3(256), 0, st, flat, out + AttLayoutH::P_TOTAL, status);
-            break;
-        default: return ADFP_E_ARG;
-    }
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
+int adfp_pack_attention(const float* flat, float* packed, void* stream) { return pack_f32_image(ADFP_NET_ATT, flat, packed, stream); }
+// The split image of a network is TWO images back to back: the "H" image (32x32x16 operand order: the training forward, the
+// single-network kernels) and the "G" image (16x16x32 operand order, adfp_decode_g.h: the inference kernels).
+long long adfp_decoder_packed_h_words(int kind) { return with_decoder(kind, [](auto n) -> long long { return n.H_WORDS + n.G_WORDS; }); }
+long long adfp_decoder_packed_ht_words(int kind) { return with_decoder(kind, [](auto n) -> long long { return n.HT_WORDS; }); }
+long long adfp_train_act_floats(int kind) { return with_decoder(kind, [](auto n) -> long long { return n.TRAIN_ACT_FLOATS; }); }
+long long adfp_attention_packed_h_words(void) { return AttImages::H_WORDS + AttImages::G_WORDS; }
+long long adfp_attention_packed_ht_words(void) { return AttImages::HT_WORDS; }
 int adfp_pack_images(int n_jobs, const adfp_pack_job* jobs, int* status, void* stream) {
     PackJobs j;
     int rc = pack_jobs_table(n_jobs, jobs, status, j); if (rc) return rc;
@@ -1610,60 +1603,21 @@ int adfp_pack_images(int n_jobs, const adfp_pack_job* jobs, int* status, void* s
     ADFP_CHECK_LAUNCH();
     return 0;
 }
-int adfp_pack_decoder_h(int kind, const float* flat, void* packed, int* status, void* stream) {
-    if (kind < ADFP_DEC_LOW || kind > ADFP_DEC_COLOR) return ADFP_E_ARG;
-    return adfp_pack_split_image(kind, ADFP_IMAGE_H | ADFP_IMAGE_G, flat, packed, status, stream);
+int adfp_pack_split_image(int net, int which, const float* flat, void* packed, int* status, void* stream) {
+    if (which & ~(ADFP_IMAGE_H | ADFP_IMAGE_G)) return ADFP_E_ARG;
+    return pack_parts(net, which, flat, packed, status, stream);
 }
-long long adfp_decoder_packed_ht_words(int kind) {
-    switch (kind) {
-        case ADFP_DEC_LOW: return DecLayoutHT<32, 1>::P_TOTAL;
-        case ADFP_DEC_HIGH: return DecLayoutHT<64, 1>::P_TOTAL;
-        case ADFP_DEC_COLOR: return DecLayoutHT<32, 4>::P_TOTAL;
-    }
-    return ADFP_E_ARG;
+int adfp_pack_decoder_h(int kind, const float* flat, void* packed, int* status, void* stream) {
+    return kind == ADFP_NET_ATT ? ADFP_E_ARG : pack_parts(kind, ADFP_IMAGE_H | ADFP_IMAGE_G, flat, packed, status, stream);
 }
 int adfp_pack_decoder_ht(int kind, const float* flat, void* packed, int* status, void* stream) {
-    if (!flat || !packed) return ADFP_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned* out = (unsigned*)packed;
-    switch (kind) {
-        case ADFP_DEC_LOW:
-            hipLaunchKernelGGL((k_pack_decoder_ht<32, 1>), dim3((DecLayoutHT<32, 1>::P_TOTAL + 255) / 256), dim3(256), 0, st, flat, out, status, ADFP_STATUS_F16_RANGE_LOW);
-            break;
-        case ADFP_DEC_HIGH:
-            hipLaunchKernelGGL((k_pack_decoder_ht<64, 1>), dim3((DecLayoutHT<64, 1>::P_TOTAL + 255) / 256), dim3(256), 0, st, flat, out, status, ADFP_STATUS_F16_RANGE_HIGH);
-            break;
-        case ADFP_DEC_COLOR:
-            hipLaunchKernelGGL((k_pack_decoder_ht<32, 4>), dim3((DecLayoutHT<32, 4>::P_TOTAL + 255) / 256), dim3(256), 0, st, flat, out, status, ADFP_STATUS_F16_RANGE_COLOR);
-            break;
-        default: return ADFP_E_ARG;
-    }
-    ADFP_CHECK_LAUNCH();
-    return 0;
+    return kind == ADFP_NET_ATT ? ADFP_E_ARG : pack_parts(kind, ADFP_IMAGE_HT, flat, packed, status, stream);
 }
-long long adfp_train_act_floats(int kind) {
-    switch (kind) {
-        case ADFP_DEC_LOW: case ADFP_DEC_COLOR: return DecStage<32>::NXM;
-        case ADFP_DEC_HIGH: return DecStage<64>::NXM;
-    }
-    return ADFP_E_ARG;
-}
-long long adfp_attention_packed_h_words(void) { return AttLayoutH::P_TOTAL + AttLayoutG::P_TOTAL; }      // H image, then G image (see adfp_decoder_packed_h_words)
 int adfp_pack_attention_h(const float* flat, void* packed, int* status, void* stream) {
-    return adfp_pack_split_image(ADFP_NET_ATT, ADFP_IMAGE_H | ADFP_IMAGE_G, flat, packed, status, stream);
+    return pack_parts(ADFP_NET_ATT, ADFP_IMAGE_H | ADFP_IMAGE_G, flat, packed, status, stream);
 }
-long long adfp_attention_packed_ht_words(void) { return AttLayoutHT::P_TOTAL; }
 int adfp_pack_attention_ht(const float* flat, void* packed, int* status, void* stream) {
-    if (!flat || !packed) return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_pack_attention_ht, dim3((AttLayoutHT::P_TOTAL + 255) / 256), dim3(256), 0, (hipStream_t)stream, flat, (unsigned*)packed, status);
-    ADFP_CHECK_LAUNCH();
-    return 0;
-}
-int adfp_pack_attention(const float* flat, float* packed, void* stream) {
-    if (!flat || !packed) return ADFP_E_ARG;
-    hipLaunchKernelGGL(k_pack_attention, dim3((AttLayout::P_TOTAL + 255) / 256), dim3(256), 0, (hipStream_t)stream, flat, packed);
-    ADFP_CHECK_LAUNCH();
-    return 0;
+    return pack_parts(ADFP_NET_ATT, ADFP_IMAGE_HT, flat, packed, status, stream);
 }
 
 int adfp_get_rays(int H, int W, float fx, float fy, float cx, float cy, const float* c2w, float* rays_o, float* rays_d, void* stream) {

@@ -43,19 +43,19 @@ class DenseLayer(nn.Linear):
 
 
 _PACK_SIZES = {}
+_SIZE_QUERY = {'f32': 'packed_floats', 'h': 'packed_h_words', 'g': 'packed_h_words', 'hg': 'packed_h_words', 'ht': 'packed_ht_words'}
+_IMAGE_PARTS = {'h': (_lib.IMAGE_H,), 'g': (_lib.IMAGE_G,), 'hg': (_lib.IMAGE_H, _lib.IMAGE_G), 'ht': (_lib.IMAGE_HT,)}
 
 
 def _pack_size(name, fmt):
-    """Element count of a packed image (int32 words for the f16-split images, floats for the exact one); constants of the library."""
+    """Element count of a packed image (int32 words for the f16-split images, floats for the exact one); constants of the library.
+    One buffer holds the H and the G layout, so 'h', 'g' and 'hg' ask the same query."""
     hit = _PACK_SIZES.get((name, fmt))
     if hit is None:
-        L = lib()
-        f = 'h' if fmt in ('g', 'hg') else fmt                 # one buffer holds the H and the G layout (adfp_pack_split_image)
         if name == 'att':
-            hit = {'h': L.adfp_attention_packed_h_words, 'ht': L.adfp_attention_packed_ht_words, 'f32': L.adfp_attention_packed_floats}[f]()
+            hit = getattr(lib(), 'adfp_attention_' + _SIZE_QUERY[fmt])()
         else:
-            kind = _lib.DEC_KIND[name]
-            hit = {'h': L.adfp_decoder_packed_h_words, 'ht': L.adfp_decoder_packed_ht_words, 'f32': L.adfp_decoder_packed_floats}[f](kind)
+            hit = getattr(lib(), 'adfp_decoder_' + _SIZE_QUERY[fmt])(_lib.DEC_KIND[name])
         _PACK_SIZES[(name, fmt)] = hit = int(hit)
     return hit
 
@@ -82,16 +82,17 @@ def flush_pack_jobs(jobs, status, device):
 
 def pack_network(name, params, fmt='f32', status=None, flat=None, out=None, defer=None):
     """Packed image of one sub-network ('low' / 'high' / 'color' / 'att') from its parameters in state_dict order.
-    fmt: 'f32' (adfp_pack_decoder / adfp_pack_attention), 'ht' (adfp_pack_*_ht); 'h' / 'g' / 'hg': the split image with its H
-    (32x32x16 order: training forward, single-network entries) / G (16x16x32 order: inference kernels) / both parts written.
+    fmt: 'f32' (the exact image: adfp_pack_decoder / adfp_pack_attention); 'ht' (the transposed f16-split image of the backward);
+    'h' / 'g' / 'hg': the split image with its H (32x32x16 order: training forward, single-network entries) / G (16x16x32 order:
+    inference kernels) / both parts written.  Every f16-split format is one or two jobs of the library's one pack kernel
+    (adfp_pack_images).
     status: the pinned status word a weight outside the f16 range is reported to (default: the process-wide one).
     out: an image of the same network and format to overwrite (a training iteration re-packs the trained networks every step:
     same-stream ordering makes the in-place rebuild safe, and the image keeps its address).
-    defer: a list -- the split-image parts and the transposed image are not packed here but appended as jobs
-    (net, ADFP_IMAGE_*, flat, packed) for flush_pack_jobs; the caller flushes before it launches anything that reads an image."""
+    defer: a list -- the jobs (net, ADFP_IMAGE_*, flat, packed) are not launched here but appended for flush_pack_jobs; the caller
+    flushes before it launches anything that reads an image.  Without it (or without room for two more jobs) they are launched at once."""
     if flat is None:
         flat = _flat_params(params)
-    sptr = _lib.status_ptr() if status is None else _lib.C.c_void_p(status.data_ptr())
     _lib.require_cuda(flat, f'{name} decoder parameters')
     L = lib()
     dev = flat.device
@@ -100,31 +101,20 @@ def pack_network(name, params, fmt='f32', status=None, flat=None, out=None, defe
     if out is not None and (out.numel() != n or out.dtype != dtype or out.device != dev):
         out = None
     with _lib.device_guard(dev):
-        stream = _lib.current_stream(dev)
         packed = out if out is not None else torch.empty(n, dtype=dtype, device=dev)
-        if defer is not None and fmt in ('h', 'g', 'hg', 'ht') and len(defer) + 2 <= 8:
-            for part, bit in (('h', _lib.IMAGE_H), ('g', _lib.IMAGE_G), ('ht', _lib.IMAGE_HT)):
-                if part == fmt or (fmt == 'hg' and part != 'ht'):
-                    defer.append((_lib.NET_ID[name], bit, flat, packed))
-            return packed
-        if fmt in ('h', 'g', 'hg'):
-            which = {'h': _lib.IMAGE_H, 'g': _lib.IMAGE_G, 'hg': _lib.IMAGE_H | _lib.IMAGE_G}[fmt]
-            _lib.check(L.adfp_pack_split_image(_lib.NET_ID[name], which, _lib.ptr(flat), _lib.ptr(packed), sptr, stream), 'adfp_pack_split_image')
-        elif fmt in ('h', 'ht'):
-            if name == 'att':
-                fn = L.adfp_pack_attention_h if fmt == 'h' else L.adfp_pack_attention_ht
-                _lib.check(fn(_lib.ptr(flat), _lib.ptr(packed), sptr, stream), 'adfp_pack_attention_' + fmt)
+        if fmt != 'f32':
+            jobs = [(_lib.NET_ID[name], part, flat, packed) for part in _IMAGE_PARTS[fmt]]
+            if defer is not None and len(defer) + 2 <= _lib.PACK_MAX_JOBS:
+                defer.extend(jobs)
             else:
-                kind = _lib.DEC_KIND[name]
-                fn = L.adfp_pack_decoder_h if fmt == 'h' else L.adfp_pack_decoder_ht
-                _lib.check(fn(kind, _lib.ptr(flat), _lib.ptr(packed), sptr, stream), 'adfp_pack_decoder_' + fmt)
+                flush_pack_jobs(jobs, status, dev)
         elif name == 'att':
             assert flat.numel() == L.adfp_attention_flat_floats()
-            _lib.check(L.adfp_pack_attention(_lib.ptr(flat), _lib.ptr(packed), stream), 'adfp_pack_attention')
+            _lib.check(L.adfp_pack_attention(_lib.ptr(flat), _lib.ptr(packed), _lib.current_stream(dev)), 'adfp_pack_attention')
         else:
             kind = _lib.DEC_KIND[name]
             assert flat.numel() == L.adfp_decoder_flat_floats(kind)
-            _lib.check(L.adfp_pack_decoder(kind, _lib.ptr(flat), _lib.ptr(packed), stream), 'adfp_pack_decoder')
+            _lib.check(L.adfp_pack_decoder(kind, _lib.ptr(flat), _lib.ptr(packed), _lib.current_stream(dev)), 'adfp_pack_decoder')
     return packed
 
 
@@ -425,8 +415,8 @@ class DF(nn.Module):
     def packed_weights(self, name, fmt='f32', key=None):
         """Packed (MFMA operand order) image of one sub-network, rebuilt only when a parameter
         changed (optimizer step bumps Parameter._version).  fmt 'f32' = exact f32-input MFMA image,
-        'h' = f16 hi/lo split image of the forward decoders (adfp_pack_decoder_h), 'ht' = the transposed split image of
-        the f16 backward (adfp_pack_decoder_ht / adfp_pack_attention_ht).  key: net_key(name) if the caller has it already.
+        'h' / 'g' / 'hg' = the H / G / both parts of the f16 hi/lo split image of the forward kernels, 'ht' = the transposed split
+        image of the f16 backward (all of them jobs of adfp_pack_images, see pack_network).  key: net_key(name) if the caller has it already.
         A stale image is rebuilt IN PLACE (same address; stream order protects kernels already queued on it)."""
         module = self.net_params(name)
         if key is None:

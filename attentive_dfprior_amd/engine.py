@@ -396,7 +396,7 @@ class Engine(object):
                     self.flush_relayout_jobs(rjobs, next(iter(c.values())).device)
                 rjobs = []
             self._owed_packs = None
-            if hand_over_packs and 0 < len(jobs) <= 8:
+            if hand_over_packs and 0 < len(jobs) <= _lib.PACK_MAX_JOBS:
                 from .decoder import pack_jobs_array
                 arr, alive = pack_jobs_array(jobs)
                 self._owed_packs = (arr, len(jobs), alive)

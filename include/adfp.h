@@ -162,7 +162,10 @@ int adfp_relayout_tsdf(const adfp_tsdf* tsdf /*host*/, float* dst, void* stream)
 /* flat state_dict-order parameters -> packed MFMA image (MLP: decoder.py:91-203) */
 int adfp_pack_decoder(int kind, const float* flat, float* packed, void* stream);
 /* same parameters -> "H" image (f16 hi/lo halves of every weight), adfp_decoder_packed_h_words(kind) 32-bit words.
- * status (may be NULL): as adfp_scene.status -- ADFP_STATUS_F16_RANGE is raised for a weight with |w| >= 65504. */
+ * status (may be NULL): as adfp_scene.status -- ADFP_STATUS_F16_RANGE is raised for a weight with |w| >= 65504.
+ * There is ONE pack kernel for the f16-split images (H, G, HT), adfp_pack_images' below; the five single-image entries
+ * adfp_pack_decoder_h / _ht, adfp_pack_attention_h / _ht and adfp_pack_split_image are wrappers that hand it a one- or two-job
+ * table (same arguments refused, same images, same status reporting as a job of adfp_pack_images). */
 long long adfp_decoder_packed_h_words(int kind);
 int adfp_pack_decoder_h(int kind, const float* flat, void* packed, int* status, void* stream);
 /* -> "T" image for the f16-split backward, adfp_decoder_packed_ht_words(kind) 32-bit words */
@@ -191,7 +194,8 @@ int adfp_pack_split_image(int net, int which, const float* flat, void* packed, i
 /* Several packed images in ONE launch (a Mapper iteration re-packs four per step: the trained networks' forward parts and their
  * transposed images): job = one image of one network.  format is exactly one of ADFP_IMAGE_H / ADFP_IMAGE_G (that part of the
  * split image buffer `packed`, as adfp_pack_split_image writes it) or ADFP_IMAGE_HT (`packed` = the transposed image of
- * adfp_pack_decoder_ht / adfp_pack_attention_ht).  Same kernels' arithmetic, same status reporting; at most ADFP_PACK_MAX_JOBS jobs. */
+ * adfp_pack_decoder_ht / adfp_pack_attention_ht).  The same kernel as those entries run, the same status reporting; at most
+ * ADFP_PACK_MAX_JOBS jobs.  A render call's adfp_render_args.pack_jobs run the same code inside the call's first launch. */
 #define ADFP_IMAGE_HT 4
 #define ADFP_PACK_MAX_JOBS 8
 typedef struct adfp_pack_job { int net; int format; const float* flat; void* packed; } adfp_pack_job;

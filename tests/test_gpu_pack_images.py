@@ -1,4 +1,6 @@
-"""GPU: the transposed f16-split weight images of the backward (adfp_pack_decoder_ht / adfp_pack_attention_ht) decoded on the
+"""GPU: the weight images.  At the end of the file: every pack route against the digests recorded from the single-image entries
+before they became wrappers of the job kernel (tests/golden/pack_images.json).  First:
+the transposed f16-split weight images of the backward (adfp_pack_decoder_ht / adfp_pack_attention_ht) decoded on the
 host and compared with the parameters they were packed from.  The layout is restated here independently of the kernels:
 (weights of ~0.1 have lo halves in the f16 subnormal range: hi + lo reproduces them to ~3e-8 absolute)
 a chain block is 2 k-steps x [hi | lo] x [lane half h] x [32 rows] x [8 halves]; k-step ks, half h, element j carries OUT
@@ -10,6 +12,7 @@ import torch
 import attentive_dfprior_amd as A
 from attentive_dfprior_amd import _lib
 from oracle import adfp_oracle as O
+import pack_images_golden as G
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
@@ -83,9 +86,10 @@ def test_attention_t_image_holds_the_transposed_weights():
 
 
 def test_pack_images_in_one_launch_equals_the_single_image_entries():
-    """adfp_pack_images (several images of several networks in ONE launch: what Engine.scene() issues per call) against
-    adfp_pack_split_image / adfp_pack_decoder_ht / adfp_pack_attention_ht one by one: every image bit for bit, and the same
-    range report for a weight the f16 split cannot hold."""
+    """adfp_pack_images with several images of several networks in ONE launch (what Engine.scene() issues per call) against
+    pack_network image by image: every image bit for bit, and the same range report for a weight the f16 split cannot hold.
+    Both sides run the library's one pack kernel (the single-image entries are wrappers of it), so this holds the job table's
+    block ranges and the deferred bookkeeping together; the anchor outside today's code is the recorded digests (tests below)."""
     import ctypes as C
     from attentive_dfprior_amd.decoder import pack_network, flush_pack_jobs
     sd = O.random_state_dict(seed=9)
@@ -131,3 +135,59 @@ def test_pack_images_in_one_launch_equals_the_single_image_entries():
     assert {'color.ht', 'att.ht', 'low.ht', 'high.ht'} <= keys, keys         # the backward's images were packed with the forward's
     (d.sum() + col.sum()).backward()
     assert all(torch.isfinite(p.grad).all() for p in dec2.parameters() if p.grad is not None)
+
+
+def image_by(route, dec, name, fmt, status):
+    """`name`'s image in format `fmt` by one route, into a buffer pre-filled with G.FILL."""
+    from attentive_dfprior_amd.decoder import pack_network, flush_pack_jobs
+    flat = dec.flat_weights(name)
+    if route.startswith('entry'):
+        return G.entry_image(name, fmt, flat, status, two_part_entry=route == 'entry2')
+    jobs = [] if route == 'deferred' else None
+    got = pack_network(name, dec.net_params(name), fmt, status=status, flat=flat, out=G.filled(name, fmt, DEV), defer=jobs)
+    if jobs is not None:
+        assert len(jobs) == (2 if fmt == 'hg' else 1)
+        flush_pack_jobs(jobs, status, DEV)
+        assert jobs == []
+    return got
+
+
+@pytest.mark.parametrize('case', ['seed9_out_of_range', 'seed5'])
+def test_every_pack_route_reproduces_the_recorded_images(case):
+    """pack_network at once, pack_network deferred + flush_pack_jobs and the C entries (adfp_pack_split_image, adfp_pack_decoder_h /
+    adfp_pack_attention_h, adfp_pack_decoder_ht / adfp_pack_attention_ht, and the f32 entries): every image of every network has
+    the recorded SHA-256, and every route leaves the recorded status word.  Packing is conversion and integer arithmetic on fixed
+    shapes: bit-exact, no tolerance."""
+    want = G.golden()['cases'][case]
+    dec = G.loaded(G.state_dicts()[case])
+    for n in G.NETS:
+        assert G.sha(dec.flat_weights(n)) == want['flat'][n], f'{n}: the INPUT differs from the recorded one (not the packing)'
+    for route, fmts in (('direct', ('hg', 'ht', 'f32')), ('deferred', ('hg', 'ht')), ('entry', ('hg', 'ht', 'f32')), ('entry2', ('hg',))):
+        status = _lib.new_status_word()
+        images = {(n, f): image_by(route, dec, n, f, status) for n in G.NETS for f in fmts}
+        torch.cuda.synchronize()
+        for (n, f), image in images.items():
+            assert G.sha(image) == want[f][n], (route, n, f)
+        if route != 'entry2':                                  # every network's split image went through: the whole word
+            assert int(status[0]) == want['status'], route
+    assert want['status'] == (_lib.STATUS_RANGE_BITS['att'] if case == 'seed9_out_of_range' else 0)
+
+
+@pytest.mark.parametrize('route', ['direct', 'deferred', 'entry'])
+def test_h_and_g_alone_write_their_part_of_the_split_image_only(route):
+    """'h' alone and 'g' alone into buffers of G.FILL: what each wrote equals the same words of the (recorded) 'hg' image, the rest
+    still holds the fill, and the two regions -- H in front, G behind it -- are disjoint and cover the buffer."""
+    case = 'seed9_out_of_range'
+    want = G.golden()['cases'][case]
+    dec, status = G.loaded(G.state_dicts()[case]), _lib.new_status_word()
+    for n in G.NETS:
+        hg, h, g = (image_by(route, dec, n, f, status) for f in ('hg', 'h', 'g'))
+        assert G.sha(hg) == want['hg'][n]
+        wrote_h, wrote_g = h != G.FILL, g != G.FILL
+        nh = int(wrote_h.sum())
+        assert 0 < nh < hg.numel() and wrote_h[:nh].all() and wrote_g[nh:].all(), n      # a prefix and the suffix behind it
+        assert not (wrote_h & wrote_g).any() and (wrote_h | wrote_g).all(), n
+        assert torch.equal(h[:nh], hg[:nh]) and torch.equal(g[nh:], hg[nh:]), n
+        assert (h[nh:] == G.FILL).all() and (g[:nh] == G.FILL).all(), n
+    torch.cuda.synchronize()
+    assert int(status[0]) == want['status']
