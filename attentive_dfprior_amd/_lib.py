@@ -2,7 +2,9 @@
 
 The header is the only statement of the C ABI.  Its structs become the ``ctypes.Structure`` classes below (``adfp_scene`` ->
 ``AdfpScene``), its prototypes the ``SYMBOLS`` table and its integer ``#define ADFP_X`` the constants ``X``: a new entry point is
-a declaration in the header plus its definition in csrc/, nothing here.
+a declaration in the header plus its definition in csrc/, nothing here.  A tool wrapper calls it as ``with on(dev) as L:
+L.adfp_x(tensor, n, ..., out)``: its argument checks, its output allocation and that one line, which names the entry point once
+(device, stream, NULL for an empty tensor and the return code are ``on``'s).
 The product path has no CPU fallback: if the HIP library is missing, ``lib()`` raises and
 every compute entry point of this package fails loudly.
 """
@@ -242,6 +244,69 @@ class device_guard(object):
             torch._C._cuda_setDevice(self.prev)
             self.prev = -1
         return False
+
+
+# ---- the tool wrappers' call path ------------------------------------------------------------------------------
+HOST_ONLY = {'adfp_mc_table', 'adfp_ingest_out_shape', 'adfp_undistort_map', 'adfp_vis_canvas_shape', 'adfp_frame_metrics_windows'}
+assert HOST_ONLY < {name for name, _, _ in SYMBOLS}
+# the entry points that end in `void* stream`: every int-returning one but adfp_version and the host-only five
+LAUNCHES = {name for name, res, _ in SYMBOLS if res is C.c_int} - HOST_ONLY - {'adfp_version'}
+
+
+_Tensor = None
+
+
+def _checked(name, *tail):
+    """lib().name as the wrappers call it: a tensor argument goes as its data pointer, None or a tensor of no elements as NULL,
+    anything else as it is; `tail` is appended; the return code goes through check() under the entry point's own name."""
+    global _Tensor
+    if _Tensor is None:
+        from torch import Tensor as _Tensor
+    fn, Tensor, void = getattr(lib(), name), _Tensor, C.c_void_p
+
+    def call(*args):
+        rc = fn(*[a if not isinstance(a, Tensor) else void(a.data_ptr()) if a.numel() else None for a in args], *tail)
+        if rc:
+            check(rc, name)
+    return call
+
+
+class on(device_guard):
+    """`with on(dev) as L: L.adfp_x(a, n, out)` = adfp_x(ptr(a), n, ptr(out), stream) on `dev`, checked: device_guard(dev), with
+    current_stream(dev) read once on entry and appended to every launch.  Only LAUNCHES; sizes and host-only calls raise."""
+
+    def __init__(self, dev):
+        device_guard.__init__(self, dev)
+        self.dev = dev
+
+    def __enter__(self):
+        device_guard.__enter__(self)
+        self.stream = current_stream(self.dev)
+        return self
+
+    def __getattr__(self, name):           # once per name and `with`: the call is kept on the instance
+        if name not in LAUNCHES:
+            raise AttributeError(f'{name} is not an entry point of include/adfp.h that ends in a stream: call it through lib()')
+        call = self.__dict__[name] = _checked(name, self.stream)
+        return call
+
+
+class _Host(object):
+    """`host.adfp_x(...)`: the HOST_ONLY entry points (no device, no stream), arguments and return code as under on()."""
+
+    def __getattr__(self, name):
+        if name not in HOST_ONLY:
+            raise AttributeError(f'{name} is not a host-only entry point of include/adfp.h')
+        return _checked(name)
+
+
+host = _Host()
+
+
+def workspace(nbytes, dev):
+    """A scratch buffer of `nbytes` (at least one, so that its pointer is never NULL) on `dev`."""
+    import torch
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
 
 
 def fill_bound(dst, values):

@@ -34,7 +34,6 @@ import torch
 from torch.utils.data import Dataset
 
 from . import _lib
-from ._lib import lib, check
 
 
 def imread_cv2(path, unchanged=False):
@@ -78,8 +77,7 @@ def undistort_map(color_hw, fx, fy, cx, cy, dist):
     h, w = int(color_hw[0]), int(color_hw[1])
     d = np.ascontiguousarray(_distortion(dist))
     out = np.empty((h, w, 2), dtype=np.int32)
-    check(lib().adfp_undistort_map(h, w, float(fx), float(fy), float(cx), float(cy), d.ctypes.data, d.size, out.ctypes.data),
-          'adfp_undistort_map')
+    _lib.host.adfp_undistort_map(h, w, float(fx), float(fy), float(cx), float(cy), d.ctypes.data, d.size, out.ctypes.data)
     return out
 
 
@@ -160,9 +158,8 @@ class FrameIngest(object):
         src = color_u8 if torch.is_tensor(color_u8) else torch.from_numpy(np.ascontiguousarray(color_u8))
         src = src.to(self.device).contiguous()
         dst = torch.empty_like(src)
-        with _lib.device_guard(self.device):
-            check(lib().adfp_undistort_image(src.data_ptr(), map.data_ptr(), h, w, dst.data_ptr(), _lib.current_stream(self.device)),
-                  'adfp_undistort_image')
+        with _lib.on(self.device) as L:
+            L.adfp_undistort_image(src, map, h, w, dst)
         return dst
 
     # ---- geometry
@@ -175,7 +172,7 @@ class FrameIngest(object):
     def out_shape_for(self, depth_hw):
         """(H, W) of the tensors a depth image of depth_hw comes back as (adfp_ingest_out_shape)."""
         H, W = C.c_int(), C.c_int()
-        check(lib().adfp_ingest_out_shape(C.byref(self._geom(depth_hw, depth_hw, False)), C.byref(H), C.byref(W)), 'adfp_ingest_out_shape')
+        _lib.host.adfp_ingest_out_shape(C.byref(self._geom(depth_hw, depth_hw, False)), C.byref(H), C.byref(W))
         return H.value, W.value
 
     @property
@@ -294,22 +291,20 @@ class FrameIngest(object):
             else:
                 srcs.append(None)
                 host.append(self._host_bytes(x))
-        with _lib.device_guard(self.device):
+        with _lib.on(self.device) as L:
             lens_map = self._map(color_hw)
             if host:
                 dev, offs = self._upload(host)
                 it = iter(offs)
                 srcs = [s if s is not None else dev.data_ptr() + next(it) for s in srcs]
-            stream = _lib.current_stream(self.device)
             for j0 in range(0, n, _lib.INGEST_MAX_JOBS):
                 m = min(_lib.INGEST_MAX_JOBS, n - j0)
                 jobs = (_lib.AdfpIngestJob * m)(*[_lib.AdfpIngestJob(srcs[j], srcs[n + j], cdst[j].data_ptr(), ddst[j].data_ptr())
                                                   for j in range(j0, j0 + m)])
                 if lens_map is None:
-                    check(lib().adfp_ingest_frames(C.byref(geom), m, jobs, stream), 'adfp_ingest_frames')
+                    L.adfp_ingest_frames(C.byref(geom), m, jobs)
                 else:
-                    check(lib().adfp_ingest_frames_undistort(C.byref(geom), lens_map.data_ptr(), m, jobs, stream),
-                          'adfp_ingest_frames_undistort')
+                    L.adfp_ingest_frames_undistort(C.byref(geom), lens_map, m, jobs)
         return result
 
 

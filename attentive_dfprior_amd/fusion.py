@@ -14,7 +14,6 @@ import numpy as np
 import torch
 
 from . import _lib, mesh
-from ._lib import lib, ptr, check
 
 
 class TSDFVolume(object):
@@ -52,12 +51,10 @@ class TSDFVolume(object):
         org = (C.c_float * 3)(*[float(v) for v in self._vol_origin])
         intr = (C.c_float * 9)(*[float(v) for v in np.asarray(cam_intr, dtype=np.float32).reshape(-1)])
         pose = (C.c_float * 16)(*[float(v) for v in np.asarray(cam_pose, dtype=np.float32).reshape(-1)])
-        with torch.cuda.device(self.device):
-            check(lib().adfp_tsdf_integrate(ptr(self._tsdf), ptr(self._weight), ptr(self._color),
-                                            int(self._vol_dim[0]), int(self._vol_dim[1]), int(self._vol_dim[2]),
-                                            C.byref(org), np.float32(self._voxel_size).item(), C.byref(intr), C.byref(pose),
-                                            ptr(packed), ptr(depth), im_h, im_w, np.float32(self._trunc_margin).item(),
-                                            float(obs_weight), _lib.current_stream(self.device)), 'adfp_tsdf_integrate')
+        with _lib.on(self.device) as L:
+            L.adfp_tsdf_integrate(self._tsdf, self._weight, self._color, int(self._vol_dim[0]), int(self._vol_dim[1]), int(self._vol_dim[2]),
+                                  C.byref(org), np.float32(self._voxel_size).item(), C.byref(intr), C.byref(pose), packed, depth, im_h, im_w,
+                                  np.float32(self._trunc_margin).item(), float(obs_weight))
         # The kernel wrote the volume through a raw pointer: tell PyTorch.  Every cached conversion of the render volume (the
         # corner-block copy of Engine.tsdf_blocks / MapperIteration) is keyed on (data_ptr, _version), and the view handed out by
         # get_render_volume() shares this counter.

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib, ptr
+from ._lib import lib
 from .tsdf_raycast import TsdfRaycaster
 
 OK, FEW_PAIRS, DEGENERATE, REJECTED = 0, 1, 2, 3
@@ -79,13 +79,12 @@ def depth_bilateral(depth, radius=2, sigma_space=1.5, sigma_depth=0.05, sigma_de
     radius, ss, sd, sz = _bilateral_numbers(radius, sigma_space, sigma_depth, sigma_depth_z2)
     H, W = depth.shape[-2:]
     V = depth.shape[0] if depth.dim() == 3 else 1
-    with _lib.device_guard(depth.device):
+    with _lib.on(depth.device) as L:
         if out is None:
             out = torch.empty_like(depth)
         elif out.dtype != torch.float32 or out.shape != depth.shape or not out.is_contiguous() or out.device != depth.device:
             raise ValueError(f'out: expected contiguous float32 {tuple(depth.shape)} on {depth.device}, got {out.dtype} {tuple(out.shape)}')
-        check(lib().adfp_depth_bilateral(ptr(depth), V, H, W, radius, ss, sd, sz, ptr(out), _lib.current_stream(depth.device)),
-              'adfp_depth_bilateral')
+        L.adfp_depth_bilateral(depth, V, H, W, radius, ss, sd, sz, out)
     return out
 
 
@@ -169,53 +168,43 @@ class DepthICP(object):
         if depth.dtype != torch.float32 or depth.dim() != 3 or tuple(depth.shape[1:]) != (self.H, self.W) or not depth.is_contiguous():
             raise ValueError(f'depth: expected contiguous float32 [V,{self.H},{self.W}], got {depth.dtype} {tuple(depth.shape)}')
         V = depth.shape[0]
-        with _lib.device_guard(depth.device):
+        with _lib.on(depth.device) as L:
             if out is None:
                 out = torch.empty((V, self.H, self.W, 3), dtype=torch.float32, device=depth.device)
-            check(lib().adfp_depth_normals(ptr(depth), V, self.H, self.W, self.fx, self.fy, self.cx, self.cy, self.max_jump, ptr(out),
-                                           _lib.current_stream(depth.device)), 'adfp_depth_normals')
+            L.adfp_depth_normals(depth, V, self.H, self.W, self.fx, self.fy, self.cx, self.cy, self.max_jump, out)
         return out
 
-    def _begin(self, guess, st):
-        check(lib().adfp_icp_begin(ptr(guess), ptr(self.state), st), 'adfp_icp_begin')
+    def _begin(self, guess, L):
+        L.adfp_icp_begin(guess, self.state)
 
-    def _step(self, maps, p_ref, stride, row, st, sums=None, points=None):
+    def _step(self, maps, p_ref, stride, row, L, sums=None, points=None):
         """points: the image the sensor's points come from when it is not the one its normals were taken of (maps' first)"""
         depth, normals = maps
         depth_s = depth[0] if points is None else points
-        check(lib().adfp_icp_step(ptr(depth_s), ptr(normals[0]), ptr(depth[1]), ptr(normals[1]), ptr(p_ref), self.H, self.W, self.fx, self.fy,
-                                  self.cx, self.cy, int(stride), self.dist_tol, self.cos_tol, self.min_pivot, self.pairs_needed(stride),
-                                  ptr(self.state), ptr(self.stats), self.stats.shape[0], int(row), ptr(sums), ptr(self.workspace),
-                                  self.workspace.numel() * 8, st), 'adfp_icp_step')
+        L.adfp_icp_step(depth_s, normals[0], depth[1], normals[1], p_ref, self.H, self.W, self.fx, self.fy, self.cx, self.cy, int(stride),
+                        self.dist_tol, self.cos_tol, self.min_pivot, self.pairs_needed(stride), self.state, self.stats,
+                        self.stats.shape[0], int(row), sums, self.workspace, self.workspace.numel() * 8)
 
-    def _end(self, row, st):
-        check(lib().adfp_icp_end(ptr(self.state), self.max_shift, self.max_angle, ptr(self.c2w_out), ptr(self.cam_out), ptr(self.stats),
-                                 self.stats.shape[0], int(row), st), 'adfp_icp_end')
+    def _end(self, row, L):
+        L.adfp_icp_end(self.state, self.max_shift, self.max_angle, self.c2w_out, self.cam_out, self.stats, self.stats.shape[0], int(row))
 
     def run_steps(self):
         """begin, the steps level by level, end, on the maps and the reference pose this object holds (refine's tail: a fixed sequence
         of launches that a HIP graph can capture).  Returns cam_out [7]."""
-        with _lib.device_guard(self.dev):
-            st = _lib.current_stream(self.dev)
-            self._begin(self.p_ref, st)
+        with _lib.on(self.dev) as L:
+            self._begin(self.p_ref, L)
             row = 0
             for stride, n in zip(self.strides, self.iters):
                 for _ in range(n):
-                    self._step((self.depth, self.normals), self.p_ref, stride, row, st, points=self.points_depth)
+                    self._step((self.depth, self.normals), self.p_ref, stride, row, L, points=self.points_depth)
                     row += 1
-            self._end(row, st)
+            self._end(row, L)
         return self.cam_out
 
     def set_frame(self, guess_c2w, gt_depth):
         """The refinement's inputs: the sensor depth, the raycast of the prior from the guess, with `bilateral` the filtered sensor
         depth (one launch), both normal maps (one launch)."""
-        if isinstance(guess_c2w, np.ndarray):
-            guess_c2w = torch.from_numpy(guess_c2w)
-        g = guess_c2w.detach().to(self.dev, torch.float32)
-        if tuple(g.shape) == (3, 4):
-            g = torch.cat([g, g.new_tensor([[0., 0., 0., 1.]])], 0)
-        if tuple(g.shape) != (4, 4):
-            raise ValueError(f'guess_c2w: expected [4,4] or [3,4], got {tuple(guess_c2w.shape)}')
+        g = _c2w44(guess_c2w, self.dev, 'guess_c2w')
         if tuple(gt_depth.shape) != (self.H, self.W):
             raise ValueError(f'gt_depth: expected [{self.H},{self.W}], got {tuple(gt_depth.shape)}')
         _lib.require_cuda(gt_depth, 'gt_depth')
@@ -253,28 +242,26 @@ class DepthICP(object):
         if tuple(depth.shape) != (2, self.H, self.W) or tuple(normals.shape) != (2, self.H, self.W, 3):
             raise ValueError(f'maps: expected [{self.H},{self.W}] depths and [{self.H},{self.W},3] normals')
         sums = torch.zeros((_lib.ICP_SUMS,), dtype=torch.float64, device=dev)
-        with _lib.device_guard(dev):
-            st = _lib.current_stream(dev)
-            self._begin(c2w, st)
-            self._step((depth, normals), p_ref, stride, 0, st, sums=sums)
+        with _lib.on(dev) as L:
+            self._begin(c2w, L)
+            self._step((depth, normals), p_ref, stride, 0, L, sums=sums)
             # no gate: the step's own result comes out
-            check(lib().adfp_icp_end(ptr(self.state), float('inf'), float('inf'), ptr(self.c2w_out), ptr(self.cam_out), None, 0, 0, st),
-                  'adfp_icp_end')
+            L.adfp_icp_end(self.state, float('inf'), float('inf'), self.c2w_out, self.cam_out, None, 0, 0)
         return sums, self.stats[0].clone(), self.c2w_out.clone(), self.cam_out.clone()
 
 
 RGB_STATS_COLUMNS = ('rgb_pairs', 'rgb_rmse')
 
 
-def _c2w44(c2w, dev):
-    """[4,4] or [3,4], numpy or torch, anywhere -> [4,4] float32 on `dev`"""
+def _c2w44(c2w, dev, what='c2w'):
+    """[4,4] or [3,4], numpy or torch, anywhere -> [4,4] float32 on `dev`; `what` names the argument in the refusal"""
     if isinstance(c2w, np.ndarray):
         c2w = torch.from_numpy(c2w)
     g = c2w.detach().to(dev, torch.float32)
     if tuple(g.shape) == (3, 4):
         g = torch.cat([g, g.new_tensor([[0., 0., 0., 1.]])], 0)
     if tuple(g.shape) != (4, 4):
-        raise ValueError(f'c2w: expected [4,4] or [3,4], got {tuple(c2w.shape)}')
+        raise ValueError(f'{what}: expected [4,4] or [3,4], got {tuple(c2w.shape)}')
     return g
 
 
@@ -323,10 +310,10 @@ class RgbdICP(DepthICP):
             raise ValueError(f'expected float32 color [{H},{W},3] and depth [{H},{W}], got {color.dtype} {tuple(color.shape)} and '
                              f'{depth.dtype} {tuple(depth.shape)}')
         color, depth = color.detach().contiguous(), depth.detach().contiguous()
-        with _lib.device_guard(depth.device):
+        with _lib.on(depth.device) as L:
             if out is None:
                 out = torch.empty((H, W, 4), dtype=torch.float32, device=depth.device)
-            check(lib().adfp_rgbd_frame_map(ptr(color), ptr(depth), H, W, ptr(out), _lib.current_stream(depth.device)), 'adfp_rgbd_frame_map')
+            L.adfp_rgbd_frame_map(color, depth, H, W, out)
         return out
 
     def set_keyframe(self, c2w, color, depth):
@@ -342,25 +329,23 @@ class RgbdICP(DepthICP):
         self.maps[1].copy_(self.maps[0])
         self.has_keyframe = True
 
-    def _rgbd_step(self, cur, normals, depth_m, p_ref, stride, row, st, sums=None, key=True):
+    def _rgbd_step(self, cur, normals, depth_m, p_ref, stride, row, L, sums=None, key=True):
         key = key and self.has_keyframe
-        check(lib().adfp_rgbd_step(ptr(cur), ptr(normals[0]), ptr(depth_m), ptr(normals[1]), ptr(p_ref), ptr(self.maps[1]) if key else None,
-                                   ptr(self.p_key) if key else None, self.H, self.W, self.fx, self.fy, self.cx, self.cy, int(stride),
-                                   self.dist_tol, self.cos_tol, self.rgb_weight, self.rgb_tol, self.min_pivot, self.pairs_needed(stride),
-                                   ptr(self.state), ptr(self.stats), ptr(self.rgb_stats), self.stats.shape[0], int(row), ptr(sums),
-                                   ptr(self.rgbd_workspace), self.rgbd_workspace.numel() * 8, st), 'adfp_rgbd_step')
+        L.adfp_rgbd_step(cur, normals[0], depth_m, normals[1], p_ref, self.maps[1] if key else None, self.p_key if key else None,
+                         self.H, self.W, self.fx, self.fy, self.cx, self.cy, int(stride), self.dist_tol, self.cos_tol, self.rgb_weight,
+                         self.rgb_tol, self.min_pivot, self.pairs_needed(stride), self.state, self.stats, self.rgb_stats,
+                         self.stats.shape[0], int(row), sums, self.rgbd_workspace, self.rgbd_workspace.numel() * 8)
 
     def run_steps(self):
         """DepthICP.run_steps with adfp_rgbd_step on the maps this object holds.  Returns cam_out [7]."""
-        with _lib.device_guard(self.dev):
-            st = _lib.current_stream(self.dev)
-            self._begin(self.p_ref, st)
+        with _lib.on(self.dev) as L:
+            self._begin(self.p_ref, L)
             row = 0
             for stride, n in zip(self.strides, self.iters):
                 for _ in range(n):
-                    self._rgbd_step(self.maps[0], self.normals, self.depth[1], self.p_ref, stride, row, st)
+                    self._rgbd_step(self.maps[0], self.normals, self.depth[1], self.p_ref, stride, row, L)
                     row += 1
-            self._end(row, st)
+            self._end(row, L)
         return self.cam_out
 
     def refine(self, guess_c2w, gt_depth, gt_color):
@@ -392,12 +377,10 @@ class RgbdICP(DepthICP):
             self.p_key.copy_(_c2w44(p_key, dev))
         self.has_keyframe = key_map is not None
         sums = torch.zeros((_lib.RGBD_SUMS,), dtype=torch.float64, device=dev)
-        with _lib.device_guard(dev):
-            st = _lib.current_stream(dev)
-            self._begin(c2w, st)
-            self._rgbd_step(cur, normals, depth_m, p_ref, stride, 0, st, sums=sums)
-            check(lib().adfp_icp_end(ptr(self.state), float('inf'), float('inf'), ptr(self.c2w_out), ptr(self.cam_out), None, 0, 0, st),
-                  'adfp_icp_end')
+        with _lib.on(dev) as L:
+            self._begin(c2w, L)
+            self._rgbd_step(cur, normals, depth_m, p_ref, stride, 0, L, sums=sums)
+            L.adfp_icp_end(self.state, float('inf'), float('inf'), self.c2w_out, self.cam_out, None, 0, 0)
         out = sums, self.stats[0].clone(), self.rgb_stats[0].clone(), self.c2w_out.clone(), self.cam_out.clone()
         self.maps[1].copy_(saved[0])
         self.p_key.copy_(saved[1])

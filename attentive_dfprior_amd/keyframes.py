@@ -12,7 +12,6 @@ import numpy as np
 import torch
 
 from . import _lib, common
-from ._lib import lib, ptr, check
 
 EDGE = 20                      # the reference's image margin (src/Mapper.py:207)
 
@@ -38,7 +37,7 @@ def keyframe_overlap_counts(idx, depth, c2w, poses, N_samples, H, W, fx, fy, cx,
     n = idx.numel()
     if n == 0:
         raise ValueError('keyframe_overlap_counts: no pixels drawn')
-    with _lib.device_guard(dev):
+    with _lib.on(dev) as L:
         i = idx.reshape(-1).to(torch.int64).contiguous()
         d = _as_tensor(depth).to(dev, torch.float32).contiguous()
         if tuple(d.shape) != (H, W):
@@ -50,9 +49,7 @@ def keyframe_overlap_counts(idx, depth, c2w, poses, N_samples, H, W, fx, fy, cx,
         K = P.shape[0]
         counts = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)        # never a null pointer, also for K = 0
         pts = torch.empty((n * N_samples, 3), dtype=torch.float32, device=dev) if return_points and K > 0 else None
-        check(lib().adfp_keyframe_overlap(ptr(i), n, ptr(d), H, W, ptr(m), int(N_samples), ptr(P) if K else None, K, float(fx),
-                                          float(fy), float(cx), float(cy), int(edge), ptr(counts), ptr(pts),
-                                          _lib.current_stream(dev)), 'adfp_keyframe_overlap')
+        L.adfp_keyframe_overlap(i, n, d, H, W, m, int(N_samples), P, K, float(fx), float(fy), float(cx), float(cy), int(edge), counts, pts)
     counts = counts[:K]
     return (counts, pts) if return_points else counts
 
@@ -220,7 +217,7 @@ class KeyframeStore(object):
         if self._n == self.capacity:
             self._grow(2 * self.capacity)
         n = self._n
-        with _lib.device_guard(self.device):
+        with _lib.on(self.device):
             self._depth[n].copy_(_as_tensor(depth).detach().reshape(self.H, self.W))
             self._color[n].copy_(_as_tensor(color).detach().reshape(self.H, self.W, 3))
             m = _as_tensor(est_c2w).detach()

@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import lib, ptr, check, require_cuda
+from ._lib import lib, require_cuda
+from .recon import as_faces, as_numpy
 
 
 def marching_cubes(values, level=0., spacing=(1., 1., 1.), origin=(0., 0., 0.), normals=False, outward='lower'):
@@ -27,14 +28,12 @@ def marching_cubes(values, level=0., spacing=(1., 1., 1.), origin=(0., 0., 0.), 
     v = values.detach().to(torch.float32).contiguous()
     X, Y, Z = (int(s) for s in v.shape)
     dev = v.device
-    L = lib()
-    nbytes = L.adfp_mc_workspace_bytes(X, Y, Z)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    nbytes = lib().adfp_mc_workspace_bytes(X, Y, Z)
+    ws = _lib.workspace(nbytes, dev)
     totals = torch.empty(2, dtype=torch.int64, device=dev)
     lev = float(np.float32(level))
-    with _lib.device_guard(dev):
-        st = _lib.current_stream(dev)
-        check(L.adfp_mc_count(ptr(v), X, Y, Z, lev, ptr(ws), nbytes, ptr(totals), st), 'adfp_mc_count')
+    with _lib.on(dev) as L:
+        L.adfp_mc_count(v, X, Y, Z, lev, ws, nbytes, totals)
         n_verts, n_faces = (int(t) for t in totals.tolist())          # the one synchronisation of the extraction
         verts = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
         keys = torch.empty(n_verts, dtype=torch.int64, device=dev)
@@ -42,9 +41,8 @@ def marching_cubes(values, level=0., spacing=(1., 1., 1.), origin=(0., 0., 0.), 
         faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
         org = (C.c_float * 3)(*[float(o) for o in origin])
         sp = (C.c_float * 3)(*[float(s) for s in spacing])
-        check(L.adfp_mc_emit(ptr(v), X, Y, Z, lev, C.byref(org), C.byref(sp), _lib.MC_OUT[outward], ptr(ws), nbytes,
-                             n_verts, n_faces, ptr(verts) if n_verts else None, ptr(nrm) if (nrm is not None and n_verts) else None,
-                             ptr(keys) if n_verts else None, n_verts, ptr(faces) if n_faces else None, n_faces, st), 'adfp_mc_emit')
+        L.adfp_mc_emit(v, X, Y, Z, lev, C.byref(org), C.byref(sp), _lib.MC_OUT[outward], ws, nbytes, n_verts, n_faces, verts, nrm, keys,
+                       n_verts, faces, n_faces)
     return verts, faces, nrm
 
 
@@ -60,10 +58,8 @@ def hull_fill(values, axes, planes, fill=100.):
         raise ValueError('hull_fill: axis lengths do not match the lattice')
     pl = torch.as_tensor(np.asarray(planes, dtype=np.float64).reshape(-1, 4)).to(dev).contiguous()
     X, Y, Z = values.shape
-    with _lib.device_guard(dev):
-        check(lib().adfp_lattice_hull_fill(ptr(values), ptr(ax[0]), ptr(ax[1]), ptr(ax[2]), X, Y, Z,
-                                           ptr(pl) if pl.shape[0] else None, int(pl.shape[0]), float(fill),
-                                           _lib.current_stream(dev)), 'adfp_lattice_hull_fill')
+    with _lib.on(dev) as L:
+        L.adfp_lattice_hull_fill(values, ax[0], ax[1], ax[2], X, Y, Z, pl, int(pl.shape[0]), float(fill))
     return values
 
 
@@ -75,9 +71,8 @@ def unpack_colors(verts_index, color_vol):
     cv = color_vol.to(torch.float32).contiguous()
     out = torch.empty((vi.shape[0], 3), dtype=torch.uint8, device=dev)
     X, Y, Z = cv.shape
-    with _lib.device_guard(dev):
-        check(lib().adfp_mesh_unpack_colors(ptr(vi) if vi.shape[0] else None, int(vi.shape[0]), ptr(cv), X, Y, Z,
-                                            ptr(out) if vi.shape[0] else None, _lib.current_stream(dev)), 'adfp_mesh_unpack_colors')
+    with _lib.on(dev) as L:
+        L.adfp_mesh_unpack_colors(vi, int(vi.shape[0]), cv, X, Y, Z, out)
     return out
 
 
@@ -86,7 +81,7 @@ def _mesh_tensors(verts, faces, what):
     if faces is None:
         raise ValueError(f'{what}: faces is None')
     require_cuda(faces, f'{what} faces')
-    f = faces.detach().reshape(-1, 3).to(torch.int32).contiguous()
+    f = as_faces(faces, faces.device)
     if verts is None:
         return None, f
     require_cuda(verts, f'{what} verts')
@@ -101,8 +96,15 @@ def _check_indices(faces, n_verts, what):
             raise ValueError(f'{what}: face indices span [{lo}, {hi}], outside [0, {n_verts})')
 
 
-def _ws(nbytes, dev):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+def _vertex_colors(colors, v, what):
+    """The optional uint8 [V,3] colours of the vertices v, contiguous on their device."""
+    if colors is None:
+        return None
+    require_cuda(colors, f'{what} colors')
+    c = colors.detach().reshape(-1, 3).to(v.device, torch.uint8).contiguous()
+    if c.shape[0] != v.shape[0]:
+        raise ValueError(f'{what}: {c.shape[0]} colours for {v.shape[0]} vertices')
+    return c
 
 
 def _face_labels(faces, n_verts, keep=None):
@@ -112,21 +114,16 @@ def _face_labels(faces, n_verts, keep=None):
     labels = torch.empty(F, dtype=torch.int32, device=dev)
     if F == 0:
         return labels
-    L = lib()
     mate = torch.empty(3 * F, dtype=torch.int32, device=dev)
     changed = torch.empty(1, dtype=torch.int32, device=dev)
-    with _lib.device_guard(dev):
-        st = _lib.current_stream(dev)
-        nbytes = L.adfp_mesh_face_labels_workspace_bytes(F)
+    with _lib.on(dev) as L:
+        nbytes = lib().adfp_mesh_face_labels_workspace_bytes(F)
         if nbytes == 0:
             raise RuntimeError(f'face_components: {F} faces are more than the int32 sort carries')
-        ws = _ws(nbytes, dev)
-        check(L.adfp_mesh_face_labels_begin(ptr(faces), F, int(n_verts), ptr(keep), ptr(mate), ptr(labels), ptr(ws), nbytes, st),
-              'adfp_mesh_face_labels_begin')
-        del ws
+        L.adfp_mesh_face_labels_begin(faces, F, int(n_verts), keep, mate, labels, _lib.workspace(nbytes, dev), nbytes)
         done, step = 0, 4
         while True:
-            check(L.adfp_mesh_face_labels_rounds(ptr(mate), ptr(labels), F, step, ptr(changed), st), 'adfp_mesh_face_labels_rounds')
+            L.adfp_mesh_face_labels_rounds(mate, labels, F, step, changed)
             done += step
             if int(changed.item()) == 0:                  # the convergence flag: one scalar per `step` rounds
                 return labels
@@ -146,27 +143,22 @@ def face_components(faces, n_verts):
 def _clean_components(v, f, seen, min_area, largest):
     dev = f.device
     V, F = int(v.shape[0]), int(f.shape[0])
-    L = lib()
-    with _lib.device_guard(dev):
-        st = _lib.current_stream(dev)
+    with _lib.on(dev) as L:
         keep = torch.empty(max(F, 1), dtype=torch.uint8, device=dev)
-        check(L.adfp_cull_faces(ptr(seen) if V else None, V, ptr(f) if F else None, F, ptr(keep), st), 'adfp_cull_faces')
+        L.adfp_cull_faces(seen, V, f, F, keep)
         labels = _face_labels(f, V, keep)
         if F:
-            nbytes = L.adfp_mesh_component_keep_workspace_bytes(F)
-            ws = _ws(nbytes, dev)
-            check(L.adfp_mesh_component_keep(ptr(v) if V else None, V, ptr(f), F, ptr(labels), 1 if largest else 0,
-                                             0.0 if largest else float(min_area), ptr(keep), ptr(ws), nbytes, st),
-                  'adfp_mesh_component_keep')
-        nbytes = L.adfp_mesh_compact_workspace_bytes(V, F)
-        ws = _ws(nbytes, dev)
+            nbytes = lib().adfp_mesh_component_keep_workspace_bytes(F)
+            L.adfp_mesh_component_keep(v, V, f, F, labels, 1 if largest else 0, 0.0 if largest else float(min_area), keep,
+                                       _lib.workspace(nbytes, dev), nbytes)
+        nbytes = lib().adfp_mesh_compact_workspace_bytes(V, F)
+        ws = _lib.workspace(nbytes, dev)
         totals = torch.empty(2, dtype=torch.int64, device=dev)
-        check(L.adfp_mesh_compact_plan(ptr(f) if F else None, F, V, ptr(keep), ptr(ws), nbytes, ptr(totals), st), 'adfp_mesh_compact_plan')
+        L.adfp_mesh_compact_plan(f, F, V, keep, ws, nbytes, totals)
         nv, nf = (int(t) for t in totals.tolist())                       # the counts: one read-back
         vo = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         fo = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-        check(L.adfp_mesh_compact_emit(ptr(v) if V else None, V, ptr(f) if F else None, F, ptr(ws), nbytes, ptr(vo) if nv else None, nv,
-                                       ptr(fo) if nf else None, nf, st), 'adfp_mesh_compact_emit')
+        L.adfp_mesh_compact_emit(v, V, f, F, ws, nbytes, vo, nv, fo, nf)
     return vo, fo
 
 
@@ -192,21 +184,18 @@ def _merge_coincident(v, f, c):
     V, F = int(v.shape[0]), int(f.shape[0])
     if V == 0:
         return v, f, c
-    L = lib()
-    with _lib.device_guard(dev):
-        st = _lib.current_stream(dev)
-        nbytes = L.adfp_mesh_merge_workspace_bytes(V)
-        ws = _ws(nbytes, dev)
+    with _lib.on(dev) as L:
+        nbytes = lib().adfp_mesh_merge_workspace_bytes(V)
+        ws = _lib.workspace(nbytes, dev)
         total = torch.empty(1, dtype=torch.int64, device=dev)
-        check(L.adfp_mesh_merge_plan(ptr(v), V, ptr(ws), nbytes, ptr(total), st), 'adfp_mesh_merge_plan')
+        L.adfp_mesh_merge_plan(v, V, ws, nbytes, total)
         n = int(total.item())
         if n == V:                                          # nothing coincides: the inputs, as the host function returns them
             return v, f, c
         vo = torch.empty((n, 3), dtype=torch.float32, device=dev)
         co = torch.empty((n, 3), dtype=torch.uint8, device=dev) if c is not None else None
         fo = torch.empty((F, 3), dtype=torch.int32, device=dev)
-        check(L.adfp_mesh_merge_emit(ptr(v), ptr(c), V, ptr(f) if F else None, F, ptr(ws), nbytes, ptr(vo), ptr(co), n,
-                                     ptr(fo) if F else None, st), 'adfp_mesh_merge_emit')
+        L.adfp_mesh_merge_emit(v, c, V, f, F, ws, nbytes, vo, co, n, fo)
     return vo, fo, co
 
 
@@ -214,13 +203,7 @@ def merge_coincident(verts, faces, colors=None):
     """mesher.merge_coincident on device tensors: vertices whose three f32 bit patterns are equal collapse into their first
     occurrence, survivors keep their order, faces and colours (uint8 [V,3]) follow.  Returns (verts, faces, colors)."""
     v, f = _mesh_tensors(verts, faces, 'merge_coincident')
-    c = None
-    if colors is not None:
-        require_cuda(colors, 'merge_coincident colors')
-        c = colors.detach().reshape(-1, 3).to(v.device, torch.uint8).contiguous()
-        if c.shape[0] != v.shape[0]:
-            raise ValueError(f'merge_coincident: {c.shape[0]} colours for {v.shape[0]} vertices')
-    return _merge_coincident(v, f, c)
+    return _merge_coincident(v, f, _vertex_colors(colors, v, 'merge_coincident'))
 
 
 # ---- mesh simplification (csrc/adfp_meshsimplify.h; contract: include/adfp.h, "mesh simplification") ---------------------------
@@ -234,27 +217,25 @@ def _simplify_vertex_clustering(v, f, voxel_size, contraction, c):
              torch.empty((0, 3), dtype=torch.uint8, device=dev) if c is not None else None)
     if V == 0 or F == 0:
         return empty
-    L = lib()
-    with _lib.device_guard(dev):
-        st = _lib.current_stream(dev)
+    with _lib.on(dev) as L:
         lo, hi = (x.tolist() for x in torch.aminmax(v, dim=0))           # the bounds: one read-back
         if not np.isfinite(lo + hi).all():
             raise ValueError('simplify_vertex_clustering: the vertices are not all finite')
-        nbytes = L.adfp_mesh_simplify_workspace_bytes(V, F)
+        nbytes = lib().adfp_mesh_simplify_workspace_bytes(V, F)
         if nbytes == 0:
             raise RuntimeError(f'simplify_vertex_clustering: {V} vertices, {F} faces are more than the int32 sort carries')
-        ws = _ws(nbytes, dev)
+        ws = _lib.workspace(nbytes, dev)
         totals = torch.empty(2, dtype=torch.int64, device=dev)
         lo_c, hi_c = (C.c_double * 3)(*lo), (C.c_double * 3)(*hi)
-        check(L.adfp_mesh_simplify_plan(ptr(v), V, ptr(f), F, ptr(c), float(voxel_size), SIMPLIFY_CONTRACTIONS[contraction],
-                                        C.byref(lo_c), C.byref(hi_c), ptr(ws), nbytes, ptr(totals), st), 'adfp_mesh_simplify_plan')
+        L.adfp_mesh_simplify_plan(v, V, f, F, c, float(voxel_size), SIMPLIFY_CONTRACTIONS[contraction], C.byref(lo_c), C.byref(hi_c), ws,
+                                  nbytes, totals)
         nv, nf = (int(t) for t in totals.tolist())                       # the counts: one read-back
         if nf == 0:
             return empty
         vo = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         fo = torch.empty((nf, 3), dtype=torch.int32, device=dev)
         co = torch.empty((nv, 3), dtype=torch.uint8, device=dev) if c is not None else None
-        check(L.adfp_mesh_simplify_emit(V, F, ptr(ws), nbytes, ptr(vo), ptr(co), nv, ptr(fo), nf, st), 'adfp_mesh_simplify_emit')
+        L.adfp_mesh_simplify_emit(V, F, ws, nbytes, vo, co, nv, fo, nf)
     return vo, fo, co
 
 
@@ -275,12 +256,7 @@ def simplify_vertex_clustering(verts, faces, voxel_size, contraction='quadric', 
         raise ValueError(f'simplify_vertex_clustering: voxel_size must be positive and finite, got {voxel_size!r}')
     if contraction not in SIMPLIFY_CONTRACTIONS:
         raise ValueError(f'simplify_vertex_clustering: contraction must be one of {sorted(SIMPLIFY_CONTRACTIONS)}, got {contraction!r}')
-    c = None
-    if colors is not None:
-        require_cuda(colors, 'simplify_vertex_clustering colors')
-        c = colors.detach().reshape(-1, 3).to(v.device, torch.uint8).contiguous()
-        if c.shape[0] != v.shape[0]:
-            raise ValueError(f'simplify_vertex_clustering: {c.shape[0]} colours for {v.shape[0]} vertices')
+    c = _vertex_colors(colors, v, 'simplify_vertex_clustering')
     _check_indices(f, int(v.shape[0]), 'simplify_vertex_clustering')
     return _simplify_vertex_clustering(v, f, vs, contraction, c)
 
@@ -293,9 +269,8 @@ def color_bytes(rgb):
     if x.shape[1] < 3:
         raise ValueError(f'color_bytes: rows of {x.shape[1]} channels')
     out = torch.empty((x.shape[0], 3), dtype=torch.uint8, device=x.device)
-    with _lib.device_guard(x.device):
-        check(lib().adfp_mesh_color_bytes(ptr(x) if x.shape[0] else None, int(x.shape[0]), int(x.shape[1]), ptr(out) if x.shape[0] else None,
-                                          _lib.current_stream(x.device)), 'adfp_mesh_color_bytes')
+    with _lib.on(x.device) as L:
+        L.adfp_mesh_color_bytes(x, int(x.shape[0]), int(x.shape[1]), out)
     return out
 
 
@@ -306,28 +281,30 @@ def vertex_normals(verts, faces, device=None):
     faces: tensors or arrays (f64 and int32 on the device are used as they are).  write_ply(path, verts, faces, colors,
     normals=vertex_normals(verts, faces)) saves the mesh with its normals."""
     v = verts if torch.is_tensor(verts) else torch.from_numpy(np.asarray(verts, dtype=np.float64))
-    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.asarray(faces, dtype=np.int64))
-    dev = torch.device(device) if device is not None else (v.device if v.is_cuda else f.device)
+    dev = torch.device(device) if device is not None else (v.device if v.is_cuda or not torch.is_tensor(faces) else faces.device)
     v = v.detach().reshape(-1, 3).to(dev, torch.float64).contiguous()
-    f = f.detach().reshape(-1, 3).to(dev, torch.int32).contiguous()
+    f = as_faces(faces, dev, np.int64)
     require_cuda(v, 'vertex_normals verts')
     V, F = int(v.shape[0]), int(f.shape[0])
     out = torch.empty((V, 3), dtype=torch.float64, device=dev)
     if V == 0:
         return out
-    L = lib()
-    nbytes = L.adfp_vertex_normals_workspace_bytes(F)
+    nbytes = lib().adfp_vertex_normals_workspace_bytes(F)
     if F and nbytes == 0:
         raise RuntimeError(f'vertex_normals: {F} faces are more than the int32 sort carries')
-    ws = _ws(nbytes, dev) if F else None
-    with _lib.device_guard(dev):
-        check(L.adfp_vertex_normals(ptr(v), V, ptr(f) if F else None, F, ptr(ws), nbytes, ptr(out), _lib.current_stream(dev)),
-              'adfp_vertex_normals')
+    with _lib.on(dev) as L:
+        L.adfp_vertex_normals(v, V, f, F, _lib.workspace(nbytes, dev) if F else None, nbytes, out)
     return out
 
 
 # ---- mesh colours from the keyframes (csrc/adfp_meshcolor.h; the rule: include/adfp.h, "mesh colours from the keyframes") ------
 BLENDS = _lib.BLEND
+
+
+def w2c_rows_own_dtype(c2w, dev):
+    """numpy poses [K,4,4] -> f32 device [K,12]: the top three rows of np.linalg.inv(c2w) in the array's own dtype, then f32, as
+    Mesher._project inverts them (recon.w2c_rows inverts a float32 copy, raycast.proj_rows negates two columns first)."""
+    return torch.from_numpy(np.ascontiguousarray(np.linalg.inv(c2w)[:, :3, :])).to(dev).float().reshape(-1, 12).contiguous()
 
 
 def _project_colors(v, n, depth, color, c2w, fx, fy, cx, cy, depth_tol, border, blend):
@@ -342,13 +319,11 @@ def _project_colors(v, n, depth, color, c2w, fx, fy, cx, cy, depth_tol, border, 
     w2c = center = None
     if K:
         m = c2w.detach().cpu().numpy()
-        w2c = torch.from_numpy(np.ascontiguousarray(np.linalg.inv(m)[:, :3, :])).to(dev).float().reshape(K, 12).contiguous()
+        w2c = w2c_rows_own_dtype(m, dev)
         center = torch.from_numpy(np.ascontiguousarray(m[:, :3, 3])).to(dev).float().contiguous()
-    with _lib.device_guard(dev):
-        check(lib().adfp_mesh_project_colors(ptr(v) if V else None, ptr(n) if V else None, V, ptr(w2c), ptr(center),
-                                             ptr(depth) if K else None, ptr(color) if K else None, K, float(fx), float(fy), float(cx),
-                                             float(cy), W, H, float(depth_tol), int(border), BLENDS[blend], ptr(rgb), ptr(wsum), ptr(count),
-                                             ptr(best), _lib.current_stream(dev)), 'adfp_mesh_project_colors')
+    with _lib.on(dev) as L:
+        L.adfp_mesh_project_colors(v, n, V, w2c, center, depth, color, K, float(fx), float(fy), float(cx), float(cy), W, H,
+                                   float(depth_tol), int(border), BLENDS[blend], rgb, wsum, count, best)
     return rgb, wsum, count, best
 
 
@@ -390,12 +365,6 @@ def project_colors(verts, normals, depth, color, c2w, fx, fy, cx, cy, depth_tol,
     return _project_colors(v, n, d.contiguous(), col.contiguous(), m, fx, fy, cx, cy, tol, int(border), blend)
 
 
-def _np(x):
-    if x is None:
-        return None
-    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-
-
 # ---- mesh bound: the convex hull of the keyframes' camera centres and back-projected valid depth pixels, as a quickhull in
 # rounds (csrc/adfp_bound.h; contracts and the fixed formulae: include/adfp.h, "mesh bound").  A point is named by its id
 # k (H W + 1) + j: j = 0 the camera centre of keyframe k, j = 1 + row W + col a pixel.  The device does the point work (support
@@ -422,8 +391,8 @@ def bound_directions(D=BOUND_DIRECTIONS):
 
 
 def _bound_scene_arrays(depth, c2w):
-    d = _np(depth)
-    m = _np(c2w)
+    d = as_numpy(depth)
+    m = as_numpy(c2w)
     if d.ndim != 3 or m.shape != (d.shape[0], 4, 4):
         raise ValueError(f'mesh bound: depth must be [K,H,W] and c2w [K,4,4], got {d.shape} and {m.shape}')
     return np.ascontiguousarray(d, np.float32), np.ascontiguousarray(m, np.float32)
@@ -520,19 +489,15 @@ class _DeviceBound(object):
         K, H, W = (int(s) for s in self.depth.shape)
         self.K, self.H, self.W = K, H, W
         self.n_ids = K * (H * W + 1)
-        self.scene = (ptr(self.depth), ptr(self.poses), K, H, W, float(fx), float(fy), float(cx), float(cy))
+        self.scene = (self.depth, self.poses, K, H, W, float(fx), float(fy), float(cx), float(cy))
 
     def support(self, dirs):
-        L = lib()
         D = int(dirs.shape[0])
         d = torch.from_numpy(np.ascontiguousarray(dirs, np.float64)).to(self.dev)
         out = torch.empty(D + 8, dtype=torch.int64, device=self.dev)          # best ids, aabb (f64 bits), counts
-        with _lib.device_guard(self.dev):
-            nbytes = L.adfp_bound_support_workspace_bytes(self.K, self.H, self.W, D)
-            ws = _ws(nbytes, self.dev)
-            base = out.data_ptr()
-            check(L.adfp_bound_support(*self.scene, ptr(d), D, ptr(ws), nbytes, C.c_void_p(base), C.c_void_p(base + 8 * D),
-                                       C.c_void_p(base + 8 * (D + 6)), _lib.current_stream(self.dev)), 'adfp_bound_support')
+        with _lib.on(self.dev) as L:
+            nbytes = lib().adfp_bound_support_workspace_bytes(self.K, self.H, self.W, D)
+            L.adfp_bound_support(*self.scene, d, D, _lib.workspace(nbytes, self.dev), nbytes, out, out[D:], out[D + 6:])
             h = out.cpu().numpy()
         return h[:D].copy(), h[D:D + 6].view(np.float64).copy(), int(h[D + 6]), int(h[D + 7])
 
@@ -541,26 +506,22 @@ class _DeviceBound(object):
         out = torch.empty((len(ids), 3), dtype=torch.float64, device=self.dev)
         if len(ids):
             t = torch.from_numpy(ids).to(self.dev)
-            with _lib.device_guard(self.dev):
-                check(lib().adfp_bound_points(*self.scene, ptr(t), len(ids), ptr(out), _lib.current_stream(self.dev)), 'adfp_bound_points')
+            with _lib.on(self.dev) as L:
+                L.adfp_bound_points(*self.scene, t, len(ids), out)
         return out.cpu().numpy()
 
     def classify(self, cand, planes, eps):
-        L = lib()
         F = int(planes.shape[0])
         ids_in, n_in = (None, self.n_ids) if cand is None else cand
         pl = torch.from_numpy(np.ascontiguousarray(planes, np.float64)).to(self.dev)
         res = torch.empty(2 * F + 1, dtype=torch.int64, device=self.dev)      # far ids, far distances (f64 bits), the count
         cap = n_in if n_in <= _BOUND_CAP_ALL else max(_BOUND_CAP_ALL, n_in // 4)
-        with _lib.device_guard(self.dev):
-            st = _lib.current_stream(self.dev)
-            nbytes = L.adfp_bound_classify_workspace_bytes(n_in)
-            ws = _ws(nbytes, self.dev)
-            base = res.data_ptr()
+        with _lib.on(self.dev) as L:
+            nbytes = lib().adfp_bound_classify_workspace_bytes(n_in)
+            ws = _lib.workspace(nbytes, self.dev)
             while True:
                 out = torch.empty(max(cap, 1), dtype=torch.int64, device=self.dev)
-                check(L.adfp_bound_classify(*self.scene, ptr(ids_in), n_in, ptr(pl), F, float(eps), ptr(ws), nbytes, ptr(out), cap,
-                                            C.c_void_p(base + 16 * F), C.c_void_p(base), C.c_void_p(base + 8 * F), st), 'adfp_bound_classify')
+                L.adfp_bound_classify(*self.scene, ids_in, n_in, pl, F, float(eps), ws, nbytes, out, cap, res[2 * F:], res, res[F:])
                 h = res.cpu().numpy()                                         # the round's one synchronisation
                 count = int(h[2 * F])
                 if count <= cap:
@@ -621,11 +582,11 @@ def depth_hull(depth, c2w, fx, fy, cx, cy, directions=None, return_stats=False, 
 def write_ply(path, verts, faces, colors=None, normals=None, ascii=False):
     """Write a triangle mesh as PLY: binary little-endian (default) or ascii.  Vertex properties x y z [nx ny nz] [red green
     blue] (float, float, uchar) and 'property list uchar int vertex_index' faces: the property list of src/fusion.py:meshwrite."""
-    v = _np(verts).astype(np.float32).reshape(-1, 3)
-    f = _np(faces).astype(np.int32).reshape(-1, 3)
+    v = as_numpy(verts).astype(np.float32).reshape(-1, 3)
+    f = as_numpy(faces).astype(np.int32).reshape(-1, 3)
     fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
-    n = _np(normals)
-    c = _np(colors)
+    n = as_numpy(normals)
+    c = as_numpy(colors)
     if n is not None:
         fields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
     if c is not None:

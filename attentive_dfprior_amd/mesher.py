@@ -188,7 +188,7 @@ class Mesher(object):
         if K == 0 or pts.shape[0] == 0:
             return seen.bool()
         c2w = torch.stack([m.detach() for m in mats]).cpu().numpy()
-        w2c = torch.from_numpy(np.ascontiguousarray(np.linalg.inv(c2w)[:, :3, :])).to(dev).float().reshape(K, 12).contiguous()
+        w2c = M.w2c_rows_own_dtype(c2w, dev)
         depth = far = None
         rule = 'frustum'
         if not get_mask_use_all_frames:
@@ -202,11 +202,9 @@ class Mesher(object):
             depth = depth.reshape(K, H, W).contiguous()
             if not self.depth_test:
                 far = (depth.reshape(K, -1).amax(1) * 1.1).contiguous()          # torch.max(depth) * 1.1, per keyframe
-        with M._lib.device_guard(dev):
-            M.check(M.lib().adfp_mesh_seen_mask(M.ptr(pts), int(pts.shape[0]), M.ptr(w2c), K, M._lib.SEEN_RULE[rule],
-                                                M.ptr(depth) if self.depth_test else None, M.ptr(far), float(self.fx), float(self.fy),
-                                                float(self.cx), float(self.cy), int(W), int(H), M.ptr(seen),
-                                                M._lib.current_stream(dev)), 'adfp_mesh_seen_mask')
+        with M._lib.on(dev) as L:
+            L.adfp_mesh_seen_mask(pts, int(pts.shape[0]), w2c, K, M._lib.SEEN_RULE[rule], depth if self.depth_test else None, far,
+                                  float(self.fx), float(self.fy), float(self.cx), float(self.cy), int(W), int(H), seen)
         return seen.bool()
 
     # ---- mesh bound ------------------------------------------------------------------------------------------------------

@@ -6,24 +6,18 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import lib, ptr, check
-from .recon import device_of, as_points, _ws
+from ._lib import lib
+from .recon import device_of, as_points, as_faces, as_numpy, pose_rows
 
 
-def _faces(faces, dev):
-    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.asarray(faces, dtype=np.int64))
-    return f.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
-
-
-def _c2w_rows(c2w, dev):
-    """[P,4,4] / [4,4] / [P,3,4] (numpy or tensor) -> f64 device [P,12]: the top three rows of each pose."""
-    t = c2w if torch.is_tensor(c2w) else torch.from_numpy(np.asarray(c2w, dtype=np.float64))
-    t = t.detach().to(device=dev, dtype=torch.float64)
-    if t.dim() == 2:
-        t = t[None]
-    if t.dim() != 3 or t.shape[1] not in (3, 4) or t.shape[2] != 4:
-        raise ValueError(f'c2w must be [P,4,4] or [4,4], got {tuple(t.shape)}')
-    return t[:, :3, :].reshape(-1, 12).contiguous()
+def near_rows(near, P, dev, what):
+    """The near planes of P views, a scalar or [P] -> contiguous f64 [P] on `dev`; `what` names the caller in the refusal."""
+    nr = torch.as_tensor(near, dtype=torch.float64).reshape(-1).to(dev)
+    if nr.numel() == 1:
+        nr = nr.expand(P)
+    if nr.numel() != P:
+        raise ValueError(f'{what}: {nr.numel()} near values for {P} views')
+    return nr.contiguous()
 
 
 class MeshBVH(object):
@@ -38,19 +32,19 @@ class MeshBVH(object):
             raise ValueError(f'MeshBVH: leaf must be one of {_lib.TRI_LEAVES}, got {leaf}')
         self.leaf = int(leaf)
         v = as_points(verts, dev, 'vertices')
-        f = _faces(faces, dev)
+        f = as_faces(faces, dev, np.int64)
         self.n_verts, self.n_faces = int(v.shape[0]), int(f.shape[0])
         if self.n_faces >= 2 ** 31 - 1024 or self.n_verts >= 2 ** 31 - 1024:
             raise ValueError(f'MeshBVH: {self.n_faces} faces / {self.n_verts} vertices are more than the BVH takes')
-        L = lib()
-        self.bvh = _ws(L.adfp_tri_bvh_bytes(self.n_faces, self.leaf), dev)
+        self.bvh = _lib.workspace(lib().adfp_tri_bvh_bytes(self.n_faces, self.leaf), dev)
         if self.n_faces:
-            wsb = L.adfp_tri_bvh_build_workspace_bytes(self.n_faces)
-            ws = _ws(wsb, dev)
-            with _lib.device_guard(dev):
-                check(L.adfp_tri_bvh_build(ptr(v) if self.n_verts else None, self.n_verts, ptr(f), self.n_faces, self.leaf,
-                                           ptr(self.bvh), self.bvh.numel(), ptr(ws), wsb, _lib.current_stream(dev)),
-                      'adfp_tri_bvh_build')
+            wsb = lib().adfp_tri_bvh_build_workspace_bytes(self.n_faces)
+            with _lib.on(dev) as L:
+                L.adfp_tri_bvh_build(v, self.n_verts, f, self.n_faces, self.leaf, self.bvh, self.bvh.numel(), _lib.workspace(wsb, dev), wsb)
+
+    def _tree(self):
+        """what the walks take as `bvh`: NULL for a mesh without faces, whose buffer holds nothing"""
+        return self.bvh if self.n_faces else None
 
     def render_depth(self, c2w, H, W, fx, fy, cx, cy, near, far, cull='none'):
         """f32 device tensor [P,H,W]: camera z of the nearest surface with near <= z <= far, 0 where there is none.  c2w: [P,4,4]
@@ -59,27 +53,19 @@ class MeshBVH(object):
         if cull not in _lib.CULL:
             raise ValueError(f"render_depth: cull must be one of {tuple(_lib.CULL)}, got {cull!r}")
         dev = self.device
-        m = _c2w_rows(c2w, dev)
+        m = pose_rows(c2w, dev)
         P = int(m.shape[0])
-        nr = torch.as_tensor(near, dtype=torch.float64).reshape(-1).to(dev)
-        if nr.numel() == 1:
-            nr = nr.expand(P)
-        if nr.numel() != P:
-            raise ValueError(f'render_depth: {nr.numel()} near values for {P} views')
-        nr = nr.contiguous()
+        nr = near_rows(near, P, dev, 'render_depth')
         depth = torch.empty((P, int(H), int(W)), dtype=torch.float32, device=dev)
         if P == 0:
             return depth
-        with _lib.device_guard(dev):
+        with _lib.on(dev) as L:
             if cull == 'none':
-                check(lib().adfp_render_depth(ptr(self.bvh) if self.n_faces else None, self.bvh.numel(), self.n_faces, self.leaf,
-                                              ptr(m), ptr(nr), float(far), P, int(H), int(W), float(fx), float(fy), float(cx),
-                                              float(cy), ptr(depth), _lib.current_stream(dev)), 'adfp_render_depth')
+                L.adfp_render_depth(self._tree(), self.bvh.numel(), self.n_faces, self.leaf, m, nr, float(far), P, int(H), int(W),
+                                    float(fx), float(fy), float(cx), float(cy), depth)
             else:
-                check(lib().adfp_render_depth_cull(ptr(self.bvh) if self.n_faces else None, self.bvh.numel(), self.n_faces,
-                                                   self.leaf, ptr(m), ptr(nr), float(far), P, int(H), int(W), float(fx), float(fy),
-                                                   float(cx), float(cy), _lib.CULL[cull], ptr(depth), _lib.current_stream(dev)),
-                      'adfp_render_depth_cull')
+                L.adfp_render_depth_cull(self._tree(), self.bvh.numel(), self.n_faces, self.leaf, m, nr, float(far), P, int(H), int(W),
+                                         float(fx), float(fy), float(cx), float(cy), _lib.CULL[cull], depth)
         return depth
 
     def render_hits(self, c2w, H, W, fx, fy, cx, cy, near, far, cull='none', want=('depth', 'face', 'bary')):
@@ -93,24 +79,17 @@ class MeshBVH(object):
         if not want or any(k not in ('depth', 'face', 'bary') for k in want):
             raise ValueError(f"render_hits: want must name some of 'depth', 'face', 'bary', got {want!r}")
         dev = self.device
-        m = _c2w_rows(c2w, dev)
+        m = pose_rows(c2w, dev)
         P = int(m.shape[0])
-        nr = torch.as_tensor(near, dtype=torch.float64).reshape(-1).to(dev)
-        if nr.numel() == 1:
-            nr = nr.expand(P)
-        if nr.numel() != P:
-            raise ValueError(f'render_hits: {nr.numel()} near values for {P} views')
-        nr = nr.contiguous()
+        nr = near_rows(near, P, dev, 'render_hits')
         H, W = int(H), int(W)
         shapes = {'depth': ((P, H, W), torch.float32), 'face': ((P, H, W), torch.int32), 'bary': ((P, H, W, 2), torch.float32)}
         out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
         if P == 0:
             return out
-        with _lib.device_guard(dev):
-            check(lib().adfp_render_hits(ptr(self.bvh) if self.n_faces else None, self.bvh.numel(), self.n_faces, self.leaf, ptr(m),
-                                         ptr(nr), float(far), P, H, W, float(fx), float(fy), float(cx), float(cy), _lib.CULL[cull],
-                                         ptr(out.get('depth')), ptr(out.get('face')), ptr(out.get('bary')),
-                                         _lib.current_stream(dev)), 'adfp_render_hits')
+        with _lib.on(dev) as L:
+            L.adfp_render_hits(self._tree(), self.bvh.numel(), self.n_faces, self.leaf, m, nr, float(far), P, H, W, float(fx), float(fy),
+                               float(cx), float(cy), _lib.CULL[cull], out.get('depth'), out.get('face'), out.get('bary'))
         return out
 
 
@@ -119,7 +98,7 @@ def proj_rows(c2w_list):
     and rounded to f32 (eval_recon.py:75-80)."""
     out = np.empty((len(c2w_list), 12), dtype=np.float32)
     for k, c2w in enumerate(c2w_list):
-        m = np.array(c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else c2w, dtype=np.float64, copy=True)
+        m = np.array(as_numpy(c2w), dtype=np.float64, copy=True)
         m[:3, 1] *= -1.0
         m[:3, 2] *= -1.0
         out[k] = np.linalg.inv(m)[:3, :4].astype(np.float32).reshape(-1)
@@ -136,9 +115,8 @@ def views_in_sight(points, c2w_list, H, W, fx, fy, cx, cy, device=None):
     if P == 0:
         return out.bool()
     n = int(v.shape[0])
-    with _lib.device_guard(dev):
-        check(lib().adfp_views_in_sight(ptr(v) if n else None, n, ptr(w), P, float(fx), float(fy), float(cx), float(cy), int(W),
-                                        int(H), ptr(out), _lib.current_stream(dev)), 'adfp_views_in_sight')
+    with _lib.on(dev) as L:
+        L.adfp_views_in_sight(v, n, w, P, float(fx), float(fy), float(cx), float(cy), int(W), int(H), out)
     return out.bool()
 
 
@@ -155,10 +133,7 @@ def depth_l1_sums(a, b):
     out = torch.empty(P, dtype=torch.float64, device=dev)
     if P == 0:
         return out
-    L = lib()
-    wsb = L.adfp_depth_l1_workspace_bytes(P, n)
-    ws = _ws(wsb, dev)
-    with _lib.device_guard(dev):
-        check(L.adfp_depth_l1_sums(ptr(a) if n else None, ptr(b) if n else None, P, n, ptr(ws), wsb, ptr(out),
-                                   _lib.current_stream(dev)), 'adfp_depth_l1_sums')
+    wsb = lib().adfp_depth_l1_workspace_bytes(P, n)
+    with _lib.on(dev) as L:
+        L.adfp_depth_l1_sums(a, b, P, n, _lib.workspace(wsb, dev), wsb, out)
     return out

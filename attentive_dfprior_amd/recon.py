@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import lib, ptr, check
+from ._lib import lib
 
 
 def device_of(*xs):
@@ -29,8 +29,31 @@ def as_points(x, dev, what='points'):
     return t
 
 
-def _ws(nbytes, dev):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+def as_faces(x, dev, dtype=None):
+    """numpy array or tensor -> detached contiguous int32 [F,3] on `dev`.  dtype: what np.asarray makes of an array before torch
+    sees it.  raycast, render_mesh and mesh.vertex_normals have always widened to np.int64 (any integer array goes through, a
+    uint32 index >= 2^31 wraps); sample_surface and faces_kept hand torch the array's own dtype (None) and so refuse what
+    torch.from_numpy refuses: the two are kept as they were."""
+    t = x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=dtype))
+    return t.detach().to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+
+
+def as_numpy(x):
+    """tensor (anywhere) or array -> numpy array on the host, None -> None"""
+    if x is None:
+        return None
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+def pose_rows(c2w, dev):
+    """[P,4,4] / [4,4] / [P,3,4] (numpy or tensor) -> f64 device [P,12]: the top three rows of each pose."""
+    t = c2w if torch.is_tensor(c2w) else torch.from_numpy(np.asarray(c2w, dtype=np.float64))
+    t = t.detach().to(device=dev, dtype=torch.float64)
+    if t.dim() == 2:
+        t = t[None]
+    if t.dim() != 3 or t.shape[1] not in (3, 4) or t.shape[2] != 4:
+        raise ValueError(f'c2w must be [P,4,4] or [4,4], got {tuple(t.shape)}')
+    return t[:, :3, :].reshape(-1, 12).contiguous()
 
 
 def _t12(transform):
@@ -49,16 +72,13 @@ class NNIndex(object):
         self.device = dev
         self.ref = as_points(ref, dev, 'reference points')
         self.n = int(self.ref.shape[0])
-        L = lib()
         if self.n >= 2 ** 31 - 1024:
             raise ValueError(f'NNIndex: {self.n} reference points are more than the index takes')
-        self.index = _ws(L.adfp_nn_index_bytes(self.n), dev)
+        self.index = _lib.workspace(lib().adfp_nn_index_bytes(self.n), dev)
         if self.n:
-            wsb = L.adfp_nn_build_workspace_bytes(self.n)
-            ws = _ws(wsb, dev)
-            with _lib.device_guard(dev):
-                check(L.adfp_nn_build(ptr(self.ref), self.n, ptr(self.index), self.index.numel(), ptr(ws), wsb,
-                                      _lib.current_stream(dev)), 'adfp_nn_build')
+            wsb = lib().adfp_nn_build_workspace_bytes(self.n)
+            with _lib.on(dev) as L:
+                L.adfp_nn_build(self.ref, self.n, self.index, self.index.numel(), _lib.workspace(wsb, dev), wsb)
 
     def query(self, points, transform=None, radius=math.inf, sort_queries=True):
         """points [M,3] -> (dist f64 [M], idx int32 [M]) device tensors.  transform: optional 3x4 (or 4x4) applied to the points
@@ -71,15 +91,12 @@ class NNIndex(object):
             return dist, idx
         if self.n == 0:
             raise ValueError('NNIndex.query: the index holds no points')
-        L = lib()
         flags = _lib.NN_SORT_QUERIES if sort_queries else 0
-        wsb = L.adfp_nn_query_workspace_bytes(m, flags)
-        ws = _ws(wsb, self.device)
+        wsb = lib().adfp_nn_query_workspace_bytes(m, flags)
         t = _t12(transform)
-        with _lib.device_guard(self.device):
-            check(L.adfp_nn_query(ptr(self.index), self.index.numel(), self.n, ptr(q), m, C.byref(t) if t is not None else None,
-                                  float(radius), flags, ptr(ws), wsb, ptr(dist), ptr(idx), _lib.current_stream(self.device)),
-                  'adfp_nn_query')
+        with _lib.on(self.device) as L:
+            L.adfp_nn_query(self.index, self.index.numel(), self.n, q, m, C.byref(t) if t is not None else None, float(radius), flags,
+                            _lib.workspace(wsb, self.device), wsb, dist, idx)
         return dist, idx
 
 
@@ -88,13 +105,10 @@ def metric_sums(dist, threshold):
     d = dist.detach().to(torch.float64).contiguous()
     dev = d.device
     n = int(d.numel())
-    L = lib()
-    wsb = L.adfp_recon_reduce_workspace_bytes(n)
-    ws = _ws(wsb, dev)
+    wsb = lib().adfp_recon_reduce_workspace_bytes(n)
     out = torch.empty(2, dtype=torch.float64, device=dev)
-    with _lib.device_guard(dev):
-        check(L.adfp_nn_metric_sums(ptr(d) if n else None, n, float(threshold), ptr(ws), wsb, ptr(out), _lib.current_stream(dev)),
-              'adfp_nn_metric_sums')
+    with _lib.on(dev) as L:
+        L.adfp_nn_metric_sums(d, n, float(threshold), _lib.workspace(wsb, dev), wsb, out)
     s, c = out.tolist()
     return s, c
 
@@ -103,16 +117,12 @@ def icp_moments(src, transform, origin, tgt, idx):
     """The 17 moments of adfp_icp_moments (count, sum d^2, sum p, sum q, sum p q^T) as a float64 numpy array."""
     dev = src.device
     n = int(src.shape[0])
-    L = lib()
-    wsb = L.adfp_recon_reduce_workspace_bytes(n)
-    ws = _ws(wsb, dev)
+    wsb = lib().adfp_recon_reduce_workspace_bytes(n)
     out = torch.empty(_lib.ICP_MOMENTS, dtype=torch.float64, device=dev)
     t = _t12(transform)
     o = (C.c_double * 3)(*[float(v) for v in origin])
-    with _lib.device_guard(dev):
-        check(L.adfp_icp_moments(ptr(src) if n else None, n, C.byref(t), C.byref(o), ptr(tgt) if tgt.shape[0] else None,
-                                 int(tgt.shape[0]), ptr(idx) if n else None, ptr(ws), wsb, ptr(out), _lib.current_stream(dev)),
-              'adfp_icp_moments')
+    with _lib.on(dev) as L:
+        L.adfp_icp_moments(src, n, C.byref(t), C.byref(o), tgt, int(tgt.shape[0]), idx, _lib.workspace(wsb, dev), wsb, out)
     return out.cpu().numpy()
 
 
@@ -131,8 +141,7 @@ def sample_surface(verts, faces, count=None, u_face=None, u_bary=None, generator
     Returns (points f64 [count,3], face_index int32 [count]) device tensors."""
     dev = torch.device(device) if device is not None else device_of(verts, faces, u_face)
     v = as_points(verts, dev, 'vertices')
-    f = (faces if torch.is_tensor(faces) else torch.from_numpy(np.asarray(faces))).to(device=dev, dtype=torch.int32)
-    f = f.reshape(-1, 3).contiguous()
+    f = as_faces(faces, dev)
     if u_face is None:
         u_face, u_bary = draw_uniforms(int(count), dev, generator)
     uf = torch.as_tensor(u_face).to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
@@ -146,12 +155,9 @@ def sample_surface(verts, faces, count=None, u_face=None, u_bary=None, generator
         return pts, fi
     if f.shape[0] == 0:
         raise ValueError('sample_surface: the mesh has no faces')
-    L = lib()
-    wsb = L.adfp_sample_surface_workspace_bytes(int(f.shape[0]))
-    ws = _ws(wsb, dev)
-    with _lib.device_guard(dev):
-        check(L.adfp_sample_surface(ptr(v), int(v.shape[0]), ptr(f), int(f.shape[0]), ptr(uf), ptr(ub), n, ptr(ws), wsb, ptr(pts),
-                                    ptr(fi), _lib.current_stream(dev)), 'adfp_sample_surface')
+    wsb = lib().adfp_sample_surface_workspace_bytes(int(f.shape[0]))
+    with _lib.on(dev) as L:
+        L.adfp_sample_surface(v, int(v.shape[0]), f, int(f.shape[0]), uf, ub, n, _lib.workspace(wsb, dev), wsb, pts, fi)
     return pts, fi
 
 
@@ -160,8 +166,7 @@ def w2c_rows(c2w_list):
     rounds the result to float32, which is what cull_mesh.py:53 gets."""
     out = np.empty((len(c2w_list), 12), dtype=np.float32)
     for k, c2w in enumerate(c2w_list):
-        m = c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else np.asarray(c2w)
-        w2c = np.linalg.inv(m.astype(np.float32))
+        w2c = np.linalg.inv(as_numpy(c2w).astype(np.float32))
         out[k] = w2c[:3, :4].astype(np.float32).reshape(-1)
     return out
 
@@ -172,20 +177,16 @@ def frustum_seen(verts, c2w_list, H, W, fx, fy, cx, cy, device=None):
     v = as_points(verts, dev, 'vertices')
     w = torch.from_numpy(w2c_rows(c2w_list)).to(dev).contiguous()
     seen = torch.empty(int(v.shape[0]), dtype=torch.uint8, device=dev)
-    with _lib.device_guard(dev):
-        check(lib().adfp_cull_vertices(ptr(v) if v.shape[0] else None, int(v.shape[0]), ptr(w) if w.shape[0] else None,
-                                       int(w.shape[0]), float(fx), float(fy), float(cx), float(cy), int(W), int(H),
-                                       ptr(seen) if v.shape[0] else None, _lib.current_stream(dev)), 'adfp_cull_vertices')
+    with _lib.on(dev) as L:
+        L.adfp_cull_vertices(v, int(v.shape[0]), w, int(w.shape[0]), float(fx), float(fy), float(cx), float(cy), int(W), int(H), seen)
     return seen
 
 
 def faces_kept(seen, faces):
     """uint8 [F] device tensor: 0 iff all three vertices of the face are unseen (adfp_cull_faces, cull_mesh.py:72-74)."""
     dev = seen.device
-    f = (faces if torch.is_tensor(faces) else torch.from_numpy(np.asarray(faces))).to(device=dev, dtype=torch.int32)
-    f = f.reshape(-1, 3).contiguous()
+    f = as_faces(faces, dev)
     keep = torch.empty(int(f.shape[0]), dtype=torch.uint8, device=dev)
-    with _lib.device_guard(dev):
-        check(lib().adfp_cull_faces(ptr(seen) if seen.numel() else None, int(seen.numel()), ptr(f) if f.shape[0] else None,
-                                    int(f.shape[0]), ptr(keep) if f.shape[0] else None, _lib.current_stream(dev)), 'adfp_cull_faces')
+    with _lib.on(dev) as L:
+        L.adfp_cull_faces(seen, int(seen.numel()), f, int(f.shape[0]), keep)
     return keep

@@ -7,8 +7,8 @@ import numpy as np
 import torch
 
 from . import _lib, mesh
-from ._lib import lib, ptr, check
-from .recon import as_points, _ws
+from ._lib import lib
+from .recon import as_points
 
 UNIT = _lib.UNIT_VOXELS
 MAX_BOX_VOXELS = 2 ** 31
@@ -56,10 +56,9 @@ def touch(depth, c2w, box, fx, fy, cx, cy, stride, depth_trunc, sdf_trunc, outsi
     if P == 0:
         return out
     dev = depth.device
-    with _lib.device_guard(dev):
-        check(lib().adfp_refuse_touch(ptr(depth), P, H, W, ptr(c2w), float(fx), float(fy), float(cx), float(cy), int(stride),
-                                      float(depth_trunc), float(sdf_trunc), box.unit_length, C.byref(_i3(box.lo)),
-                                      C.byref(_i3(box.dim)), ptr(out), ptr(outside), _lib.current_stream(dev)), 'adfp_refuse_touch')
+    with _lib.on(dev) as L:
+        L.adfp_refuse_touch(depth, P, H, W, c2w, float(fx), float(fy), float(cx), float(cy), int(stride), float(depth_trunc),
+                            float(sdf_trunc), box.unit_length, C.byref(_i3(box.lo)), C.byref(_i3(box.dim)), out, outside)
     return out
 
 
@@ -70,10 +69,9 @@ def integrate(tsdf, weight, box, units, depth, w2c, touched, fx, fy, cx, cy, sdf
     if n == 0 or P == 0:
         return
     dev = tsdf.device
-    with _lib.device_guard(dev):
-        check(lib().adfp_refuse_integrate(ptr(tsdf), ptr(weight), C.byref(_i3(box.lo)), C.byref(_i3(box.dim)), box.voxel, ptr(units),
-                                          n, ptr(depth), ptr(w2c), ptr(touched), P, H, W, float(fx), float(fy), float(cx), float(cy),
-                                          float(sdf_trunc), float(depth_trunc), _lib.current_stream(dev)), 'adfp_refuse_integrate')
+    with _lib.on(dev) as L:
+        L.adfp_refuse_integrate(tsdf, weight, C.byref(_i3(box.lo)), C.byref(_i3(box.dim)), box.voxel, units, n, depth, w2c, touched,
+                                P, H, W, float(fx), float(fy), float(cx), float(cy), float(sdf_trunc), float(depth_trunc))
 
 
 def extract(tsdf, weight, box):
@@ -110,12 +108,9 @@ def voxel_down_sample(points, voxel_size, device=None):
     hi3 = (C.c_double * 3)(*hi.tolist())
     out = torch.empty((n, 3), dtype=torch.float64, device=dev)
     cnt = torch.empty(n, dtype=torch.int32, device=dev)
-    L = lib()
-    wsb = L.adfp_voxel_down_sample_workspace_bytes(n)
-    ws = _ws(wsb, dev)
-    with _lib.device_guard(dev):
-        check(L.adfp_voxel_down_sample(ptr(p), n, float(voxel_size), C.byref(lo3), C.byref(hi3), ptr(ws), wsb, ptr(out), ptr(cnt),
-                                       ptr(total), _lib.current_stream(dev)), 'adfp_voxel_down_sample')
+    wsb = lib().adfp_voxel_down_sample_workspace_bytes(n)
+    with _lib.on(dev) as L:
+        L.adfp_voxel_down_sample(p, n, float(voxel_size), C.byref(lo3), C.byref(hi3), _lib.workspace(wsb, dev), wsb, out, cnt, total)
     m = int(total.item())
     return out[:m], cnt[:m]
 

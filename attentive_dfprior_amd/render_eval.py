@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, synthetic
-from ._lib import check, lib
+from ._lib import lib
 
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 MAX_LEVELS = 5
@@ -62,7 +62,7 @@ class FrameMetrics(object):
         self.gt_color_dtype = gt_color_dtype
         self._geom = _lib.AdfpMetricsGeom(self.H, self.W, self.levels, int(gt_color_dtype == torch.float64))
         win = (C.c_longlong * MAX_LEVELS)()
-        check(lib().adfp_frame_metrics_windows(C.byref(self._geom), win), 'adfp_frame_metrics_windows')
+        _lib.host.adfp_frame_metrics_windows(C.byref(self._geom), win)
         self.windows = [int(v) for v in win]
         self._ws_bytes = lib().adfp_frame_metrics_workspace_bytes(C.byref(self._geom))
         self._ws = torch.empty(self._ws_bytes // 8, dtype=torch.float64, device=self.device)
@@ -89,10 +89,8 @@ class FrameMetrics(object):
             raise ValueError(f'add: gt_depth {tuple(gt_depth.shape)}, gt_color {tuple(gt_color.shape)}, depth {tuple(depth.shape)}, '
                              f'color {tuple(color.shape)} are not one {self.H} x {self.W} frame')
         row = self.count
-        with _lib.device_guard(dev):
-            check(lib().adfp_frame_metrics(C.byref(self._geom), _lib.ptr(gt_depth), _lib.ptr(gt_color), _lib.ptr(depth), _lib.ptr(color),
-                                           _lib.ptr(self._table[row]), _lib.ptr(self._ws), self._ws_bytes, _lib.current_stream(dev)),
-                  'adfp_frame_metrics')
+        with _lib.on(dev) as L:
+            L.adfp_frame_metrics(C.byref(self._geom), gt_depth, gt_color, depth, color, self._table[row], self._ws, self._ws_bytes)
         self.count += 1
         return row
 

@@ -25,9 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib, mesh
-from ._lib import lib, ptr, check
-from .raycast import MeshBVH, _c2w_rows, _faces
-from .recon import device_of, as_points
+from ._lib import lib
+from .raycast import MeshBVH, near_rows
+from .recon import device_of, as_points, as_faces, pose_rows
 
 CHUNK = 100                                         # views per launch and download: recon_eval.metric_2d's
 
@@ -47,7 +47,7 @@ class MeshViews(object):
         dev = torch.device(device) if device is not None else device_of(verts, faces)
         self.device = dev
         self.verts = as_points(verts, dev, 'vertices')
-        self.faces = _faces(faces, dev)
+        self.faces = as_faces(faces, dev, np.int64)
         self.colors = None
         if colors is not None:
             c = colors if torch.is_tensor(colors) else torch.from_numpy(np.ascontiguousarray(colors))
@@ -67,7 +67,7 @@ class MeshViews(object):
         if mode not in _lib.SHADE_MODE:
             raise ValueError(f'MeshViews: mode must be one of {tuple(_lib.SHADE_MODE)}, got {mode!r}')
         dev = self.device
-        m = _c2w_rows(c2w, dev)
+        m = pose_rows(c2w, dev)
         face = face.to(dev, torch.int32).contiguous()
         bary = bary.to(dev, torch.float32).contiguous()
         if face.dim() == 2:
@@ -84,13 +84,10 @@ class MeshViews(object):
             return out
         alb = (_lib.C.c_float * 3)(*[float(a) for a in albedo])
         bg = (_lib.C.c_ubyte * 3)(*[int(b) for b in background])
-        V, F = int(self.verts.shape[0]), int(self.faces.shape[0])
-        with _lib.device_guard(dev):
-            check(lib().adfp_shade_hits(ptr(face), ptr(bary), P, H, W, ptr(self.verts) if V else None, V,
-                                        ptr(self.faces) if F else None, F, ptr(m), float(fx), float(fy), float(cx), float(cy),
-                                        ptr(self.normals), ptr(self.colors), _lib.C.byref(alb), float(ambient), _lib.C.byref(bg),
-                                        _lib.SHADE_MODE[mode], ptr(out.get('normal')), ptr(out.get('rgb')),
-                                        _lib.current_stream(dev)), 'adfp_shade_hits')
+        with _lib.on(dev) as L:
+            L.adfp_shade_hits(face, bary, P, H, W, self.verts, int(self.verts.shape[0]), self.faces, int(self.faces.shape[0]), m, float(fx),
+                              float(fy), float(cx), float(cy), self.normals, self.colors, _lib.C.byref(alb), float(ambient),
+                              _lib.C.byref(bg), _lib.SHADE_MODE[mode], out.get('normal'), out.get('rgb'))
         return out
 
     def render(self, c2w, H, W, fx, fy, cx, cy, near=None, far=20.0, mode='shaded', cull='none', ambient=0.3,
@@ -99,14 +96,14 @@ class MeshViews(object):
         'normal': f32 [P,H,W,3] (camera space, toward the camera), 'rgb': uint8 [P,H,W,3]}.  c2w: [P,4,4] or [4,4], OpenCV axes;
         near=None is a hundredth of the mesh's longest side (calc_2d_metric's rule).  The views go through the kernels `chunk` at
         a time, so the face and barycentric images of only one chunk are alive at once."""
-        m = _c2w_rows(c2w, self.device)
+        m = pose_rows(c2w, self.device)
         P = int(m.shape[0])
         near = self.near if near is None else near
-        nr = torch.as_tensor(near, dtype=torch.float64).reshape(-1)
+        nr = near_rows(near, P, self.device, 'render_hits')          # refused here as render_hits would refuse it
         parts = {k: [] for k in ('depth', 'face', 'normal', 'rgb')}
         for p0 in range(0, max(P, 1), chunk):
             mc = m[p0:p0 + chunk].reshape(-1, 3, 4)
-            h = self.bvh.render_hits(mc, H, W, fx, fy, cx, cy, nr if nr.numel() == 1 else nr[p0:p0 + chunk], far, cull)
+            h = self.bvh.render_hits(mc, H, W, fx, fy, cx, cy, nr[p0:p0 + chunk], far, cull)
             s = self.shade(h['face'], h['bary'], mc, fx, fy, cx, cy, mode, ambient, albedo, background)
             for k, t in (('depth', h['depth']), ('face', h['face']), ('normal', s['normal']), ('rgb', s['rgb'])):
                 parts[k].append(t)
@@ -127,7 +124,7 @@ def draw_segments(rgb, depth, c2w, fx, fy, cx, cy, segments, colors, ranges=None
     if rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[3] != 3 or not rgb.is_contiguous():
         raise ValueError(f'draw_segments: rgb must be a contiguous uint8 [P,H,W,3] tensor, got {rgb.dtype} {tuple(rgb.shape)}')
     P, H, W = (int(s) for s in rgb.shape[:3])
-    m = _c2w_rows(c2w, dev)
+    m = pose_rows(c2w, dev)
     if int(m.shape[0]) != P:
         raise ValueError(f'draw_segments: {int(m.shape[0])} poses for {P} views')
     if depth is not None:
@@ -162,13 +159,11 @@ def draw_segments(rgb, depth, c2w, fx, fy, cx, cy, segments, colors, ranges=None
         need = lib().adfp_draw_segments_workspace_bytes(n, n_listed)
         if need and (ws is None or ws.numel() < need):
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        with _lib.device_guard(dev):
-            check(lib().adfp_draw_segments(ptr(rgb[p0:p0 + n]), ptr(depth[p0:p0 + n]) if depth is not None else None,
-                                           ptr(seg[p0:p0 + n]) if want_seg else None, n, H, W, ptr(m[p0:p0 + n]), float(fx), float(fy),
-                                           float(cx), float(cy), ptr(s) if N else None, ptr(c) if N else None, N,
-                                           ptr(r[p0:p0 + n]) if r is not None else None, R, n_listed, 0.5 * float(width), float(near_clip),
-                                           float(bias[0]), float(bias[1]), float(hidden_alpha), ptr(ws), need,
-                                           _lib.current_stream(dev)), 'adfp_draw_segments')
+        with _lib.on(dev) as L:
+            L.adfp_draw_segments(rgb[p0:p0 + n], depth[p0:p0 + n] if depth is not None else None, seg[p0:p0 + n] if want_seg else None,
+                                 n, H, W, m[p0:p0 + n], float(fx), float(fy), float(cx), float(cy), s, c, N,
+                                 r[p0:p0 + n] if r is not None else None, R, n_listed, 0.5 * float(width), float(near_clip),
+                                 float(bias[0]), float(bias[1]), float(hidden_alpha), ws, need)
     return seg
 
 

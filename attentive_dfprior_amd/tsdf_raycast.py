@@ -17,7 +17,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib, ptr
 from .engine import Engine
 
 
@@ -67,9 +66,7 @@ class TsdfRaycaster(object):
         V = m.shape[0]
         if step is None:
             step = 0.5 * self.voxel()
-        L = lib()
-        with _lib.device_guard(dev):
-            st = _lib.current_stream(dev)
+        with _lib.on(dev) as L:
             td = _lib.AdfpTsdf()
             keep = []
             self._engine.fill_tsdf(td, t, keep)
@@ -91,8 +88,7 @@ class TsdfRaycaster(object):
                     raise ValueError(f'out: expected contiguous float32 [{V},{int(H)},{int(W)}] on {dev}, got {out.dtype} {tuple(out.shape)}')
                 depth = out
             n =torch.zeros((1,), dtype=torch.int64, device=dev) if count else None
-            check(L.adfp_tsdf_raycast(C.byref(td), C.byref(b), ptr(bricks), nbytes, ptr(m), V, int(H), int(W), fx, fy, cx, cy,
-                                      float(near), float(far), float(step), 0 if skip else _lib.CAST_NO_SKIP, ptr(depth), ptr(n), st),
-                  'adfp_tsdf_raycast')
+            L.adfp_tsdf_raycast(C.byref(td), C.byref(b), bricks, nbytes, m, V, int(H), int(W), fx, fy, cx, cy, float(near), float(far),
+                                float(step), 0 if skip else _lib.CAST_NO_SKIP, depth, n)
         out = depth[0] if single else depth
         return (out, int(n.item())) if count else out

@@ -17,9 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib, mesh
-from ._lib import lib, ptr, check
 from .raycast import MeshBVH
-from .recon import as_points, sample_surface, w2c_rows
+from .recon import as_numpy, as_points, sample_surface, w2c_rows
 
 # metres by which a hit must lie in front of the point to occlude it, so that a surface point is not hidden by the face it lies
 # on.  Unpinned: the reference has no such test.  The package's own choice, below the 5 cm the 3D metrics resolve and far above
@@ -36,8 +35,7 @@ def opencv_rows(c2w_list):
     negated) in OpenCV axes -- the float32 pose widened to f64 with columns 1 and 2 negated back."""
     out = np.empty((len(c2w_list), 12), dtype=np.float64)
     for k, c2w in enumerate(c2w_list):
-        m = c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else np.asarray(c2w)
-        m = m.astype(np.float32).astype(np.float64)
+        m = as_numpy(c2w).astype(np.float32).astype(np.float64)
         m[:3, 1] *= -1.0
         m[:3, 2] *= -1.0
         out[k] = m[:3, :4].reshape(-1)
@@ -59,11 +57,9 @@ def points_visible(bvh, points, c2w_list, H, W, fx, fy, cx, cy, eps=OCCLUSION_EP
     seen = torch.empty(n, dtype=torch.uint8, device=dev)
     if n == 0:
         return seen
-    with _lib.device_guard(dev):
-        check(lib().adfp_points_visible(ptr(bvh.bvh) if bvh.n_faces else None, bvh.bvh.numel(), bvh.n_faces, bvh.leaf, ptr(v), n,
-                                        ptr(w) if P else None, ptr(m) if P else None, P, float(fx), float(fy), float(cx),
-                                        float(cy), int(W), int(H), float(near), float(eps), ptr(seen), _lib.current_stream(dev)),
-              'adfp_points_visible')
+    with _lib.on(dev) as L:
+        L.adfp_points_visible(bvh._tree(), bvh.bvh.numel(), bvh.n_faces, bvh.leaf, v, n, w, m, P, float(fx), float(fy), float(cx), float(cy),
+                              int(W), int(H), float(near), float(eps), seen)
     return seen
 
 

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import lib
 from .common import get_camera_from_tensor
 
 STATS = ('vmax', 'n_valid', 'depth_abs_sum', 'color_sq_sum', 'n_nonfinite', 'n_color')      # adfp_vis_panels' stats[], in order
@@ -50,7 +50,7 @@ class Visualizer(object):
         """(rows, cols) of the canvas of an H x W frame (adfp_vis_canvas_shape)."""
         rows, cols = C.c_int(), C.c_int()
         geom = _lib.AdfpVisGeom(H, W, self.stride, self.gap, 0)
-        check(lib().adfp_vis_canvas_shape(C.byref(geom), C.byref(rows), C.byref(cols)), 'adfp_vis_canvas_shape')
+        _lib.host.adfp_vis_canvas_shape(C.byref(geom), C.byref(rows), C.byref(cols))
         return rows.value, cols.value
 
     def _buffers_for(self, H, W, f64, device):
@@ -82,10 +82,8 @@ class Visualizer(object):
             raise ValueError(f'panels: gt_depth {tuple(gt_depth.shape)}, gt_color {tuple(gt_color.shape)}, depth {tuple(depth.shape)}, '
                              f'color {tuple(color.shape)} are not one frame')
         geom, ws, ws_bytes, canvas, stats = self._buffers_for(H, W, f64, dev)
-        with _lib.device_guard(dev):
-            check(lib().adfp_vis_panels(C.byref(geom), _lib.ptr(gt_depth), _lib.ptr(gt_color), _lib.ptr(depth), _lib.ptr(color),
-                                        _lib.ptr(canvas), _lib.ptr(stats), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev)),
-                  'adfp_vis_panels')
+        with _lib.on(dev) as L:
+            L.adfp_vis_panels(C.byref(geom), gt_depth, gt_color, depth, color, canvas, stats, ws, ws_bytes)
         return canvas, stats
 
     def panels(self, gt_depth, gt_color, depth, color):

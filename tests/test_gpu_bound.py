@@ -197,3 +197,9 @@ def test_get_mesh_runs_on_bound_planes_alone(tmp_path, monkeypatch):
     store = KeyframeStore.from_keyframe_dict(kfs, sc.H, sc.W, DEV)
     z2 = m.get_mesh(str(tmp_path / 'mesh2.ply'), c, dec, kfs, est, 2, tsdf, DEV, color=True, clean_mesh=True, keyframe_store=store)
     assert np.array_equal(z, z2) and (tmp_path / 'mesh2.ply').read_bytes() == out.read_bytes()
+
+
+def test_points_of_no_ids():
+    b = mesh._DeviceBound(*on_device(BC.cloud('mini')))
+    got = b.points(np.zeros(0, np.int64))
+    assert got.shape == (0, 3) and got.dtype == np.float64

@@ -183,3 +183,15 @@ def test_command_line_2d(tmp_path):
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1 and lines[0].startswith('Depth L1:')
     assert np.isfinite(float(lines[0].split(':')[1]))
+
+
+def test_no_views_and_no_pixels():
+    pts = torch.rand((7, 3), dtype=torch.float64, device=DEV)
+    none = raycast.views_in_sight(pts, [], 500, 500, 300.0, 300.0, 249.5, 249.5)
+    assert none.shape == (0,) and none.dtype == torch.bool
+    a = torch.zeros((0, 5, 4), dtype=torch.float32, device=DEV)
+    got = raycast.depth_l1_sums(a, a.clone())
+    assert got.shape == (0,) and got.dtype == torch.float64
+    b = torch.zeros((3, 0), dtype=torch.float32, device=DEV)                 # three views of no pixels
+    got = raycast.depth_l1_sums(b, b.clone())
+    assert got.shape == (3,) and got.dtype == torch.float64 and (got == 0).all()

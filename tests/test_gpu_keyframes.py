@@ -229,3 +229,9 @@ def test_store_feeds_get_samples_multi_bit_exact():
     slow = [torch.cat([p[k].float() for p in parts]) for k in range(4)]
     for a, b in zip(fast, slow):
         assert torch.equal(a, b)
+
+
+def test_no_pixels_drawn_is_refused():
+    with pytest.raises(ValueError, match='no pixels drawn'):
+        KF.keyframe_overlap_counts(torch.zeros(0, dtype=torch.int64, device=DEV), torch.ones((4, 4)), torch.eye(4), torch.eye(4)[None], 16,
+                                   4, 4, 4.0, 4.0, 1.5, 1.5)

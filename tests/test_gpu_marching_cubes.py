@@ -162,3 +162,13 @@ def test_tsdf_volume_get_mesh():
     pc = vol.get_point_cloud()
     assert pc.shape == (len(verts), 6)
     assert np.array_equal(pc[:, 3:], ref_col.astype(pc.dtype))
+
+
+def test_hull_fill_without_planes_and_unpack_colors_without_vertices():
+    """max over no planes is not > 0: nothing is outside, nothing is filled.  No vertices: no colours."""
+    vals = torch.arange(24, dtype=torch.float32, device=DEV).reshape(2, 3, 4).contiguous()
+    before = vals.clone()
+    axes = [np.linspace(0, 1, n, dtype=np.float32) for n in (2, 3, 4)]
+    assert mesh.hull_fill(vals, axes, np.zeros((0, 4)), 100.) is vals and torch.equal(vals, before)
+    out = mesh.unpack_colors(torch.zeros((0, 3), dtype=torch.float32, device=DEV), torch.zeros((2, 3, 4), dtype=torch.float32, device=DEV))
+    assert out.shape == (0, 3) and out.dtype == torch.uint8

@@ -255,19 +255,16 @@ def test_compaction_scans_more_tiles_than_one_round():
     verts = rng.standard_normal((nv, 3)).astype(np.float32)
     used = np.zeros(nv, bool)
     used[faces[keep]] = True
-    L = M.lib()
     v, f, k = (torch.from_numpy(a).to(DEV) for a in (verts, faces, keep.astype(np.uint8)))
-    with M._lib.device_guard(v.device):
-        st = M._lib.current_stream(v.device)
-        nbytes = L.adfp_mesh_compact_workspace_bytes(nv, nf)
+    with M._lib.on(v.device) as L:
+        nbytes = M.lib().adfp_mesh_compact_workspace_bytes(nv, nf)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
         totals = torch.empty(2, dtype=torch.int64, device=DEV)
-        M.check(L.adfp_mesh_compact_plan(M.ptr(f), nf, nv, M.ptr(k), M.ptr(ws), nbytes, M.ptr(totals), st), 'adfp_mesh_compact_plan')
+        L.adfp_mesh_compact_plan(f, nf, nv, k, ws, nbytes, totals)
         assert tuple(totals.tolist()) == (int(used.sum()), int(keep.sum()))
         vo = torch.empty((int(used.sum()), 3), dtype=torch.float32, device=DEV)
         fo = torch.empty((int(keep.sum()), 3), dtype=torch.int32, device=DEV)
-        M.check(L.adfp_mesh_compact_emit(M.ptr(v), nv, M.ptr(f), nf, M.ptr(ws), nbytes, M.ptr(vo), vo.shape[0], M.ptr(fo), fo.shape[0], st),
-                'adfp_mesh_compact_emit')
+        L.adfp_mesh_compact_emit(v, nv, f, nf, ws, nbytes, vo, vo.shape[0], fo, fo.shape[0])
     assert np.array_equal(vo.cpu().numpy().view(np.int32), verts[used].view(np.int32))
     assert np.array_equal(fo.cpu().numpy(), (np.cumsum(used) - used)[faces[keep]])
 
@@ -508,3 +505,31 @@ def test_get_mesh_takes_a_keyframe_store(tmp_path):
     m.get_mesh(str(a), c, dec, kfs, est, 2, tsdf, DEV)
     m.get_mesh(str(b), c, dec, kfs, est, 2, tsdf, DEV, keyframe_store=store)
     assert a.read_bytes() == b.read_bytes()
+
+
+def test_empty_inputs():
+    """No vertices, no faces, no rows: empty tensors of the documented shape and dtype."""
+    v0 = torch.zeros((0, 3), dtype=torch.float32, device=DEV)
+    f0 = torch.zeros((0, 3), dtype=torch.int32, device=DEV)
+    gv, gf = M.clean_components(v0, f0, torch.zeros(0, dtype=torch.bool, device=DEV), min_area=0.0)
+    assert gv.shape == (0, 3) and gv.dtype == torch.float32 and gf.shape == (0, 3) and gf.dtype == torch.int32
+    gv, gf = M.clean_components(v0, f0, torch.zeros(0, dtype=torch.uint8, device=DEV), largest=True)
+    assert gv.shape == (0, 3) and gf.shape == (0, 3)
+    assert M.face_components(f0, 0).shape == (0,)
+    # coincident vertices that no face uses: merged all the same, the (empty) faces follow
+    dup = np.array([[1, 2, 3], [4, 5, 6], [1, 2, 3]], np.float32)
+    col = np.arange(9, dtype=np.uint8).reshape(3, 3)
+    assert check_merge(dup, np.zeros((0, 3), np.int32), col) == 2
+    out = M.color_bytes(torch.zeros((0, 4), dtype=torch.float32, device=DEV))
+    assert out.shape == (0, 3) and out.dtype == torch.uint8
+
+
+def test_seen_mask_without_keyframes_or_points():
+    m = Mesher.__new__(Mesher)
+    m.H, m.W, m.fx, m.fy, m.cx, m.cy, m.depth_test = 8, 8, 8.0, 8.0, 3.5, 3.5, False
+    pts = torch.rand((5, 3), device=DEV)
+    none = m.seen_mask(pts, [], torch.eye(4)[None], 0, DEV)
+    assert none.shape == (5,) and none.dtype == torch.bool and not none.any()
+    kf = [{'est_c2w': torch.eye(4), 'depth': torch.ones((8, 8))}]
+    none = m.seen_mask(pts[:0], kf, torch.eye(4)[None], 0, DEV)
+    assert none.shape == (0,) and none.dtype == torch.bool

@@ -112,3 +112,17 @@ def test_caller_made_face_image():
     assert (np.abs(gc.astype(int) - rgb.astype(int))[~unsure] == 0).all()
     only = mv.shade(torch.from_numpy(face), torch.from_numpy(bary), np.eye(4), *cam[2:], background=(1, 2, 3), want=('rgb',))
     assert list(only) == ['rgb'] and torch.equal(only['rgb'], got['rgb'])
+
+
+def test_no_views_and_a_mesh_of_nothing():
+    verts, faces = S.mesh('uniform')
+    mv = render_mesh.MeshViews(verts, faces, None, DEV, smooth=True)
+    none = mv.shade(torch.zeros((0, 4, 6), dtype=torch.int32), torch.zeros((0, 4, 6, 2)), np.zeros((0, 4, 4)), 5.0, 5.0, 2.5, 1.5)
+    assert none['normal'].shape == (0, 4, 6, 3) and none['normal'].dtype == torch.float32
+    assert none['rgb'].shape == (0, 4, 6, 3) and none['rgb'].dtype == torch.uint8
+    r = mv.render(np.zeros((0, 4, 4)), 4, 6, 5.0, 5.0, 2.5, 1.5)
+    assert r['depth'].shape == (0, 4, 6) and r['face'].shape == (0, 4, 6) and r['rgb'].shape == (0, 4, 6, 3)
+    nothing = render_mesh.MeshViews(np.zeros((0, 3)), np.zeros((0, 3), np.int64), None, DEV, smooth=True)
+    r = nothing.render(np.eye(4), 4, 6, 5.0, 5.0, 2.5, 1.5, background=(1, 2, 3))
+    assert (r['depth'] == 0).all() and (r['face'] == -1).all() and (r['normal'] == 0).all()
+    assert r['rgb'].shape == (1, 4, 6, 3) and (r['rgb'].reshape(-1, 3).cpu() == torch.tensor([1, 2, 3], dtype=torch.uint8)).all()

@@ -337,3 +337,15 @@ def test_color_mesh_command_line(finished_run, tmp_path, capsys):
     # the default output name, the newest checkpoint by default (it is the one used above)
     covered, V = color_mesh.main([path, '--default_config', SR.DEFAULT, '--input_mesh', with_colors])
     assert os.path.exists(str(tmp_path / 'room_projected.ply')) and '00011.tar' in capsys.readouterr().out
+
+
+def test_no_vertices_and_no_keyframes():
+    d = torch.ones((2, 8, 8), dtype=torch.float32, device=DEV)
+    c = torch.ones((2, 8, 8, 3), dtype=torch.float32, device=DEV)
+    m = torch.eye(4)[None].repeat(2, 1, 1)
+    v = torch.tensor([[0.0, 0.0, 1.0], [0.1, 0.0, 1.0]], device=DEV)
+    rgb, wsum, count, best = M.project_colors(v[:0], None, d, c, m, 8, 8, 3.5, 3.5, 0.1)
+    assert rgb.shape == (0, 3) and wsum.shape == (0,) and count.shape == (0,) and best.shape == (0,)
+    assert (rgb.dtype, wsum.dtype, count.dtype, best.dtype) == (torch.float32, torch.float32, torch.int32, torch.int32)
+    rgb, wsum, count, best = M.project_colors(v, None, d[:0], c[:0], m[:0], 8, 8, 3.5, 3.5, 0.1)
+    assert rgb.shape == (2, 3) and (rgb == 0).all() and (wsum == 0).all() and (count == 0).all() and (best == -1).all()

@@ -345,3 +345,39 @@ def test_command_lines(tmp_path):
     r = subprocess.run([sys.executable, '-m', 'attentive_dfprior_amd.recon_eval', '--rec_mesh', rec_p, '--gt_mesh', gtc, '-2d'],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and 'not built' in r.stderr
+
+
+def test_empty_inputs():
+    """V = 0, F = 0, P = 0 views, M = 0 queries: empty or all-zero tensors of the documented shape and dtype, or the ValueError."""
+    none3 = torch.zeros((0, 3), dtype=torch.float64, device=DEV)
+    index = recon.NNIndex(none3)
+    assert index.n == 0
+    d, i = index.query(none3)
+    assert d.shape == (0,) and d.dtype == torch.float64 and i.shape == (0,) and i.dtype == torch.int32
+    with pytest.raises(ValueError, match='holds no points'):
+        index.query(torch.zeros((1, 3), dtype=torch.float64, device=DEV))
+    assert recon.metric_sums(torch.zeros(0, dtype=torch.float64, device=DEV), 0.05) == (0.0, 0.0)
+    eye = np.eye(4)
+    tgt = torch.rand((5, 3), dtype=torch.float64, device=DEV)
+    no_idx = torch.zeros(0, dtype=torch.int32, device=DEV)
+    for t in (tgt, none3):
+        m = recon.icp_moments(none3, eye, (0.0, 0.0, 0.0), t, no_idx)
+        assert m.shape == (17,) and m.dtype == np.float64 and (m == 0).all()
+    v, f = R.room_mesh(0.2)
+    u = torch.zeros(0, dtype=torch.float64, device=DEV)
+    pts, fi = recon.sample_surface(v, f, u_face=u, u_bary=u.reshape(0, 2), device=DEV)
+    assert pts.shape == (0, 3) and pts.dtype == torch.float64 and fi.shape == (0,) and fi.dtype == torch.int32
+    pts, fi = recon.sample_surface(v, f[:0], u_face=u, u_bary=u.reshape(0, 2), device=DEV)      # no draws: the faces are not looked at
+    assert pts.shape == (0, 3) and fi.shape == (0,)
+    with pytest.raises(ValueError, match='no faces'):
+        recon.sample_surface(v, f[:0], 3, device=DEV)
+    poses = [torch.eye(4) for _ in range(3)]
+    cam = (680, 1200, 600., 600., 599.5, 339.5)
+    seen = recon.frustum_seen(np.zeros((0, 3)), poses, *cam, device=DEV)
+    assert seen.shape == (0,) and seen.dtype == torch.uint8
+    seen = recon.frustum_seen(v, [], *cam, device=DEV)
+    assert seen.shape == (len(v),) and seen.dtype == torch.uint8 and (seen == 0).all()
+    keep = recon.faces_kept(seen, f[:0])
+    assert keep.shape == (0,) and keep.dtype == torch.uint8
+    keep = recon.faces_kept(seen[:0].contiguous(), np.zeros((0, 3), np.int64))
+    assert keep.shape == (0,)

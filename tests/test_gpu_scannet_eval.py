@@ -319,3 +319,20 @@ def test_missing_input_names_the_file(tmp_path, monkeypatch, capsys):
         run_cli(str(tmp_path), monkeypatch)
     assert e.value.code != 0
     assert '0077_00.obj' in capsys.readouterr().err
+
+
+def test_touch_and_integrate_without_views_or_units():
+    dev = torch.device(DEV)
+    box = refusion.UnitBox([-6, -6, -6], [14, 13, 12], 0.01)
+    outside = torch.zeros(1, dtype=torch.int32, device=dev)
+    none = refusion.touch(torch.zeros((0, 6, 8), device=dev), torch.zeros((0, 12), dtype=torch.float64, device=dev), box, FX, FY, CX, CY,
+                          4, 5.0, 0.03, outside)
+    assert none.shape == (0, box.n_units) and none.dtype == torch.uint8 and int(outside.item()) == 0
+    tsdf = torch.full((4, 4, 4), 0.25, device=dev)
+    weight = torch.zeros((4, 4, 4), device=dev)
+    d = torch.ones((1, 6, 8), device=dev)
+    w2c = torch.zeros((1, 12), dtype=torch.float32, device=dev)
+    touched = torch.zeros((1, box.n_units), dtype=torch.uint8, device=dev)
+    refusion.integrate(tsdf, weight, box, torch.zeros(0, dtype=torch.int32, device=dev), d, w2c, touched, FX, FY, CX, CY, 0.03, 5.0)
+    refusion.integrate(tsdf, weight, box, torch.zeros(1, dtype=torch.int32, device=dev), d[:0], w2c[:0], touched[:0], FX, FY, CX, CY, 0.03, 5.0)
+    assert (tsdf == 0.25).all() and (weight == 0).all()

@@ -238,3 +238,11 @@ def test_command_line_round_trip(tmp_path, capsys):
     simplify_mesh.main([str(src), str(dst), '--voxel_size', str(vs), '--contraction', 'average'])
     m = M.read_ply(str(dst))
     assert m.normals is None and np.array_equal(m.verts.astype(np.float32), ref['average'][0]) and np.array_equal(m.colors, ref['average'][2])
+
+
+def test_no_vertices():
+    v0 = torch.zeros((0, 3), dtype=torch.float32, device=DEV)
+    f0 = torch.zeros((0, 3), dtype=torch.int32, device=DEV)
+    vo, fo, co = M.simplify_vertex_clustering(v0, f0, 0.1, colors=torch.zeros((0, 3), dtype=torch.uint8, device=DEV))
+    assert vo.shape == (0, 3) and vo.dtype == torch.float32 and fo.shape == (0, 3) and fo.dtype == torch.int32
+    assert co.shape == (0, 3) and co.dtype == torch.uint8

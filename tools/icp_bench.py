@@ -102,12 +102,13 @@ def main():
     got = icp.c2w_out.cpu().numpy()
     e0, e1 = icp_ref.pose_error(G.numpy(), P.cpu().numpy()), icp_ref.pose_error(got, P.cpu().numpy())
     fused = TrackerIteration(rend, dec, sc.c, sc.tsdf_volume, tb, GEO[0], GEO[1], *GEO[2:], 20, 20)
-    st = _lib.current_stream(torch.device(DEV))
+    dev = torch.device(DEV)
 
     def one_step(stride):
         def fn():
-            icp._begin(icp.p_ref, st)
-            icp._step((icp.depth, icp.normals), icp.p_ref, stride, 0, st)
+            with _lib.on(dev) as L:
+                icp._begin(icp.p_ref, L)
+                icp._step((icp.depth, icp.normals), icp.p_ref, stride, 0, L)
         return fn
 
     def track10():
@@ -130,8 +131,9 @@ def main():
 
     def joint_step(stride):
         def fn():
-            rgbd._begin(rgbd.p_ref, st)
-            rgbd._rgbd_step(rgbd.maps[0], rgbd.normals, rgbd.depth[1], rgbd.p_ref, stride, 0, st)
+            with _lib.on(dev) as L:
+                rgbd._begin(rgbd.p_ref, L)
+                rgbd._rgbd_step(rgbd.maps[0], rgbd.normals, rgbd.depth[1], rgbd.p_ref, stride, 0, L)
         return fn
 
     def rgbd_refine():
