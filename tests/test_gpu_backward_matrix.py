@@ -48,6 +48,11 @@ Not the product: one case per launcher and per branch of a selector.  Which bran
 
   No rays / no points: zero gradients, nothing launched on the points.
 
+  Every cell above runs on the mini scene's one geometry (high and colour one shape, low the coarser lattice).  The branches that need
+  another one -- a third lattice on the in-kernel scatter beside the sorted one (run_decode_bwd_h), no plan for a coarse axis below 2 or
+  above 256 cells (plan_sorted_scatter), the refusal of a binned axis above 1 023 cells (scatter_bins) -- are
+  tests/test_gpu_grid_lattices.py's, on these 429 points; tests/test_lattice_cases.py shows on the CPU which case reaches which.
+
 Chunk edges (test_chunk_edges): STG_ROWS_MAX = 163 840 staging rows; the second chunk of a loop starts above 163 840 points (exact
 attention), 170 393 (exact HIGH), 177 493 (exact LOW and COLOR), 327 680 (f16-split attention) and 473 316 (f16-split staged
 decoders).  Reference: with a loss that is a plain sum over rays, the gradient of a batch is the gradient of its first half plus that

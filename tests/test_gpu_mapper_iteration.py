@@ -12,6 +12,7 @@ import attentive_dfprior_amd as A
 from attentive_dfprior_amd import common, mapping, synthetic
 from oracle import adfp_oracle as O
 from conftest import make_cfg, to_dev, assert_close, assert_adam_trajectory
+import lattice_cases as LC
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
@@ -21,9 +22,12 @@ STAGE_LR = {'low': dict(low=0.1, high=0.0, color=0.0, decoders=0.0, mlp=0.0),
 SCHEDULE = [('low', False), ('low', False), ('high', True), ('high', False), ('color', False), ('color', False)]
 
 
-def setup(samples=(32, 16)):
-    """samples: (N_samples, N_surface) of the renderer."""
+def setup(samples=(32, 16), lattice=None):
+    """samples: (N_samples, N_surface) of the renderer.  lattice: a case of tests/lattice_cases.py -- its grid shapes replace the
+    scene's (the frustum masks below follow them)."""
     sc = synthetic.mini_scene()
+    if lattice is not None:
+        sc.c = LC.make_grids(lattice)
     sd = O.random_state_dict(seed=3)
     dec = A.DF()
     dec.load_state_dict(sd)
@@ -67,9 +71,12 @@ def reference_path(sc, dec, rend, rays, masks):
     return {k: v.detach().clone() for k, v in grids.items()}, {n: p.detach().clone() for n, p in dec.named_parameters()}, losses
 
 
-@pytest.mark.parametrize('use_graph', [False, True])
-def test_fused_iteration_follows_the_reference_shaped_path(use_graph):
-    sc, dec, rend, rays, masks = setup()
+@pytest.mark.parametrize('use_graph,lattice', [(False, None), (True, None), (True, 'three_lattices')], ids=['False', 'True', 'True-three_lattices'])
+def test_fused_iteration_follows_the_reference_shaped_path(use_graph, lattice):
+    """three_lattices: the high grid is a third lattice -- the side lane, BWD_GRIDS_PREZEROED, the graph replay and a backward that mixes
+    the sorted and the in-kernel scatter in one call."""
+    sc, dec, rend, rays, masks = setup(lattice=lattice)
+    assert all(int(m.sum()) > 0 for m in masks.values()) and {tuple(m.shape) for m in masks.values()} == {tuple(v.shape[2:]) for v in sc.c.values()}
     dec2 = copy.deepcopy(dec)
     g_ref, p_ref, l_ref = reference_path(sc, dec, rend, rays, masks)
 
