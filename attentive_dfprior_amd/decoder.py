@@ -89,8 +89,8 @@ def pack_network(name, params, fmt='f32', status=None, flat=None, out=None, defe
     status: the pinned status word a weight outside the f16 range is reported to (default: the process-wide one).
     out: an image of the same network and format to overwrite (a training iteration re-packs the trained networks every step:
     same-stream ordering makes the in-place rebuild safe, and the image keeps its address).
-    defer: a list -- the jobs (net, ADFP_IMAGE_*, flat, packed) are not launched here but appended for flush_pack_jobs; the caller
-    flushes before it launches anything that reads an image.  Without it (or without room for two more jobs) they are launched at once."""
+    defer: a list (the `packs` of an engine.Deferred batch) -- the jobs (net, ADFP_IMAGE_*, flat, packed) are not launched here but
+    appended for flush_pack_jobs; the caller flushes before it launches anything that reads an image.  Without it (or without room for two more jobs) they are launched at once."""
     if flat is None:
         flat = _flat_params(params)
     _lib.require_cuda(flat, f'{name} decoder parameters')
@@ -333,7 +333,6 @@ class DF(nn.Module):
         self._engine = None
         self._status = None     # pinned status word of THIS module (see _lib.new_status_word)
         self._exact_latch = set()   # networks ('low' / 'high' / 'color' / 'att' / 'bwd') switched to the exact f32 kernels
-        self._pack_jobs = None      # a list while Engine.scene() collects this call's pack jobs (flush_pack_jobs), else None
         self._foreign = False       # True: the parameters live in ANOTHER process's memory (see __setstate__)
         self._foreign_serial = 0
 
@@ -412,39 +411,41 @@ class DF(nn.Module):
         return key
 
     # ---- weight images for the kernels -------------------------------------------------
-    def packed_weights(self, name, fmt='f32', key=None):
+    def packed_weights(self, name, fmt='f32', key=None, defer=None):
         """Packed (MFMA operand order) image of one sub-network, rebuilt only when a parameter
         changed (optimizer step bumps Parameter._version).  fmt 'f32' = exact f32-input MFMA image,
         'h' / 'g' / 'hg' = the H / G / both parts of the f16 hi/lo split image of the forward kernels, 'ht' = the transposed split
         image of the f16 backward (all of them jobs of adfp_pack_images, see pack_network).  key: net_key(name) if the caller has it already.
-        A stale image is rebuilt IN PLACE (same address; stream order protects kernels already queued on it)."""
+        A stale image is rebuilt IN PLACE (same address; stream order protects kernels already queued on it).
+        defer: the caller's batch of put-off conversions (engine.Deferred) -- the pack jobs of a split / transposed image go into its
+        one launch (defer.packs), and the cache slot written for them is noted there: the cache calls the image current at once,
+        and the batch takes the slot back if its jobs never run."""
         module = self.net_params(name)
         if key is None:
             key = _version_key(module)
-        if fmt in ('h', 'g', 'hg'):
+        jobs = None if defer is None or fmt == 'f32' else defer.packs
+        split = fmt in ('h', 'g', 'hg')
+        slot = name + '.split' if split else name if fmt == 'f32' else name + '.' + fmt
+        hit = self._packed.get(slot)
+        if split:
             # ONE buffer, two layouts: 'h' (the training forward, sub-networks on their own) and 'g' (the inference kernels) are
             # kept current separately -- a training iteration re-packs only the H part of a trained network, a frame only the G part
-            slot = name + '.split'
-            hit = self._packed.get(slot)
             need = [p for p in (('h', 'g') if fmt == 'hg' else (fmt,)) if hit is None or hit[2].get(p) != key]
             if not need:
                 return hit[1]
-            flat = self.flat_weights(name, key)
-            packed = pack_network(name, module, 'hg' if len(need) == 2 else need[0], status=self.status_word(), flat=flat,
-                                  out=None if hit is None else hit[1], defer=self._pack_jobs)
-            keys = dict(hit[2]) if hit is not None and hit[1] is packed else {}
-            for p in need:
-                keys[p] = key
-            self._packed[slot] = (key, packed, keys)
-            return packed
-        slot = name if fmt == 'f32' else name + '.' + fmt
-        hit = self._packed.get(slot)
-        if hit is not None and hit[0] == key:
+            fmt = 'hg' if len(need) == 2 else need[0]
+        elif hit is not None and hit[0] == key:
             return hit[1]
-        flat = self.flat_weights(name, key)
-        packed = pack_network(name, module, fmt, status=self.status_word(), flat=flat, out=None if hit is None else hit[1],
-                              defer=self._pack_jobs if fmt == 'ht' else None)
-        self._packed[slot] = (key, packed)
+        packed = pack_network(name, module, fmt, status=self.status_word(), flat=self.flat_weights(name, key),
+                              out=None if hit is None else hit[1], defer=jobs)
+        if split:
+            keys = dict(hit[2]) if hit is not None and hit[1] is packed else {}
+            keys.update((p, key) for p in need)
+            self._packed[slot] = (key, packed, keys)
+        else:
+            self._packed[slot] = (key, packed)
+        if jobs is not None:
+            defer.pack_slots.append(slot)
         return packed
 
     def __deepcopy__(self, memo):
@@ -454,14 +455,13 @@ class DF(nn.Module):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k in ('_packed', '_engine', '_plists', '_status', '_pack_jobs'):
+            if k in ('_packed', '_engine', '_plists', '_status'):
                 continue
             setattr(new, k, copy.deepcopy(v, memo))
         new._packed = {}
         new._plists = {}
         new._engine = None
         new._status = None
-        new._pack_jobs = None
         for m in new.modules():
             m.__dict__.pop('_foreign', None)
         new._foreign, new._foreign_serial = False, 0     # the copy's tensors are this process's own
@@ -476,7 +476,6 @@ class DF(nn.Module):
         d['_plists'] = {}
         d['_engine'] = None
         d['_status'] = None
-        d['_pack_jobs'] = None
         return d
 
     def __setstate__(self, state):

@@ -6,22 +6,69 @@ workspace, and caches the two per-call conversions the kernels need
   * feature grids  [1,32,Z,Y,X] (src/DF_Prior.py:243-264)  ->  channels-last [Z,Y,X,32]
   * decoder parameters -> packed MFMA images (decoder.DF.packed_weights)
 
-keyed on ``(data_ptr, _version, shape)`` because the Mapper re-materialises the grids every
+keyed on ``tensor_key`` because the Mapper re-materialises the grids every
 iteration (src/Mapper.py:382-388) and the Tracker reads them from another process.
 
 PyTorch here is device memory + streams only; no arithmetic of the hot path runs in torch.
 """
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
 from . import _lib
 from ._lib import lib, ptr, check
+from .decoder import flush_pack_jobs, pack_jobs_array
 
 
 def _host_bound(t):
     """[3,2] tensor (any device) -> nested python floats (one device sync if on GPU)."""
     return [[float(v) for v in row] for row in t.detach().to('cpu', torch.float64).tolist()]
+
+
+def tensor_key(t):
+    """What a cached conversion of tensor `t` is valid for: its address, its version counter (every in-place write PyTorch sees
+    bumps it), its shape and its strides."""
+    return t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride())
+
+
+# A cache entry: the key of the source tensor, the conversion, and the source's STORAGE -- (data_ptr, _version) identifies the
+# contents only as long as the allocator cannot hand the same address, at version 0, to the next tensor.  Field 1 is the value.
+Cached = namedtuple('Cached', 'key value storage')
+# ... of Engine._grid_cache: adopted = the copy is its holder's (adopt_grid_cl), never recycled as a re-layout destination
+CachedGrid = namedtuple('CachedGrid', 'key value storage adopted')
+
+
+def still_names(entry, t):
+    """Does cache entry `entry` (or None) still describe tensor `t` as it stands?"""
+    return entry is not None and entry.key == tensor_key(t)
+
+
+def pinned(t, value, adopted=None):
+    """The cache entry that calls `value` the conversion of `t` as it stands, with t's storage pinned (adopted: a _grid_cache one)."""
+    if adopted is None:
+        return Cached(tensor_key(t), value, t.untyped_storage())
+    return CachedGrid(tensor_key(t), value, t.untyped_storage(), adopted)
+
+
+def as_dev(t, dtype, dev):
+    """Input tensor -> what a kernel reads: detached, `dtype` on `dev`, contiguous; converted or copied only where it has to be
+    (these paths are bound by host time).  None passes through."""
+    if t is None:
+        return None
+    t = t.detach()
+    if t.dtype != dtype or t.device != dev:
+        t = t.to(dev, dtype)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def points_desc(pts):
+    """Points [P,3] f64 / f32 (anything else is read as f32) -> (AdfpPoints, the prepared tensor it points to, PTS_F64 / PTS_F32)."""
+    mode = _lib.PTS_F64 if pts.dtype == torch.float64 else _lib.PTS_F32
+    pts = as_dev(pts, torch.float64 if mode == _lib.PTS_F64 else torch.float32, pts.device)
+    ap = _lib.AdfpPoints()
+    ap.mode, ap.n_points, ap.pts = mode, pts.shape[0], pts.data_ptr()
+    return ap, pts, mode
 
 
 _ACT_FLOATS = {}
@@ -35,7 +82,6 @@ def _flat_floats(name):
         L = lib()
         hit = _FLAT_FLOATS[name] = int(L.adfp_attention_flat_floats() if name == 'att' else L.adfp_decoder_flat_floats(_lib.DEC_KIND[name]))
     return hit
-
 
 
 def _train_act_floats(name):
@@ -53,6 +99,22 @@ def math_mode():
     if m not in ('f16x3', 'f32'):
         raise RuntimeError(f'ADFP_MATH={m}: expected f16x3 or f32')
     return m
+
+
+def side_lane_mode():
+    """(on?, stages) of the backward's second lane from ADFP_SIDE_LANE: unset / empty / 1 / on / true / yes = on for the default
+    stages, 0 / off / false / no = off, <stage>[+<stage>] (low, high, color) = on for exactly those."""
+    import os
+    v = os.environ.get('ADFP_SIDE_LANE', '')
+    default = frozenset(('high', 'color'))
+    if v in ('', '1', 'on', 'true', 'yes'):
+        return True, default
+    if v in ('0', 'off', 'false', 'no'):
+        return False, default
+    for tok in v.split('+'):
+        if tok not in ('low', 'high', 'color'):
+            raise RuntimeError(f'ADFP_SIDE_LANE={v}: {tok!r} is not a stage (low, high, color); expected 0, 1 or <stage>[+<stage>]')
+    return True, frozenset(v.split('+'))
 
 
 class _PrivateWorkspaces(object):
@@ -75,13 +137,78 @@ _STAGE_GRIDS = {'low': (('low', 'grid_low'),), 'high': (('low', 'grid_low'), ('h
                 'color': (('low', 'grid_low'), ('high', 'grid_high'), ('color', 'grid_color'))}
 
 
+_GRID_KEYS = _STAGE_GRIDS['color']
+_NETS = ('low', 'high', 'color', 'att')      # the order of the flat parameter gradients in a gradient bucket
+
+
 def _align256(n):
     return (n + 255) & ~255
 
 
+def grad_plan(c, need_grid, need_flat, have_grids=(), have_flats=()):
+    """The layout of the gradient outputs a backward allocates itself, in ONE bucket: (floats of the bucket, {'g<grid>' / 'f<net>':
+    slice(offset, end) of it}) -- the wanted grids first (their channel-major copies are written with 16-byte stores), then the wanted flat
+    parameter gradients; have_grids / have_flats name the outputs the caller owns.  dist.allreduce_grads finds the whole bucket
+    contiguous -- the .grad tensors autograd keeps are views of it -- and all-reduces it in place, with no packing copy either
+    way: render_backward and zero_grad_bucket (a rank with no rays) both lay it out HERE."""
+    spans, off = {}, 0
+    for name, key in _GRID_KEYS:
+        if need_grid.get(name) and name not in have_grids:
+            spans['g' + name] = slice(off, off + c[key].numel())
+            off = spans['g' + name].stop
+    for name in _NETS:
+        if need_flat.get(name) and name not in have_flats:
+            spans['f' + name] = slice(off, off + _flat_floats(name))
+            off = spans['f' + name].stop
+    return off, spans
+
+
+class Deferred(object):
+    """What one call has put off into ONE launch each: grid re-layouts (Engine.grid_cl(defer=)) and weight-image packs
+    (DF.packed_weights(defer=)).  The caches call a conversion current as soon as it is recorded here, so the batch also notes
+    the cache slots it wrote, and takes exactly those back when it is abandoned: left through an exception -- a launch that
+    returns non-zero raises one (check) -- while jobs are pending.  `with Deferred(engine, decoders) as batch:` ends in one of
+    two ways: flush() launches the jobs now; hand_over() gives them to a render call as tables of its first launch, and they
+    stay pending until the `with` block is left."""
+
+    def __init__(self, engine, decoders):
+        self.engine, self.decoders = engine, decoders
+        self.relayouts = []      # (src, dst, voxels)
+        self.packs = []          # (net, part, flat, packed): pack_network(defer=) appends them
+        self.grid_names = []     # the Engine._grid_cache names written for the re-layouts
+        self.pack_slots = []     # the decoders._packed slots written for the packs
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is not None and (self.relayouts or self.packs):      # the caches would vouch for copies nobody wrote
+            for name in self.grid_names:
+                self.engine._grid_cache.pop(name, None)
+            for slot in self.pack_slots:
+                self.decoders._packed.pop(slot, None)
+        return False
+
+    def flush(self, device):
+        if self.relayouts:
+            arr, n, _ = Engine.relayout_jobs_array(self.relayouts)
+            with _lib.device_guard(device):
+                check(lib().adfp_relayout_grids(n, arr, 0, _lib.current_stream(device)), 'adfp_relayout_grids')
+            del self.relayouts[:]
+        flush_pack_jobs(self.packs, self.decoders.status_word(), device)
+
+    def hand_over(self, device):
+        """((re-layout table, count) or None, (pack table, count) or None) for adfp_render_args; the batch keeps the tensors alive.
+        At most ADFP_PACK_MAX_JOBS packs fit one table: more are launched here."""
+        rl = self.engine.relayout_jobs_array(self.relayouts)[:2] if self.relayouts else None
+        if 0 < len(self.packs) <= _lib.PACK_MAX_JOBS:
+            return rl, (pack_jobs_array(self.packs)[0], len(self.packs))
+        flush_pack_jobs(self.packs, self.decoders.status_word(), device)
+        return rl, None
+
+
 class Engine(object):
     def __init__(self):
-        import os
         # ADFP_BWD_* bits handed to the backward entries (adfp_backward_args.options): 0 = the library's own choice of path
         self.bwd_options = 0
         # Test / diagnostic switch: the training state also carries dbg_masks_* buffers, into which the EXACT backward kernels
@@ -90,21 +217,17 @@ class Engine(object):
         self._ws = None          # forward scratch, grow-only (stream order makes the reuse safe)
         self._bws = None         # backward scratch, same
         self._gcl = {}           # channels-last gradient scratch per grid (render_backward)
-        self._grid_cache = {}    # key name -> (key, channels-last tensor)
-        self._tsdf_cb = None     # (key, corner-block copy, pinned source storage) of the last TSDF volume asked for (tsdf_blocks)
-        self._tsdf_bricks = None  # (key, empty-space bitmap, pinned source storage) of the last TSDF volume raycast (tsdf_bricks)
-        self._bound_cache = {}   # id -> (key, host list)
+        self._grid_cache = {}    # key name -> CachedGrid(key, channels-last tensor, pinned source storage, adopted)
+        self._tsdf_cb = None     # Cached(key, corner-block copy, pinned source storage) of the last TSDF volume asked for (tsdf_blocks)
+        self._tsdf_bricks = None  # Cached(key, empty-space bitmap, pinned source storage) of the last TSDF volume raycast (tsdf_bricks)
+        self._bound_cache = {}   # id -> Cached(key, host list, pinned source storage)
         # The backward's second lane (adfp_backward_args.side_stream): the spatial sort of the sample points runs beside the backward
         # kernels instead of in front of them.  ADFP_SIDE_LANE=0 in the host's environment keeps everything on one stream (A/B runs).
-        self.use_side_lane = os.environ.get('ADFP_SIDE_LANE', '1') not in ('0', 'off', 'false', 'no')
         # ... and for which stages: the lane pays when the backward's main path is longer than the sort (nine launches, ~55 us + two
         # cross-stream hops).  Fused iteration at office0, 5 000 x 64, one stream -> lane: stage low 0.204 -> 0.215 ms, high 0.408 ->
         # 0.390, colour 0.695 -> 0.672 (profiles/r06_ab_side_lane.txt).  ADFP_SIDE_LANE=<stage>[+<stage>] overrides.
-        lane_env = os.environ.get('ADFP_SIDE_LANE', '')
-        self.side_lane_stages = frozenset(lane_env.split('+')) if lane_env and lane_env[0] in 'lhc' else frozenset(('high', 'color'))
+        self.use_side_lane, self.side_lane_stages = side_lane_mode()
         self._side = {}          # device -> (torch.cuda.Stream, [two torch.cuda.Event])
-        self._owed_packs = None  # (job table, count, keep-alive) scene(hand_over_packs=True) leaves for the render call's first launch
-        self._owed_relayouts = None   # the same for grid conversions (adfp_render_args.relayout_jobs)
 
     # ---- caches --------------------------------------------------------------------------
     def _alloc_scratch(self, nbytes, device):
@@ -145,17 +268,10 @@ class Engine(object):
         """The gradient outputs of render_backward for a batch of ZERO rays: the same single-allocation layout (grids first, then
         the flat parameter gradients), zero-filled -- a rank whose ray shard is empty then contributes to dist.allreduce_grads
         through the same in-place path as every other rank."""
-        sizes = [('g' + n, c[k].numel()) for n, k in (('low', 'grid_low'), ('high', 'grid_high'), ('color', 'grid_color')) if need_grid.get(n)]
-        sizes += [('f' + n, _flat_floats(n)) for n in ('low', 'high', 'color', 'att') if need_flat.get(n)]
-        bucket = torch.zeros((sum(v for _, v in sizes),), dtype=torch.float32, device=dev)
-        grids, flats, off = {}, {}, 0
-        for tag, nfl in sizes:
-            if tag[0] == 'g':
-                key = 'grid_' + tag[1:]
-                grids[tag[1:]] = bucket[off:off + nfl].view(c[key].shape)
-            else:
-                flats[tag[1:]] = bucket[off:off + nfl]
-            off += nfl
+        total, spans = grad_plan(c, need_grid, need_flat)
+        bucket = torch.zeros((total,), dtype=torch.float32, device=dev)
+        grids = {n: bucket[spans['g' + n]].view(c[k].shape) for n, k in _GRID_KEYS if 'g' + n in spans}
+        flats = {n: bucket[spans['f' + n]] for n in _NETS if 'f' + n in spans}
         return grids, flats
 
     def _cl_scratch(self, name, shape, device):
@@ -195,53 +311,59 @@ class Engine(object):
         return _PrivateWorkspaces(self)
 
     def host_bound(self, t, slot):
-        key = (t.data_ptr(), t._version, t.device)
         hit = self._bound_cache.get(slot)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        val = _host_bound(t)
-        self._bound_cache[slot] = (key, val, t.untyped_storage())     # pins the storage, see grid_cl
-        return val
+        if not still_names(hit, t):
+            hit = self._bound_cache[slot] = pinned(t, _host_bound(t))
+        return hit.value
 
     def adopt_grid_cl(self, name, g, shadow):
         """`shadow` IS the channels-last copy of grid `g` as it stands (the caller keeps it coherent: mapping.MapperIteration updates
         both in one Adam kernel): the next scene() finds it in the cache instead of re-laying the grid out."""
-        key = (g.data_ptr(), g._version, g.shape, g.stride())
-        self._grid_cache[name] = (key, shadow, g.untyped_storage(), 'adopted')      # never recycled as a re-layout destination
+        hit = self._grid_cache[name] = pinned(g, shadow, adopted=True)      # never recycled as a re-layout destination
+        return hit
+
+    def sync_shadow(self, name, g, shadow, held):
+        """For a holder that keeps its own channels-last `shadow` of grid `g` (the two fused iterations): `held` is the entry the
+        holder got from the last call for this shadow (None: re-lay out whatever the key says).  If it no longer names `g` -- the grid was replaced
+        or written since -- the grid is re-laid out into the shadow, here and now; then the shadow is adopted as what scene() finds
+        for the grid.  Returns the entry to hold."""
+        if not still_names(held, g):
+            src = as_dev(g, torch.float32, g.device)
+            Z, Y, X = g.shape[2:]
+            with _lib.device_guard(g.device):
+                check(lib().adfp_relayout_grid(ptr(src), ptr(shadow), 32, Z, Y, X, _lib.current_stream(g.device)), 'adfp_relayout_grid')
+            return self.adopt_grid_cl(name, g, shadow)
+        self._grid_cache[name] = held                  # still the truth: the slot is shared (another holder, a clear()), so say it again
+        return held
 
     def grid_cl(self, name, g, defer=None):
-        """channels-last copy of a [1,32,Z,Y,X] grid, converted by adfp_relayout_grid -- or, with `defer` (a list), recorded there as
-        a job (src, dst, voxels, keep-alive) for ONE launch of the caller's (flush_relayout_jobs / adfp_render_args.relayout_jobs); the
-        cache calls the copy current at once, so a caller that fails to run the jobs must drop the entry (scene() does)."""
+        """channels-last copy of a [1,32,Z,Y,X] grid, converted by adfp_relayout_grid -- or, with `defer` (a Deferred), recorded there
+        as a job (src, dst, voxels) for ONE launch of the caller's (Deferred.flush / adfp_render_args.relayout_jobs); the cache calls
+        the copy current at once, and the batch takes the entry back if its jobs never run."""
         _lib.require_cuda(g, name)
         if g.dim() != 5 or g.shape[0] != 1 or g.shape[1] != 32:
             raise RuntimeError(f'{name}: expected [1,32,Z,Y,X], got {tuple(g.shape)}')
-        key = (g.data_ptr(), g._version, g.shape, g.stride())
         hit = self._grid_cache.get(name)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        src = g.detach()
-        if src.dtype != torch.float32:
-            src = src.float()
-        src = src.contiguous()
+        if still_names(hit, g):
+            return hit.value
+        src = as_dev(g, torch.float32, g.device)
         Z, Y, X = src.shape[2:]
-        if hit is not None and len(hit) == 3 and hit[1].shape == (Z, Y, X, 32) and hit[1].device == src.device:
-            dst = hit[1]
+        if hit is not None and not hit.adopted and hit.value.shape == (Z, Y, X, 32) and hit.value.device == src.device:
+            dst = hit.value
         else:
             dst = torch.empty((Z, Y, X, 32), dtype=torch.float32, device=src.device)
-        if defer is not None and len(defer) < _lib.RELAYOUT_MAX_JOBS:
-            defer.append((src, dst, Z * Y * X))
+        if defer is not None and len(defer.relayouts) < _lib.RELAYOUT_MAX_JOBS:
+            defer.relayouts.append((src, dst, Z * Y * X))
+            defer.grid_names.append(name)
         else:
             check(lib().adfp_relayout_grid(ptr(src), ptr(dst), 32, Z, Y, X, _lib.current_stream(src.device)),
                   'adfp_relayout_grid')
-        # the cache entry keeps the source's storage alive: (data_ptr, _version) identifies the contents only as
-        # long as the allocator cannot hand the same address to another tensor
-        self._grid_cache[name] = (key, dst, g.untyped_storage())
+        self._grid_cache[name] = pinned(g, dst, adopted=False)
         return dst
 
     def tsdf_blocks(self, tsdf_volume):
         """The CORNER-BLOCK copy of a TSDF volume (adfp_relayout_tsdf: [X][Y][Z][8] float32, one aligned 32-byte piece per
-        trilinear lookup), built once per volume and cached on (data_ptr, _version, shape, strides) with the source's storage
+        trilinear lookup), built once per volume and cached on tensor_key with the source's storage
         pinned -- the TSDF is static for a whole run (get_tsdf.py writes it once, src/DF_Prior.py:86-91 loads it).  8 x the
         volume's bytes (room0: 6.3 GB, the 1024^3 stress volume: 34 GB of the 288 GB); None when that does not fit in half of
         the free memory."""
@@ -249,10 +371,8 @@ class Engine(object):
         _lib.require_cuda(t, 'tsdf_volume')
         if t.dtype != torch.float32 or t.dim() != 5 or t.shape[0] != 1 or t.shape[1] != 1:
             return None
-        key = (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()))
-        hit = self._tsdf_cb
-        if hit is not None and hit[0] == key:
-            return hit[1]
+        if still_names(self._tsdf_cb, t):
+            return self._tsdf_cb.value
         Z, Y, X = t.shape[2:]
         need = 32 * Z * Y * X
         self._tsdf_cb = None                                  # a stale copy goes first
@@ -269,7 +389,7 @@ class Engine(object):
             td = _lib.AdfpTsdf()
             self.fill_tsdf(td, t, [])
             check(lib().adfp_relayout_tsdf(C.byref(td), ptr(cb), _lib.current_stream(dev)), 'adfp_relayout_tsdf')
-        self._tsdf_cb = (key, cb, t.untyped_storage())
+        self._tsdf_cb = pinned(t, cb)
         return cb
 
     def invalidate_tsdf_blocks(self):
@@ -281,23 +401,18 @@ class Engine(object):
 
     def tsdf_blocks_cached(self, tsdf_volume):
         """The corner-block copy of `tsdf_volume` if this engine holds a current one, else None: never builds it."""
-        t, hit = tsdf_volume, self._tsdf_cb
-        if hit is not None and hit[0] == (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride())):
-            return hit[1]
-        return None
+        return self._tsdf_cb.value if still_names(self._tsdf_cb, tsdf_volume) else None
 
     def tsdf_bricks(self, tsdf_volume):
         """The empty-space bitmap of a TSDF volume (adfp_tsdf_bricks_build: one bit per brick of 8^3 voxels, int32 words), built
-        once per volume and cached beside the corner-block copy, on the same key -- (data_ptr, _version, shape, strides) with the
+        once per volume and cached beside the corner-block copy, on the same key -- tensor_key with the
         source's storage pinned -- and dropped by the same invalidate_tsdf_blocks.  49 KB for room0, 93 KB for office0."""
         t = tsdf_volume
         _lib.require_cuda(t, 'tsdf_volume')
         if t.dtype != torch.float32 or t.dim() != 5 or t.shape[0] != 1 or t.shape[1] != 1:
             raise RuntimeError(f'tsdf_volume: expected float32 [1,1,Z,Y,X], got {t.dtype} {tuple(t.shape)}')
-        key = (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()))
-        hit = self._tsdf_bricks
-        if hit is not None and hit[0] == key:
-            return hit[1]
+        if still_names(self._tsdf_bricks, t):
+            return self._tsdf_bricks.value
         Z, Y, X = t.shape[2:]
         nbytes = int(lib().adfp_tsdf_bricks_bytes(Z, Y, X))
         if nbytes == 0:
@@ -308,7 +423,7 @@ class Engine(object):
             td = _lib.AdfpTsdf()
             self.fill_tsdf(td, t, [])
             check(lib().adfp_tsdf_bricks_build(C.byref(td), ptr(bricks), nbytes, _lib.current_stream(dev)), 'adfp_tsdf_bricks_build')
-        self._tsdf_bricks = (key, bricks, t.untyped_storage())
+        self._tsdf_bricks = pinned(t, bricks)
         return bricks
 
     def refresh_tsdf_blocks(self, tsdf_volume, cb):
@@ -321,23 +436,28 @@ class Engine(object):
 
     @staticmethod
     def relayout_jobs_array(rjobs):
-        """(ctypes array, count, keep-alive) of deferred grid conversions (grid_cl(defer=...))."""
+        """(ctypes array, count, keep-alive) of grid conversions (src, dst, voxels): the table of one adfp_relayout_grids launch."""
         arr = (_lib.AdfpRelayoutJob * len(rjobs))()
         for k, (src, dst, vox) in enumerate(rjobs):
             arr[k].src, arr[k].dst, arr[k].voxels = src.data_ptr(), dst.data_ptr(), vox
         return arr, len(rjobs), [t for j in rjobs for t in j[:2]]
 
-    def flush_relayout_jobs(self, rjobs, device):
-        if not rjobs:
-            return
-        arr, n, _ = self.relayout_jobs_array(rjobs)
-        with _lib.device_guard(device):
-            check(lib().adfp_relayout_grids(n, arr, 0, _lib.current_stream(device)), 'adfp_relayout_grids')
-
     # ---- descriptor ----------------------------------------------------------------------
     def scene(self, decoders, c, tsdf_volume, tsdf_bnds, bound, stage, backward=False, ht_nets=(), keys=None, images=None, state=None,
-              tsdf_blocks=False, hand_over_packs=False):
-        """Returns (AdfpScene, keepalive list).  Forward: every network of the stage takes its f16-split image (ADFP_MATH=f16x3 and
+              tsdf_blocks=False):
+        """Returns (AdfpScene, keepalive list); the grid conversions and image packs it needs are launched before it returns (ONE
+        launch each).  The arguments are build_scene's."""
+        with Deferred(self, decoders) as batch:
+            built = self.build_scene(batch, decoders, c, tsdf_volume, tsdf_bnds, bound, stage, backward, ht_nets, keys, images, state,
+                                     tsdf_blocks)
+            batch.flush(next(iter(c.values())).device)
+        return built
+
+    def build_scene(self, batch, decoders, c, tsdf_volume, tsdf_bnds, bound, stage, backward=False, ht_nets=(), keys=None, images=None,
+                    state=None, tsdf_blocks=False):
+        """(AdfpScene, keepalive list), with the grid conversions and the split / transposed image packs the call has to (re)do
+        recorded in `batch` (a Deferred): the caller flushes it (scene) or hands it to its launch (render_forward).
+        Forward: every network of the stage takes its f16-split image (ADFP_MATH=f16x3 and
         not latched to exact, DF.uses_split) or its exact f32 image, plus -- when any split image is in use -- the flat parameters
         the device-side f32 repair path needs (adfp_scene.flat_*).  Backward: the exact f32 images, except for the decoders named
         in `ht_nets`: those get their transposed f16-split image (the caller has checked that the forward left their ReLU masks).
@@ -352,81 +472,49 @@ class Engine(object):
         sc.status = decoders.status_word().data_ptr()
         keep = []
         _lib.fill_bound(sc.bound, self.host_bound(bound, 'bound'))
-        rjobs = []                               # grids to convert: ONE launch (inside the render call, or flush_relayout_jobs below)
         nets = _STAGE_NETS[stage]
         if keys is None:
             keys = {}
         split = math_mode() == 'f16x3'
         latch = decoders._exact_latch
         any_split = False
-        from .decoder import flush_pack_jobs
-        jobs = decoders._pack_jobs = []          # the split / transposed images this call has to (re)build: packed in ONE launch below
-        try:
-            for field, key in _STAGE_GRIDS[stage]:
-                g = self.grid_cl(key, c[key], defer=rjobs)
-                keep.append(g)
-                gd = getattr(sc, field)
-                gd.data = g.data_ptr()
-                gd.Z, gd.Y, gd.X = g.shape[0], g.shape[1], g.shape[2]
-            for n in nets:
-                k = keys.get(n)
-                if k is None:
-                    k = keys[n] = decoders.net_key(n)
-                if backward:
-                    if n in ht_nets:
-                        setattr(sc, 'ht_' + n, decoders.packed_weights(n, 'ht', k).data_ptr())
-                    else:
-                        setattr(sc, 'w_' + n, decoders.packed_weights(n, 'f32', k).data_ptr())
-                elif split and n not in latch:
-                    setattr(sc, 'h_' + n, decoders.packed_weights(n, images or self.image_parts(stage, n, latch, state), k).data_ptr())
-                    any_split = True
-                    # a TRAINING forward whose state has mask room for the network: its backward will read the transposed image --
-                    # packed now, in the same launch (the backward finds it current: the parameters do not change in between)
-                    if state is not None and ('masks_' + n) in state and not state.get('bwd_exact'):
-                        decoders.packed_weights(n, 'ht', k)
+        for field, key in _STAGE_GRIDS[stage]:
+            g = self.grid_cl(key, c[key], defer=batch)
+            keep.append(g)
+            gd = getattr(sc, field)
+            gd.data = g.data_ptr()
+            gd.Z, gd.Y, gd.X = g.shape[0], g.shape[1], g.shape[2]
+        for n in nets:
+            k = keys.get(n)
+            if k is None:
+                k = keys[n] = decoders.net_key(n)
+            if backward:
+                if n in ht_nets:
+                    setattr(sc, 'ht_' + n, decoders.packed_weights(n, 'ht', k, defer=batch).data_ptr())
                 else:
                     setattr(sc, 'w_' + n, decoders.packed_weights(n, 'f32', k).data_ptr())
-            # hand_over_packs: the caller's render call packs them in its first launch (adfp_render_args.pack_jobs); at most
-            # ADFP_PACK_MAX_JOBS fit one table
-            self._owed_relayouts = None
-            if rjobs:
-                if hand_over_packs:
-                    self._owed_relayouts = self.relayout_jobs_array(rjobs)
-                else:
-                    self.flush_relayout_jobs(rjobs, next(iter(c.values())).device)
-                rjobs = []
-            self._owed_packs = None
-            if hand_over_packs and 0 < len(jobs) <= _lib.PACK_MAX_JOBS:
-                from .decoder import pack_jobs_array
-                arr, alive = pack_jobs_array(jobs)
-                self._owed_packs = (arr, len(jobs), alive)
-                del jobs[:]
+            elif split and n not in latch:
+                part = images or self.image_parts(stage, n, latch, state)
+                setattr(sc, 'h_' + n, decoders.packed_weights(n, part, k, defer=batch).data_ptr())
+                any_split = True
+                # a TRAINING forward whose state has mask room for the network: its backward will read the transposed image --
+                # packed now, in the same launch (the backward finds it current: the parameters do not change in between)
+                if state is not None and ('masks_' + n) in state and not state.get('bwd_exact'):
+                    decoders.packed_weights(n, 'ht', k, defer=batch)
             else:
-                flush_pack_jobs(jobs, decoders.status_word(), next(iter(c.values())).device)
-            if any_split:
-                for n in nets:
-                    setattr(sc, 'flat_' + n, decoders.flat_weights(n, keys[n]).data_ptr())
-            if stage != 'low':
-                _lib.fill_bound(sc.tsdf_bnds, self.host_bound(tsdf_bnds, 'tsdf_bnds'))
-                self.fill_tsdf(sc.tsdf, tsdf_volume, keep)
-                if tsdf_blocks is not None and tsdf_blocks is not False and not backward:
-                    # True: this engine's cached copy (None: not float32 / no room -- the plain volume serves); a tensor: the caller's own copy
-                    cb = tsdf_blocks if isinstance(tsdf_blocks, torch.Tensor) else self.tsdf_blocks(tsdf_volume)
-                    if cb is not None:
-                        sc.tsdf.corner_blocks = cb.data_ptr()
-                        keep.append(cb)
-        except BaseException:
-            # packed_weights(defer=...) has already recorded the deferred images as current in decoders._packed; if this call dies
-            # before they are packed (still in `jobs`) or handed to a render call (self._owed_packs), the cache would vouch for images
-            # nobody wrote: forget all of them, the next call re-packs
-            if jobs or self._owed_packs is not None:
-                decoders._packed = {}
-            if rjobs or self._owed_relayouts is not None:      # the same for channels-last copies nobody wrote
-                self._grid_cache = {k: v for k, v in self._grid_cache.items() if len(v) == 4}
-            self._owed_packs = self._owed_relayouts = None
-            raise
-        finally:
-            decoders._pack_jobs = None
+                setattr(sc, 'w_' + n, decoders.packed_weights(n, 'f32', k).data_ptr())
+        if any_split:
+            for n in nets:
+                setattr(sc, 'flat_' + n, decoders.flat_weights(n, keys[n]).data_ptr())
+        if stage != 'low':
+            _lib.fill_bound(sc.tsdf_bnds, self.host_bound(tsdf_bnds, 'tsdf_bnds'))
+            self.fill_tsdf(sc.tsdf, tsdf_volume, keep)
+            if tsdf_blocks is not None and tsdf_blocks is not False and not backward:
+                # True: this engine's cached copy (None: not float32 / no room -- the plain volume serves); a tensor: the caller's own copy
+                cb = tsdf_blocks if isinstance(tsdf_blocks, torch.Tensor) else self.tsdf_blocks(tsdf_volume)
+                if cb is not None:
+                    sc.tsdf.corner_blocks = cb.data_ptr()
+                    keep.append(cb)
         return sc, keep
 
     # ---- training state --------------------------------------------------------------------
@@ -600,13 +688,7 @@ class Engine(object):
         dev = pts.device
         saved = None
         with _lib.device_guard(dev):
-            if pts.dtype == torch.float64:
-                mode = _lib.PTS_F64
-            else:
-                mode = _lib.PTS_F32
-                if pts.dtype != torch.float32:
-                    pts = pts.float()
-            pts = pts.detach().contiguous()
+            ap, pts, mode = points_desc(pts)
             P = pts.shape[0]
             raw = torch.empty((P, 4), dtype=torch.float32, device=dev)
             w = torch.empty((P,), dtype=torch.float32, device=dev)
@@ -617,10 +699,6 @@ class Engine(object):
                 decoders.absorb_status()          # BEFORE the state is laid out: a network that latches to exact now gets no mask room
                 saved = self.train_state(P, stage, dev, decoders, need_flat)
             sc, keep = self.scene(decoders, c, tsdf_volume, tsdf_bnds, bound, stage, keys=keys, state=saved)
-            ap = _lib.AdfpPoints()
-            ap.mode = mode
-            ap.n_points = P
-            ap.pts = pts.data_ptr()
             ws = self.workspace(P, dev)
             st = None
             if train:
@@ -634,27 +712,24 @@ class Engine(object):
     def eval_points_backward(self, decoders, c, tsdf_volume, tsdf_bnds, bound, stage, apply_bound_rule, saved, g_raw, g_w,
                              need_grid, need_flat, need_pts):
         """Returns (grid grads dict in the reference's [1,32,Z,Y,X] layout, flat parameter grads dict, d/d pts [P,3] f32 or None)."""
-        pts = saved['pts']
+        ap, pts, _ = points_desc(saved['pts'])              # the forward's prepared tensor: nothing is converted again
         dev = pts.device
         L = lib()
         with _lib.device_guard(dev):
             P = pts.shape[0]
             sc, keep = self.scene(decoders, c, tsdf_volume, tsdf_bnds, bound, stage, backward=True,
                                   ht_nets=self.ht_nets(saved, need_flat, need_pts, need_grid), keys=saved.get('keys'))
-            ap = _lib.AdfpPoints()
-            ap.mode, ap.n_points, ap.pts = saved['mode'], P, pts.data_ptr()
             a = _lib.AdfpPointsBackwardArgs()
             a.stage, a.flags, a.state = _lib.STAGE[stage], 1 if apply_bound_rule else 0, saved['_state']
-            graw = None if g_raw is None else g_raw.detach().to(dev, torch.float32).contiguous()
-            gw = None if g_w is None else g_w.detach().to(dev, torch.float32).contiguous()
+            graw, gw = as_dev(g_raw, torch.float32, dev), as_dev(g_w, torch.float32, dev)
             a.g_raw, a.g_w = _lib.ptr(graw), _lib.ptr(gw)
             grids_cl, flats = {}, {}
-            for name, key in (('low', 'grid_low'), ('high', 'grid_high'), ('color', 'grid_color')):
+            for name, key in _GRID_KEYS:
                 if need_grid.get(name):
                     Z, Y, X = c[key].shape[2:]
                     grids_cl[name] = torch.empty((Z, Y, X, 32), dtype=torch.float32, device=dev)
                     setattr(a, 'g_grid_' + name, grids_cl[name].data_ptr())
-            for name in ('low', 'high', 'color', 'att'):
+            for name in _NETS:
                 if need_flat.get(name):
                     flats[name] = torch.empty((_flat_floats(name),), dtype=torch.float32, device=dev)
                     setattr(a, 'g_flat_' + name, flats[name].data_ptr())
@@ -665,25 +740,21 @@ class Engine(object):
             a.options = self.bwd_options
             stream = _lib.current_stream(dev)
             check(L.adfp_eval_points_backward(C.byref(sc), C.byref(ap), C.byref(a), stream), 'adfp_eval_points_backward')
-            grids = {}
-            if grids_cl:
-                arr = (_lib.AdfpRelayoutJob * len(grids_cl))()
-                for k, (name, g) in enumerate(grids_cl.items()):
-                    Z, Y, X = g.shape[:3]
-                    out = torch.empty((1, 32, Z, Y, X), dtype=torch.float32, device=dev)
-                    arr[k].src, arr[k].dst, arr[k].voxels = g.data_ptr(), out.data_ptr(), Z * Y * X
-                    grids[name] = out
-                check(L.adfp_relayout_grids(len(grids_cl), arr, 1, stream), 'adfp_relayout_grids')
+            grids = {name: torch.empty((1, 32) + tuple(g.shape[:3]), dtype=torch.float32, device=dev) for name, g in grids_cl.items()}
+            self._grads_to_reference_layout(grids_cl, grids, stream)
         return grids, flats, g_pts
+
+    def _grads_to_reference_layout(self, grids_cl, grids, stream):
+        """The kernels' channels-last grid gradients grids_cl[name] [Z,Y,X,32] -> grids[name] [1,32,Z,Y,X]: ONE launch."""
+        if grids_cl:
+            arr, n, _ = self.relayout_jobs_array([(g, grids[name], g.numel() // 32) for name, g in grids_cl.items()])
+            check(lib().adfp_relayout_grids(n, arr, 1, stream), 'adfp_relayout_grids')
 
     def sample_tsdf(self, pts, tsdf_volume, tsdf_bnds):
         _lib.require_cuda(pts, 'points')
         dev = pts.device
         with _lib.device_guard(dev):
-            mode = _lib.PTS_F64 if pts.dtype == torch.float64 else _lib.PTS_F32
-            if mode == _lib.PTS_F32 and pts.dtype != torch.float32:
-                pts = pts.float()
-            pts = pts.detach().reshape(-1, 3).contiguous()
+            ap, pts, _ = points_desc(pts.reshape(-1, 3))
             P = pts.shape[0]
             out = torch.empty((P,), dtype=torch.float32, device=dev)
             if P == 0:
@@ -693,77 +764,72 @@ class Engine(object):
             self.fill_tsdf(td, tsdf_volume, keep)
             b = _lib.Bound()
             _lib.fill_bound(b, self.host_bound(tsdf_bnds, 'tsdf_bnds'))
-            ap = _lib.AdfpPoints()
-            ap.mode = mode
-            ap.n_points = P
-            ap.pts = pts.data_ptr()
             check(lib().adfp_sample_tsdf(C.byref(td), C.byref(b), C.byref(ap), ptr(out), _lib.current_stream(dev)),
                   'adfp_sample_tsdf')
         return out
 
     # ---- one sub-network alone (MLP.forward / mlp_tsdf.forward, reference decoder.py:177-203, :240-258) --------------
+    @staticmethod
+    def _run_single(mlp, name, dev, n, launch):
+        """launch(sc) with the minimal scene of ONE network on its own: the process-wide status word and the module's own image,
+        f16-split (h_<name>) or exact (w_<name>).  A sub-network on its own is a convenience entry without the device-side repair:
+        after a split run over n > 0 rows the range word is read (one sync) and, if it tripped, the module is marked _single_exact
+        and launch runs once more, on the exact image (and the module stays there)."""
+        while True:
+            use_h = math_mode() == 'f16x3' and not mlp.__dict__.get('_single_exact')
+            _lib.check_status()
+            sc = _lib.AdfpScene()
+            sc.status = _lib.status_word().data_ptr()
+            packed = mlp._single_packed(name, 'h' if use_h else 'f32')
+            setattr(sc, ('h_' if use_h else 'w_') + name, packed.data_ptr())
+            launch(sc)
+            if not (n and use_h and _lib.check_status(sync=True, device=dev) & _lib.STATUS_F16_RANGE):
+                return
+            mlp.__dict__['_single_exact'] = True
+
     def decode_single(self, mlp, pts, c, bound):
         """pts [P,3] f64/f32 -> [P] (low / high decoder) or [P,4] (colour decoder)."""
         _lib.require_cuda(pts, 'points')
         dev = pts.device
         name = mlp.name
-        use_h = math_mode() == 'f16x3' and not mlp.__dict__.get('_single_exact')
         with _lib.device_guard(dev):
-            mode = _lib.PTS_F64 if pts.dtype == torch.float64 else _lib.PTS_F32
-            if mode == _lib.PTS_F32 and pts.dtype != torch.float32:
-                pts = pts.float()
-            pts = pts.detach().contiguous()
+            ap, pts, _ = points_desc(pts)
             P = pts.shape[0]
-            _lib.check_status()
-            sc = _lib.AdfpScene()
-            sc.status = _lib.status_word().data_ptr()
-            _lib.fill_bound(sc.bound, self.host_bound(bound, 'bound.' + name))
-            packed = mlp._single_packed(name, 'h' if use_h else 'f32')
-            setattr(sc, ('h_' if use_h else 'w_') + name, packed.data_ptr())
-            keep = []
-            for field, key in [(name, 'grid_' + name)] + ([('low', 'grid_low')] if name == 'high' else []):
-                g = self.grid_cl(key, c[key])
-                keep.append(g)
-                gd = getattr(sc, field)
-                gd.data, gd.Z, gd.Y, gd.X = g.data_ptr(), g.shape[0], g.shape[1], g.shape[2]
-            ap = _lib.AdfpPoints()
-            ap.mode, ap.n_points, ap.pts = mode, P, pts.data_ptr()
             out = torch.empty((P,) if name == 'high' else (P, 4), dtype=torch.float32, device=dev)
-            if P:
-                check(lib().adfp_decode_single(C.byref(sc), C.byref(ap), _lib.DEC_KIND[name], ptr(out), _lib.current_stream(dev)),
-                      'adfp_decode_single')
-                # a sub-network on its own is a convenience entry without the device-side repair: look at the range word now
-                # and, if it tripped, evaluate again on the exact kernel (and stay there)
-                if use_h and _lib.check_status(sync=True, device=dev) & _lib.STATUS_F16_RANGE:
-                    mlp.__dict__['_single_exact'] = True
-                    return self.decode_single(mlp, pts, c, bound)
+
+            def launch(sc):
+                _lib.fill_bound(sc.bound, self.host_bound(bound, 'bound.' + name))
+                keep = []
+                for field, key in [(name, 'grid_' + name)] + ([('low', 'grid_low')] if name == 'high' else []):
+                    g = self.grid_cl(key, c[key])
+                    keep.append(g)
+                    gd = getattr(sc, field)
+                    gd.data, gd.Z, gd.Y, gd.X = g.data_ptr(), g.shape[0], g.shape[1], g.shape[2]
+                if P:
+                    check(lib().adfp_decode_single(C.byref(sc), C.byref(ap), _lib.DEC_KIND[name], ptr(out), _lib.current_stream(dev)),
+                          'adfp_decode_single')
+            self._run_single(mlp, name, dev, P, launch)
             return out[:, 3].contiguous() if name == 'low' else out
 
     def attention_rows(self, mlp, pts, occ, tsdf_volume, tsdf_bnds):
         """(fused occupancy [M], attention weight [M]) of mlp_tsdf.forward at the points pts [M,3] with occupancies occ [M]."""
         _lib.require_cuda(pts, 'points')
         dev = pts.device
-        use_h = math_mode() == 'f16x3' and not mlp.__dict__.get('_single_exact')
         tv = self.sample_tsdf(pts, tsdf_volume, tsdf_bnds)
         with _lib.device_guard(dev):
             M = tv.shape[0]
-            occ = occ.detach().to(dev, torch.float32).contiguous()
+            occ = as_dev(occ, torch.float32, dev)
             if occ.shape[0] != M:
                 raise RuntimeError(f'mlp_tsdf: {occ.shape[0]} occupancies for {M} points')
-            _lib.check_status()
-            sc = _lib.AdfpScene()
-            sc.status = _lib.status_word().data_ptr()
-            packed = mlp._single_packed('att', 'h' if use_h else 'f32')
-            setattr(sc, 'h_att' if use_h else 'w_att', packed.data_ptr())
             out4 = torch.empty((M, 4), dtype=torch.float32, device=dev)
             w = torch.empty((M,), dtype=torch.float32, device=dev)
             u = torch.empty((M,), dtype=torch.float32, device=dev)
-            if M:
-                check(lib().adfp_attention_rows(C.byref(sc), ptr(occ), ptr(tv), M, ptr(out4), ptr(w), ptr(u), _lib.current_stream(dev)),
-                      'adfp_attention_rows')
-                if use_h and _lib.check_status(sync=True, device=dev) & _lib.STATUS_F16_RANGE:
-                    mlp.__dict__['_single_exact'] = True
-                    return self.attention_rows(mlp, pts, occ, tsdf_volume, tsdf_bnds)
+
+            def launch(sc):
+                if M:
+                    check(lib().adfp_attention_rows(C.byref(sc), ptr(occ), ptr(tv), M, ptr(out4), ptr(w), ptr(u),
+                                                    _lib.current_stream(dev)), 'adfp_attention_rows')
+            self._run_single(mlp, 'att', dev, M, launch)
             return out4[:, 3].contiguous(), w
 
     # ---- a4..a13 ---------------------------------------------------------------------------
@@ -778,7 +844,9 @@ class Engine(object):
         the call's first launch (adfp_render_args.prefilter_bound): keep is written, the far clamp is the kept rays' max depth."""
         f32 = torch.float32
         if frame is not None:
-            fdepth = frame['depth'].detach().reshape(-1)
+            if train:
+                raise ValueError('render_forward: a frame job (frame=) is an inference call, not one with train=True')
+            fdepth = frame['depth'].reshape(-1)
             _lib.require_cuda(fdepth, 'gt_depth')
             dev = fdepth.device
         else:
@@ -786,31 +854,21 @@ class Engine(object):
             dev = rays_o.device
         with _lib.device_guard(dev):
             if frame is not None:
-                if fdepth.dtype != f32 or not fdepth.is_contiguous():
-                    fdepth = fdepth.float().contiguous()
+                fdepth = as_dev(fdepth, f32, dev)
                 N = int(frame['n_rays'])
                 if fdepth.numel() != int(frame['H']) * int(frame['W']) or not (0 <= depth_max_first_ray and depth_max_first_ray + N <= fdepth.numel()):
                     raise RuntimeError(f"frame job: gt_depth has {fdepth.numel()} pixels for a {frame['H']}x{frame['W']} frame, pixels "
                                        f'[{depth_max_first_ray}, {depth_max_first_ray + N}) asked for')
-                fc2w = frame['c2w'].detach().to(dev, f32).contiguous()
+                fc2w = as_dev(frame['c2w'], f32, dev)
                 if fc2w.numel() < 12:
                     raise RuntimeError(f'c2w: expected [3,4] or [4,4], got {tuple(fc2w.shape)}')
                 ro = torch.empty((N, 3), dtype=f32, device=dev)
                 rd = torch.empty((N, 3), dtype=f32, device=dev)
                 gd = fdepth[depth_max_first_ray:depth_max_first_ray + N]
             else:
-                ro = rays_o.detach()
-                if ro.dtype != f32 or not ro.is_contiguous():
-                    ro = ro.float().contiguous()
-                rd = rays_d.detach()
-                if rd.dtype != f32 or not rd.is_contiguous():
-                    rd = rd.float().contiguous()
+                ro, rd = as_dev(rays_o, f32, dev), as_dev(rays_d, f32, dev)
                 N = ro.shape[0]
-                gd = None
-                if gt_depth is not None:
-                    gd = gt_depth.detach().reshape(-1)
-                    if gd.dtype != f32 or not gd.is_contiguous():
-                        gd = gd.float().contiguous()
+                gd = None if gt_depth is None else as_dev(gt_depth.reshape(-1), f32, dev)
             S = n_samples + (n_surface if gd is not None else 0)
             depth = torch.empty((N,), dtype=torch.float64, device=dev)
             unc = torch.empty((N,), dtype=torch.float64, device=dev)
@@ -829,17 +887,17 @@ class Engine(object):
                                    for n in _STAGE_NETS[stage])
                 decoders.absorb_status()          # BEFORE the state is laid out (see eval_points_forward)
                 aux = self.train_state(P, stage, dev, decoders, need_flat, extra=extra)
-            sc, keep = self.scene(decoders, c, tsdf_volume, tsdf_bnds, bound, stage, keys=keys, state=aux, tsdf_blocks=tsdf_blocks,
-                                  hand_over_packs=True)
-            owed, self._owed_packs = self._owed_packs, None
-            owed_rl, self._owed_relayouts = self._owed_relayouts, None
-            launched = False
-            try:
+            # the grid conversions and image packs this call needs stay pending in `batch` until its own launch has carried them:
+            # leaving the block through an exception before that takes their cache entries back
+            with Deferred(self, decoders) as batch:
+                sc, keep = self.build_scene(batch, decoders, c, tsdf_volume, tsdf_bnds, bound, stage, keys=keys, state=aux,
+                                            tsdf_blocks=tsdf_blocks)
                 a = _lib.AdfpRenderArgs()
-                if owed is not None:                     # this call's first launch packs them beside its zero fill
-                    a.pack_jobs, a.n_pack_jobs = owed[0], owed[1]
-                if owed_rl is not None:                  # ... and converts the grids
-                    a.relayout_jobs, a.n_relayout_jobs = owed_rl[0], owed_rl[1]
+                relayouts, packs = batch.hand_over(dev)
+                if packs is not None:                    # this call's first launch packs them beside its zero fill
+                    a.pack_jobs, a.n_pack_jobs = packs
+                if relayouts is not None:                # ... and converts the grids
+                    a.relayout_jobs, a.n_relayout_jobs = relayouts
                 a.stage = _lib.STAGE[stage]
                 a.n_rays = N
                 a.n_samples = n_samples
@@ -850,7 +908,7 @@ class Engine(object):
                 a.rays_d = rd.data_ptr()
                 a.gt_depth = gd.data_ptr() if gd is not None else None
                 if perturb > 0:
-                    t_rand = t_rand.to(dev, f32).contiguous()
+                    t_rand = as_dev(t_rand, f32, dev)
                     a.t_rand = t_rand.data_ptr()
                 a.depth_max_segment = int(depth_max_segment)
                 a.depth_max_first_ray = int(depth_max_first_ray)
@@ -863,7 +921,7 @@ class Engine(object):
                     fj.depth, fj.rays_o, fj.rays_d = fdepth.data_ptr(), ro.data_ptr(), rd.data_ptr()
                     a.frame = C.pointer(fj)
                 if depth_max is not None:
-                    depth_max = depth_max.to(dev, f32).reshape(-1).contiguous()
+                    depth_max = as_dev(depth_max.reshape(-1), f32, dev)
                     a.depth_max = depth_max.data_ptr()
                 a.depth = depth.data_ptr()
                 a.uncertainty = unc.data_ptr()
@@ -885,12 +943,6 @@ class Engine(object):
                 a.workspace = ws.data_ptr()
                 a.workspace_bytes = ws.numel()
                 check(lib().adfp_render_forward(C.byref(sc), C.byref(a), _lib.current_stream(dev)), 'adfp_render_forward')
-                launched = True
-            finally:
-                if owed is not None and not launched:      # the images the cache already calls current were never packed
-                    decoders._packed = {}
-                if owed_rl is not None and not launched:   # nor the channels-last copies written
-                    self._grid_cache = {k: v for k, v in self._grid_cache.items() if len(v) == 4}
         return depth, unc, color, weight, aux
 
     # ---- a15 -------------------------------------------------------------------------------
@@ -922,54 +974,28 @@ class Engine(object):
             a.rays_o, a.rays_d = ro.data_ptr(), saved['rays_d'].data_ptr()
             a.z_vals, a.raw = saved['ptrs']['z_vals'], saved['ptrs']['raw']
             a.state = saved['_state']
-
-            def prep(t, dtype):
-                if t is None:
-                    return None
-                t = t.detach()
-                if t.dtype != dtype or t.device != dev:
-                    t = t.to(dev, dtype)
-                return t if t.is_contiguous() else t.contiguous()
-            gd, gu, gc, gw = prep(g_depth, torch.float64), prep(g_unc, torch.float64), prep(g_color, f32), prep(g_weight, f32)
+            gd, gu = as_dev(g_depth, torch.float64, dev), as_dev(g_unc, torch.float64, dev)
+            gc, gw = as_dev(g_color, f32, dev), as_dev(g_weight, f32, dev)
             a.g_depth, a.g_uncertainty = _lib.ptr(gd), _lib.ptr(gu)
             a.g_color, a.g_weight = _lib.ptr(gc), _lib.ptr(gw)
             if ray_keep is not None:
                 a.ray_keep = ray_keep.data_ptr()
-            grids_cl, flats = {}, {}
-            direct = {}
-            # Gradient outputs the caller did not provide come out of ONE allocation (the three grids first: their channel-major
-            # copies are written with 16-byte stores; then the flat parameter gradients): one torch.empty instead of five, and
-            # dist.allreduce_grads finds the whole bucket contiguous -- the .grad tensors autograd keeps are views of it -- and
-            # all-reduces it in place, with no packing copy either way.
-            own_grid = [(name, key) for name, key in (('low', 'grid_low'), ('high', 'grid_high'), ('color', 'grid_color'))
-                        if need_grid.get(name) and not (out_grids_cl and name in out_grids_cl) and not (out_grids and name in out_grids)]
-            own_flat = [name for name in ('low', 'high', 'color', 'att') if need_flat.get(name) and not (out_flats and name in out_flats)]
-            bucket, boff = None, {}
-            if own_grid or own_flat:
-                off = 0
-                for name, key in own_grid:
-                    boff['g' + name] = off
-                    off += c[key].numel()
-                for name in own_flat:
-                    boff['f' + name] = off
-                    off += _flat_floats(name)
-                bucket = torch.empty((off,), dtype=f32, device=dev)
-            for name, key in (('low', 'grid_low'), ('high', 'grid_high'), ('color', 'grid_color')):
+            out_grids, out_flats, out_grids_cl = out_grids or {}, out_flats or {}, out_grids_cl or {}
+            # gradient outputs the caller did not provide come out of ONE allocation, laid out by grad_plan: one torch.empty instead of five
+            total, spans = grad_plan(c, need_grid, need_flat, (*out_grids_cl, *out_grids), out_flats)
+            bucket = torch.empty((total,), dtype=f32, device=dev) if total else None
+            grids, grids_cl, flats = {}, {}, {}
+            for name, key in _GRID_KEYS:
                 if need_grid.get(name):
-                    Z, Y, X = c[key].shape[2:]
-                    if out_grids_cl and name in out_grids_cl:
-                        direct[name] = out_grids_cl[name]
-                        setattr(a, 'g_grid_' + name, direct[name].data_ptr())
-                        continue
-                    grids_cl[name] = self._cl_scratch(name, (Z, Y, X, 32), dev)
-                    setattr(a, 'g_grid_' + name, grids_cl[name].data_ptr())
-            for name in ('low', 'high', 'color', 'att'):
-                if need_flat.get(name):
-                    if out_flats and name in out_flats:
-                        flats[name] = out_flats[name]
+                    if name in out_grids_cl:
+                        g = grids[name] = out_grids_cl[name]           # the kernels' own layout: handed back as it is
                     else:
-                        o = boff['f' + name]
-                        flats[name] = bucket[o:o + _flat_floats(name)]
+                        Z, Y, X = c[key].shape[2:]
+                        g = grids_cl[name] = self._cl_scratch(name, (Z, Y, X, 32), dev)
+                    setattr(a, 'g_grid_' + name, g.data_ptr())
+            for name in _NETS:
+                if need_flat.get(name):
+                    flats[name] = out_flats[name] if name in out_flats else bucket[spans['f' + name]]
                     setattr(a, 'g_flat_' + name, flats[name].data_ptr())
             g_ro = g_rd = None
             if need_rays:
@@ -989,17 +1015,7 @@ class Engine(object):
                 for k in range(2):
                     a.side_events[k] = lane[1][k].cuda_event
             check(L.adfp_render_backward(C.byref(sc), C.byref(a), stream), 'adfp_render_backward')
-            grids = dict(direct)
-            if grids_cl:                                  # the kernels' channels-last gradients -> the reference's layout: ONE launch
-                arr = (_lib.AdfpRelayoutJob * len(grids_cl))()
-                for k, (name, g) in enumerate(grids_cl.items()):
-                    Z, Y, X = g.shape[:3]
-                    if out_grids and name in out_grids:
-                        out = out_grids[name]
-                    else:
-                        o = boff['g' + name]
-                        out = bucket[o:o + 32 * Z * Y * X].view(1, 32, Z, Y, X)
-                    arr[k].src, arr[k].dst, arr[k].voxels = g.data_ptr(), out.data_ptr(), Z * Y * X
-                    grids[name] = out
-                check(L.adfp_relayout_grids(len(grids_cl), arr, 1, stream), 'adfp_relayout_grids')
+            for name, g in grids_cl.items():
+                grids[name] = out_grids[name] if name in out_grids else bucket[spans['g' + name]].view(c['grid_' + name].shape)
+            self._grads_to_reference_layout(grids_cl, grids, stream)
         return grids, flats, (g_ro, g_rd)

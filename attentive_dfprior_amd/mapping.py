@@ -176,7 +176,7 @@ class MapperIteration(object):
         def cl_like(g):
             return torch.zeros((g.shape[2], g.shape[3], g.shape[4], g.shape[1]), dtype=torch.float32, device=dev)
         self.shadow = {k: cl_like(g) for k, g in c.items()}
-        self._shadow_version = {k: None for k in c}              # c[k]._version the shadow was last made coherent with
+        self._shadow_held = {k: None for k in c}                 # the cache entry (engine.CachedGrid) naming c[k] as the shadow last matched it
         self.gstate = {k: (cl_like(g), cl_like(g)) for k, g in c.items()}
         self.nets = tuple(train)
         attr = {'low': 'low_decoder', 'high': 'high_decoder', 'color': 'color_decoder', 'att': 'mlp'}
@@ -583,15 +583,9 @@ class MapperIteration(object):
 
     def _sync_shadows(self):
         """Before a forward: every grid's channels-last shadow is what the engine's layout cache holds for it.  A grid somebody
-        else wrote since our last step (its version is not the one we left) is re-laid out into the shadow first."""
-        eng = self.rend._engine
+        else wrote since our last step (its key is not the one we left) is re-laid out into the shadow first."""
         for k, g in self.c.items():
-            if self._shadow_version[k] != g._version:
-                with torch.cuda.device(self.dev):
-                    Z, Y, X = g.shape[2:]
-                    check(lib().adfp_relayout_grid(ptr(g), ptr(self.shadow[k]), 32, Z, Y, X, _lib.current_stream(self.dev)), 'adfp_relayout_grid')
-                self._shadow_version[k] = g._version
-            eng.adopt_grid_cl(k, g, self.shadow[k])
+            self._shadow_held[k] = self.rend._engine.sync_shadow(k, g, self.shadow[k], self._shadow_held[k])
 
     def _drop_volatile_cache_entries(self):
         self.rend._engine._grid_cache.clear()
@@ -603,8 +597,7 @@ class MapperIteration(object):
         for t in self._versioned:
             torch.autograd.graph.increment_version(t)        # updated through raw pointers: invalidate (data_ptr, _version) caches
         for k, g in self.c.items():                          # ... except the shadows: the Adam kernel kept them coherent
-            self._shadow_version[k] = g._version
-            self.rend._engine.adopt_grid_cl(k, g, self.shadow[k])
+            self._shadow_held[k] = self.rend._engine.adopt_grid_cl(k, g, self.shadow[k])
 
     @torch.no_grad()
     def input_buffers(self, N):

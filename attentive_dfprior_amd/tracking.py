@@ -27,7 +27,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import lib, ptr, check
+from ._lib import lib, check
 
 
 class TrackerIteration(object):
@@ -177,22 +177,13 @@ class TrackerIteration(object):
         eng = self.rend._engine
         for k, g in self.c.items():
             _lib.require_cuda(g, k)
-            src = (g.data_ptr(), g._version, g.shape, g.stride())
             sh = self._shadow.get(k)
             Z, Y, X = g.shape[2:]
             if sh is None or sh.shape != (Z, Y, X, 32) or sh.device != g.device:
                 sh = self._shadow[k] = torch.empty((Z, Y, X, 32), dtype=torch.float32, device=g.device)
                 self._shadow_src[k] = None
-            held = self._shadow_src[k]
-            if held is None or held[0] != src:
-                gc = g.detach()
-                if gc.dtype != torch.float32 or not gc.is_contiguous():
-                    gc = gc.float().contiguous()
-                check(lib().adfp_relayout_grid(ptr(gc), ptr(sh), 32, Z, Y, X, _lib.current_stream(g.device)), 'adfp_relayout_grid')
-                # the entry keeps the source's STORAGE alive: (data_ptr, _version) names the contents only as long as the allocator
-                # cannot hand the same address, at version 0, to the next grid (a grid replaced twice between two steps)
-                self._shadow_src[k] = (src, g.untyped_storage())
-            eng.adopt_grid_cl(k, g, sh)
+            # the held entry keeps the source's STORAGE alive (a grid replaced twice between two steps: see engine.Cached)
+            self._shadow_src[k] = eng.sync_shadow(k, g, sh, self._shadow_src[k])
 
     def _draw(self, n):
         H0, H1, W0, W1 = self.window

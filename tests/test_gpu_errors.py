@@ -110,7 +110,9 @@ def test_missing_weight_image_and_bad_stage():
 def test_a_failed_call_leaves_no_conversion_the_caches_vouch_for():
     """scene() defers the grid conversions and the weight-image packs of a call into ONE launch each and records them as current at
     once.  A call that dies in between -- here: the third grid has the wrong shape, after the first two were deferred -- must not
-    leave cache entries for copies nobody wrote: the next, correct call renders what a fresh renderer renders, bit for bit."""
+    leave cache entries for copies nobody wrote: the next, correct call renders what a fresh renderer renders, bit for bit.
+    The same for a call scene() accepts and the library refuses before its first launch (S = 241 + 16 > ADFP_MAX_SAMPLES): the
+    conversions were handed to a launch that never happened."""
     sc, dec, rend, ro, rd, gd = _setup()
     tb = sc.tsdf_bnds.to(DEV)
     with torch.no_grad():
@@ -122,7 +124,18 @@ def test_a_failed_call_leaves_no_conversion_the_caches_vouch_for():
     rend._engine._grid_cache.clear()
     with torch.no_grad(), pytest.raises(RuntimeError, match='grid_color'):
         rend.render_batch_ray(bad, dec, rd, ro, DEV, sc.tsdf_volume, tb, 'color', gt_depth=gd)
-    assert rend._engine._owed_relayouts is None and rend._engine._owed_packs is None
+    cached = {entry[0][0] for entry in rend._engine._grid_cache.values()}      # the data_ptr of every entry's key
+    assert not any(g.data_ptr() in cached for g in fresh.values())
+    with torch.no_grad():
+        got = rend.render_batch_ray(fresh, dec, rd, ro, DEV, sc.tsdf_volume, tb, 'color', gt_depth=gd)
+    for x, y in zip(got, want):
+        assert torch.equal(x, y)
+    dec._packed.clear()
+    rend._engine._grid_cache.clear()
+    rend.N_samples = 241
+    with torch.no_grad(), pytest.raises(RuntimeError, match='UNSUPPORTED|unsupported'):
+        rend.render_batch_ray(fresh, dec, rd, ro, DEV, sc.tsdf_volume, tb, 'color', gt_depth=gd)
+    rend.N_samples = 32
     with torch.no_grad():
         got = rend.render_batch_ray(fresh, dec, rd, ro, DEV, sc.tsdf_volume, tb, 'color', gt_depth=gd)
     for x, y in zip(got, want):

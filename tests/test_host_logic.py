@@ -215,3 +215,49 @@ def test_bench_full_is_opt_in(monkeypatch):
     assert bench.parse().full is False
     monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5', '--full'])
     assert bench.parse().full is True
+
+
+def test_side_lane_switch_is_parsed_strictly(monkeypatch):
+    """ADFP_SIDE_LANE: unset / empty / 1 / on / true / yes = the lane for the default stages (high, colour); 0 / off / false / no =
+    no lane; otherwise '+'-separated stage names, and anything else is an error that names the token (Engine() touches no device)."""
+    from attentive_dfprior_amd.engine import Engine
+    stages = ('low', 'high', 'color')
+    monkeypatch.delenv('ADFP_SIDE_LANE', raising=False)
+    assert [Engine().lane_for(s) for s in stages] == [False, True, True]
+    for on in ('', '1', 'on', 'true', 'yes'):
+        monkeypatch.setenv('ADFP_SIDE_LANE', on)
+        assert [Engine().lane_for(s) for s in stages] == [False, True, True], on
+    for off in ('0', 'off', 'false', 'no'):
+        monkeypatch.setenv('ADFP_SIDE_LANE', off)
+        assert not any(Engine().lane_for(s) for s in stages), off
+    monkeypatch.setenv('ADFP_SIDE_LANE', 'low+high+color')
+    assert all(Engine().lane_for(s) for s in stages)
+    monkeypatch.setenv('ADFP_SIDE_LANE', 'low')
+    assert [Engine().lane_for(s) for s in stages] == [True, False, False]
+    for bad, token in (('colour', 'colour'), ('high+clr', 'clr')):
+        monkeypatch.setenv('ADFP_SIDE_LANE', bad)
+        with pytest.raises(RuntimeError, match=token):
+            Engine()
+
+
+def test_a_frame_job_is_refused_for_a_training_forward():
+    """render_forward(frame=..., train=True): ValueError before any tensor is looked at (every other argument is None)."""
+    from attentive_dfprior_amd.engine import Engine
+    with pytest.raises(ValueError, match='frame'):
+        Engine().render_forward(None, None, None, None, None, None, None, None, None, None, None, frame={'n_rays': 1}, train=True)
+
+
+def test_tensor_key_follows_address_version_shape_and_strides():
+    from attentive_dfprior_amd.engine import tensor_key, still_names, pinned
+    t = torch.arange(24.0).reshape(2, 3, 4)
+    key = tensor_key(t)
+    assert key == tensor_key(t) == (t.data_ptr(), t._version, (2, 3, 4), (12, 4, 1))
+    entry = pinned(t, 'value')
+    assert still_names(entry, t) and entry[1] == 'value' and entry.storage.data_ptr() == t.untyped_storage().data_ptr()
+    assert tensor_key(t.transpose(1, 2)) != key                 # the same memory through other strides
+    assert tensor_key(t.view(6, 4)) != key                      # ... and through another shape
+    assert tensor_key(t.clone()) != key                         # the same values somewhere else
+    assert not still_names(entry, t.clone()) and not still_names(None, t)
+    t.add_(1.0)                                                 # an in-place write bumps the version
+    assert tensor_key(t) != key and not still_names(entry, t)
+    assert pinned(t, 'v', adopted=True).adopted is True and pinned(t, 'v', adopted=False)[1] == 'v'
